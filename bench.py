@@ -306,6 +306,28 @@ def parity_sample(prm, scenes, out, n_sample, cores):
     return par, cpu_s
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res):
+    """`--dump-outputs`: the result tensors of one solve launch (smpc_result_batch: what a caller of smpc_solve_batch
+    receives) as out_dir/<name>.npy in float64 (the int32 fields convert exactly). If all of them would exceed 64 MB, the
+    same fixed, seeded sample of scenes is taken from every array and its indices are written as scene_index.npy."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {k: v.cpu().numpy().astype(np.float64) for k, v in res.items()}
+    B = next(iter(arrs.values())).shape[0]
+    per_scene = sum(a[0].nbytes for a in arrs.values())
+    if B * per_scene > DUMP_LIMIT_BYTES:
+        n = (DUMP_LIMIT_BYTES - 4096) // (per_scene + 8)      # the index array and the .npy headers count too
+        idx = np.sort(np.random.default_rng(0x5EED0001).choice(B, n, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+        arrs["scene_index"] = idx.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def dry_run(args, rank, local_rank, world):
     """`--dry-run`: the launch / rendezvous / reduction plumbing of the N > 1 path on CPU ranks (gloo), with NO solve at
     all — not a measurement: value is null and the line says so. What it exercises is what an 8-GPU run adds to the
@@ -368,7 +390,13 @@ def main():
                          "scene batch of its own each)")
     ap.add_argument("--dry-run", action="store_true",
                     help="exercise the N-rank launch / reduction path on CPU ranks (gloo) without solving anything")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result arrays of the last timed step (rank 0's shard) as "
+                         "DIR/<name>.npy in float64, at most 64 MB in all (beyond that a fixed, seeded sample of scenes, "
+                         "whose indices go to DIR/scene_index.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` launched plainly: become the launcher of N ranks (before any GPU call), relay rank 0's line
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -457,6 +485,10 @@ def main():
         ev1[k].record(hip_streams[i])
     barrier()
     elapsed = time.perf_counter() - t0
+    last_step = None
+    if args.dump_outputs and rank == 0:
+        # a device copy now (the lone launches below write stream 0's result set again), written out after the measurements
+        last_step = {k: v.clone() for k, v in results[(args.steps - 1) % n_streams][1].items()}
     step_ms = np.array([ev0[k].elapsed_time(ev1[k]) for k in range(args.steps)])
     span_ms = max(ev0[0].elapsed_time(e) for e in ev1)
     # per-launch device time of the solve kernel alone (library-side HIP events around its last launch per handle)
@@ -678,6 +710,8 @@ def main():
             extra("closed_loop", closed_loop_extras, prm, scenes, local_rank)
         real_stdout.write(json.dumps(line) + "\n")
         real_stdout.flush()
+    if last_step is not None:
+        dump_outputs(args.dump_outputs, last_step)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -2,7 +2,6 @@
 import os
 
 import numpy as np
-import pytest
 
 from nav2_social_mpc_controller_amd.params import OptimizerParams
 from nav2_social_mpc_controller_amd.scenes import SceneBatch, make_scenes, uniform
@@ -52,19 +51,33 @@ def test_yaml_reader_handles_a_nav2_shaped_file(tmp_path):
     assert p.max_time == 1.5 and p.rollout_steps == 28
 
 
-def test_benchmark_presets_are_the_shipped_parameter_files():
-    """OptimizerParams.soc_work_obst_benchmark / obst_only_benchmark against what the YAML reader finds in the reference's
-    own params/*_in_benchmark.yaml:104-136 (read here, in the build container; the GPU box does not have the reference)."""
-    ref = "/root/reference/params"
+def test_benchmark_presets_are_the_shipped_parameter_files(tmp_path):
+    """OptimizerParams.soc_work_obst_benchmark / obst_only_benchmark / params_yaml against what the YAML reader finds in
+    the reference's own params/*_in_benchmark.yaml:104-136 and params/params.yaml:24-56. Their FollowPath sections are
+    stored in tests/golden/benchmark_params.json (tests/golden/make_golden_params.py) and put back into a nav2-shaped
+    file, behind other nodes as in the shipped files, for the reader."""
+    import json
+    import yaml
+
     a, b = OptimizerParams.soc_work_obst_benchmark(), OptimizerParams.obst_only_benchmark()
     assert (a.social_weight, a.agent_angle_weight, a.obstacle_weight, a.proxemics_weight) == (120.0, 40.0, 0.13, 90.0)
     assert (b.social_weight, b.agent_angle_weight, b.obstacle_weight, b.proxemics_weight) == (0.0, 0.0, 0.13, 90.0)
     assert a.dims(a.rollout_steps) == (18, 6, 3, 6, 226, 3) and a.rollout_steps == 28
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present on this machine")
-    assert OptimizerParams.from_yaml(os.path.join(ref, "soc_work_obst_parameters_in_benchmark.yaml")) == a
-    assert OptimizerParams.from_yaml(os.path.join(ref, "obst_only_parameters_in_benchmark.yaml")) == b
-    assert OptimizerParams.from_yaml(os.path.join(ref, "params.yaml")) == OptimizerParams.params_yaml()
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "benchmark_params.json")) as f:
+        shipped = json.load(f)
+
+    def read(name):
+        doc = {"bt_navigator": {"ros__parameters": {"use_sim_time": True}},
+               "controller_server": {"ros__parameters": {"controller_frequency": 20.0, "FollowPath": dict(
+                   plugin="nav2_social_mpc_controller::SocialMPCController", **shipped[name])}},
+               "local_costmap": {"local_costmap": {"ros__parameters": {"width": 4, "height": 4, "resolution": 0.05}}}}
+        f = tmp_path / name
+        f.write_text(yaml.safe_dump(doc))
+        return OptimizerParams.from_yaml(str(f))
+
+    assert read("soc_work_obst_parameters_in_benchmark.yaml") == a
+    assert read("obst_only_parameters_in_benchmark.yaml") == b
+    assert read("params.yaml") == OptimizerParams.params_yaml()
 
 
 def test_time_step_is_a_widened_float():
