@@ -402,7 +402,6 @@ __device__ inline void cubic_hermite(double p0, double p1, double p2, double p3,
 // cc is then byte (cc - start) of its row's dword — also at the edges, where several taps share a cell.
 struct CostPatch {
   uint32_t row[4];   // bytes start .. start + 3 of the four clamped rows
-  uint32_t sh;       // bit offsets (0, 8, 16, 24) of the four taps inside a row dword, 5 bits each
 };
 
 // Integer cell of a coordinate, kept defined for wild values (clamping below makes any far-outside index equivalent).
@@ -428,14 +427,9 @@ __device__ inline void bicubic_fetch(const uint8_t* __restrict__ map, int size_x
       __builtin_memcpy(&v, q + (size_t)i * size_x, 4);  // unaligned dword
       p.row[i] = v;
     }
-    p.sh = 0u | (8u << 5) | (16u << 10) | (24u << 15);
     return;
   }
   const int start = min(max(col - 1, 0), size_x - 4);
-  uint32_t sh = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) sh |= (uint32_t)(8 * (min(max(col - 1 + j, 0), size_x - 1) - start)) << (5 * j);
-  p.sh = sh;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int rr = min(max(row - 1 + i, 0), size_y - 1);
@@ -445,19 +439,26 @@ __device__ inline void bicubic_fetch(const uint8_t* __restrict__ map, int size_x
   }
 }
 
-// (r, c) must be the coordinates the patch was fetched for
+// (r, c) must be the coordinates the patch was fetched for. The bit offsets of the clamped taps inside a row dword are
+// derived here from c, not at the fetch: carried in the patch across the agent loop they were one register more than K1
+// <3,32> has (one spilled VGPR).
 template <bool kInterior>
-__device__ inline void bicubic_eval(const CostPatch& p, double r, double c, double& f, double& dfdr, double& dfdc) {
+__device__ inline void bicubic_eval(const CostPatch& p, int size_x, double r, double c, double& f, double& dfdr,
+                                    double& dfdc) {
   const double tr = r - floor(r), tc = c - floor(c);
+  uint32_t sh[4] = {0u, 8u, 16u, 24u};
+  if (!kInterior) {
+    const int col = cell_index(c, size_x);
+    const int start = min(max(col - 1, 0), size_x - 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sh[j] = (uint32_t)(8 * (min(max(col - 1 + j, 0), size_x - 1) - start));
+  }
   double fv[4], dv[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     double t[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (kInterior) t[j] = (double)((p.row[i] >> (8 * j)) & 0xffu);
-      else t[j] = (double)((p.row[i] >> ((p.sh >> (5 * j)) & 31u)) & 0xffu);
-    }
+    for (int j = 0; j < 4; ++j) t[j] = (double)((p.row[i] >> sh[j]) & 0xffu);
     cubic_hermite(t[0], t[1], t[2], t[3], tc, fv[i], dv[i]);
   }
   double unused;
@@ -1193,8 +1194,8 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
     // the same expressions as at the fetch (recomputed rather than kept in registers across the agent loop)
     const double ob_ic = (X + 0.25 * c1 - cst[4]) * inv_res, ob_ir = (Y + 0.25 * s1 - cst[5]) * inv_res;
     double f, dfdr, dfdc;
-    if (patch_interior) bicubic_eval<true>(patch, ob_ir, ob_ic, f, dfdr, dfdc);
-    else if (wide_map) bicubic_eval<false>(patch, ob_ir, ob_ic, f, dfdr, dfdc);
+    if (patch_interior) bicubic_eval<true>(patch, k.size_x, ob_ir, ob_ic, f, dfdr, dfdc);
+    else if (wide_map) bicubic_eval<false>(patch, k.size_x, ob_ir, ob_ic, f, dfdr, dfdc);
     else bicubic(c.map, k.size_x, k.size_y, ob_ir, ob_ic, f, dfdr, dfdc);  // maps narrower than one patch: byte by byte
     const double r = w.obstacle_w * f;
     const double gx = w.obstacle_w * dfdc * inv_res, gy = w.obstacle_w * dfdr * inv_res;

@@ -137,7 +137,7 @@ struct Sample {
 // LineSearch::InterpolatingPolynomialMinimizingStepSize with CUBIC interpolation:
 // fit a polynomial through {lowerbound, current[, previous]} (values and directional derivatives), minimise on
 // [lo, hi]. scratch: >= 96 doubles of LDS.
-__device__ __attribute__((noinline)) double interpolate_step(const Sample& lower, const Sample& previous, const Sample& current,
+__device__ __attribute__((always_inline)) inline double interpolate_step(const Sample& lower, const Sample& previous, const Sample& current,
                                           double lo, double hi, double* scratch) {
   if (!current.value_valid) return fmin(fmax(current.x * 0.5, lo), hi);
   double* A = scratch;          // 36
