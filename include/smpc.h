@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMPC_ABI_VERSION 4
+#define SMPC_ABI_VERSION 5
 #define SMPC_MAX_BLOCKS 10 /* nb <= 10  => P <= 20; every nb in 1..10 is instantiated */
 #define SMPC_MAX_LM_ITERATIONS 100000 /* smpc_create refuses a larger max_iterations: a persistent wave must reach its exit */
 #define SMPC_MAX_STEPS 63  /* T <= 63: one lane per pose of the rollout (T + 1 poses in a 64-lane wavefront) */
@@ -268,6 +268,38 @@ int smpc_stage_people_batch(smpc_handle* h, const smpc_scene_batch* scenes, doub
  * error [B] (enum smpc_projection_error; may be NULL). Returns SMPC_ERR_INVALID_ARG for an empty / malformed grid
  * (the reference throws, src/optimizer.cpp:676-687). */
 int smpc_project_people_batch(smpc_handle* h, const smpc_projection_batch* in, double* people_proj, int32_t* error);
+
+/* ---- The ObstacleDistance grid of people projection, computed from the costmaps (csrc/smpc_distance.hpp) -------------
+ * The reference receives it from another node (src/optimizer.cpp:593-605; ":597 TODO use the costmap to compute the
+ * obstacles"). Here: an exact Euclidean nearest-obstacle transform of every scene's costmap. A cell is an obstacle when
+ * cost >= obstacle_min_cost (254 = LETHAL_OBSTACLE is the usual choice); cost 255 (NO_INFORMATION) only when
+ * unknown_is_obstacle != 0. indexes[g][y][x] = ox + oy * size_x of the obstacle cell minimising dx^2 + dy^2 in integer
+ * cells, ties to the smallest linear index (an obstacle cell points at itself); distances[g][y][x] =
+ * (float)(sqrt((double)d2) * (double)(float)resolution) in metres. A grid without any obstacle cell: every index is
+ * size_x * size_y and every distance +inf — people projection then reports SMPC_PROJ_INDEX_OUT_OF_BOUNDS for that
+ * scene's people, where the reference throws (:707-713). g runs over B grids, or one when costmap_shared. The output
+ * goes to smpc_projection_batch as it is: od_shared = costmap_shared, od_width / od_height = size_x / size_y,
+ * od_origin = the costmap origin, od_resolution = (float)resolution. size_x <= 4096, size_y <= 32768. */
+typedef struct smpc_obstacle_distance_in {
+  int32_t B;
+  int32_t size_x, size_y;        /* cells; >= 1 */
+  int32_t on_device;             /* 0: host pointers, 1: device pointers (outputs follow) */
+  const uint8_t* costmap;        /* [B or 1][size_y][size_x] (smpc_scene_batch.costmap) */
+  int32_t costmap_shared;        /* 1: one costmap, one output grid */
+  uint8_t obstacle_min_cost;     /* 1..255 */
+  uint8_t unknown_is_obstacle;
+  uint8_t reserved[2];
+  double resolution;             /* costmap resolution in metres; the distances use it as float */
+} smpc_obstacle_distance_in;
+
+typedef struct smpc_obstacle_distance_out {
+  uint32_t* indexes;    /* [B or 1][size_y][size_x] ObstacleDistance.indexes */
+  float* distances;     /* [B or 1][size_y][size_x] ObstacleDistance.distances; NULL: not written */
+  int32_t* n_obstacles; /* [B or 1] obstacle cells of each grid; may be NULL */
+} smpc_obstacle_distance_out;
+
+/* Returns SMPC_ERR_INVALID_ARG for an empty grid or a bad argument, SMPC_ERR_UNSUPPORTED beyond the size limits. */
+int smpc_obstacle_distance_batch(smpc_handle* h, const smpc_obstacle_distance_in* in, smpc_obstacle_distance_out* out);
 
 /* ---- warm start / input formatting for B scenes ------------------------------------------------
  * TrajectoryMemory (trajectory_memory.hpp:30-49; a process-wide singleton in the reference) as one caller-owned record

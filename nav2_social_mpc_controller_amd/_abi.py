@@ -6,7 +6,7 @@ Struct layouts must stay in lock-step with include/smpc.h (checked by tests/test
 """
 import ctypes as C
 
-SMPC_ABI_VERSION = 4
+SMPC_ABI_VERSION = 5
 SMPC_MAX_BLOCKS = 10
 
 # enum smpc_linear_solver (mirrors OptimizerParams::solver_types, reference optimizer.hpp:71-77)
@@ -115,6 +115,29 @@ class SmpcPeopleBatch(C.Structure):
         ("size_x", C.c_int32),
         ("size_y", C.c_int32),
         ("resolution", C.c_double),
+    ]
+
+
+class SmpcObstacleDistanceIn(C.Structure):
+    _fields_ = [
+        ("B", C.c_int32),
+        ("size_x", C.c_int32),
+        ("size_y", C.c_int32),
+        ("on_device", C.c_int32),
+        ("costmap", C.c_void_p),
+        ("costmap_shared", C.c_int32),
+        ("obstacle_min_cost", C.c_uint8),
+        ("unknown_is_obstacle", C.c_uint8),
+        ("reserved", C.c_uint8 * 2),
+        ("resolution", C.c_double),
+    ]
+
+
+class SmpcObstacleDistanceOut(C.Structure):
+    _fields_ = [
+        ("indexes", C.c_void_p),
+        ("distances", C.c_void_p),
+        ("n_obstacles", C.c_void_p),
     ]
 
 
@@ -236,6 +259,7 @@ EXPORTED_SYMBOLS = [
     "smpc_eval_batch",
     "smpc_project_people_batch",
     "smpc_people_to_status_batch",
+    "smpc_obstacle_distance_batch",
     "smpc_format_to_optimize_batch",
     "smpc_memory_store_batch",
     "smpc_trajectorize_path_batch",

@@ -16,6 +16,7 @@
 
 #include "smpc_lm.hpp"
 #include "smpc_project.hpp"
+#include "smpc_distance.hpp"
 #include "smpc_format.hpp"
 #include "smpc_trajectorize.hpp"
 #include "smpc_path_window.hpp"
@@ -687,6 +688,48 @@ int smpc_project_people_batch(smpc_handle* h, const smpc_projection_batch* in, d
   if (!in->on_device) {
     SMPC_TRY(st.down(people_proj, p.people_proj, B * (T + 1) * 6 * N, h->stream));
     SMPC_TRY(st.down(error, p.error, B, h->stream));
+    SMPC_TRY(st.finish(h->stream));
+  }
+  return SMPC_OK;
+}
+
+int smpc_obstacle_distance_batch(smpc_handle* h, const smpc_obstacle_distance_in* in, smpc_obstacle_distance_out* out) {
+  if (!h || !in || !out || !out->indexes) { set_error("null handle / input / output"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B < 0) { set_error("bad B"); return SMPC_ERR_INVALID_ARG; }
+  if (!in->costmap || in->size_x < 1 || in->size_y < 1) { set_error("costmap grid is empty"); return SMPC_ERR_INVALID_ARG; }
+  if (in->obstacle_min_cost < 1) { set_error("obstacle_min_cost must be 1..255"); return SMPC_ERR_INVALID_ARG; }
+  if (!(in->resolution > 0.0)) { set_error("costmap resolution must be > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (in->size_x > smpc::kOdMaxW || in->size_y > smpc::kOdMaxH) {
+    set_error("costmap larger than 4096 x 32768 cells is not supported"); return SMPC_ERR_UNSUPPORTED;
+  }
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::DistParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.W = in->size_x; p.H = in->size_y;
+  p.min_cost = in->obstacle_min_cost; p.unknown_is_obstacle = in->unknown_is_obstacle ? 1 : 0;
+  p.resolution = (float)in->resolution;
+  const size_t ngrid = in->costmap_shared ? 1 : (size_t)in->B, cells = ngrid * (size_t)in->size_x * in->size_y;
+  Staging st(h);
+  if (in->on_device) {
+    p.costmap = in->costmap; p.indexes = out->indexes; p.distances = out->distances; p.n_obstacles = out->n_obstacles;
+  } else {
+    SMPC_TRY(st.up(in->costmap, cells, &p.costmap, h->stream));
+    SMPC_TRY(st.out(out->indexes, cells, &p.indexes));
+    SMPC_TRY(st.out(out->distances, cells, &p.distances));
+    SMPC_TRY(st.out(out->n_obstacles, ngrid, &p.n_obstacles));
+  }
+  if (ngrid > 0) {
+    SMPC_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
+    SMPC_TRY(st.flush_up(h->stream));
+    hipLaunchKernelGGL(smpc::smpc_obstacle_distance_kernel, dim3((unsigned)ngrid), dim3(smpc::kOdThreads), 0, h->stream, p);
+    SMPC_HIP_CHECK(hipGetLastError());
+    SMPC_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+  }
+  if (!in->on_device) {
+    SMPC_TRY(st.down(out->indexes, p.indexes, cells, h->stream));
+    SMPC_TRY(st.down(out->distances, p.distances, cells, h->stream));
+    SMPC_TRY(st.down(out->n_obstacles, p.n_obstacles, ngrid, h->stream));
     SMPC_TRY(st.finish(h->stream));
   }
   return SMPC_OK;

@@ -4,6 +4,7 @@
     field-of-view filter + people_to_status (src/social_mpc_controller.cpp:196-214, src/optimizer.cpp:454-482)
                                                                                    -> smpc_people_to_status_batch
     format_to_optimize + TrajectoryMemory   (src/optimizer.cpp:172-190, 484-551)  -> smpc_format_to_optimize_batch
+    ObstacleDistance grid (optional, once)   (src/optimizer.cpp:593-605, 'TODO')   -> smpc_obstacle_distance_batch
     project_people                           (src/optimizer.cpp:554-728)           -> smpc_project_people_batch
     problem assembly + ceres::Solve + unpack (src/optimizer.cpp:197-446)           -> smpc_solve_batch
     memory store                             (src/optimizer.cpp:448-449)           -> smpc_memory_store_batch
@@ -60,12 +61,17 @@ class TickRecord:
 
 
 class BatchEpisode:
-    def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray,
-                 od_origin: np.ndarray, od_resolution: float, device: int = 0, plan: np.ndarray = None,
+    def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
+                 od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
                  plan_len: np.ndarray = None, traj_params: TrajectorizerParams = None, fov_angle: float = None,
-                 order_hint: bool = False, plan_window: tuple = None):
+                 order_hint: bool = False, plan_window: tuple = None, obstacles_from_costmap: bool = False,
+                 obstacle_min_cost: int = 254, unknown_is_obstacle: bool = False):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
-        od_*: one ObstacleDistance grid shared by all scenes. plan [B,L,2] + plan_len [B] + traj_params: global plans,
+        od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
+        scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
+        are computed on the device from the scenes' costmaps once, here (smpc_obstacle_distance_batch with
+        obstacle_min_cost / unknown_is_obstacle; an episode's costmaps are fixed): one per scene, or one for a shared
+        costmap, with the costmap's origin and resolution. plan [B,L,2] + plan_len [B] + traj_params: global plans,
         trajectorized on the device every tick (the plan must stay longer than the horizon for the whole episode).
         fov_angle: field-of-view half angle of the people filter (reference default pi/4); None = no filter.
         plan_window: (max_robot_pose_search_dist, dist_threshold): every tick starts with PathHandler::transformGlobalPlan
@@ -113,10 +119,29 @@ class BatchEpisode:
         self.costmap_origin = torch.from_numpy(scenes.costmap_origin).to(self.dev)
         self.costmap_shared = scenes.costmap_shared
         self.size_x, self.size_y, self.resolution = scenes.size_x, scenes.size_y, scenes.resolution
-        self.od_indexes = torch.from_numpy(np.ascontiguousarray(od_indexes, np.uint32).view(np.int32)).to(self.dev)
-        self.od_origin = torch.from_numpy(np.ascontiguousarray(od_origin, np.float64).reshape(1, 2)).to(self.dev)
-        self.od_h, self.od_w = int(od_indexes.shape[-2]), int(od_indexes.shape[-1])
-        self.od_resolution = float(od_resolution)
+        if obstacles_from_costmap:
+            grids = 1 if self.costmap_shared else B
+            self.od_shared = 1 if self.costmap_shared else 0
+            self.od_h, self.od_w = self.size_y, self.size_x
+            self.od_resolution = float(np.float32(self.resolution))
+            self.od_origin = self.costmap_origin
+            self.od_indexes = torch.empty((grids, self.od_h, self.od_w), dtype=torch.int32, device=self.dev)
+            ob = BatchSolver.obstacle_distance_c(B, self.size_x, self.size_y, self.costmap_shared, self.resolution, 1,
+                                                 obstacle_min_cost, unknown_is_obstacle)
+            ob.costmap = self.costmap.data_ptr()
+            self.solver.obstacle_distance_device(ob, self.od_indexes.data_ptr())
+        else:
+            if od_indexes is None or od_origin is None or od_resolution is None:
+                raise ValueError("od_indexes, od_origin and od_resolution are needed unless obstacles_from_costmap=True")
+            od_indexes = np.asarray(od_indexes)
+            per_scene = od_indexes.ndim == 3 and od_indexes.shape[0] > 1
+            if per_scene:
+                assert od_indexes.shape[0] == B and np.shape(od_origin) == (B, 2), "per-scene grids: od_indexes [B,h,w], od_origin [B,2]"
+            self.od_shared = 0 if per_scene else 1
+            self.od_indexes = torch.from_numpy(np.ascontiguousarray(od_indexes, np.uint32).view(np.int32)).to(self.dev)
+            self.od_origin = torch.from_numpy(np.ascontiguousarray(od_origin, np.float64).reshape(-1 if per_scene else 1, 2)).to(self.dev)
+            self.od_h, self.od_w = int(od_indexes.shape[-2]), int(od_indexes.shape[-1])
+            self.od_resolution = float(od_resolution)
         # TrajectoryMemory, one record per scene
         self.mem_path = torch.zeros((B, T + 1, 3), **f64)
         self.mem_cmds = torch.zeros((B, T + 1, 2), **f64)
@@ -261,7 +286,7 @@ class BatchEpisode:
         pb.B, pb.T, pb.N, pb.on_device = B, T, N, 1
         pb.max_time, pb.time_step = float(prm.max_time), float(prm.time_step)
         pb.init_people, pb.robot_path = self.people.data_ptr(), self.robot_status.data_ptr()
-        pb.od_indexes, pb.od_shared = self.od_indexes.data_ptr(), 1
+        pb.od_indexes, pb.od_shared = self.od_indexes.data_ptr(), self.od_shared
         pb.od_width, pb.od_height, pb.od_resolution = self.od_w, self.od_h, self.od_resolution
         pb.od_origin = self.od_origin.data_ptr()
         s.project_people_device(pb, self.people_proj.data_ptr(), self.proj_error.data_ptr())
@@ -411,7 +436,8 @@ class ShardedEpisode:
                  od_origin: np.ndarray, od_resolution: float, device: int = 0, plan: np.ndarray = None,
                  plan_len: np.ndarray = None, traj_params: TrajectorizerParams = None, fov_angle: float = None,
                  shards: int = 3, order_hint: bool = False, graphs: bool = True, solve_share: int = None,
-                 plan_window: tuple = None):
+                 plan_window: tuple = None, obstacles_from_costmap: bool = False, obstacle_min_cost: int = 254,
+                 unknown_is_obstacle: bool = False):
         import torch
 
         self.torch = torch
@@ -421,13 +447,18 @@ class ShardedEpisode:
         self.slices = [slice(edges[k], edges[k + 1]) for k in range(shards) if edges[k + 1] > edges[k]]
         self.streams = concurrent_streams(len(self.slices), f"cuda:{device}")
         self.parts = []
+        od_indexes = None if od_indexes is None else np.asarray(od_indexes)
+        per_scene_od = od_indexes is not None and od_indexes.ndim == 3 and od_indexes.shape[0] > 1
         for sl, st in zip(self.slices, self.streams):
             idx = np.arange(sl.start, sl.stop)
+            odi, odo = (od_indexes[idx], np.asarray(od_origin)[idx]) if per_scene_od else (od_indexes, od_origin)
             with torch.cuda.stream(st):  # the shard's solver handle binds to the stream current at construction
                 self.parts.append(BatchEpisode(
-                    params, scenes.select(idx), np.asarray(w_ref)[idx], od_indexes, od_origin, od_resolution, device=device,
+                    params, scenes.select(idx), np.asarray(w_ref)[idx], odi, odo, od_resolution, device=device,
                     plan=None if plan is None else plan[idx], plan_len=None if plan_len is None else plan_len[idx],
-                    traj_params=traj_params, fov_angle=fov_angle, order_hint=order_hint, plan_window=plan_window))
+                    traj_params=traj_params, fov_angle=fov_angle, order_hint=order_hint, plan_window=plan_window,
+                    obstacles_from_costmap=obstacles_from_costmap, obstacle_min_cost=obstacle_min_cost,
+                    unknown_is_obstacle=unknown_is_obstacle))
         self.B = B
         self.graphs = graphs
         for part in self.parts:  # every shard's persistent solve grid takes its share of the resident wavefronts

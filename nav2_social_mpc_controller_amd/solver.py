@@ -12,8 +12,8 @@ import os
 import numpy as np
 
 from . import _abi
-from ._abi import (SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcParams, SmpcPeopleBatch, SmpcPlanWindowBatch,
-                   SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
+from ._abi import (SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcObstacleDistanceIn, SmpcObstacleDistanceOut,
+                   SmpcParams, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
 from .params import OptimizerParams, TrajectorizerParams
 from .scenes import SceneBatch
 
@@ -64,6 +64,8 @@ def load_library():
     lib.smpc_eval_batch.restype = C.c_int
     lib.smpc_project_people_batch.argtypes = [C.c_void_p, C.POINTER(SmpcProjectionBatch), C.c_void_p, C.c_void_p]
     lib.smpc_project_people_batch.restype = C.c_int
+    lib.smpc_obstacle_distance_batch.argtypes = [C.c_void_p, C.POINTER(SmpcObstacleDistanceIn), C.POINTER(SmpcObstacleDistanceOut)]
+    lib.smpc_obstacle_distance_batch.restype = C.c_int
     lib.smpc_people_to_status_batch.argtypes = [C.c_void_p, C.POINTER(SmpcPeopleBatch), C.c_void_p, C.c_void_p]
     lib.smpc_people_to_status_batch.restype = C.c_int
     lib.smpc_format_to_optimize_batch.argtypes = [C.c_void_p, C.POINTER(SmpcFormatBatch), C.POINTER(SmpcFormatOut)]
@@ -238,6 +240,49 @@ class BatchSolver:
         _check(self.lib, self.lib.smpc_project_people_batch(self._h, C.byref(pb), out.ctypes.data, err.ctypes.data),
                "smpc_project_people_batch")
         return out, err
+
+    # -- the ObstacleDistance grid of the projection, from the costmaps (smpc_obstacle_distance_batch) -----------
+    @staticmethod
+    def obstacle_distance_c(B: int, size_x: int, size_y: int, costmap_shared: bool, resolution: float, on_device: int,
+                            obstacle_min_cost: int = 254, unknown_is_obstacle: bool = False) -> SmpcObstacleDistanceIn:
+        ob = SmpcObstacleDistanceIn()
+        ob.B, ob.size_x, ob.size_y, ob.on_device = int(B), int(size_x), int(size_y), int(on_device)
+        ob.costmap_shared = 1 if costmap_shared else 0
+        if not 1 <= int(obstacle_min_cost) <= 255:
+            raise SmpcError(f"obstacle_min_cost must be 1..255, got {obstacle_min_cost}")
+        ob.obstacle_min_cost, ob.unknown_is_obstacle = int(obstacle_min_cost), 1 if unknown_is_obstacle else 0
+        ob.resolution = float(resolution)
+        return ob
+
+    def obstacle_distance(self, costmap: np.ndarray, resolution: float, obstacle_min_cost: int = 254,
+                          unknown_is_obstacle: bool = False, distances: bool = True):
+        """costmap [B,H,W] uint8 (one grid per scene) or [H,W] (one shared grid). Returns dict(indexes [..,H,W] uint32,
+        distances [..,H,W] float32 or None, n_obstacles [B or 1] int32): the exact nearest-obstacle transform of
+        include/smpc.h, shaped like `costmap`."""
+        costmap = np.ascontiguousarray(costmap, np.uint8)
+        shared = costmap.ndim == 2
+        cm = costmap[None] if shared else costmap
+        G, H, W = cm.shape
+        ob = self.obstacle_distance_c(G, W, H, shared, resolution, 0, obstacle_min_cost, unknown_is_obstacle)
+        ob.costmap = cm.ctypes.data if cm.size else None
+        out = {"indexes": np.zeros(cm.shape, np.uint32), "distances": np.zeros(cm.shape, np.float32) if distances else None,
+               "n_obstacles": np.zeros(G, np.int32)}
+        oo = SmpcObstacleDistanceOut()
+        oo.indexes, oo.n_obstacles = out["indexes"].ctypes.data, out["n_obstacles"].ctypes.data
+        oo.distances = out["distances"].ctypes.data if distances else None
+        _check(self.lib, self.lib.smpc_obstacle_distance_batch(self._h, C.byref(ob), C.byref(oo)), "smpc_obstacle_distance_batch")
+        if shared:
+            out["indexes"] = out["indexes"][0]
+            out["distances"] = None if out["distances"] is None else out["distances"][0]
+        return out
+
+    def obstacle_distance_device(self, ob: SmpcObstacleDistanceIn, indexes_ptr: int, distances_ptr: int = 0,
+                                 n_obstacles_ptr: int = 0):
+        """Device pointers in and out (ob.on_device == 1), asynchronous on the handle's stream."""
+        assert ob.on_device == 1
+        oo = SmpcObstacleDistanceOut()
+        oo.indexes, oo.distances, oo.n_obstacles = indexes_ptr or None, distances_ptr or None, n_obstacles_ptr or None
+        _check(self.lib, self.lib.smpc_obstacle_distance_batch(self._h, C.byref(ob), C.byref(oo)), "smpc_obstacle_distance_batch")
 
     # -- initial-guess generator (SURVEY §8 row f3): PathTrajectorizer::trajectorize for B plans ------------------
     @staticmethod

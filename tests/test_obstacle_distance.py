@@ -1,0 +1,350 @@
+"""The ObstacleDistance grid computed from the costmaps (smpc_obstacle_distance_batch, csrc/smpc_distance.hpp): an exact
+Euclidean nearest-obstacle transform, ties to the smallest linear index. The checker below states that contract by brute
+force; the kernel must match it bit for bit, and its grid must drive people projection and the closed-loop episode the
+way a host-built grid does."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from nav2_social_mpc_controller_amd import _abi
+from nav2_social_mpc_controller_amd import solver as S
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "smpc.h")
+
+
+# ---- the checker -------------------------------------------------------------------------------------------------------
+def obstacle_mask(costmap, min_cost=254, unknown_is_obstacle=False):
+    c = np.asarray(costmap)
+    return (c >= min_cost) & ((c != 255) | bool(unknown_is_obstacle))
+
+
+def checker(costmap, resolution, min_cost=254, unknown_is_obstacle=False):
+    """One grid [H,W] -> (indexes uint32, distances float32, n_obstacles): for every cell the obstacle minimising
+    (dx^2 + dy^2, ox + oy * W) lexicographically; no obstacle: index W * H, distance +inf."""
+    H, W = costmap.shape
+    mask = obstacle_mask(costmap, min_cost, unknown_is_obstacle)
+    n_obs = int(mask.sum())
+    if n_obs == 0:
+        return np.full((H, W), W * H, np.uint32), np.full((H, W), np.inf, np.float32), 0
+    # candidates: obstacle cells with a free 4-neighbour (or the grid edge). An obstacle whose four neighbours are all
+    # obstacles is never the lexicographic minimum of a free cell: its neighbour towards that cell is strictly nearer.
+    # Obstacle cells themselves are at d2 = 0 from themselves only.
+    pad = np.pad(mask, 1, constant_values=False)
+    inner = pad[:-2, 1:-1] & pad[2:, 1:-1] & pad[1:-1, :-2] & pad[1:-1, 2:]
+    obs = np.flatnonzero((mask & ~inner).reshape(-1))
+    ox, oy = obs % W, obs // W
+    cells = np.arange(H * W)
+    cx, cy = cells % W, cells // W
+    idx = np.empty(H * W, np.int64)
+    d2 = np.empty(H * W, np.int64)
+    step = max(1, (1 << 22) // obs.size)
+    for a in range(0, H * W, step):
+        dd = (cx[a:a + step, None] - ox[None]) ** 2 + (cy[a:a + step, None] - oy[None]) ** 2
+        key = dd * (W * H) + obs[None]          # lexicographic (d2, index): index < W * H
+        k = key.min(axis=1)
+        d2[a:a + step], idx[a:a + step] = k // (W * H), k % (W * H)
+    self_ = mask.reshape(-1)
+    idx[self_], d2[self_] = cells[self_], 0
+    dist = (np.sqrt(d2.astype(np.float64)) * np.float64(np.float32(resolution))).astype(np.float32)
+    return idx.astype(np.uint32).reshape(H, W), dist.reshape(H, W), n_obs
+
+
+def checker_batch(costmaps, resolution, **kw):
+    outs = [checker(c, resolution, **kw) for c in costmaps]
+    return np.stack([o[0] for o in outs]), np.stack([o[1] for o in outs]), np.array([o[2] for o in outs], np.int32)
+
+
+def random_map(rng, H, W, density=0.02, values=(254,)):
+    cm = np.zeros((H, W), np.uint8)
+    m = rng.uniform(size=(H, W)) < density
+    cm[m] = rng.choice(np.asarray(values, np.uint8), size=int(m.sum()))
+    return cm
+
+
+# ---- CPU ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed,H,W,density", [(1, 40, 40, 0.01), (2, 37, 61, 0.05), (3, 64, 17, 0.002), (4, 25, 25, 0.3)])
+def test_checker_distances_match_scipy(seed, H, W, density):
+    ndimage = pytest.importorskip("scipy.ndimage")
+    rng = np.random.default_rng(seed)
+    cm = random_map(rng, H, W, density)
+    cm[rng.integers(H), rng.integers(W)] = 254   # at least one obstacle
+    idx, dist, n = checker(cm, 1.0)
+    want = ndimage.distance_transform_edt(~obstacle_mask(cm))
+    assert n == int(obstacle_mask(cm).sum())
+    assert np.array_equal(dist, want.astype(np.float32))
+    # the index points at an obstacle at exactly that distance
+    oy, ox = idx // W, idx % W
+    yy, xx = np.mgrid[0:H, 0:W]
+    assert obstacle_mask(cm)[oy, ox].all()
+    assert np.allclose(np.sqrt((xx - ox) ** 2 + (yy - oy) ** 2), want, rtol=0, atol=1e-12)
+
+
+def test_checker_tie_rule_and_empty_grid():
+    cm = np.zeros((5, 5), np.uint8)
+    cm[2, 0] = cm[2, 4] = cm[0, 2] = 254                     # (2, 2) is 2 cells from all three
+    idx, dist, n = checker(cm, 0.5)
+    assert n == 3 and idx[2, 2] == 2 + 0 * 5                  # smallest linear index wins: (x 2, y 0)
+    assert idx[2, 0] == 10 and dist[2, 0] == 0.0              # an obstacle points at itself
+    idx, dist, n = checker(np.zeros((3, 4), np.uint8), 0.5)
+    assert n == 0 and (idx == 12).all() and np.isinf(dist).all()
+
+
+def test_obstacle_distance_symbol_is_declared_and_exported():
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    assert re.search(r"\bint\s+smpc_obstacle_distance_batch\s*\(", src)
+    assert "smpc_obstacle_distance_batch" in _abi.EXPORTED_SYMBOLS
+    assert os.path.exists(S.LIB_PATH), "run __graft_entry__.build() first"
+    out = subprocess.check_output(["nm", "-D", "--defined-only", S.LIB_PATH], text=True)
+    assert "smpc_obstacle_distance_batch" in {line.split()[-1] for line in out.splitlines() if line.strip()}
+
+
+def test_obstacle_distance_struct_layouts_match_the_c_header(tmp_path):
+    probes = [("smpc_obstacle_distance_in", _abi.SmpcObstacleDistanceIn, "costmap_shared"),
+              ("smpc_obstacle_distance_in", _abi.SmpcObstacleDistanceIn, "unknown_is_obstacle"),
+              ("smpc_obstacle_distance_in", _abi.SmpcObstacleDistanceIn, "resolution"),
+              ("smpc_obstacle_distance_out", _abi.SmpcObstacleDistanceOut, "n_obstacles")]
+    body = "".join(f'printf("%zu %zu\\n", sizeof({c}), offsetof({c}, {f}));\n' for c, _, f in probes)
+    prog = tmp_path / "layout_od.c"
+    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "smpc.h"\nint main(void){\n' + body + 'return 0;}\n')
+    exe = tmp_path / "layout_od"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
+    for (cname, py, field), line in zip(probes, subprocess.check_output([str(exe)], text=True).splitlines()):
+        size, off = (int(v) for v in line.split())
+        assert size == C.sizeof(py) and off == getattr(py, field).offset, (cname, field)
+
+
+# ---- GPU: the kernel against the checker ----------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def solver():
+    from nav2_social_mpc_controller_amd.params import OptimizerParams
+    return S.BatchSolver(OptimizerParams.readme())
+
+
+def assert_equal_to_checker(got, costmaps, resolution, **kw):
+    idx, dist, n = checker_batch(costmaps, resolution, **kw)
+    assert np.array_equal(got["indexes"].reshape(idx.shape), idx)
+    if got["distances"] is not None:
+        assert np.array_equal(got["distances"].reshape(dist.shape).view(np.uint32), dist.view(np.uint32))
+    assert np.array_equal(got["n_obstacles"], n)
+
+
+@pytest.mark.gpu
+def test_gpu_random_scene_costmaps(solver):
+    from nav2_social_mpc_controller_amd.params import OptimizerParams
+    from nav2_social_mpc_controller_amd.scenes import make_scenes
+    sc = make_scenes(OptimizerParams.readme(), 64, 3, map_cells=200)
+    got = solver.obstacle_distance(sc.costmap, sc.resolution)
+    assert_equal_to_checker(got, sc.costmap, sc.resolution)
+    assert (got["n_obstacles"] > 0).all()
+
+
+@pytest.mark.gpu
+def test_gpu_empty_full_and_single_obstacle_maps(solver):
+    H, W = 48, 48
+    maps = np.zeros((5, H, W), np.uint8)
+    maps[1] = 254                                   # all obstacles
+    maps[2, 17, 30] = 254                           # single obstacle
+    maps[3, 0, 0] = 255                             # only an unknown cell: no obstacle by default
+    maps[4, H - 1, W - 1] = 254                     # single obstacle in the far corner
+    got = solver.obstacle_distance(maps, 0.05)
+    assert_equal_to_checker(got, maps, 0.05)
+    assert (got["indexes"][0] == H * W).all() and np.isinf(got["distances"][0]).all() and got["n_obstacles"][0] == 0
+    assert (got["indexes"][1].reshape(-1) == np.arange(H * W)).all() and (got["distances"][1] == 0).all()
+    assert (got["indexes"][2] == 30 + 17 * W).all()
+    assert got["n_obstacles"].tolist() == [0, H * W, 1, 0, 1]
+
+
+@pytest.mark.gpu
+def test_gpu_symmetric_ties_go_to_the_smallest_index(solver):
+    H, W = 41, 41
+    maps = np.zeros((4, H, W), np.uint8)
+    maps[0, 20, 0] = maps[0, 20, 40] = maps[0, 0, 20] = maps[0, 40, 20] = 254        # a plus: centre equidistant
+    maps[1, 0, 0] = maps[1, 0, 40] = maps[1, 40, 0] = maps[1, 40, 40] = 254          # four corners
+    yy, xx = np.mgrid[0:H, 0:W]
+    maps[2][(xx - 20) ** 2 + (yy - 20) ** 2 == 225] = 254                           # a ring of radius 15 (3-4-5 points)
+    maps[3][::8, ::8] = 254                                                          # a lattice: ties everywhere
+    got = solver.obstacle_distance(maps, 0.1)
+    assert_equal_to_checker(got, maps, 0.1)
+    assert got["indexes"][0, 20, 20] == 20 and got["indexes"][1, 20, 20] == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W,density", [(37, 211, 0.01), (211, 37, 0.01), (1, 1, 0.0), (1, 1, 1.0), (1, 300, 0.01),
+                                         (300, 1, 0.01), (512, 512, 0.0005)])
+def test_gpu_non_square_and_extreme_sizes(solver, H, W, density):
+    rng = np.random.default_rng(H * 1000 + W)
+    maps = np.stack([random_map(rng, H, W, density) for _ in range(2)])
+    if density == 1.0:
+        maps[:] = 254
+    got = solver.obstacle_distance(maps, 0.05)
+    assert_equal_to_checker(got, maps, 0.05)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("min_cost", [253, 254])
+@pytest.mark.parametrize("unknown", [False, True])
+def test_gpu_obstacle_threshold_and_unknown_cells(solver, min_cost, unknown):
+    rng = np.random.default_rng(min_cost + 2 * unknown)
+    maps = np.stack([random_map(rng, 60, 80, 0.01, values=(252, 253, 254, 255)) for _ in range(6)])
+    maps[5] = 0
+    maps[5, 30, 40] = 255                           # nothing but an unknown cell
+    got = solver.obstacle_distance(maps, 0.05, obstacle_min_cost=min_cost, unknown_is_obstacle=unknown)
+    assert_equal_to_checker(got, maps, 0.05, min_cost=min_cost, unknown_is_obstacle=unknown)
+    assert got["n_obstacles"][5] == (1 if unknown else 0)
+
+
+@pytest.mark.gpu
+def test_gpu_shared_costmap_device_pointers_and_no_distances(solver):
+    import torch
+    from nav2_social_mpc_controller_amd.params import OptimizerParams
+    from nav2_social_mpc_controller_amd.scenes import make_scenes
+    sc = make_scenes(OptimizerParams.readme(), 8, 3, map_cells=120)
+    want_idx, want_dist, want_n = checker_batch(sc.costmap, sc.resolution)
+    # shared costmap (host pointers): one output grid
+    one = solver.obstacle_distance(sc.costmap[3], sc.resolution)
+    assert one["indexes"].shape == (120, 120) and np.array_equal(one["indexes"], want_idx[3])
+    assert np.array_equal(one["distances"], want_dist[3]) and one["n_obstacles"].tolist() == [want_n[3]]
+    # distances = NULL: the same indexes
+    got = solver.obstacle_distance(sc.costmap, sc.resolution, distances=False)
+    assert got["distances"] is None and np.array_equal(got["indexes"], want_idx)
+    # device pointers, per-scene and shared
+    dev = "cuda:0"
+    cm = torch.from_numpy(sc.costmap).to(dev)
+    for shared in (False, True):
+        G = 1 if shared else sc.B
+        idx = torch.full((G, 120, 120), -1, dtype=torch.int32, device=dev)
+        dist = torch.zeros((G, 120, 120), dtype=torch.float32, device=dev)
+        n = torch.zeros(G, dtype=torch.int32, device=dev)
+        ob = S.BatchSolver.obstacle_distance_c(sc.B, 120, 120, shared, sc.resolution, 1)
+        ob.costmap = cm.data_ptr()
+        solver.obstacle_distance_device(ob, idx.data_ptr(), dist.data_ptr(), n.data_ptr())
+        torch.cuda.synchronize()
+        assert np.array_equal(idx.cpu().numpy().view(np.uint32), want_idx[:G])
+        assert np.array_equal(dist.cpu().numpy(), want_dist[:G]) and np.array_equal(n.cpu().numpy(), want_n[:G])
+        idx.fill_(-1)
+        solver.obstacle_distance_device(ob, idx.data_ptr())   # indexes only
+        torch.cuda.synchronize()
+        assert np.array_equal(idx.cpu().numpy().view(np.uint32), want_idx[:G])
+
+
+@pytest.mark.gpu
+def test_gpu_bad_arguments_are_refused(solver):
+    cm = np.zeros((1, 10, 10), np.uint8)
+    with pytest.raises(S.SmpcError):
+        solver.obstacle_distance(np.zeros((1, 0, 10), np.uint8), 0.05)        # empty grid
+    with pytest.raises(S.SmpcError):
+        solver.obstacle_distance(cm, 0.05, obstacle_min_cost=0)
+    with pytest.raises(S.SmpcError):
+        solver.obstacle_distance(cm, 0.0)
+    ob = S.BatchSolver.obstacle_distance_c(1, 10, 10, False, 0.05, 0)
+    ob.costmap = cm.ctypes.data
+    oo = _abi.SmpcObstacleDistanceOut()                                          # no indexes buffer
+    assert solver.lib.smpc_obstacle_distance_batch(solver._h, C.byref(ob), C.byref(oo)) == -1
+    big = np.zeros((1, 2, 5000), np.uint8)
+    with pytest.raises(S.SmpcError):
+        solver.obstacle_distance(big, 0.05)                                      # wider than 4096 columns
+
+
+# ---- the chain: the kernel's grid drives the Social Force Model's obstacle force --------------------------------------
+def chain_case(map_cells, B=12):
+    """Scenes whose people stand next to the costmap's discs: every person is moved to 0.15-0.4 m beside a random obstacle
+    cell. Returns (scenes, init_people [B,N,6], robot_path [B,T+1,6])."""
+    from nav2_social_mpc_controller_amd.params import OptimizerParams
+    from nav2_social_mpc_controller_amd.scenes import make_scenes
+    prm = OptimizerParams.readme()
+    sc = make_scenes(prm, B, 3, map_cells=map_cells, standing_fraction=0.3, seed=0x0B57AC1E)
+    rng = np.random.default_rng(map_cells)
+    init = sc.people[:, 0].transpose(0, 2, 1).copy()                       # [B,N,6]
+    for b in range(B):
+        oy, ox = np.nonzero(sc.costmap[b] >= 254)
+        for a in range(init.shape[1]):
+            k = rng.integers(len(ox))
+            ang, r = rng.uniform(-np.pi, np.pi), rng.uniform(0.15, 0.4)
+            init[b, a, 0] = sc.costmap_origin[b, 0] + (ox[k] + 0.5) * sc.resolution + r * np.cos(ang)
+            init[b, a, 1] = sc.costmap_origin[b, 1] + (oy[k] + 0.5) * sc.resolution + r * np.sin(ang)
+    T, dt = sc.T, sc.dt
+    path = np.zeros((B, T + 1, 6))
+    path[:, :, 0:2] = sc.path_pts
+    d = np.diff(sc.path_pts, axis=1)
+    path[:, :-1, 2] = np.arctan2(d[..., 1], d[..., 0])
+    path[:, -1, 2] = path[:, -2, 2]
+    path[:, :, 3] = np.arange(T + 1) * dt
+    path[:, :, 4] = 0.6
+    return prm, sc, init, path
+
+
+@pytest.mark.gpu
+def test_chain_projection_on_the_kernel_grid_matches_the_checker_grid(solver):
+    from nav2_social_mpc_controller_amd.episode import far_obstacle_grid
+    from oracle import pyref_sfm
+    prm, sc, init, path = chain_case(200)
+    res = float(np.float32(sc.resolution))
+    grid = solver.obstacle_distance(sc.costmap, sc.resolution, distances=False)["indexes"]
+    want_idx = checker_batch(sc.costmap, sc.resolution)[0]
+    assert np.array_equal(grid, want_idx)
+    got, err = solver.project_people(init, path, grid, sc.costmap_origin, res, prm.max_time, prm.time_step)
+    assert (err == 0).sum() >= len(err) - 2
+    far = np.stack([far_obstacle_grid(200, sc.resolution, o)[0] for o in sc.costmap_origin])
+    gfar, efar = solver.project_people(init, path, far, sc.costmap_origin, res, prm.max_time, prm.time_step)
+    n_checked = 0
+    for b in np.flatnonzero(err == 0):
+        od = dict(width=200, height=200, resolution=res, origin_x=sc.costmap_origin[b, 0], origin_y=sc.costmap_origin[b, 1],
+                  indexes=want_idx[b])
+        want = pyref_sfm.project_people(init[b], path[b], od, prm.max_time, prm.time_step, theta_zero_convention=True)
+        assert np.max(np.abs(got[b].transpose(0, 2, 1) - want)) < 1e-9, b
+        n_checked += 1
+    assert n_checked >= 8
+    live = (err == 0) & (efar == 0)
+    # the obstacle force is live: people next to walls move differently from the run whose grid points far away (by
+    # centimetres to a metre where the wall is in their way; where it is behind them the force decays within steps)
+    diff = np.abs(got[live, 1:, 0:2] - gfar[live, 1:, 0:2]).max(axis=(1, 2, 3))
+    assert diff.max() > 0.1 and (diff > 1e-5).sum() >= 3, diff
+
+
+@pytest.mark.gpu
+def test_chain_100x100_costmap_keeps_the_grid_not_valid_quirk(solver):
+    prm, sc, init, path = chain_case(100, B=4)
+    grid = solver.obstacle_distance(sc.costmap, sc.resolution, distances=False)["indexes"]
+    assert grid.shape == (4, 100, 100) and (grid < 100 * 100).all()
+    got, err = solver.project_people(init, path, grid, sc.costmap_origin, float(np.float32(sc.resolution)), prm.max_time,
+                                     prm.time_step)
+    assert (err == 0).all() and np.all(got[:, 1:, 3, :] == -1.0)   # "NOT valid" grid (src/optimizer.cpp:598-603)
+
+
+@pytest.mark.gpu
+def test_chain_empty_costmap_reports_index_out_of_bounds(solver):
+    prm, sc, init, path = chain_case(120, B=2)
+    cm = sc.costmap.copy()
+    cm[1] = 0
+    grid = solver.obstacle_distance(cm, sc.resolution, distances=False)["indexes"]
+    _, err = solver.project_people(init, path, grid, sc.costmap_origin, float(np.float32(sc.resolution)), prm.max_time,
+                                   prm.time_step)
+    assert err[1] == 2                                               # SMPC_PROJ_INDEX_OUT_OF_BOUNDS (the reference throws)
+
+
+# ---- the episode ----------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_episode_obstacles_from_costmap_equals_the_checker_grid():
+    from nav2_social_mpc_controller_amd.episode import BatchEpisode
+    from nav2_social_mpc_controller_amd.params import OptimizerParams
+    from nav2_social_mpc_controller_amd.scenes import make_scenes, uniform
+    prm = OptimizerParams.readme()
+    B = 16
+    sc = make_scenes(prm, B, 3, map_cells=400, n_valid=2)         # 20 m maps: the crowd stays inside for the episode
+    w_ref = (uniform(0x5EED0001, np.arange(B), 6)[:, 0] * 2.0 - 1.0) * 0.6
+    want_idx = checker_batch(sc.costmap, sc.resolution)[0]
+    ep_k = BatchEpisode(prm, sc, w_ref, obstacles_from_costmap=True)
+    ep_c = BatchEpisode(prm, sc, w_ref, want_idx, sc.costmap_origin, float(np.float32(sc.resolution)))
+    assert np.array_equal(ep_k.od_indexes.cpu().numpy().view(np.uint32), want_idx)
+    for tick in range(3):
+        rk, rc = ep_k.tick(record=True), ep_c.tick(record=True)
+        assert (rk.proj_error == 0).all(), tick
+        assert np.array_equal(rk.people_proj, rc.people_proj), tick
+        for k in ("cmds", "status", "path"):
+            assert np.array_equal(rk.result[k], rc.result[k]), (tick, k)
+        assert np.array_equal(ep_k.pose.cpu().numpy(), ep_c.pose.cpu().numpy())
