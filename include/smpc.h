@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMPC_ABI_VERSION 5
+#define SMPC_ABI_VERSION 6
 #define SMPC_MAX_BLOCKS 10 /* nb <= 10  => P <= 20; every nb in 1..10 is instantiated */
 #define SMPC_MAX_LM_ITERATIONS 100000 /* smpc_create refuses a larger max_iterations: a persistent wave must reach its exit */
 #define SMPC_MAX_STEPS 63  /* T <= 63: one lane per pose of the rollout (T + 1 poses in a 64-lane wavefront) */
@@ -110,6 +110,16 @@ typedef struct smpc_params {
 /* Fill with the reference's code defaults (src/optimizer.cpp:26-82) and hard-coded literals. */
 void smpc_params_default(smpc_params* p);
 
+/* Per-scene values of the fields of smpc_params with the same names (smpc_scene_batch.scene_params): the nine critic
+ * weights, the velocity critic's target speed and the bounds of the bounded parameter blocks. Everything else — horizon,
+ * block length, tolerances, iteration cap, linear solver — stays the handle's, since it shapes the problem or the loop. */
+typedef struct smpc_scene_params {
+  double distance_w, socialwork_w, velocity_w, angle_w, agent_angle_w, proxemics_w, velocity_feasibility_w,
+         obstacle_w, goal_align_w;
+  double desired_linear_vel;
+  double v_min, v_max, w_min, w_max;
+} smpc_scene_params;
+
 /* One batch of independent scenes. All scenes share T, N, dt, costmap geometry.
  * Row layout of every scene: 8 rows per step when the scene has people, 5 when it has none (has_people[i] == 0),
  * plus the feasibility rows; output arrays of smpc_eval_batch are always strided by M = 8 T + n_feasibility (the
@@ -161,6 +171,13 @@ typedef struct smpc_scene_batch {
    * T_scene[b] < 1 (a path of fewer than two poses, for which Optimizer::optimize returns false, :158-162): status
    * SMPC_FAILURE with reason SMPC_REASON_SHORT_PATH. NULL: every scene has T steps. */
   const int32_t* T_scene; /* [B] */
+
+  /* Optional: the critic weights and velocity bounds of each scene (smpc_solve_batch and smpc_eval_batch). Scene b is
+   * solved / evaluated exactly — bit for bit — as a handle whose smpc_params held row b's 14 values (and this handle's
+   * values of every other field) would solve / evaluate it in the same batch. Host arrays are checked: every value
+   * finite, v_min <= v_max and w_min <= w_max (else SMPC_ERR_INVALID_ARG, nothing launched); device arrays are the
+   * caller's responsibility, like order and T_scene. NULL: every scene takes the handle's values. */
+  const smpc_scene_params* scene_params; /* [B] */
 } smpc_scene_batch;
 
 #define SMPC_NO_TARGET 1e300 /* people_aux: AgentAngleCost is inactive at this step */

@@ -6,7 +6,7 @@ Struct layouts must stay in lock-step with include/smpc.h (checked by tests/test
 """
 import ctypes as C
 
-SMPC_ABI_VERSION = 5
+SMPC_ABI_VERSION = 6
 SMPC_MAX_BLOCKS = 10
 
 # enum smpc_linear_solver (mirrors OptimizerParams::solver_types, reference optimizer.hpp:71-77)
@@ -55,6 +55,16 @@ class SmpcParams(C.Structure):
     ]
 
 
+# smpc_scene_params: per-scene values of the SmpcParams fields with the same names (smpc_scene_batch.scene_params)
+SCENE_PARAM_FIELDS = ("distance_w", "socialwork_w", "velocity_w", "angle_w", "agent_angle_w", "proxemics_w",
+                      "velocity_feasibility_w", "obstacle_w", "goal_align_w", "desired_linear_vel",
+                      "v_min", "v_max", "w_min", "w_max")
+
+
+class SmpcSceneParams(C.Structure):
+    _fields_ = [(f, C.c_double) for f in SCENE_PARAM_FIELDS]
+
+
 class SmpcSceneBatch(C.Structure):
     _fields_ = [
         ("B", C.c_int32),
@@ -78,6 +88,7 @@ class SmpcSceneBatch(C.Structure):
         ("people_aux", C.c_void_p),
         ("order", C.c_void_p),
         ("T_scene", C.c_void_p),
+        ("scene_params", C.c_void_p),
     ]
 
 

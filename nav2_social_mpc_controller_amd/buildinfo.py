@@ -8,7 +8,7 @@ import hashlib
 import os
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-SOURCE_SUFFIXES = (".hpp", ".hip", ".h", ".sh")
+SOURCE_SUFFIXES = (".hpp", ".hip", ".inc", ".h", ".sh")
 
 
 def csrc_digest(root: str = CSRC) -> str:

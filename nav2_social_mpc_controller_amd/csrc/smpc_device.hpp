@@ -75,6 +75,7 @@ struct KParams {
   int e_row_order;  // 0: reference (step-major) row order, 1: critic-major (smpc_eval_batch_out.row_order)
   MathTab mt;  // polynomial coefficients of smpc_math.hpp, read through scalar loads
   AtanNodeTab an;  // nodes of atan2_unit(), copied into LDS by every wave (load_atan_nodes)
+  const smpc_scene_params* scene_params;  // [B] per-scene weights / bounds (smpc_scene_batch.scene_params): the sp kernels
 };
 
 // Cross-lane sum of the per-lane Gram shares (solve kernel): values go through LDS in chunks of whole columns of the
@@ -110,6 +111,7 @@ struct LdsLayout {
   int part;     // [T][kPart] helper lanes only: the partial sums a helper hands to the owner lane of a step
   int hz;       // [4]        the scene's own horizon (kernels with per-scene T): ints T, CH, bl, last block, feasibility
                 //            rows, bounded blocks
+  int sp;       // [14]       sp kernels only: the scene's smpc_scene_params row (weights, target speed, bounds)
   int lanec;    // [3][T]     per step: path point x, y (path_pts[t+1]) and agent-angle target (kNoTarget = none)
   int lm;       // LM vectors / matrices / scalars
   int gram;     // [(P+1)^2] Gram [J r]^T [J r] of the latest sweep, dense and symmetric
@@ -141,8 +143,11 @@ __host__ __device__ inline int helper_owner_agents(int T, int N, int W) {
   return ((N - A) * 250 > 2 * (60 * U + 120)) ? A : N;
 }
 
+constexpr int kSceneParamDoubles = sizeof(smpc_scene_params) / sizeof(double);  // 14
+
 // W: the slot width of the kernel the layout is for (32: two scenes per wave, 64: one; slot_width() / solve_slot_width())
-__host__ __device__ inline LdsLayout make_layout(int T, int N, int P, int kind, int W) {
+// sp: the layout of the sp kernels (per-scene weights and bounds, smpc_scene_batch.scene_params): 14 doubles more per slot
+__host__ __device__ inline LdsLayout make_layout(int T, int N, int P, int kind, int W, bool sp = false) {
   LdsLayout L;
   const bool with_lm = kind == kLayoutSolve;
   int o = 0;
@@ -156,6 +161,7 @@ __host__ __device__ inline LdsLayout make_layout(int T, int N, int P, int kind, 
   }
   L.cst = o; o += 8;
   L.hz = o; o += 4;
+  L.sp = o; if (sp) o += kSceneParamDoubles;
   L.stepst = o; L.part = o;
   if (kind != kLayoutStage && helper_owner_agents(T, N, W) < N) { o += 4 * T; L.part = o; o += kPart * T; }
   L.lanec = o; o += 3 * T;
@@ -656,10 +662,12 @@ __device__ inline int block_end(int b, const Horizon& h) {
 // Load the slot's scene constants and the per-step side data of its staged people block (valid masks, agent-angle
 // tags) into LDS; the records themselves stay in global memory (c.ag). Executed by all W lanes of the slot (other
 // slots may be masked off).
-template <int W, bool kVT = false>
+template <int W, bool kVT = false, bool kSP = false>
 __device__ inline void load_scene(Ctx& c, int scene) {
   const auto& k = *c.kp;
   const int T = k.T, N = k.N, sl = c.sl;
+  if (kSP && sl < kSceneParamDoubles)  // the scene's row of smpc_scene_params, one value per lane
+    (c.lds + c.L.sp)[sl] = reinterpret_cast<const double*>(k.scene_params + scene)[sl];
   int Th = T;  // the scene's own horizon
   if (kVT) {
     const int Traw = k.T_scene ? k.T_scene[scene] : T;
@@ -701,6 +709,12 @@ __device__ inline void load_scene(Ctx& c, int scene) {
   }
 }
 
+// A field of smpc_scene_params where it is used: the slot's own row in LDS (kSP, the sp kernels: written by load_scene();
+// with two scenes per wave the two halves hold different rows, so the value is a per-lane operand, read at each use rather
+// than held in registers through the sweep) or `prm`, the handle's smpc_params (a launch constant, scalar loads).
+#define SMPC_SCENE_PRM(c, kSP, prm, field) \
+  ((kSP) ? (c).lds[(c).L.sp + offsetof(smpc_scene_params, field) / sizeof(double)] : (prm).field)
+
 // ------------------------------------------------------------------------------------------------
 // The sweep (kernel K1's body): residuals + Jacobian rows + Gram at the slot's parameters xp[P] (LDS or global,
 // slot-uniform). All 64 lanes of the wave call it together (each slot on its own scene). The Gram is returned
@@ -717,7 +731,7 @@ __device__ inline void load_scene(Ctx& c, int scene) {
 // and gradient there, LineSearchFunction::Evaluate), and most sweeps of a solve are such samples. c.gram_full tells
 // the caller what it got (wave-uniform). Every entry is summed in the same order whichever way it is produced.
 struct NeedAll { __device__ inline bool operator()() const { return true; } };
-template <int NB, int W, bool kRows, bool kVT = false, class NeedRest = NeedAll>
+template <int NB, int W, bool kRows, bool kVT = false, bool kSP = false, class NeedRest = NeedAll>
 __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double* out_J, NeedRest need_rest = NeedRest()) {
   constexpr int P = 2 * NB;
   const auto& k = *c.kp;
@@ -986,7 +1000,7 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
     soc[13] += 2.0 * (vb * (-s1 * qh[2] + c1 * qh[3]));
     soc[14] += 2.0 * (c1 * qh[2] + s1 * qh[3]);
     // a3 social work: w (|sum F|^2 + sum |G|^2 + 1e-6), critics/social_work_cost_function.hpp:125-147
-    const double wsoc = k.prm.socialwork_w;
+    const double wsoc = SMPC_SCENE_PRM(c, kSP, k.prm, socialwork_w);
     const double wr = soc[0] * soc[0] + soc[1] * soc[1];
     sw_r = wsoc * (wr + soc[10] + 1e-6);
     sw_gx = wsoc * (2.0 * (soc[0] * soc[2] + soc[1] * soc[3]) + soc[11]);
@@ -1051,6 +1065,7 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
   //               same pipe: measured slower than plain VALU accumulation).
   constexpr int Q = P + 1;
   const auto& w = k.prm;
+#define SPRM(f) SMPC_SCENE_PRM(c, kSP, w, f)  // the weights and the target speed of this slot's scene
   const bool lane_live = sl < Th;
   const bool people = c.has_people;
   const int rows_per_step = people ? 8 : 5;
@@ -1115,8 +1130,8 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
       const double aa_target = (c.lds + c.L.lanec)[2 * T + tl];
       if (aa_target != kNoTarget) {
         const double ad = wrap_angle(th1 - aa_target);
-        r = w.agent_angle_w * (ad * ad);
-        gth = w.agent_angle_w * 2.0 * ad;
+        r = SPRM(agent_angle_w) * (ad * ad);
+        gth = SPRM(agent_angle_w) * 2.0 * ad;
       }
       if (kRows) emit(0, live, people, r, 0.0, 0.0, gth, 0.0);
       else {  // (a slot without people beside one with people has no steering target: r = gth = 0 already)
@@ -1137,7 +1152,7 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
     // a4 proxemics: w alpha exp(-min_a d^2 / d0^2) over valid agents
     {
       const double e = 3.0 * exp_tab(&k.mt, -pbest / (0.5 * 0.5));
-      double r = w.proxemics_w * e;
+      double r = SPRM(proxemics_w) * e;
       double gx = r * (-2.0 * pdx / (0.5 * 0.5)), gy = r * (-2.0 * pdy / (0.5 * 0.5));
       if (people && pbest == 1.7976931348623157e308) {
         // no valid agent: the reference's dual evaluation gives (-max / d0^2) = -inf and inf * 0 = NaN tangents
@@ -1156,21 +1171,21 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
   // a6 velocity
   {
     double r = 0.0, gv = 0.0;
-    if (sl < CH) { const double d = w.desired_linear_vel - vb; r = w.velocity_w * d * d; gv = -2.0 * w.velocity_w * d; }
+    if (sl < CH) { const double d = SPRM(desired_linear_vel) - vb; r = SPRM(velocity_w) * d * d; gv = -2.0 * SPRM(velocity_w) * d; }
     if (kRows) emit(o5 + 0, lane_live, true, r, 0.0, 0.0, 0.0, gv);
     else { Avv = fma(gv, gv, Avv); bv = fma(gv, r, bv); cc = fma(r, r, cc); }
   }
   // a8 goal align
   {
     const double a = wrap_angle(cst[3] - th1);
-    const double r = w.goal_align_w * a * a, gth = -2.0 * w.goal_align_w * a;
+    const double r = SPRM(goal_align_w) * a * a, gth = -2.0 * SPRM(goal_align_w) * a;
     if (kRows) emit(o5 + 1, lane_live, true, r, 0.0, 0.0, gth, 0.0);
     else { Att = fma(gth, gth, Att); bt = fma(gth, r, bt); cc = fma(r, r, cc); }
   }
   // a2 distance (path follow -> final point; path align -> point sl+1)
   {
     const double ddx = X - cst[6], ddy = Y - cst[7], q2 = ddx * ddx + ddy * ddy;
-    const double r = w.distance_w * q2 * q2, gx = 4.0 * w.distance_w * q2 * ddx, gy = 4.0 * w.distance_w * q2 * ddy;
+    const double r = SPRM(distance_w) * q2 * q2, gx = 4.0 * SPRM(distance_w) * q2 * ddx, gy = 4.0 * SPRM(distance_w) * q2 * ddy;
     if (kRows) emit(o5 + 2, lane_live, true, r, gx, gy, 0.0, 0.0);
     else {
       Axx = fma(gx, gx, Axx); Axy = fma(gx, gy, Axy); Ayy = fma(gy, gy, Ayy);
@@ -1180,7 +1195,7 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
   {
     const double* lanec = c.lds + c.L.lanec;
     const double ddx = X - lanec[tl], ddy = Y - lanec[T + tl], q2 = ddx * ddx + ddy * ddy;
-    const double r = w.angle_w * q2 * q2, gx = 4.0 * w.angle_w * q2 * ddx, gy = 4.0 * w.angle_w * q2 * ddy;
+    const double r = SPRM(angle_w) * q2 * q2, gx = 4.0 * SPRM(angle_w) * q2 * ddx, gy = 4.0 * SPRM(angle_w) * q2 * ddy;
     if (kRows) emit(o5 + 3, lane_live, true, r, gx, gy, 0.0, 0.0);
     else {
       Axx = fma(gx, gx, Axx); Axy = fma(gx, gy, Axy); Ayy = fma(gy, gy, Ayy);
@@ -1197,9 +1212,9 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
     if (patch_interior) bicubic_eval<true>(patch, k.size_x, ob_ir, ob_ic, f, dfdr, dfdc);
     else if (wide_map) bicubic_eval<false>(patch, k.size_x, ob_ir, ob_ic, f, dfdr, dfdc);
     else bicubic(c.map, k.size_x, k.size_y, ob_ir, ob_ic, f, dfdr, dfdc);  // maps narrower than one patch: byte by byte
-    const double r = w.obstacle_w * f;
-    const double gx = w.obstacle_w * dfdc * inv_res, gy = w.obstacle_w * dfdr * inv_res;
-    const double gth = w.obstacle_w * (dfdc * (-0.25 * s1) + dfdr * (0.25 * c1)) * inv_res;
+    const double r = SPRM(obstacle_w) * f;
+    const double gx = SPRM(obstacle_w) * dfdc * inv_res, gy = SPRM(obstacle_w) * dfdr * inv_res;
+    const double gth = SPRM(obstacle_w) * (dfdc * (-0.25 * s1) + dfdr * (0.25 * c1)) * inv_res;
     if (kRows) emit(o5 + 4, lane_live, true, r, gx, gy, gth, 0.0);
     else {
       Axx = fma(gx, gx, Axx); Axy = fma(gx, gy, Axy); Axt = fma(gx, gth, Axt);
@@ -1224,11 +1239,11 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
       for (int q = 1; q < NB; ++q) {
         if (q == sl) {
           const double lin = xp[2 * q] - xp[2 * q - 2], ang = xp[2 * q + 1] - xp[2 * q - 1];
-          r = w.velocity_feasibility_w * lin * lin + w.velocity_feasibility_w * ang * ang;
-          row[2 * q] = 2.0 * w.velocity_feasibility_w * lin;
-          row[2 * q - 2] = -2.0 * w.velocity_feasibility_w * lin;
-          row[2 * q + 1] = 2.0 * w.velocity_feasibility_w * ang;
-          row[2 * q - 1] = -2.0 * w.velocity_feasibility_w * ang;
+          r = SPRM(velocity_feasibility_w) * lin * lin + SPRM(velocity_feasibility_w) * ang * ang;
+          row[2 * q] = 2.0 * SPRM(velocity_feasibility_w) * lin;
+          row[2 * q - 2] = -2.0 * SPRM(velocity_feasibility_w) * lin;
+          row[2 * q + 1] = 2.0 * SPRM(velocity_feasibility_w) * ang;
+          row[2 * q - 1] = -2.0 * SPRM(velocity_feasibility_w) * ang;
         }
       }
       if (live) {
@@ -1264,7 +1279,7 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
     double* frow = c.wave_lds + c.slot * ((NB > 1 ? NB - 1 : 1) * Q);
     if (sl >= 1 && sl <= hz.nfeas) {
       const double lin = xp[2 * sl] - xp[2 * sl - 2], ang = xp[2 * sl + 1] - xp[2 * sl - 1];
-      const double wf = w.velocity_feasibility_w;
+      const double wf = SPRM(velocity_feasibility_w);
       double* fr = frow + (sl - 1) * Q;
 #pragma unroll
       for (int q = 0; q < Q; ++q) fr[q] = 0.0;
@@ -1355,6 +1370,7 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
   wave_lds_fence();  // Gram visible to every lane of the slot; the cos/sin block may be rewritten by the next sweep
   SMPC_STAMP(c, 5);
   return view;
+#undef SPRM
 }
 
 // A sweep result is usable iff every residual and Jacobian entry was finite: a non-finite entry makes the

@@ -4,9 +4,12 @@
 //   smpc_solve_kernel<NB,W>  persistent sweep engine: whole ceres::Solve-equivalent (reference
 //                            src/optimizer.cpp:241-446) per scene, LM state resident in registers / LDS for all
 //                            <= max_iterations iterations, scenes pulled from a device-side queue;
-//   smpc_eval_kernel<NB,W>   K1: one residual + Jacobian sweep, rows written to HBM (parity + roofline runs).
+//   smpc_eval_kernel<NB,W>   K1: one residual + Jacobian sweep, rows written to HBM (parity + roofline runs);
+//   smpc_solve_sp_kernel<NB,W> / smpc_eval_sp_kernel<NB,W>: the same with per-scene weights and velocity bounds
+//                            (smpc_scene_batch.scene_params) and per-scene horizons.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -132,8 +135,13 @@ namespace {
 using KernelFn = void (*)(const smpc::KParams);
 
 // vt: the batch carries a horizon per scene (smpc_scene_batch.T_scene): the instantiation that reads T, CH, bl of each
-// scene from LDS instead of taking them as launch constants
-template <int NB> KernelFn pick_w(int W, bool eval, bool vt) {
+// scene from LDS instead of taking them as launch constants. sp: the batch carries weights and bounds per scene
+// (smpc_scene_batch.scene_params): the sp kernels, which read the horizon per scene as well (T_scene or T).
+template <int NB> KernelFn pick_w(int W, bool eval, bool vt, bool sp) {
+  if (sp) {
+    if (W == 32) return eval ? smpc::smpc_eval_sp_kernel<NB, 32> : smpc::smpc_solve_sp_kernel<NB, 32>;
+    return eval ? smpc::smpc_eval_sp_kernel<NB, 64> : smpc::smpc_solve_sp_kernel<NB, 64>;
+  }
   if (vt) {
     if (W == 32) return eval ? smpc::smpc_eval_kernel<NB, 32, true> : smpc::smpc_solve_kernel<NB, 32, true>;
     return eval ? smpc::smpc_eval_kernel<NB, 64, true> : smpc::smpc_solve_kernel<NB, 64, true>;
@@ -142,21 +150,21 @@ template <int NB> KernelFn pick_w(int W, bool eval, bool vt) {
   return eval ? smpc::smpc_eval_kernel<NB, 64> : smpc::smpc_solve_kernel<NB, 64>;
 }
 
-KernelFn pick(int nb, int W, bool eval, bool vt = false) {
+KernelFn pick(int nb, int W, bool eval, bool vt = false, bool sp = false) {
 #ifdef SMPC_ONLY_NB  // development builds: one instantiation only (seconds instead of a minute to compile)
-  return nb == SMPC_ONLY_NB ? pick_w<SMPC_ONLY_NB>(W, eval, vt) : nullptr;
+  return nb == SMPC_ONLY_NB ? pick_w<SMPC_ONLY_NB>(W, eval, vt, sp) : nullptr;
 #else
   switch (nb) {
-    case 1: return pick_w<1>(W, eval, vt);
-    case 2: return pick_w<2>(W, eval, vt);
-    case 3: return pick_w<3>(W, eval, vt);
-    case 4: return pick_w<4>(W, eval, vt);
-    case 5: return pick_w<5>(W, eval, vt);
-    case 6: return pick_w<6>(W, eval, vt);
-    case 7: return pick_w<7>(W, eval, vt);
-    case 8: return pick_w<8>(W, eval, vt);
-    case 9: return pick_w<9>(W, eval, vt);
-    case 10: return pick_w<10>(W, eval, vt);
+    case 1: return pick_w<1>(W, eval, vt, sp);
+    case 2: return pick_w<2>(W, eval, vt, sp);
+    case 3: return pick_w<3>(W, eval, vt, sp);
+    case 4: return pick_w<4>(W, eval, vt, sp);
+    case 5: return pick_w<5>(W, eval, vt, sp);
+    case 6: return pick_w<6>(W, eval, vt, sp);
+    case 7: return pick_w<7>(W, eval, vt, sp);
+    case 8: return pick_w<8>(W, eval, vt, sp);
+    case 9: return pick_w<9>(W, eval, vt, sp);
+    case 10: return pick_w<10>(W, eval, vt, sp);
     default: return nullptr;
   }
 #endif
@@ -375,8 +383,9 @@ int solve_slot_width(const smpc_handle* h, const smpc::KParams& k) {
 int launch(smpc_handle* h, bool eval, smpc::KParams& k) {
   const int W = eval ? smpc::slot_width(k.T, k.N) : solve_slot_width(h, k);
   const int S = smpc::kWave / W;
-  KernelFn fn = pick(k.nb, W, eval, k.T_scene != nullptr);
-  const smpc::LdsLayout L = smpc::make_layout(k.T, k.N, k.P, eval ? smpc::kLayoutEval : smpc::kLayoutSolve, W);
+  const bool sp = k.scene_params != nullptr;
+  KernelFn fn = pick(k.nb, W, eval, k.T_scene != nullptr, sp);
+  const smpc::LdsLayout L = smpc::make_layout(k.T, k.N, k.P, eval ? smpc::kLayoutEval : smpc::kLayoutSolve, W, sp);
   k.hp_A = smpc::helper_owner_agents(k.T, k.N, W);
   if (std::getenv("SMPC_NO_HELPERS")) k.hp_A = k.N;  // experiment knob (the LDS layout keeps the helper regions)
   // behind the slot blocks: the feasibility rows of every slot (solve) or the row staging blocks + parked sensitivities (K1)
@@ -448,6 +457,19 @@ int launch(smpc_handle* h, bool eval, smpc::KParams& k) {
   return SMPC_OK;
 }
 
+// Host rows of smpc_scene_batch.scene_params: every value finite, v_min <= v_max, w_min <= w_max.
+int check_scene_params(const smpc_scene_params* sp, size_t B) {
+  for (size_t i = 0; i < B; ++i) {
+    const double* v = reinterpret_cast<const double*>(sp + i);
+    for (int j = 0; j < smpc::kSceneParamDoubles; ++j)
+      if (!std::isfinite(v[j])) { set_error("scene_params[" + std::to_string(i) + "]: every value must be finite"); return SMPC_ERR_INVALID_ARG; }
+    if (!(sp[i].v_min <= sp[i].v_max) || !(sp[i].w_min <= sp[i].w_max)) {
+      set_error("scene_params[" + std::to_string(i) + "]: needs v_min <= v_max and w_min <= w_max"); return SMPC_ERR_INVALID_ARG;
+    }
+  }
+  return SMPC_OK;
+}
+
 int bind_inputs(smpc_handle* h, const smpc_scene_batch* sb, const Dims& d, smpc::KParams* k, Staging* st) {
   const size_t B = sb->B, T = sb->T, N = sb->N;
   const size_t nmaps = sb->costmap_shared ? 1 : B;
@@ -455,12 +477,17 @@ int bind_inputs(smpc_handle* h, const smpc_scene_batch* sb, const Dims& d, smpc:
     k->pose0 = sb->pose0; k->init_params = sb->init_params; k->path_pts = sb->path_pts; k->goal_yaw = sb->goal_yaw;
     k->people = sb->people; k->has_people = sb->has_people; k->costmap = sb->costmap; k->costmap_origin = sb->costmap_origin;
     k->T_scene = sb->T_scene;  // device array: trusted, the kernel clamps every entry into 1..T
+    k->scene_params = sb->scene_params;  // device array: trusted (the caller's responsibility, include/smpc.h)
     return SMPC_OK;
   }
   if (sb->T_scene) {
     for (size_t i = 0; i < B; ++i)
       if (sb->T_scene[i] < 1 || sb->T_scene[i] > sb->T) { set_error("T_scene entries must lie in 1..T"); return SMPC_ERR_INVALID_ARG; }
     SMPC_TRY(st->up(sb->T_scene, B, &k->T_scene, h->stream));
+  }
+  if (sb->scene_params) {
+    SMPC_TRY(check_scene_params(sb->scene_params, B));
+    SMPC_TRY(st->up(sb->scene_params, B, &k->scene_params, h->stream));
   }
   SMPC_TRY(st->up(sb->pose0, B * 3, &k->pose0, h->stream));
   SMPC_TRY(st->up(sb->init_params, B * d.P, &k->init_params, h->stream));

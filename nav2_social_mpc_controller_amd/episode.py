@@ -26,7 +26,7 @@ import numpy as np
 
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
-from .params import OptimizerParams, TrajectorizerParams
+from .params import OptimizerParams, TrajectorizerParams, check_scene_param_rows
 from .scenes import SceneBatch
 from .solver import BatchSolver
 
@@ -65,7 +65,7 @@ class BatchEpisode:
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
                  plan_len: np.ndarray = None, traj_params: TrajectorizerParams = None, fov_angle: float = None,
                  order_hint: bool = False, plan_window: tuple = None, obstacles_from_costmap: bool = False,
-                 obstacle_min_cost: int = 254, unknown_is_obstacle: bool = False):
+                 obstacle_min_cost: int = 254, unknown_is_obstacle: bool = False, scene_params: np.ndarray = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -80,7 +80,10 @@ class BatchEpisode:
         the costmap's larger side); the plans are pruned as the robots
         advance. None: the global plans go to the trajectorizer as they are.
         order_hint: hand the solve kernel's queue the scenes sorted by the previous tick's sweep counts, longest first
-        (smpc_scene_batch.order; the results are the same, the lone launch is shorter)."""
+        (smpc_scene_batch.order; the results are the same, the lone launch is shorter).
+        scene_params [B,14]: critic weights, target speed and velocity bounds of every robot (smpc_scene_batch.scene_params,
+        e.g. params.scene_param_rows), handed to every tick's solve; None: `params`' values for every robot. Only the
+        solve takes them: the trajectorizer and the rest of the tick keep the episode-wide parameters."""
         import torch
 
         self.torch = torch
@@ -182,6 +185,10 @@ class BatchEpisode:
         self.cmd_vel = torch.zeros((B, 2), **f64)                      # the command returned to the robot this tick
         self.cmd_source = torch.zeros(B, dtype=torch.int32, device=self.dev)  # 0 optimised, 1 trajectorizer, 2 creep, 3 none
         self.order_hint = order_hint
+        self.scene_params = None
+        if scene_params is not None:
+            sp = check_scene_param_rows(scene_params, B)
+            self.scene_params = torch.from_numpy(sp).to(self.dev)  # device rows: checked here, not by the library
         self.graph = None
         self.gstream = None
         # queue order for the next solve (from the last solve's sweep counts; index order before the first one)
@@ -305,6 +312,8 @@ class BatchEpisode:
             sb.order = self.order.data_ptr()  # longest scenes of the previous period first
         if self.plan is not None:
             sb.T_scene = self.T_scene.data_ptr()
+        if self.scene_params is not None:
+            sb.scene_params = self.scene_params.data_ptr()
         s.solve_device(sb, self.rb)
         if timing is not None:
             timing["solve_ms"] = s.last_kernel_ms()
@@ -437,7 +446,7 @@ class ShardedEpisode:
                  plan_len: np.ndarray = None, traj_params: TrajectorizerParams = None, fov_angle: float = None,
                  shards: int = 3, order_hint: bool = False, graphs: bool = True, solve_share: int = None,
                  plan_window: tuple = None, obstacles_from_costmap: bool = False, obstacle_min_cost: int = 254,
-                 unknown_is_obstacle: bool = False):
+                 unknown_is_obstacle: bool = False, scene_params: np.ndarray = None):
         import torch
 
         self.torch = torch
@@ -458,7 +467,8 @@ class ShardedEpisode:
                     plan=None if plan is None else plan[idx], plan_len=None if plan_len is None else plan_len[idx],
                     traj_params=traj_params, fov_angle=fov_angle, order_hint=order_hint, plan_window=plan_window,
                     obstacles_from_costmap=obstacles_from_costmap, obstacle_min_cost=obstacle_min_cost,
-                    unknown_is_obstacle=unknown_is_obstacle))
+                    unknown_is_obstacle=unknown_is_obstacle,
+                    scene_params=None if scene_params is None else np.asarray(scene_params)[idx]))
         self.B = B
         self.graphs = graphs
         for part in self.parts:  # every shard's persistent solve grid takes its share of the resident wavefronts

@@ -4,11 +4,17 @@ Field names follow the reference's ROS parameter names (`<plugin>.optimizer.*`, 
 `<plugin>.trajectorizer.{time_step,max_time}`); defaults are the reference's *code* defaults. `from_yaml`
 reads a params/*.yaml-shaped file (the `FollowPath:` section of a Nav2 controller_server configuration).
 """
-from dataclasses import dataclass, asdict
+from dataclasses import dataclass, asdict, fields
 
 import numpy as np
 
-from ._abi import LINEAR_SOLVER, SmpcParams
+from ._abi import LINEAR_SOLVER, SCENE_PARAM_FIELDS, SmpcParams
+
+# the OptimizerParams field behind each smpc_scene_params field (struct order)
+SCENE_ROW_FIELDS = ("distance_weight", "social_weight", "velocity_weight", "angle_weight", "agent_angle_weight",
+                    "proxemics_weight", "velocity_feasibility_weight", "obstacle_weight", "goal_align_weight",
+                    "desired_linear_vel", "v_min", "v_max", "w_min", "w_max")
+assert len(SCENE_ROW_FIELDS) == len(SCENE_PARAM_FIELDS)
 
 
 @dataclass
@@ -104,6 +110,11 @@ class OptimizerParams:
         p.tol_needs_successful_step = int(self.tol_needs_successful_step)
         return p
 
+    def scene_row(self) -> np.ndarray:
+        """The 14 values one row of smpc_scene_batch.scene_params takes from this parameter set, in struct order
+        (_abi.SCENE_PARAM_FIELDS): nine weights, desired_linear_vel, v_min, v_max, w_min, w_max."""
+        return np.array([float(getattr(self, f)) for f in SCENE_ROW_FIELDS], dtype=np.float64)
+
     def dims(self, T: int, has_people: bool = True):
         """(CH, bl, nb, P, M, n_bounded) exactly as src/optimizer.cpp:248-249, 364, 373 derive them."""
         CH = min(self.control_horizon, T)
@@ -191,3 +202,42 @@ class OptimizerParams:
             if k in traj:
                 kw[k] = traj[k]
         return OptimizerParams(**kw)
+
+
+def scene_param_rows(param_sets, assignment) -> np.ndarray:
+    """Rows of smpc_scene_batch.scene_params [B,14]: scene b takes param_sets[assignment[b]]'s scene_row(). The sets may
+    differ only in the 14 per-scene values; anything else (control_horizon, parameter_block_length, tolerances,
+    max_iterations, linear_solver_type, time_step, ...) shapes the problem or the solver loop and stays the handle's, so
+    a set that differs there is refused (ValueError)."""
+    param_sets = list(param_sets)
+    if not param_sets:
+        raise ValueError("no parameter sets")
+    shared = [f.name for f in fields(OptimizerParams) if f.name not in SCENE_ROW_FIELDS]
+    base = param_sets[0]
+    for i, p in enumerate(param_sets[1:], 1):
+        bad = [n for n in shared if getattr(p, n) != getattr(base, n)]
+        if bad:
+            raise ValueError(f"parameter set {i} differs from set 0 in {', '.join(bad)}: only the per-scene weights, "
+                             "desired_linear_vel and velocity bounds may differ within one batch")
+    assignment = np.asarray(assignment)
+    if assignment.ndim != 1 or not np.issubdtype(assignment.dtype, np.integer):
+        raise ValueError("assignment must be a 1-D integer array")
+    if assignment.size and (assignment.min() < 0 or assignment.max() >= len(param_sets)):
+        raise ValueError("assignment indexes outside the parameter sets")
+    table = np.stack([p.scene_row() for p in param_sets])
+    return np.ascontiguousarray(table[assignment])
+
+
+def check_scene_param_rows(rows, B: int) -> np.ndarray:
+    """rows as the [B,14] float64 array smpc_scene_batch.scene_params takes, checked as the library checks host rows:
+    every value finite, v_min <= v_max and w_min <= w_max (ValueError otherwise). For callers that hand the rows over as
+    device memory, which the library does not check."""
+    sp = np.ascontiguousarray(rows, np.float64)
+    if sp.shape != (B, len(SCENE_PARAM_FIELDS)):
+        raise ValueError(f"scene_params: expected shape {(B, len(SCENE_PARAM_FIELDS))}, got {sp.shape}")
+    col = {f: i for i, f in enumerate(SCENE_PARAM_FIELDS)}
+    if not np.isfinite(sp).all():
+        raise ValueError("scene_params: every value must be finite")
+    if not ((sp[:, col["v_min"]] <= sp[:, col["v_max"]]).all() and (sp[:, col["w_min"]] <= sp[:, col["w_max"]]).all()):
+        raise ValueError("scene_params: needs v_min <= v_max and w_min <= w_max")
+    return sp

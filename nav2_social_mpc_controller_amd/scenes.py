@@ -9,10 +9,11 @@ from typing import Optional
 
 import numpy as np
 
-from ._abi import SmpcSceneBatch
+from ._abi import SCENE_PARAM_FIELDS, SmpcSceneBatch
 from .params import OptimizerParams
 
 _MASK = np.uint64(0xFFFFFFFFFFFFFFFF)
+SCENE_PARAM_COUNT = len(SCENE_PARAM_FIELDS)  # doubles per row of SceneBatch.scene_params
 
 
 def _splitmix64(x: np.ndarray) -> np.ndarray:
@@ -52,6 +53,9 @@ class SceneBatch:
     # optional horizon of each scene, 1 <= T_scene[b] <= T (smpc_scene_batch.T_scene): of path_pts / people the first
     # T_scene[b] + 1 rows of scene b count, of init_params the first P_b entries; None: every scene has T steps
     T_scene: Optional[np.ndarray] = None
+    # optional critic weights, target speed and velocity bounds of each scene [B,14] float64 in smpc_scene_params order
+    # (smpc_scene_batch.scene_params; params.scene_param_rows builds them); None: every scene takes the handle's values
+    scene_params: Optional[np.ndarray] = None
 
     @property
     def B(self) -> int:
@@ -81,6 +85,9 @@ class SceneBatch:
             assert a.flags["C_CONTIGUOUS"]
         if self.T_scene is not None:
             assert self.T_scene.shape == (B,) and self.T_scene.dtype == np.int32 and self.T_scene.flags["C_CONTIGUOUS"]
+        if self.scene_params is not None:
+            assert (self.scene_params.shape == (B, SCENE_PARAM_COUNT) and self.scene_params.dtype == np.float64
+                    and self.scene_params.flags["C_CONTIGUOUS"])
 
     def to_c(self) -> SmpcSceneBatch:
         """C view over the host arrays (arrays stay owned by this object)."""
@@ -100,6 +107,8 @@ class SceneBatch:
         sb.resolution = self.resolution
         if self.T_scene is not None:
             sb.T_scene = self.T_scene.ctypes.data
+        if self.scene_params is not None:
+            sb.scene_params = self.scene_params.ctypes.data
         return sb
 
     def to_device(self, device="cuda:0"):
@@ -110,6 +119,8 @@ class SceneBatch:
              ("pose0", "init_params", "path_pts", "goal_yaw", "people", "has_people", "costmap", "costmap_origin")}
         if self.T_scene is not None:
             t["T_scene"] = torch.from_numpy(self.T_scene).to(device)
+        if self.scene_params is not None:
+            t["scene_params"] = torch.from_numpy(self.scene_params).to(device)
         sb = SmpcSceneBatch()
         sb.B, sb.T, sb.N, sb.on_device = self.B, self.T, self.N, 1
         sb.dt = self.dt
@@ -128,7 +139,8 @@ class SceneBatch:
                           np.ascontiguousarray(self.init_params[idx]), np.ascontiguousarray(self.path_pts[idx]),
                           np.ascontiguousarray(self.goal_yaw[idx]), np.ascontiguousarray(self.people[idx]),
                           np.ascontiguousarray(self.has_people[idx]), cm, co, self.resolution, self.costmap_shared,
-                          None if self.T_scene is None else np.ascontiguousarray(self.T_scene[idx]))
+                          None if self.T_scene is None else np.ascontiguousarray(self.T_scene[idx]),
+                          None if self.scene_params is None else np.ascontiguousarray(self.scene_params[idx]))
 
     def with_horizons(self, T_scene) -> "SceneBatch":
         """The same scenes with a horizon per scene: scene b keeps its first T_scene[b] + 1 poses / people rows; its goal
@@ -147,20 +159,30 @@ class SceneBatch:
         return SceneBatch(Tb, self.N, self.dt, sub.pose0, np.ascontiguousarray(sub.init_params[:, :P_b]),
                           np.ascontiguousarray(sub.path_pts[:, :Tb + 1]), sub.goal_yaw,
                           np.ascontiguousarray(sub.people[:, :Tb + 1]), sub.has_people, sub.costmap, sub.costmap_origin,
-                          self.resolution, self.costmap_shared)
+                          self.resolution, self.costmap_shared, scene_params=sub.scene_params)
+
+    def with_scene_params(self, scene_params) -> "SceneBatch":
+        """The same scenes with weights and velocity bounds per scene (rows [B,14], e.g. from params.scene_param_rows);
+        None: the handle's for every scene."""
+        out = self.select(np.arange(self.B))
+        out.scene_params = None if scene_params is None else np.ascontiguousarray(scene_params, np.float64)
+        out.validate(self.init_params.shape[1])
+        return out
 
     def save(self, path: str):
+        extra = {} if self.scene_params is None else {"scene_params": self.scene_params}
         np.savez_compressed(path, T=self.T, N=self.N, dt=self.dt, pose0=self.pose0, init_params=self.init_params,
                             path_pts=self.path_pts, goal_yaw=self.goal_yaw, people=self.people,
                             has_people=self.has_people, costmap=self.costmap, costmap_origin=self.costmap_origin,
-                            resolution=self.resolution, costmap_shared=self.costmap_shared)
+                            resolution=self.resolution, costmap_shared=self.costmap_shared, **extra)
 
     @staticmethod
     def load(path: str) -> "SceneBatch":
         z = np.load(path, allow_pickle=False)
         return SceneBatch(int(z["T"]), int(z["N"]), float(z["dt"]), z["pose0"], z["init_params"], z["path_pts"],
                           z["goal_yaw"], z["people"], z["has_people"], z["costmap"], z["costmap_origin"],
-                          float(z["resolution"]), bool(z["costmap_shared"]))
+                          float(z["resolution"]), bool(z["costmap_shared"]),
+                          scene_params=np.ascontiguousarray(z["scene_params"]) if "scene_params" in z.files else None)
 
 
 def make_scenes(params: OptimizerParams, B: int, N: int, seed: int = 0x5EED0001, first_scene: int = 0,

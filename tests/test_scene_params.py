@@ -1,0 +1,187 @@
+"""Per-scene critic weights and velocity bounds (`smpc_scene_batch.scene_params`), host side: the C ABI layout, the
+register budget of the sp kernels and the Python plumbing (CPU only; the device behaviour is in
+tests/test_gpu_scene_params.py)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from nav2_social_mpc_controller_amd import _abi
+from nav2_social_mpc_controller_amd.params import OptimizerParams, scene_param_rows
+from nav2_social_mpc_controller_amd.scenes import SceneBatch, make_scenes
+from test_kernel_budget import HIPCC, MAX_VGPRS, CSRC, parse_resource_remarks
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_abi_version_is_6():
+    from nav2_social_mpc_controller_amd import solver as S
+    assert _abi.SMPC_ABI_VERSION == 6
+    assert S.load_library().smpc_abi_version() == 6
+
+
+def test_scene_params_layout_matches_the_c_header(tmp_path):
+    fields = _abi.SCENE_PARAM_FIELDS
+    body = 'printf("%zu %zu %zu\\n", sizeof(smpc_scene_params), sizeof(smpc_scene_batch), offsetof(smpc_scene_batch, scene_params));\n'
+    body += "".join(f'printf("%zu\\n", offsetof(smpc_scene_params, {f}));\n' for f in fields)
+    prog = tmp_path / "sp_layout.c"
+    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "smpc.h"\nint main(void){\n' + body + "return 0;}\n")
+    exe = tmp_path / "sp_layout"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
+    lines = subprocess.check_output([str(exe)], text=True).splitlines()
+    size, sb_size, off = (int(v) for v in lines[0].split())
+    assert size == C.sizeof(_abi.SmpcSceneParams) == 14 * 8
+    assert sb_size == C.sizeof(_abi.SmpcSceneBatch)
+    assert off == _abi.SmpcSceneBatch.scene_params.offset
+    assert _abi.SmpcSceneBatch._fields_[-1][0] == "scene_params"  # appended: every earlier offset is unchanged
+    for f, line in zip(fields, lines[1:]):
+        assert int(line) == getattr(_abi.SmpcSceneParams, f).offset, f
+
+
+def test_scene_row_follows_the_struct_order():
+    p = OptimizerParams.readme().replace(desired_linear_vel=0.55, v_min=0.05, v_max=0.5, w_min=-1.1, w_max=1.2)
+    row = p.scene_row()
+    c = p.to_c()
+    assert [n for n, _ in _abi.SmpcSceneParams._fields_] == list(_abi.SCENE_PARAM_FIELDS)
+    assert row.dtype == np.float64 and row.shape == (14,)
+    assert list(row) == [getattr(c, f) for f in _abi.SCENE_PARAM_FIELDS]
+
+
+def test_rows_helper_assigns_and_refuses_structural_differences():
+    a, b = OptimizerParams.soc_work_obst_benchmark(), OptimizerParams.obst_only_benchmark()
+    rows = scene_param_rows([a, b], [0, 1, 1, 0])
+    assert rows.shape == (4, 14) and rows.flags["C_CONTIGUOUS"]
+    assert np.array_equal(rows[0], a.scene_row()) and np.array_equal(rows[1], b.scene_row())
+    assert np.array_equal(rows[2], b.scene_row()) and np.array_equal(rows[3], a.scene_row())
+    assert np.array_equal(scene_param_rows([a], np.zeros(3, int)), np.tile(a.scene_row(), (3, 1)))
+    for kw in (dict(control_horizon=12), dict(parameter_block_length=4), dict(fn_tol=1e-6), dict(gradient_tol=1e-9),
+               dict(param_tol=1e-8), dict(max_iterations=30), dict(linear_solver_type="DENSE_QR"), dict(time_step=0.1),
+               dict(max_time=2.0), dict(fixed_iterations=1)):
+        with pytest.raises(ValueError, match=next(iter(kw))):
+            scene_param_rows([a, b.replace(**kw)], [0, 1])
+    with pytest.raises(ValueError):
+        scene_param_rows([a, b], [0, 2])
+
+
+def _batch():
+    prm = OptimizerParams.readme()
+    sc = make_scenes(prm, 6, 3, map_cells=40, seed=11)
+    rows = scene_param_rows([prm, prm.replace(social_weight=7.0, v_max=0.4)], [0, 1, 0, 1, 1, 0])
+    return prm, sc, sc.with_scene_params(rows), rows
+
+
+def test_scene_batch_carries_scene_params():
+    prm, plain, sc, rows = _batch()
+    assert plain.scene_params is None and plain.to_c().scene_params is None
+    assert np.array_equal(sc.scene_params, rows)
+    assert sc.to_c().scene_params == sc.scene_params.ctypes.data
+    sub = sc.select([4, 1])
+    assert np.array_equal(sub.scene_params, rows[[4, 1]])
+    cut = sc.cut([5, 2, 3], sc.T - 4, 4)
+    assert np.array_equal(cut.scene_params, rows[[5, 2, 3]])
+    hz = sc.with_horizons(np.full(sc.B, sc.T - 1))
+    assert np.array_equal(hz.scene_params, rows)
+    with pytest.raises(AssertionError):
+        sc.with_scene_params(rows[:, :13])
+
+
+def test_save_load_round_trip(tmp_path):
+    prm, plain, sc, rows = _batch()
+    sc.save(str(tmp_path / "sp.npz"))
+    back = SceneBatch.load(str(tmp_path / "sp.npz"))
+    assert np.array_equal(back.scene_params, rows) and back.scene_params.dtype == np.float64
+    plain.save(str(tmp_path / "plain.npz"))
+    assert SceneBatch.load(str(tmp_path / "plain.npz")).scene_params is None
+    # the committed fixtures (written before the field existed) load as they did
+    g = SceneBatch.load(os.path.join(ROOT, "tests", "golden", "cfg3_n8_scenes.npz"))
+    assert g.scene_params is None and g.to_c().scene_params is None
+
+
+# ---- register budget of the sp kernels (compile time, like tests/test_kernel_budget.py) ----------------------------
+SP_KERNELS = {
+    "solve_sp<3,32>": "_ZN4smpc20smpc_solve_sp_kernelILi3ELi32EEEvNS_7KParamsE",
+    "K1_sp<3,32>": "_ZN4smpc19smpc_eval_sp_kernelILi3ELi32EEEvNS_7KParamsE",
+}
+VT_SOLVE = "_ZN4smpc17smpc_solve_kernelILi3ELi32ELb1EEEvNS_7KParamsE"  # the per-scene-horizon kernel the sp path extends
+
+
+@pytest.fixture(scope="module")
+def usage(tmp_path_factory):
+    if not os.access(HIPCC, os.X_OK):
+        pytest.skip(f"{HIPCC} (the compiler build.sh invokes) not available")
+    obj = str(tmp_path_factory.mktemp("sp_budget") / "smpc_nb3.o")
+    r = subprocess.run(["bash", os.path.join(CSRC, "build.sh"), "-DSMPC_ONLY_NB=3", "--cuda-device-only", "-c",
+                        "-Rpass-analysis=kernel-resource-usage"],
+                       env={**os.environ, "SMPC_OUT": obj}, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return parse_resource_remarks(r.stderr)
+
+
+@pytest.mark.parametrize("name", sorted(SP_KERNELS))
+def test_sp_kernel_keeps_three_waves(usage, name):
+    r = usage.get(SP_KERNELS[name])
+    assert r is not None, f"{name}: no resource remark (instantiation missing?)"
+    assert r["VGPRs"] <= MAX_VGPRS, f"{name}: {r['VGPRs']} VGPRs > {MAX_VGPRS}"
+    assert r["SGPRs Spill"] == 0, f"{name}: {r['SGPRs Spill']} spilled SGPRs"
+    assert r["Occupancy [waves/SIMD]"] >= 3, f"{name}: occupancy {r['Occupancy [waves/SIMD]']}"
+
+
+def test_sp_k1_has_no_spill_and_no_private_segment(usage):
+    r = usage[SP_KERNELS["K1_sp<3,32>"]]
+    assert r["VGPRs Spill"] == 0 and r["ScratchSize [bytes/lane]"] == 0, r
+
+
+def test_sp_solve_spills_no_more_than_the_per_scene_horizon_kernel(usage):
+    """The sp solve kernel reads its horizon per scene like smpc_solve_kernel<3,32,true>, whose 12 spilled VGPRs (20 B
+    private segment) it shares; the per-scene weights and bounds must not add to them."""
+    r, vt = usage[SP_KERNELS["solve_sp<3,32>"]], usage[VT_SOLVE]
+    assert r["VGPRs Spill"] <= vt["VGPRs Spill"], (r, vt)
+    assert r["ScratchSize [bytes/lane]"] <= vt["ScratchSize [bytes/lane]"], (r, vt)
+
+
+def test_sp_k1_one_scene_per_wave_spills_no_more_than_recorded(usage):
+    """K1 sp <3,64> (outside the issue's <3,32> budget) at the values DESIGN §4 records: 3 waves per SIMD, at most 4
+    spilled VGPRs and a 20 B private segment."""
+    r = usage["_ZN4smpc19smpc_eval_sp_kernelILi3ELi64EEEvNS_7KParamsE"]
+    assert r["VGPRs"] <= MAX_VGPRS and r["Occupancy [waves/SIMD]"] >= 3, r
+    assert r["VGPRs Spill"] <= 4 and r["ScratchSize [bytes/lane]"] <= 20, r
+
+
+def test_source_digest_covers_every_file_the_build_reads(tmp_path):
+    """buildinfo.csrc_digest() ties committed profiles to the device sources: every file csrc/ includes must be in it,
+    the kernel bodies in csrc/*.inc among them."""
+    import re
+    import shutil
+
+    from nav2_social_mpc_controller_amd.buildinfo import SOURCE_SUFFIXES, csrc_digest
+
+    included = set()
+    for name in os.listdir(CSRC):
+        if name.endswith((".hip", ".hpp", ".inc")):
+            included |= set(re.findall(r'#include "([^"/]+)"', open(os.path.join(CSRC, name)).read()))
+    assert {"smpc_solve_kernel.inc", "smpc_eval_kernel.inc"} <= included
+    for name in included:
+        assert name.endswith(SOURCE_SUFFIXES), name
+    root = tmp_path / "csrc"
+    shutil.copytree(CSRC, root, ignore=shutil.ignore_patterns("*.so", "*.o", "__pycache__"))
+    before = csrc_digest(str(root))
+    with open(root / "smpc_solve_kernel.inc", "a") as f:
+        f.write("// edit\n")
+    assert csrc_digest(str(root)) != before
+
+
+def test_row_check_uses_the_struct_fields():
+    from nav2_social_mpc_controller_amd.params import check_scene_param_rows
+
+    rows = scene_param_rows([OptimizerParams.readme()], np.zeros(3, int))
+    assert np.array_equal(check_scene_param_rows(rows, 3), rows)
+    col = {f: i for i, f in enumerate(_abi.SCENE_PARAM_FIELDS)}
+    for f, v in (("v_min", 0.9), ("w_max", -2.0), ("obstacle_w", np.nan), ("desired_linear_vel", np.inf)):
+        bad = rows.copy()
+        bad[1, col[f]] = v
+        with pytest.raises(ValueError):
+            check_scene_param_rows(bad, 3)
+    with pytest.raises(ValueError):
+        check_scene_param_rows(rows, 4)
