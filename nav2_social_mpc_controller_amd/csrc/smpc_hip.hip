@@ -112,22 +112,22 @@ __global__ __launch_bounds__(256) void smpc_fp64_peak_kernel(double* out, int it
 }  // namespace smpc
 
 struct smpc_handle {
-  smpc_params prm;
-  int device;
-  int num_cu;
-  hipStream_t stream;
-  hipEvent_t ev0, ev1;
-  bool timed;
-  int* queue;  // device-side scene queue head
-  int share;   // smpc_set_solve_share: concurrent solve launches the persistent grid leaves room for
-  double* stage_rec;  // staged people block of the latest call that did not bring its own (grow-only)
-  double* stage_aux;
-  size_t stage_rec_bytes, stage_aux_bytes;
-  char* stage;        // grow-only arena for host-pointer calls (the plugin's B = 1 use): no hipMalloc per call
-  size_t stage_cap;
-  size_t stage_want;  // high-water mark of the calls so far
-  char* pin;          // page-locked host mirror of the arena's first pin_cap bytes: the small arrays of a host-pointer call
-  size_t pin_cap;     // travel in ONE copy each way instead of one pageable hipMemcpy per array (Staging, below)
+  smpc_params prm{};
+  int device = 0;
+  int num_cu = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool timed = false;
+  int* queue = nullptr;  // device-side scene queue head
+  int share = 1;         // smpc_set_solve_share: concurrent solve launches the persistent grid leaves room for
+  double* stage_rec = nullptr;  // staged people block of the latest call that did not bring its own (grow-only)
+  double* stage_aux = nullptr;
+  size_t stage_rec_bytes = 0, stage_aux_bytes = 0;
+  char* stage = nullptr;  // grow-only arena for host-pointer calls (the plugin's B = 1 use): no hipMalloc per call
+  size_t stage_cap = 0;
+  size_t stage_want = 0;  // high-water mark of the calls so far
+  char* pin = nullptr;    // page-locked host mirror of the arena's first pin_cap bytes: the small arrays of a host-pointer call
+  size_t pin_cap = 0;     // travel in ONE copy each way instead of one pageable hipMemcpy per array (Staging, below)
 };
 
 namespace {
@@ -198,33 +198,30 @@ void fill_kparams(const smpc_handle* h, const smpc_scene_batch* sb, const Dims& 
   smpc::fill_atan_nodes(&k->an);
 }
 
-#define SMPC_TRY_(expr) do { int _rc = (expr); if (_rc != SMPC_OK) return _rc; } while (0)
+#define SMPC_TRY(expr) do { int _rc = (expr); if (_rc != SMPC_OK) return _rc; } while (0)
 
-// Host-pointer batches are staged through device memory by this helper: sub-allocations of the handle's arena, which
-// grows to the high-water mark at the start of the next call (every host-pointer call ends with a stream synchronise,
-// so nothing is in flight then); what does not fit meanwhile comes from hipMalloc and is freed when the call returns.
+// Every batch entry point takes host or device pointers (on_device) and names each of its arrays once, here: in(), out()
+// or inout(), with the kernel parameter to fill, the caller's pointer and the element count. Device pointers are passed
+// through. Host arrays are staged through device memory: sub-allocations of the handle's arena, which grows to the
+// high-water mark at the start of the next call (every host-pointer call ends with a stream synchronise, so nothing is
+// in flight then); what does not fit meanwhile comes from hipMalloc and is freed when the call returns.
 // The plugin's own call (B = 1: a dozen arrays of a few hundred bytes and one costmap) used to spend more time in its 16
 // pageable hipMemcpy calls than in its kernels. The head of the arena (kPinBytes) therefore has a page-locked mirror on
 // the host: inputs that land there are gathered in the mirror and cross in ONE asynchronous copy (flush_up(), before the
 // first kernel of the call), outputs that land there come back in one copy and are handed out from the mirror
-// (finish()). What lies beyond the mirror (large batches) is copied array by array as before.
+// (finish()). What lies beyond the mirror (large batches) is copied array by array.
 constexpr size_t kPinBytes = 8u << 20;
-struct Staging {
-  smpc_handle* h;
-  size_t off = 0, need = 0;
-  size_t up_lo = SIZE_MAX, up_hi = 0;  // arena bytes [up_lo, up_hi) wait in the mirror for flush_up()
-  struct Deferred { void* host; size_t off, bytes; };
-  std::vector<Deferred> downs;         // outputs inside the mirrored range: fetched by finish()
-  std::vector<void*> overflow;
-  explicit Staging(smpc_handle* handle) : h(handle) {
-    if (h && h->stage_want > h->stage_cap) {
+class Staging {
+ public:
+  Staging(smpc_handle* handle, bool on_device) : h(handle), host(!on_device) {
+    if (h->stage_want > h->stage_cap) {
       if (h->stage) (void)hipFree(h->stage);
       h->stage = nullptr; h->stage_cap = 0;
       const size_t cap = h->stage_want + h->stage_want / 4;
       void* p = nullptr;
       if (hipMalloc(&p, cap) == hipSuccess) { h->stage = static_cast<char*>(p); h->stage_cap = cap; }
     }
-    if (h && h->stage) {
+    if (h->stage) {
       const size_t want = h->stage_cap < kPinBytes ? h->stage_cap : kPinBytes;
       if (h->pin_cap < want) {
         if (h->pin) (void)hipHostFree(h->pin);
@@ -236,12 +233,59 @@ struct Staging {
   }
   ~Staging() {
     for (void* p : overflow) (void)hipFree(p);
-    if (h && need > h->stage_want) h->stage_want = need;
+    if (need > h->stage_want) h->stage_want = need;
   }
+  // n elements the kernel reads / writes / reads and updates in place
+  template <typename T> int in(const T*& dev, const T* src, size_t n) { return bind(dev, src, src, nullptr, n * sizeof(T)); }
+  template <typename T> int out(T*& dev, T* dst, size_t n) { return bind(dev, dst, nullptr, dst, n * sizeof(T)); }
+  template <typename T> int inout(T*& dev, T* buf, size_t n) { return bind(dev, buf, buf, buf, n * sizeof(T)); }
+  // the gathered inputs cross here (timed() does it before the kernels)
+  int flush_up() {
+    if (up_hi > up_lo) SMPC_HIP_CHECK(hipMemcpyAsync(h->stage + up_lo, h->pin + up_lo, up_hi - up_lo, hipMemcpyHostToDevice, h->stream));
+    up_lo = SIZE_MAX; up_hi = 0;
+    return SMPC_OK;
+  }
+  // The kernels of a call, between the events smpc_last_kernel_ms() reads: the inputs have crossed before ev0, so the
+  // time is the kernels' alone. `kernels` launches them on h->stream and returns SMPC_OK or an error code.
+  template <typename F> int timed(F&& kernels) {
+    SMPC_TRY(flush_up());
+    SMPC_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
+    SMPC_TRY(kernels());
+    SMPC_HIP_CHECK(hipGetLastError());
+    SMPC_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    return SMPC_OK;
+  }
+  // End of the call. Host pointers: the outputs come back (those in the mirror in one copy), the stream is drained and
+  // the results are handed out. Device pointers: nothing to do, the call stays asynchronous.
+  int finish() {
+    if (!host) return SMPC_OK;
+    SMPC_TRY(flush_up());  // a call that launched nothing (empty batch)
+    size_t lo = SIZE_MAX, hi = 0;
+    for (const Back& b : backs) {
+      if (b.off == SIZE_MAX) { SMPC_HIP_CHECK(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, h->stream)); continue; }
+      if (b.off < lo) lo = b.off;
+      if (b.off + b.bytes > hi) hi = b.off + b.bytes;
+    }
+    if (hi > lo) SMPC_HIP_CHECK(hipMemcpyAsync(h->pin + lo, h->stage + lo, hi - lo, hipMemcpyDeviceToHost, h->stream));
+    SMPC_HIP_CHECK(hipStreamSynchronize(h->stream));
+    for (const Back& b : backs)
+      if (b.off != SIZE_MAX) std::memcpy(b.host, h->pin + b.off, b.bytes);
+    return SMPC_OK;
+  }
+
+ private:
+  struct Back { void* host; const void* dev; size_t off, bytes; };  // off: in the mirror, or SIZE_MAX
+  smpc_handle* h;
+  bool host;
+  size_t off = 0, need = 0;
+  size_t up_lo = SIZE_MAX, up_hi = 0;  // arena bytes [up_lo, up_hi) wait in the mirror for flush_up()
+  std::vector<Back> backs;             // outputs, fetched by finish()
+  std::vector<void*> overflow;
   int take(size_t bytes, void** out) {
     const size_t sz = (bytes + 255) & ~(size_t)255;
     need += sz;
-    if (h && h->stage && off + sz <= h->stage_cap) { *out = h->stage + off; off += sz; return SMPC_OK; }
+    if (h->stage && off + sz <= h->stage_cap) { *out = h->stage + off; off += sz; return SMPC_OK; }
     void* p = nullptr;
     SMPC_HIP_CHECK(hipMalloc(&p, sz));
     overflow.push_back(p);
@@ -250,64 +294,36 @@ struct Staging {
   }
   // offset of a device pointer inside the mirrored head of the arena, or SIZE_MAX
   size_t mirrored(const void* dev, size_t bytes) const {
-    if (!h || !h->stage || !h->pin) return SIZE_MAX;
+    if (!h->stage || !h->pin) return SIZE_MAX;
     const char* p = static_cast<const char*>(dev);
     if (p < h->stage || p + bytes > h->stage + h->pin_cap) return SIZE_MAX;
     return (size_t)(p - h->stage);
   }
-  template <typename T> int up(const T* host, size_t n, const T** dev, hipStream_t st) {
-    *dev = nullptr;
-    if (!host || n == 0) return SMPC_OK;
+  template <typename P> int bind(P& dev, P caller, const void* up, void* back, size_t bytes) {
+    if (!host) { dev = caller; return SMPC_OK; }
     void* p = nullptr;
-    SMPC_TRY_(take(n * sizeof(T), &p));
-    const size_t o = mirrored(p, n * sizeof(T));
-    if (o != SIZE_MAX) {
-      std::memcpy(h->pin + o, host, n * sizeof(T));
+    SMPC_TRY(stage(up, back, bytes, &p));
+    dev = static_cast<P>(p);
+    return SMPC_OK;
+  }
+  // Device room for a host array of `bytes`: `up` (if any) gathered in the mirror or copied now, `back` (if any) the
+  // host array finish() copies the result to. A null array or an empty one binds a null device pointer.
+  int stage(const void* up, void* back, size_t bytes, void** dev) {
+    *dev = nullptr;
+    if ((!up && !back) || bytes == 0) return SMPC_OK;
+    SMPC_TRY(take(bytes, dev));
+    const size_t o = mirrored(*dev, bytes);
+    if (up && o != SIZE_MAX) {
+      std::memcpy(h->pin + o, up, bytes);
       if (o < up_lo) up_lo = o;
-      if (o + n * sizeof(T) > up_hi) up_hi = o + n * sizeof(T);
-    } else {
-      SMPC_HIP_CHECK(hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, st));
+      if (o + bytes > up_hi) up_hi = o + bytes;
+    } else if (up) {
+      SMPC_HIP_CHECK(hipMemcpyAsync(*dev, up, bytes, hipMemcpyHostToDevice, h->stream));
     }
-    *dev = static_cast<const T*>(p);
-    return SMPC_OK;
-  }
-  // the gathered inputs cross here: every entry point calls it before its first kernel launch
-  int flush_up(hipStream_t st) {
-    if (up_hi > up_lo) SMPC_HIP_CHECK(hipMemcpyAsync(h->stage + up_lo, h->pin + up_lo, up_hi - up_lo, hipMemcpyHostToDevice, st));
-    up_lo = SIZE_MAX; up_hi = 0;
-    return SMPC_OK;
-  }
-  template <typename T> int out(T* host, size_t n, T** dev) {
-    *dev = nullptr;
-    if (!host || n == 0) return SMPC_OK;
-    void* p = nullptr;
-    SMPC_TRY_(take(n * sizeof(T), &p));
-    *dev = static_cast<T*>(p);
-    return SMPC_OK;
-  }
-  template <typename T> int down(T* host, const T* dev, size_t n, hipStream_t st) {
-    if (!host || !dev || n == 0) return SMPC_OK;
-    const size_t o = mirrored(dev, n * sizeof(T));
-    if (o != SIZE_MAX) { downs.push_back({host, o, n * sizeof(T)}); return SMPC_OK; }
-    SMPC_HIP_CHECK(hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, st));
-    return SMPC_OK;
-  }
-  // end of a host-pointer call: the deferred outputs in one copy, the stream drained, the results handed out
-  int finish(hipStream_t st) {
-    if (up_hi > up_lo) SMPC_TRY_(flush_up(st));  // a call that launched nothing (empty batch)
-    if (!downs.empty()) {
-      size_t lo = SIZE_MAX, hi = 0;
-      for (const Deferred& d : downs) { if (d.off < lo) lo = d.off; if (d.off + d.bytes > hi) hi = d.off + d.bytes; }
-      SMPC_HIP_CHECK(hipMemcpyAsync(h->pin + lo, h->stage + lo, hi - lo, hipMemcpyDeviceToHost, st));
-    }
-    SMPC_HIP_CHECK(hipStreamSynchronize(st));
-    for (const Deferred& d : downs) std::memcpy(d.host, h->pin + d.off, d.bytes);
-    downs.clear();
+    if (back) backs.push_back({back, *dev, o, bytes});
     return SMPC_OK;
   }
 };
-
-#define SMPC_TRY(expr) do { int _rc = (expr); if (_rc != SMPC_OK) return _rc; } while (0)
 
 int grow(double** buf, size_t* have, size_t need, hipStream_t st) {
   if (need <= *have) return SMPC_OK;
@@ -341,15 +357,13 @@ int bind_people(smpc_handle* h, const smpc_scene_batch* sb, smpc::KParams& k, St
   if (sb->N == 0) return SMPC_OK;
   const size_t nrec = (size_t)sb->B * sb->N * sb->T * 4, naux = (size_t)sb->B * sb->T * 2;
   if (sb->people_records) {
-    if (sb->on_device) { k.people_rec = sb->people_records; k.people_aux = sb->people_aux; return SMPC_OK; }
-    SMPC_TRY_(st->up(sb->people_records, nrec, &k.people_rec, h->stream));
-    SMPC_TRY_(st->up(sb->people_aux, naux, &k.people_aux, h->stream));
-    return SMPC_OK;
+    SMPC_TRY(st->in(k.people_rec, sb->people_records, nrec));
+    return st->in(k.people_aux, sb->people_aux, naux);
   }
-  SMPC_TRY_(grow(&h->stage_rec, &h->stage_rec_bytes, nrec * sizeof(double), h->stream));
-  SMPC_TRY_(grow(&h->stage_aux, &h->stage_aux_bytes, naux * sizeof(double), h->stream));
-  SMPC_TRY_(st->flush_up(h->stream));
-  SMPC_TRY_(launch_stage(h, k, h->stage_rec, h->stage_aux));
+  SMPC_TRY(grow(&h->stage_rec, &h->stage_rec_bytes, nrec * sizeof(double), h->stream));
+  SMPC_TRY(grow(&h->stage_aux, &h->stage_aux_bytes, naux * sizeof(double), h->stream));
+  SMPC_TRY(st->flush_up());
+  SMPC_TRY(launch_stage(h, k, h->stage_rec, h->stage_aux));
   k.people_rec = h->stage_rec; k.people_aux = h->stage_aux;
   return SMPC_OK;
 }
@@ -380,7 +394,7 @@ int solve_slot_width(const smpc_handle* h, const smpc::KParams& k) {
   return (k.B <= per_cu * h->num_cu / share) ? 64 : 32;
 }
 
-int launch(smpc_handle* h, bool eval, smpc::KParams& k) {
+int launch(smpc_handle* h, Staging& st, bool eval, smpc::KParams& k) {
   const int W = eval ? smpc::slot_width(k.T, k.N) : solve_slot_width(h, k);
   const int S = smpc::kWave / W;
   const bool sp = k.scene_params != nullptr;
@@ -428,11 +442,7 @@ int launch(smpc_handle* h, bool eval, smpc::KParams& k) {
     k.stamps = d_stamps;
   }
 #endif
-  SMPC_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
-  hipLaunchKernelGGL(fn, dim3(grid), dim3(smpc::kWave), shmem, h->stream, k);
-  SMPC_HIP_CHECK(hipGetLastError());
-  SMPC_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-  h->timed = true;
+  SMPC_TRY(st.timed([&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(smpc::kWave), shmem, h->stream, k); return SMPC_OK; }));
 #ifdef SMPC_STAMPS
   {
     SMPC_HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -470,34 +480,25 @@ int check_scene_params(const smpc_scene_params* sp, size_t B) {
   return SMPC_OK;
 }
 
-int bind_inputs(smpc_handle* h, const smpc_scene_batch* sb, const Dims& d, smpc::KParams* k, Staging* st) {
+int bind_inputs(const smpc_scene_batch* sb, const Dims& d, smpc::KParams* k, Staging* st) {
   const size_t B = sb->B, T = sb->T, N = sb->N;
   const size_t nmaps = sb->costmap_shared ? 1 : B;
-  if (sb->on_device) {
-    k->pose0 = sb->pose0; k->init_params = sb->init_params; k->path_pts = sb->path_pts; k->goal_yaw = sb->goal_yaw;
-    k->people = sb->people; k->has_people = sb->has_people; k->costmap = sb->costmap; k->costmap_origin = sb->costmap_origin;
-    k->T_scene = sb->T_scene;  // device array: trusted, the kernel clamps every entry into 1..T
-    k->scene_params = sb->scene_params;  // device array: trusted (the caller's responsibility, include/smpc.h)
-    return SMPC_OK;
-  }
-  if (sb->T_scene) {
+  // host rows are checked here; device arrays are trusted (the caller's responsibility, include/smpc.h: the kernel
+  // clamps every T_scene entry into 1..T)
+  if (!sb->on_device && sb->T_scene)
     for (size_t i = 0; i < B; ++i)
       if (sb->T_scene[i] < 1 || sb->T_scene[i] > sb->T) { set_error("T_scene entries must lie in 1..T"); return SMPC_ERR_INVALID_ARG; }
-    SMPC_TRY(st->up(sb->T_scene, B, &k->T_scene, h->stream));
-  }
-  if (sb->scene_params) {
-    SMPC_TRY(check_scene_params(sb->scene_params, B));
-    SMPC_TRY(st->up(sb->scene_params, B, &k->scene_params, h->stream));
-  }
-  SMPC_TRY(st->up(sb->pose0, B * 3, &k->pose0, h->stream));
-  SMPC_TRY(st->up(sb->init_params, B * d.P, &k->init_params, h->stream));
-  SMPC_TRY(st->up(sb->path_pts, B * (T + 1) * 2, &k->path_pts, h->stream));
-  SMPC_TRY(st->up(sb->goal_yaw, B, &k->goal_yaw, h->stream));
-  if (!sb->people_records) SMPC_TRY(st->up(sb->people, B * (T + 1) * 6 * N, &k->people, h->stream));
-  SMPC_TRY(st->up(sb->has_people, B, &k->has_people, h->stream));
-  SMPC_TRY(st->up(sb->costmap, nmaps * (size_t)sb->size_x * sb->size_y, &k->costmap, h->stream));
-  SMPC_TRY(st->up(sb->costmap_origin, nmaps * 2, &k->costmap_origin, h->stream));
-  return SMPC_OK;
+  if (!sb->on_device && sb->scene_params) SMPC_TRY(check_scene_params(sb->scene_params, B));
+  SMPC_TRY(st->in(k->T_scene, sb->T_scene, B));
+  SMPC_TRY(st->in(k->scene_params, sb->scene_params, B));
+  SMPC_TRY(st->in(k->pose0, sb->pose0, B * 3));
+  SMPC_TRY(st->in(k->init_params, sb->init_params, B * d.P));
+  SMPC_TRY(st->in(k->path_pts, sb->path_pts, B * (T + 1) * 2));
+  SMPC_TRY(st->in(k->goal_yaw, sb->goal_yaw, B));
+  if (!sb->people_records) SMPC_TRY(st->in(k->people, sb->people, B * (T + 1) * 6 * N));  // else read by no kernel
+  SMPC_TRY(st->in(k->has_people, sb->has_people, B));
+  SMPC_TRY(st->in(k->costmap, sb->costmap, nmaps * (size_t)sb->size_x * sb->size_y));
+  return st->in(k->costmap_origin, sb->costmap_origin, nmaps * 2);
 }
 
 }  // namespace
@@ -552,18 +553,6 @@ smpc_handle* smpc_create(const smpc_params* p, int device) {
   smpc_handle* h = new smpc_handle();
   h->prm = *p;
   h->device = device;
-  h->stream = nullptr;
-  h->timed = false;
-  h->queue = nullptr;
-  h->share = 1;
-  h->stage_rec = nullptr;
-  h->stage_aux = nullptr;
-  h->stage_rec_bytes = h->stage_aux_bytes = 0;
-  h->stage = nullptr;
-  h->stage_cap = 0;
-  h->stage_want = 0;
-  h->pin = nullptr;
-  h->pin_cap = 0;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) != hipSuccess) { set_error("hipGetDeviceProperties failed"); delete h; return nullptr; }
   h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -619,53 +608,33 @@ int smpc_solve_batch(smpc_handle* h, const smpc_scene_batch* sb, smpc_result_bat
   SMPC_HIP_CHECK(hipSetDevice(h->device));
   smpc::KParams k;
   fill_kparams(h, sb, d, &k);
-  Staging st(h);
-  SMPC_TRY(bind_inputs(h, sb, d, &k, &st));
+  Staging st(h, sb->on_device);
+  SMPC_TRY(bind_inputs(sb, d, &k, &st));
   SMPC_TRY(bind_people(h, sb, k, &st));
   const size_t B = sb->B, T = sb->T;
-  if (sb->order) {  // queue order hint
-    if (sb->on_device) {
-      k.order = sb->order;
-    } else {
-      std::vector<uint8_t> seen(B, 0);
-      for (size_t i = 0; i < B; ++i) {
-        const int32_t v = sb->order[i];
-        if (v < 0 || (size_t)v >= B || seen[v]) { set_error("order is not a permutation of 0..B-1"); return SMPC_ERR_INVALID_ARG; }
-        seen[v] = 1;
-      }
-      SMPC_TRY(st.up(sb->order, B, &k.order, h->stream));
+  if (sb->order && !sb->on_device) {  // queue order hint
+    std::vector<uint8_t> seen(B, 0);
+    for (size_t i = 0; i < B; ++i) {
+      const int32_t v = sb->order[i];
+      if (v < 0 || (size_t)v >= B || seen[v]) { set_error("order is not a permutation of 0..B-1"); return SMPC_ERR_INVALID_ARG; }
+      seen[v] = 1;
     }
   }
-  if (sb->on_device) {
-    k.o_params = out->params; k.o_cmds = out->cmds; k.o_path = out->path; k.o_status = out->status; k.o_reason = out->reason;
-    k.o_iterations = out->iterations; k.o_evaluations = out->evaluations; k.o_initial_cost = out->initial_cost; k.o_final_cost = out->final_cost;
-    // a device-side order cannot be checked here: should it not be a permutation, the scenes it leaves out must not keep
-    // the status of an earlier call — every status starts as SMPC_NOT_SOLVED (-1) and is overwritten by the scene's solve
-    if (k.order && k.o_status && sb->B > 0) SMPC_HIP_CHECK(hipMemsetAsync(k.o_status, 0xFF, (size_t)sb->B * sizeof(int32_t), h->stream));
-    return launch(h, false, k);
-  }
-  SMPC_TRY(st.out(out->params, B * d.P, &k.o_params));
-  SMPC_TRY(st.out(out->cmds, B * (T + 1) * 2, &k.o_cmds));
-  SMPC_TRY(st.out(out->path, B * (T + 1) * 3, &k.o_path));
-  SMPC_TRY(st.out(out->status, B, &k.o_status));
-  SMPC_TRY(st.out(out->reason, B, &k.o_reason));
-  SMPC_TRY(st.out(out->iterations, B, &k.o_iterations));
-  SMPC_TRY(st.out(out->evaluations, B, &k.o_evaluations));
-  SMPC_TRY(st.out(out->initial_cost, B, &k.o_initial_cost));
-  SMPC_TRY(st.out(out->final_cost, B, &k.o_final_cost));
-  SMPC_TRY(st.flush_up(h->stream));
-  SMPC_TRY(launch(h, false, k));
-  SMPC_TRY(st.down(out->params, k.o_params, B * d.P, h->stream));
-  SMPC_TRY(st.down(out->cmds, k.o_cmds, B * (T + 1) * 2, h->stream));
-  SMPC_TRY(st.down(out->path, k.o_path, B * (T + 1) * 3, h->stream));
-  SMPC_TRY(st.down(out->status, k.o_status, B, h->stream));
-  SMPC_TRY(st.down(out->reason, k.o_reason, B, h->stream));
-  SMPC_TRY(st.down(out->iterations, k.o_iterations, B, h->stream));
-  SMPC_TRY(st.down(out->evaluations, k.o_evaluations, B, h->stream));
-  SMPC_TRY(st.down(out->initial_cost, k.o_initial_cost, B, h->stream));
-  SMPC_TRY(st.down(out->final_cost, k.o_final_cost, B, h->stream));
-  SMPC_TRY(st.finish(h->stream));
-  return SMPC_OK;
+  SMPC_TRY(st.in(k.order, sb->order, B));
+  SMPC_TRY(st.out(k.o_params, out->params, B * d.P));
+  SMPC_TRY(st.out(k.o_cmds, out->cmds, B * (T + 1) * 2));
+  SMPC_TRY(st.out(k.o_path, out->path, B * (T + 1) * 3));
+  SMPC_TRY(st.out(k.o_status, out->status, B));
+  SMPC_TRY(st.out(k.o_reason, out->reason, B));
+  SMPC_TRY(st.out(k.o_iterations, out->iterations, B));
+  SMPC_TRY(st.out(k.o_evaluations, out->evaluations, B));
+  SMPC_TRY(st.out(k.o_initial_cost, out->initial_cost, B));
+  SMPC_TRY(st.out(k.o_final_cost, out->final_cost, B));
+  // a device-side order cannot be checked here: should it not be a permutation, the scenes it leaves out must not keep
+  // the status of an earlier call — every status starts as SMPC_NOT_SOLVED (-1) and is overwritten by the scene's solve
+  if (sb->on_device && k.order && k.o_status && B > 0) SMPC_HIP_CHECK(hipMemsetAsync(k.o_status, 0xFF, B * sizeof(int32_t), h->stream));
+  SMPC_TRY(launch(h, st, false, k));
+  return st.finish();
 }
 
 int smpc_project_people_batch(smpc_handle* h, const smpc_projection_batch* in, double* people_proj, int32_t* error) {
@@ -690,34 +659,19 @@ int smpc_project_people_batch(smpc_handle* h, const smpc_projection_batch* in, d
   p.od_shared = in->od_shared; p.od_width = in->od_width; p.od_height = in->od_height;
   const size_t B = in->B, T = in->T, N = in->N;
   const size_t ngrid = in->od_shared ? 1 : B;
-  Staging st(h);
-  if (in->on_device) {
-    p.init_people = in->init_people; p.robot_path = in->robot_path; p.od_indexes = in->od_indexes; p.od_origin = in->od_origin;
-    p.people_proj = people_proj; p.error = error;
-  } else {
-    SMPC_TRY(st.up(in->init_people, B * N * 6, &p.init_people, h->stream));
-    SMPC_TRY(st.up(in->robot_path, B * (T + 1) * 6, &p.robot_path, h->stream));
-    SMPC_TRY(st.up(in->od_indexes, ngrid * (size_t)in->od_width * in->od_height, &p.od_indexes, h->stream));
-    SMPC_TRY(st.up(in->od_origin, ngrid * 2, &p.od_origin, h->stream));
-    SMPC_TRY(st.out(people_proj, B * (T + 1) * 6 * N, &p.people_proj));
-    SMPC_TRY(st.out(error, B, &p.error));
-  }
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.init_people, in->init_people, B * N * 6));
+  SMPC_TRY(st.in(p.robot_path, in->robot_path, B * (T + 1) * 6));
+  SMPC_TRY(st.in(p.od_indexes, in->od_indexes, ngrid * (size_t)in->od_width * in->od_height));
+  SMPC_TRY(st.in(p.od_origin, in->od_origin, ngrid * 2));
+  SMPC_TRY(st.out(p.people_proj, people_proj, B * (T + 1) * 6 * N));
+  SMPC_TRY(st.out(p.error, error, B));
   if (B > 0) {
     const int per_wave = smpc::kWave / (G * p.H);
     const int grid = (int)((B + per_wave - 1) / per_wave);
-    SMPC_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
-    SMPC_TRY(st.flush_up(h->stream));
-    hipLaunchKernelGGL(smpc::smpc_project_kernel, dim3(grid), dim3(smpc::kWave), 0, h->stream, p);
-    SMPC_HIP_CHECK(hipGetLastError());
-    SMPC_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
+    SMPC_TRY(st.timed([&] { hipLaunchKernelGGL(smpc::smpc_project_kernel, dim3(grid), dim3(smpc::kWave), 0, h->stream, p); return SMPC_OK; }));
   }
-  if (!in->on_device) {
-    SMPC_TRY(st.down(people_proj, p.people_proj, B * (T + 1) * 6 * N, h->stream));
-    SMPC_TRY(st.down(error, p.error, B, h->stream));
-    SMPC_TRY(st.finish(h->stream));
-  }
-  return SMPC_OK;
+  return st.finish();
 }
 
 int smpc_obstacle_distance_batch(smpc_handle* h, const smpc_obstacle_distance_in* in, smpc_obstacle_distance_out* out) {
@@ -736,30 +690,18 @@ int smpc_obstacle_distance_batch(smpc_handle* h, const smpc_obstacle_distance_in
   p.min_cost = in->obstacle_min_cost; p.unknown_is_obstacle = in->unknown_is_obstacle ? 1 : 0;
   p.resolution = (float)in->resolution;
   const size_t ngrid = in->costmap_shared ? 1 : (size_t)in->B, cells = ngrid * (size_t)in->size_x * in->size_y;
-  Staging st(h);
-  if (in->on_device) {
-    p.costmap = in->costmap; p.indexes = out->indexes; p.distances = out->distances; p.n_obstacles = out->n_obstacles;
-  } else {
-    SMPC_TRY(st.up(in->costmap, cells, &p.costmap, h->stream));
-    SMPC_TRY(st.out(out->indexes, cells, &p.indexes));
-    SMPC_TRY(st.out(out->distances, cells, &p.distances));
-    SMPC_TRY(st.out(out->n_obstacles, ngrid, &p.n_obstacles));
-  }
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.costmap, in->costmap, cells));
+  SMPC_TRY(st.out(p.indexes, out->indexes, cells));
+  SMPC_TRY(st.out(p.distances, out->distances, cells));
+  SMPC_TRY(st.out(p.n_obstacles, out->n_obstacles, ngrid));
   if (ngrid > 0) {
-    SMPC_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
-    SMPC_TRY(st.flush_up(h->stream));
-    hipLaunchKernelGGL(smpc::smpc_obstacle_distance_kernel, dim3((unsigned)ngrid), dim3(smpc::kOdThreads), 0, h->stream, p);
-    SMPC_HIP_CHECK(hipGetLastError());
-    SMPC_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
+    SMPC_TRY(st.timed([&] {
+      hipLaunchKernelGGL(smpc::smpc_obstacle_distance_kernel, dim3((unsigned)ngrid), dim3(smpc::kOdThreads), 0, h->stream, p);
+      return SMPC_OK;
+    }));
   }
-  if (!in->on_device) {
-    SMPC_TRY(st.down(out->indexes, p.indexes, cells, h->stream));
-    SMPC_TRY(st.down(out->distances, p.distances, cells, h->stream));
-    SMPC_TRY(st.down(out->n_obstacles, p.n_obstacles, ngrid, h->stream));
-    SMPC_TRY(st.finish(h->stream));
-  }
-  return SMPC_OK;
+  return st.finish();
 }
 
 int smpc_people_to_status_batch(smpc_handle* h, const smpc_people_batch* in, double* init_people, uint8_t* has_people) {
@@ -777,34 +719,21 @@ int smpc_people_to_status_batch(smpc_handle* h, const smpc_people_batch* in, dou
   }
   p.fov_angle = in->fov_angle; p.costmap_shared = in->costmap_shared; p.size_x = in->size_x; p.size_y = in->size_y;
   p.resolution = in->resolution;
-  Staging st(h);
-  if (in->on_device) {
-    p.people = in->people; p.count = in->count; p.init_people = init_people; p.has_people = has_people;
-    p.robot_pose = in->robot_pose; p.costmap_origin = in->costmap_origin;
-  } else {
-    SMPC_TRY(st.up(in->people, B * Np * 5, &p.people, h->stream));
-    SMPC_TRY(st.up(in->count, B, &p.count, h->stream));
-    if (filter) {
-      SMPC_TRY(st.up(in->robot_pose, B * 3, &p.robot_pose, h->stream));
-      SMPC_TRY(st.up(in->costmap_origin, (in->costmap_shared ? 1 : B) * 2, &p.costmap_origin, h->stream));
-    }
-    SMPC_TRY(st.out(init_people, B * N * 6, &p.init_people));
-    SMPC_TRY(st.out(has_people, B, &p.has_people));
-  }
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.people, in->people, B * Np * 5));
+  SMPC_TRY(st.in(p.count, in->count, B));
+  SMPC_TRY(st.in(p.robot_pose, in->robot_pose, B * 3));
+  // read by the field-of-view filter alone
+  SMPC_TRY(st.in(p.costmap_origin, filter ? in->costmap_origin : nullptr, (in->costmap_shared ? 1 : B) * 2));
+  SMPC_TRY(st.out(p.init_people, init_people, B * N * 6));
+  SMPC_TRY(st.out(p.has_people, has_people, B));
   if (B > 0) {
-    SMPC_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
-    SMPC_TRY(st.flush_up(h->stream));
-    hipLaunchKernelGGL(smpc::smpc_people_to_status_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, p);
-    SMPC_HIP_CHECK(hipGetLastError());
-    SMPC_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
+    SMPC_TRY(st.timed([&] {
+      hipLaunchKernelGGL(smpc::smpc_people_to_status_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, p);
+      return SMPC_OK;
+    }));
   }
-  if (!in->on_device) {
-    SMPC_TRY(st.down(init_people, p.init_people, B * N * 6, h->stream));
-    SMPC_TRY(st.down(has_people, p.has_people, B, h->stream));
-    SMPC_TRY(st.finish(h->stream));
-  }
-  return SMPC_OK;
+  return st.finish();
 }
 
 int smpc_format_to_optimize_batch(smpc_handle* h, const smpc_format_batch* in, smpc_format_out* out) {
@@ -829,54 +758,31 @@ int smpc_format_to_optimize_batch(smpc_handle* h, const smpc_format_batch* in, s
   if (in->n_poses && !in->memory.length) {
     set_error("n_poses needs memory.length: records of scenes with horizons of their own differ in size"); return SMPC_ERR_INVALID_ARG;
   }
-  Staging st(h);
-  if (in->on_device) {
-    p.path = in->path; p.cmds = in->cmds; p.speed = in->speed; p.n_poses = in->n_poses;
-    p.prev_path = in->memory.prev_path; p.prev_cmds = in->memory.prev_cmds; p.valid = in->memory.valid; p.length = in->memory.length;
-    p.robot_status = out->robot_status; p.pose0 = out->pose0; p.init_params = out->init_params;
-    p.path_pts = out->path_pts; p.goal_yaw = out->goal_yaw; p.T_scene = out->T_scene;
-  } else {
-    const double* c = nullptr; const int32_t* ci = nullptr;
-    SMPC_TRY(st.up(in->n_poses, B, &p.n_poses, h->stream));
-    SMPC_TRY(st.up(static_cast<const int32_t*>(in->memory.length), B * 2, &ci, h->stream)); p.length = const_cast<int32_t*>(ci);
-    SMPC_TRY(st.out(out->T_scene, B, &p.T_scene));
-    SMPC_TRY(st.up(in->path, B * rows * 3, &p.path, h->stream));
-    SMPC_TRY(st.up(in->cmds, B * rows * 2, &p.cmds, h->stream));
-    SMPC_TRY(st.up(in->speed, B * 2, &p.speed, h->stream));
-    SMPC_TRY(st.up(static_cast<const double*>(in->memory.prev_path), B * Tp * 3, &c, h->stream)); p.prev_path = const_cast<double*>(c);
-    SMPC_TRY(st.up(static_cast<const double*>(in->memory.prev_cmds), B * Tp * 2, &c, h->stream)); p.prev_cmds = const_cast<double*>(c);
-    SMPC_TRY(st.up(static_cast<const int32_t*>(in->memory.valid), B, &ci, h->stream)); p.valid = const_cast<int32_t*>(ci);
-    SMPC_TRY(st.out(out->robot_status, B * Tp * 6, &p.robot_status));
-    SMPC_TRY(st.out(out->pose0, B * 3, &p.pose0));
-    SMPC_TRY(st.out(out->init_params, B * (size_t)d.P, &p.init_params));
-    SMPC_TRY(st.out(out->path_pts, B * Tp * 2, &p.path_pts));
-    SMPC_TRY(st.out(out->goal_yaw, B, &p.goal_yaw));
-  }
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.n_poses, in->n_poses, B));
+  SMPC_TRY(st.inout(p.length, in->memory.length, B * 2));
+  SMPC_TRY(st.out(p.T_scene, out->T_scene, B));
+  SMPC_TRY(st.in(p.path, in->path, B * rows * 3));
+  SMPC_TRY(st.in(p.cmds, in->cmds, B * rows * 2));
+  SMPC_TRY(st.in(p.speed, in->speed, B * 2));
+  SMPC_TRY(st.inout(p.prev_path, in->memory.prev_path, B * Tp * 3));
+  SMPC_TRY(st.inout(p.prev_cmds, in->memory.prev_cmds, B * Tp * 2));
+  SMPC_TRY(st.inout(p.valid, in->memory.valid, B));
+  SMPC_TRY(st.out(p.robot_status, out->robot_status, B * Tp * 6));
+  SMPC_TRY(st.out(p.pose0, out->pose0, B * 3));
+  SMPC_TRY(st.out(p.init_params, out->init_params, B * (size_t)d.P));
+  SMPC_TRY(st.out(p.path_pts, out->path_pts, B * Tp * 2));
+  SMPC_TRY(st.out(p.goal_yaw, out->goal_yaw, B));
   if (B > 0) {
     const long long n = (long long)B * (long long)Tp;
-    SMPC_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
-    SMPC_TRY(st.flush_up(h->stream));
-    hipLaunchKernelGGL(smpc::smpc_format_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, p);
-    SMPC_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(smpc::smpc_format_mark_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, p);
-    SMPC_HIP_CHECK(hipGetLastError());
-    SMPC_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
+    SMPC_TRY(st.timed([&] {
+      hipLaunchKernelGGL(smpc::smpc_format_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, p);
+      SMPC_HIP_CHECK(hipGetLastError());
+      hipLaunchKernelGGL(smpc::smpc_format_mark_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, p);
+      return SMPC_OK;
+    }));
   }
-  if (!in->on_device) {
-    SMPC_TRY(st.down(out->robot_status, p.robot_status, B * Tp * 6, h->stream));
-    SMPC_TRY(st.down(out->pose0, p.pose0, B * 3, h->stream));
-    SMPC_TRY(st.down(out->init_params, p.init_params, B * (size_t)d.P, h->stream));
-    SMPC_TRY(st.down(out->path_pts, p.path_pts, B * Tp * 2, h->stream));
-    SMPC_TRY(st.down(out->goal_yaw, p.goal_yaw, B, h->stream));
-    SMPC_TRY(st.down(in->memory.prev_path, p.prev_path, B * Tp * 3, h->stream));
-    SMPC_TRY(st.down(in->memory.prev_cmds, p.prev_cmds, B * Tp * 2, h->stream));
-    SMPC_TRY(st.down(in->memory.valid, p.valid, B, h->stream));
-    SMPC_TRY(st.down(in->memory.length, p.length, B * 2, h->stream));
-    SMPC_TRY(st.down(out->T_scene, p.T_scene, B, h->stream));
-    SMPC_TRY(st.finish(h->stream));
-  }
-  return SMPC_OK;
+  return st.finish();
 }
 
 int smpc_memory_store_batch(smpc_handle* h, int32_t B_, int32_t T, int32_t on_device, const int32_t* status,
@@ -885,46 +791,31 @@ int smpc_memory_store_batch(smpc_handle* h, int32_t B_, int32_t T, int32_t on_de
     set_error("null handle / array / memory record"); return SMPC_ERR_INVALID_ARG;
   }
   if (B_ < 0 || T < 1) { set_error("bad B/T"); return SMPC_ERR_INVALID_ARG; }
+  if (T_scene && !memory->length) {
+    set_error("T_scene needs memory.length: records of scenes with horizons of their own differ in size"); return SMPC_ERR_INVALID_ARG;
+  }
   SMPC_HIP_CHECK(hipSetDevice(h->device));
   const size_t B = B_, Tp = (size_t)T + 1;
   smpc::StoreParams p;
   std::memset(&p, 0, sizeof(p));
   p.B = B_; p.T = T;
-  Staging st(h);
-  if (T_scene && !memory->length) {
-    set_error("T_scene needs memory.length: records of scenes with horizons of their own differ in size"); return SMPC_ERR_INVALID_ARG;
-  }
-  if (on_device) {
-    p.status = status; p.path = path; p.cmds = cmds; p.T_scene = T_scene;
-    p.prev_path = memory->prev_path; p.prev_cmds = memory->prev_cmds; p.valid = memory->valid; p.length = memory->length;
-  } else {
-    const double* c = nullptr; const int32_t* ci = nullptr;
-    SMPC_TRY(st.up(T_scene, B, &p.T_scene, h->stream));
-    SMPC_TRY(st.up(static_cast<const int32_t*>(memory->length), B * 2, &ci, h->stream)); p.length = const_cast<int32_t*>(ci);
-    SMPC_TRY(st.up(status, B, &p.status, h->stream));
-    SMPC_TRY(st.up(path, B * Tp * 3, &p.path, h->stream));
-    SMPC_TRY(st.up(cmds, B * Tp * 2, &p.cmds, h->stream));
-    SMPC_TRY(st.up(static_cast<const double*>(memory->prev_path), B * Tp * 3, &c, h->stream)); p.prev_path = const_cast<double*>(c);
-    SMPC_TRY(st.up(static_cast<const double*>(memory->prev_cmds), B * Tp * 2, &c, h->stream)); p.prev_cmds = const_cast<double*>(c);
-    SMPC_TRY(st.up(static_cast<const int32_t*>(memory->valid), B, &ci, h->stream)); p.valid = const_cast<int32_t*>(ci);
-  }
+  Staging st(h, on_device);
+  SMPC_TRY(st.in(p.T_scene, T_scene, B));
+  SMPC_TRY(st.inout(p.length, memory->length, B * 2));
+  SMPC_TRY(st.in(p.status, status, B));
+  SMPC_TRY(st.in(p.path, path, B * Tp * 3));
+  SMPC_TRY(st.in(p.cmds, cmds, B * Tp * 2));
+  SMPC_TRY(st.inout(p.prev_path, memory->prev_path, B * Tp * 3));
+  SMPC_TRY(st.inout(p.prev_cmds, memory->prev_cmds, B * Tp * 2));
+  SMPC_TRY(st.inout(p.valid, memory->valid, B));
   if (B > 0) {
     const long long n = (long long)B * (long long)Tp;
-    SMPC_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
-    SMPC_TRY(st.flush_up(h->stream));
-    hipLaunchKernelGGL(smpc::smpc_memory_store_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, p);
-    SMPC_HIP_CHECK(hipGetLastError());
-    SMPC_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
+    SMPC_TRY(st.timed([&] {
+      hipLaunchKernelGGL(smpc::smpc_memory_store_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, p);
+      return SMPC_OK;
+    }));
   }
-  if (!on_device) {
-    SMPC_TRY(st.down(memory->prev_path, p.prev_path, B * Tp * 3, h->stream));
-    SMPC_TRY(st.down(memory->prev_cmds, p.prev_cmds, B * Tp * 2, h->stream));
-    SMPC_TRY(st.down(memory->valid, p.valid, B, h->stream));
-    SMPC_TRY(st.down(memory->length, p.length, B * 2, h->stream));
-    SMPC_TRY(st.finish(h->stream));
-  }
-  return SMPC_OK;
+  return st.finish();
 }
 
 int smpc_trajectorize_path_batch(smpc_handle* h, const smpc_trajectorize_batch* in, smpc_trajectorize_out* out) {
@@ -940,20 +831,15 @@ int smpc_trajectorize_path_batch(smpc_handle* h, const smpc_trajectorize_batch* 
   p.desired_linear_vel = in->desired_linear_vel; p.lookahead_dist = in->lookahead_dist;
   p.max_angular_vel = in->max_angular_vel; p.time_step = in->time_step;
   smpc::fill_math_table(&p.mt);
-  Staging st(h);
-  if (in->on_device) {
-    p.plan = in->plan; p.plan_len = in->plan_len; p.robot_pose = in->robot_pose;
-    p.path = out->path; p.cmds = out->cmds; p.cmds_vy = out->cmds_vy; p.n_poses = out->n_poses; p.error = out->error;
-  } else {
-    SMPC_TRY(st.up(in->plan, B * L * 2, &p.plan, h->stream));
-    SMPC_TRY(st.up(in->plan_len, B, &p.plan_len, h->stream));
-    SMPC_TRY(st.up(in->robot_pose, B * 3, &p.robot_pose, h->stream));
-    SMPC_TRY(st.out(out->path, B * S1 * 3, &p.path));
-    SMPC_TRY(st.out(out->cmds, B * S1 * 2, &p.cmds));
-    SMPC_TRY(st.out(out->cmds_vy, B * S1, &p.cmds_vy));
-    SMPC_TRY(st.out(out->n_poses, B, &p.n_poses));
-    SMPC_TRY(st.out(out->error, B, &p.error));
-  }
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.plan, in->plan, B * L * 2));
+  SMPC_TRY(st.in(p.plan_len, in->plan_len, B));
+  SMPC_TRY(st.in(p.robot_pose, in->robot_pose, B * 3));
+  SMPC_TRY(st.out(p.path, out->path, B * S1 * 3));
+  SMPC_TRY(st.out(p.cmds, out->cmds, B * S1 * 2));
+  SMPC_TRY(st.out(p.cmds_vy, out->cmds_vy, B * S1));
+  SMPC_TRY(st.out(p.n_poses, out->n_poses, B));
+  SMPC_TRY(st.out(p.error, out->error, B));
   if (B > 0) {
     const int per_wave = smpc::kWave / smpc::kTrajGroup;
     // plans of up to 512 poses stay in registers (kR poses per lane of a 16-lane group); the raw step outputs are parked
@@ -966,38 +852,28 @@ int smpc_trajectorize_path_batch(smpc_handle* h, const smpc_trajectorize_batch* 
     const size_t park = park_wave * (threads / smpc::kWave);
     const dim3 grid((unsigned)((B + per_block - 1) / per_block)), block(threads);
     const int need = (int)((L + smpc::kTrajGroup - 1) / smpc::kTrajGroup);
-    SMPC_TRY(st.flush_up(h->stream));
-    SMPC_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
     // plans over 512 poses: one-wavefront blocks of the 8-slot kernel with the reachable poses compacted into LDS
     const size_t list_wave = (size_t)per_wave * 8 * smpc::kTrajGroup * 2 * sizeof(double);
-    if (need > 32 && park_wave + list_wave <= 48 * 1024) {
-      p.compact = 1;
-      hipLaunchKernelGGL(smpc::smpc_trajectorize_kernel<8>, dim3((unsigned)((B + per_wave - 1) / per_wave)), dim3(smpc::kWave),
-                         park_wave + list_wave, h->stream, p);
-    } else if (need > 32 || park > 48 * 1024) {
-      hipLaunchKernelGGL(smpc::smpc_trajectorize_long_kernel, dim3((unsigned)((B + per_wave - 1) / per_wave)), dim3(smpc::kWave), 0, h->stream, p);
-    } else if (need <= 8) {
-      hipLaunchKernelGGL(smpc::smpc_trajectorize_kernel<8>, grid, block, park, h->stream, p);
-    } else if (need <= 16) {
-      hipLaunchKernelGGL(smpc::smpc_trajectorize_kernel<16>, grid, block, park, h->stream, p);
-    } else if (need <= 25) {
-      hipLaunchKernelGGL(smpc::smpc_trajectorize_kernel<25>, grid, block, park, h->stream, p);
-    } else {
-      hipLaunchKernelGGL(smpc::smpc_trajectorize_kernel<32>, grid, block, park, h->stream, p);
-    }
-    SMPC_HIP_CHECK(hipGetLastError());
-    SMPC_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
+    SMPC_TRY(st.timed([&] {
+      if (need > 32 && park_wave + list_wave <= 48 * 1024) {
+        p.compact = 1;
+        hipLaunchKernelGGL(smpc::smpc_trajectorize_kernel<8>, dim3((unsigned)((B + per_wave - 1) / per_wave)), dim3(smpc::kWave),
+                           park_wave + list_wave, h->stream, p);
+      } else if (need > 32 || park > 48 * 1024) {
+        hipLaunchKernelGGL(smpc::smpc_trajectorize_long_kernel, dim3((unsigned)((B + per_wave - 1) / per_wave)), dim3(smpc::kWave), 0, h->stream, p);
+      } else if (need <= 8) {
+        hipLaunchKernelGGL(smpc::smpc_trajectorize_kernel<8>, grid, block, park, h->stream, p);
+      } else if (need <= 16) {
+        hipLaunchKernelGGL(smpc::smpc_trajectorize_kernel<16>, grid, block, park, h->stream, p);
+      } else if (need <= 25) {
+        hipLaunchKernelGGL(smpc::smpc_trajectorize_kernel<25>, grid, block, park, h->stream, p);
+      } else {
+        hipLaunchKernelGGL(smpc::smpc_trajectorize_kernel<32>, grid, block, park, h->stream, p);
+      }
+      return SMPC_OK;
+    }));
   }
-  if (!in->on_device) {
-    SMPC_TRY(st.down(out->path, p.path, B * S1 * 3, h->stream));
-    SMPC_TRY(st.down(out->cmds, p.cmds, B * S1 * 2, h->stream));
-    SMPC_TRY(st.down(out->cmds_vy, p.cmds_vy, B * S1, h->stream));
-    SMPC_TRY(st.down(out->n_poses, p.n_poses, B, h->stream));
-    SMPC_TRY(st.down(out->error, p.error, B, h->stream));
-    SMPC_TRY(st.finish(h->stream));
-  }
-  return SMPC_OK;
+  return st.finish();
 }
 
 int smpc_transform_global_plan_batch(smpc_handle* h, const smpc_plan_window_batch* in, double* window, int32_t* window_len,
@@ -1010,38 +886,22 @@ int smpc_transform_global_plan_batch(smpc_handle* h, const smpc_plan_window_batc
   smpc::WindowParams p;
   std::memset(&p, 0, sizeof(p));
   p.B = in->B; p.L = in->L; p.search_dist = in->max_robot_pose_search_dist; p.dist_threshold = in->dist_threshold;
-  Staging st(h);
-  if (in->on_device) {
-    p.plan = in->plan; p.plan_len = in->plan_len; p.plan_start = in->plan_start; p.robot_pose = in->robot_pose;
-    p.to_local = in->to_local; p.window = window; p.window_len = window_len; p.error = error;
-  } else {
-    const int32_t* start_in = nullptr;
-    SMPC_TRY(st.up(in->plan, B * L * 2, &p.plan, h->stream));
-    SMPC_TRY(st.up(in->plan_len, B, &p.plan_len, h->stream));
-    SMPC_TRY(st.up(static_cast<const int32_t*>(in->plan_start), B, &start_in, h->stream));
-    p.plan_start = const_cast<int32_t*>(start_in);  // device copy: read, updated in place, copied back below
-    SMPC_TRY(st.up(in->robot_pose, B * 3, &p.robot_pose, h->stream));
-    if (in->to_local) SMPC_TRY(st.up(in->to_local, B * 3, &p.to_local, h->stream));
-    SMPC_TRY(st.out(window, B * L * 2, &p.window));
-    SMPC_TRY(st.out(window_len, B, &p.window_len));
-    SMPC_TRY(st.out(error, B, &p.error));
-  }
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.plan, in->plan, B * L * 2));
+  SMPC_TRY(st.in(p.plan_len, in->plan_len, B));
+  SMPC_TRY(st.inout(p.plan_start, in->plan_start, B));
+  SMPC_TRY(st.in(p.robot_pose, in->robot_pose, B * 3));
+  SMPC_TRY(st.in(p.to_local, in->to_local, B * 3));
+  SMPC_TRY(st.out(p.window, window, B * L * 2));
+  SMPC_TRY(st.out(p.window_len, window_len, B));
+  SMPC_TRY(st.out(p.error, error, B));
   if (B > 0) {
-    SMPC_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
-    SMPC_TRY(st.flush_up(h->stream));
-    hipLaunchKernelGGL(smpc::smpc_plan_window_kernel, dim3((unsigned)B), dim3(smpc::kWave), 0, h->stream, p);
-    SMPC_HIP_CHECK(hipGetLastError());
-    SMPC_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
+    SMPC_TRY(st.timed([&] {
+      hipLaunchKernelGGL(smpc::smpc_plan_window_kernel, dim3((unsigned)B), dim3(smpc::kWave), 0, h->stream, p);
+      return SMPC_OK;
+    }));
   }
-  if (!in->on_device) {
-    SMPC_TRY(st.down(window, p.window, B * L * 2, h->stream));
-    SMPC_TRY(st.down(window_len, p.window_len, B, h->stream));
-    SMPC_TRY(st.down(in->plan_start, static_cast<const int32_t*>(p.plan_start), B, h->stream));
-    SMPC_TRY(st.down(error, p.error, B, h->stream));
-    SMPC_TRY(st.finish(h->stream));
-  }
-  return SMPC_OK;
+  return st.finish();
 }
 
 int smpc_select_command_batch(smpc_handle* h, int32_t B_, int32_t T, int32_t traj_rows, int32_t on_device, const int32_t* traj_n_poses,
@@ -1054,33 +914,21 @@ int smpc_select_command_batch(smpc_handle* h, int32_t B_, int32_t T, int32_t tra
   smpc::SelectParams p;
   std::memset(&p, 0, sizeof(p));
   p.B = B_; p.T = T; p.rows = traj_rows;
-  Staging st(h);
-  if (on_device) {
-    p.traj_n = traj_n_poses; p.traj_cmds = traj_cmds; p.status = status; p.cmds = cmds; p.cmd_vel = cmd_vel; p.source = source;
-    p.window_error = window_error;
-  } else {
-    SMPC_TRY(st.up(window_error, B, &p.window_error, h->stream));
-    SMPC_TRY(st.up(traj_n_poses, B, &p.traj_n, h->stream));
-    SMPC_TRY(st.up(traj_cmds, B * (size_t)traj_rows * 2, &p.traj_cmds, h->stream));
-    SMPC_TRY(st.up(status, B, &p.status, h->stream));
-    SMPC_TRY(st.up(cmds, B * ((size_t)T + 1) * 2, &p.cmds, h->stream));
-    SMPC_TRY(st.out(cmd_vel, B * 2, &p.cmd_vel));
-    SMPC_TRY(st.out(source, B, &p.source));
-  }
+  Staging st(h, on_device);
+  SMPC_TRY(st.in(p.window_error, window_error, B));
+  SMPC_TRY(st.in(p.traj_n, traj_n_poses, B));
+  SMPC_TRY(st.in(p.traj_cmds, traj_cmds, B * (size_t)traj_rows * 2));
+  SMPC_TRY(st.in(p.status, status, B));
+  SMPC_TRY(st.in(p.cmds, cmds, B * ((size_t)T + 1) * 2));
+  SMPC_TRY(st.out(p.cmd_vel, cmd_vel, B * 2));
+  SMPC_TRY(st.out(p.source, source, B));
   if (B > 0) {
-    SMPC_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
-    SMPC_TRY(st.flush_up(h->stream));
-    hipLaunchKernelGGL(smpc::smpc_select_command_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, p);
-    SMPC_HIP_CHECK(hipGetLastError());
-    SMPC_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
+    SMPC_TRY(st.timed([&] {
+      hipLaunchKernelGGL(smpc::smpc_select_command_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, p);
+      return SMPC_OK;
+    }));
   }
-  if (!on_device) {
-    SMPC_TRY(st.down(cmd_vel, p.cmd_vel, B * 2, h->stream));
-    SMPC_TRY(st.down(source, p.source, B, h->stream));
-    SMPC_TRY(st.finish(h->stream));
-  }
-  return SMPC_OK;
+  return st.finish();
 }
 
 int smpc_stage_people_batch(smpc_handle* h, const smpc_scene_batch* sb, double* records, double* aux) {
@@ -1095,30 +943,19 @@ int smpc_stage_people_batch(smpc_handle* h, const smpc_scene_batch* sb, double* 
   smpc::fill_math_table(&k.mt);
   const size_t B = sb->B, T = sb->T, N = sb->N;
   const size_t nrec = B * N * T * 4, naux = B * T * 2;
-  Staging st(h);
-  double *drec = records, *daux = aux;
-  if (sb->on_device) {
-    k.pose0 = sb->pose0; k.people = sb->people; k.has_people = sb->has_people;
-  } else {
-    SMPC_TRY(st.up(sb->pose0, B * 3, &k.pose0, h->stream));
-    SMPC_TRY(st.up(sb->people, B * (T + 1) * 6 * N, &k.people, h->stream));
-    SMPC_TRY(st.up(sb->has_people, B, &k.has_people, h->stream));
-    SMPC_TRY(st.out(records, nrec, &drec));
-    SMPC_TRY(st.out(aux, naux, &daux));
-    SMPC_HIP_CHECK(hipMemsetAsync(drec, 0, nrec * sizeof(double), h->stream));  // scenes without people: defined bytes
+  Staging st(h, sb->on_device);
+  double *drec = nullptr, *daux = nullptr;
+  SMPC_TRY(st.in(k.pose0, sb->pose0, B * 3));
+  SMPC_TRY(st.in(k.people, sb->people, B * (T + 1) * 6 * N));
+  SMPC_TRY(st.in(k.has_people, sb->has_people, B));
+  SMPC_TRY(st.out(drec, records, nrec));
+  SMPC_TRY(st.out(daux, aux, naux));
+  if (!sb->on_device) {  // scenes without people: defined bytes
+    SMPC_HIP_CHECK(hipMemsetAsync(drec, 0, nrec * sizeof(double), h->stream));
     SMPC_HIP_CHECK(hipMemsetAsync(daux, 0, naux * sizeof(double), h->stream));
   }
-  SMPC_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
-  SMPC_TRY(st.flush_up(h->stream));
-  SMPC_TRY(launch_stage(h, k, drec, daux));
-  SMPC_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-  h->timed = true;
-  if (!sb->on_device) {
-    SMPC_TRY(st.down(records, drec, nrec, h->stream));
-    SMPC_TRY(st.down(aux, daux, naux, h->stream));
-    SMPC_TRY(st.finish(h->stream));
-  }
-  return SMPC_OK;
+  SMPC_TRY(st.timed([&] { return launch_stage(h, k, drec, daux); }));
+  return st.finish();
 }
 
 double smpc_fp64_peak_probe(smpc_handle* h, int32_t iters) {
@@ -1153,20 +990,17 @@ int smpc_math_probe(smpc_handle* h, int32_t fn, int32_t n, const double* a, cons
   p.fn = fn; p.n = n;
   smpc::fill_math_table(&p.mt);
   smpc::fill_atan_nodes(&p.an);
-  Staging st(h);
-  SMPC_TRY(st.up(a, (size_t)n * (fn == 7 ? 8 : 1), &p.a, h->stream));
-  SMPC_TRY(st.up(b, (size_t)n, &p.b, h->stream));
-  SMPC_TRY(st.out(out0, (size_t)n, &p.o0));
-  SMPC_TRY(st.out(out1, (size_t)n, &p.o1));
-  if (n > 0) {
-    SMPC_TRY(st.flush_up(h->stream));
+  Staging st(h, false);  // host arrays only
+  SMPC_TRY(st.in(p.a, a, (size_t)n * (fn == 7 ? 8 : 1)));
+  SMPC_TRY(st.in(p.b, b, (size_t)n));
+  SMPC_TRY(st.out(p.o0, out0, (size_t)n));
+  SMPC_TRY(st.out(p.o1, out1, (size_t)n));
+  if (n > 0) {  // a diagnostic: not timed
+    SMPC_TRY(st.flush_up());
     hipLaunchKernelGGL(smpc::smpc_math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, p);
     SMPC_HIP_CHECK(hipGetLastError());
   }
-  SMPC_TRY(st.down(out0, p.o0, (size_t)n, h->stream));
-  SMPC_TRY(st.down(out1, p.o1, (size_t)n, h->stream));
-  SMPC_TRY(st.finish(h->stream));
-  return SMPC_OK;
+  return st.finish();
 }
 
 int smpc_eval_batch(smpc_handle* h, const smpc_scene_batch* sb, const double* params, smpc_eval_batch_out* out) {
@@ -1177,30 +1011,18 @@ int smpc_eval_batch(smpc_handle* h, const smpc_scene_batch* sb, const double* pa
   SMPC_HIP_CHECK(hipSetDevice(h->device));
   smpc::KParams k;
   fill_kparams(h, sb, d, &k);
-  Staging st(h);
-  SMPC_TRY(bind_inputs(h, sb, d, &k, &st));
+  Staging st(h, sb->on_device);
+  SMPC_TRY(bind_inputs(sb, d, &k, &st));
   SMPC_TRY(bind_people(h, sb, k, &st));
   const size_t B = sb->B;
-  if (sb->on_device) {
-    k.e_x = params;
-    k.e_residuals = out->residuals; k.e_jacobian = out->jacobian; k.e_cost = out->cost; k.e_gradient = out->gradient;
-    k.e_row_order = out->row_order;
-    return launch(h, true, k);
-  }
   k.e_row_order = out->row_order;
-  SMPC_TRY(st.up(params, B * d.P, &k.e_x, h->stream));
-  SMPC_TRY(st.out(out->residuals, B * d.M, &k.e_residuals));
-  SMPC_TRY(st.out(out->jacobian, B * d.M * d.P, &k.e_jacobian));
-  SMPC_TRY(st.out(out->cost, B, &k.e_cost));
-  SMPC_TRY(st.out(out->gradient, B * d.P, &k.e_gradient));
-  SMPC_TRY(st.flush_up(h->stream));
-  SMPC_TRY(launch(h, true, k));
-  SMPC_TRY(st.down(out->residuals, k.e_residuals, B * d.M, h->stream));
-  SMPC_TRY(st.down(out->jacobian, k.e_jacobian, B * d.M * d.P, h->stream));
-  SMPC_TRY(st.down(out->cost, k.e_cost, B, h->stream));
-  SMPC_TRY(st.down(out->gradient, k.e_gradient, B * d.P, h->stream));
-  SMPC_TRY(st.finish(h->stream));
-  return SMPC_OK;
+  SMPC_TRY(st.in(k.e_x, params, B * d.P));
+  SMPC_TRY(st.out(k.e_residuals, out->residuals, B * d.M));
+  SMPC_TRY(st.out(k.e_jacobian, out->jacobian, B * d.M * d.P));
+  SMPC_TRY(st.out(k.e_cost, out->cost, B));
+  SMPC_TRY(st.out(k.e_gradient, out->gradient, B * d.P));
+  SMPC_TRY(launch(h, st, true, k));
+  return st.finish();
 }
 
 }  // extern "C"
