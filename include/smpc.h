@@ -50,7 +50,9 @@ enum smpc_linear_solver {
 /* Per-scene termination, mirrors ceres::TerminationType as far as Optimizer::optimize observes it
  * (summary.IsSolutionUsable(), src/optimizer.cpp:384). */
 enum smpc_status {
-  SMPC_NOT_SOLVED = -1,    /* only with a device-side `order` that is not a permutation: the scene was never handed out */
+  SMPC_NOT_SOLVED = -1,    /* only with a device-side `order` that is not a permutation: the scene was never handed out.
+                              NOT usable (the reference has no such state; this library's convention): the memory store
+                              skips it and the returned command falls back to the trajectorizer's, as for FAILURE */
   SMPC_CONVERGENCE = 0,    /* usable */
   SMPC_NO_CONVERGENCE = 1, /* usable (iteration cap) */
   SMPC_FAILURE = 2         /* NOT usable: non-finite initial evaluation or 5 consecutive invalid steps */
@@ -360,7 +362,9 @@ int smpc_people_to_status_batch(smpc_handle* h, const smpc_people_batch* in, dou
 /* Optimizer::format_to_optimize (src/optimizer.cpp:484-551) for B scenes whose incoming path has already been cut to
  * T + 1 poses (the cut to round(max_time / time_step) - 1 poses, :492-497, is a host-side length decision), followed by
  * what Optimizer::optimize derives from its result before building the problem (:197-261). Scenes with an empty memory
- * record first store the incoming path / cmds in it (:177-183) and then blend with that copy, like the reference. */
+ * record first store the incoming path / cmds in it (:177-183) and then blend with that copy, like the reference. A path
+ * of fewer than two poses (n_poses[b] < 2: the window threw, trajectorize returned false, or a 1-pose path) leaves the
+ * record as it is, empty or not: Optimizer::optimize returns before the seed (:158-162). */
 typedef struct smpc_format_batch {
   int32_t B;
   int32_t T;          /* T + 1 poses of every path are formatted */
@@ -396,8 +400,8 @@ typedef struct smpc_format_out {
 int smpc_format_to_optimize_batch(smpc_handle* h, const smpc_format_batch* in, smpc_format_out* out);
 
 /* The TrajectoryMemory store at the end of Optimizer::optimize (src/optimizer.cpp:448-449): scenes whose solve was
- * usable (status != SMPC_FAILURE; the reference returns before the store otherwise, :384-388) keep the optimised path
- * and commands for the next call. path / cmds / status are smpc_result_batch arrays. */
+ * usable (status SMPC_CONVERGENCE or SMPC_NO_CONVERGENCE; the reference returns before the store otherwise, :384-388)
+ * keep the optimised path and commands for the next call. SMPC_FAILURE and SMPC_NOT_SOLVED leave the record as it is. path / cmds / status are smpc_result_batch arrays. */
 int smpc_memory_store_batch(smpc_handle* h, int32_t B, int32_t T, int32_t on_device, const int32_t* status,
                             const double* path, const double* cmds, smpc_memory_batch* memory,
                             const int32_t* T_scene /* [B] horizons of the solve (its T_scene), or NULL: T everywhere */);
@@ -474,8 +478,9 @@ int smpc_transform_global_plan_batch(smpc_handle* h, const smpc_plan_window_batc
                                      int32_t* error);
 
 /* The command SocialMPCController::computeVelocityCommands returns (src/social_mpc_controller.cpp:171-256; SURVEY §8 row
- * f4) for B robots: cmds[0] of a usable solve (:250-256), the trajectorizer's first command when the optimisation was
- * not usable (:241-245), (0.1, 0) when trajectorize returned false (:180-189), and nothing at all when
+ * f4) for B robots: cmds[0] of a usable solve (status SMPC_CONVERGENCE or SMPC_NO_CONVERGENCE, :250-256), the
+ * trajectorizer's first command when the optimisation was not usable (any other status, SMPC_NOT_SOLVED included,
+ * :241-245), (0.1, 0) when trajectorize returned false (:180-189), and nothing at all when
  * transformGlobalPlan threw (src/path_handler.cpp:44-47, 100-103: the exception leaves computeVelocityCommands and the
  * controller server publishes no command for the cycle). source [B]: 0 optimised, 1 trajectorizer command, 2 the
  * 0.1 m/s fallback, 3 no command (cmd_vel is written as zeros). A path shorter than T + 1 poses is not a fallback case:

@@ -59,10 +59,12 @@ __global__ __launch_bounds__(256) void smpc_format_kernel(const FormatParams p) 
   const int ncmd = p.n_poses ? max(n - 1, 0) : Tp;  // commands that arrive: one per step taken (trajectorize :262-269)
   const bool have = p.valid[s] != 0;
   // memory.previous_path.poses.size() == 0: previous := current, the whole incoming path and commands (:177-183; as
-  // much of them as the record's T + 1 rows hold); the blend below then runs against that copy
-  const int plen = have ? (p.length ? p.length[2 * s] : Tp) : min(n, Tp);
-  const int clen = have ? (p.length ? p.length[2 * s + 1] : Tp) : min(ncmd, Tp);
-  if (!have) {
+  // much of them as the record's T + 1 rows hold); the blend below then runs against that copy. A path of fewer than
+  // two poses never gets there (Optimizer::optimize returns first, :158-162): its record stays empty.
+  const bool seed = !have && n >= 2;
+  const int plen = have ? (p.length ? p.length[2 * s] : Tp) : (seed ? min(n, Tp) : 0);
+  const int clen = have ? (p.length ? p.length[2 * s + 1] : Tp) : (seed ? min(ncmd, Tp) : 0);
+  if (seed) {
     if (i < plen) { p.prev_path[3 * e] = p.path[3 * ei]; p.prev_path[3 * e + 1] = p.path[3 * ei + 1]; p.prev_path[3 * e + 2] = p.path[3 * ei + 2]; }
     if (i < clen) { p.prev_cmds[2 * e] = p.cmds[2 * ei]; p.prev_cmds[2 * e + 1] = p.cmds[2 * ei + 1]; }
   }
@@ -113,13 +115,15 @@ __global__ __launch_bounds__(256) void smpc_format_kernel(const FormatParams p) 
 }
 
 // Second pass of the format step: mark freshly filled memory records valid (after every lane of the first kernel has
-// read the flag) and note how much they hold.
+// read the flag) and note how much they hold. Only a path of two poses or more fills a record: the reference's test is
+// on the incoming path, before the cut (:158-162 ahead of :177-183).
 __global__ __launch_bounds__(256) void smpc_format_mark_kernel(const FormatParams p) {
   SMPC_CHAIN_PRIORITY();
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= p.B || p.valid[s] != 0) return;
   int n, kept;
   format_lengths(p, s, n, kept);
+  if (n < 2) return;
   p.valid[s] = 1;
   if (p.length) {
     p.length[2 * s] = min(n, p.T + 1);
@@ -209,7 +213,10 @@ __global__ __launch_bounds__(256) void smpc_memory_store_kernel(const StoreParam
   const int Tp = p.T + 1;
   if (gid >= (long long)p.B * Tp) return;
   const int s = (int)(gid / Tp), i = (int)(gid - (long long)s * Tp);
-  if (p.status[s] == 2 /* SMPC_FAILURE */) return;  // the reference returns false before the store (:384-388)
+  // only a usable solve is stored: the reference returns false before the store otherwise (:384-388); SMPC_NOT_SOLVED
+  // (a scene the order left out, its result rows unspecified) counts as unusable
+  const int st = p.status[s];
+  if (st != 0 /* SMPC_CONVERGENCE */ && st != 1 /* SMPC_NO_CONVERGENCE */) return;
   const int Tb = p.T_scene ? min(max(p.T_scene[s], 1), p.T) : p.T;  // the path and the commands of a solve have Tb + 1 entries
   if (i > Tb) return;
   const size_t e = (size_t)gid;
@@ -246,7 +253,7 @@ __global__ __launch_bounds__(256) void smpc_select_command_kernel(const SelectPa
     src = 3; v = 0.0; w = 0.0;
   } else if (n <= 0) {  // trajectorize() returned false: "using fallback cmd_vel" (:180-189)
     src = 2; v = 0.1; w = 0.0;
-  } else if (p.status[s] == 2 /* SMPC_FAILURE */) {  // optimize() returned false: cmds = init_cmds (:241-245)
+  } else if (p.status[s] != 0 && p.status[s] != 1) {  // not usable (FAILURE, NOT_SOLVED): cmds = init_cmds (:241-245)
     src = 1; v = p.traj_cmds[(size_t)s * p.rows * 2]; w = p.traj_cmds[(size_t)s * p.rows * 2 + 1];
   } else {
     src = 0; v = p.cmds[(size_t)s * (p.T + 1) * 2]; w = p.cmds[(size_t)s * (p.T + 1) * 2 + 1];

@@ -7,6 +7,11 @@ Follows, per scene:
   Optimizer::format_to_optimize                   reference src/optimizer.cpp:484-551
   what optimize() derives from optim_status       reference src/optimizer.cpp:197-261, 298
   TrajectoryMemory store                          reference src/optimizer.cpp:448-449 (skipped on an unusable solve, :384-388)
+  the returned command                            reference src/social_mpc_controller.cpp:171-256
+
+The memory rules: a path of fewer than two poses leaves the record as it is (Optimizer::optimize returns before the seed,
+:158-162); only a usable solve (status 0 or 1) is stored, and only it returns cmds[0]. SMPC_NOT_SOLVED (-1, a scene
+that a device `order` left out) counts as unusable: this project's convention, the reference has no such state.
 """
 import math
 
@@ -45,14 +50,15 @@ def format_to_optimize(path, cmds, speed, memory, current_path_w, current_cmds_w
     for s in range(B):
         n = Tp if n_poses is None else max(int(n_poses[s]), 0)
         ncmd = Tp if n_poses is None else max(n - 1, 0)
-        if not memory["valid"][s]:  # :177-183: previous := the whole incoming path / commands (what the record can hold)
+        if not memory["valid"][s] and n >= 2:  # :177-183 (after the < 2 poses return, :158-162): previous := the whole
+            # incoming path / commands (what the record can hold)
             keep_p, keep_c = min(n, Tp), min(ncmd, Tp)
             memory["prev_path"][s, :keep_p] = path[s, :keep_p]
             memory["prev_cmds"][s, :keep_c] = cmds[s, :keep_c]
             memory["valid"][s] = 1
             if "length" in memory:
                 memory["length"][s] = (keep_p, keep_c)
-        plen, clen = (memory["length"][s] if "length" in memory else (Tp, Tp))
+        plen, clen = (memory["length"][s] if "length" in memory else (Tp, Tp)) if memory["valid"][s] else (0, 0)
         pp, pc = memory["prev_path"][s], memory["prev_cmds"][s]
         kept = n
         if max_poses > 0 and n > max_poses:  # :491-497
@@ -84,10 +90,18 @@ def format_to_optimize(path, cmds, speed, memory, current_path_w, current_cmds_w
     return out
 
 
+def usable(status) -> bool:
+    """summary.IsSolutionUsable() (:384): SMPC_CONVERGENCE or SMPC_NO_CONVERGENCE; FAILURE and NOT_SOLVED are not."""
+    return int(status) in (0, 1)
+
+
 def memory_store(status, path, cmds, memory, T_scene=None):
+    """The store of :448-449 for the usable solves; T_scene [B] horizons of the solve (clamped into 1..T, as the solve
+    clamps them)."""
+    T = path.shape[1] - 1
     for s in range(len(status)):
-        if status[s] != 2:
-            n = path.shape[1] if T_scene is None else int(T_scene[s]) + 1
+        if usable(status[s]):
+            n = path.shape[1] if T_scene is None else min(max(int(T_scene[s]), 1), T) + 1
             memory["prev_path"][s, :n] = path[s, :n]
             memory["prev_cmds"][s, :n] = cmds[s, :n]
             memory["valid"][s] = 1
@@ -126,3 +140,21 @@ def fov_filter(people, count, robot_pose, fov_angle, origin, size_x, size_y, res
         if float(abs(rel)) < fov_angle:
             keep.append(a)
     return keep
+
+
+def select_command(traj_n, traj_cmds, status, cmds, window_error=None):
+    """The command computeVelocityCommands returns, per scene (reference src/social_mpc_controller.cpp:171-256):
+    source 3 (no command) when transformGlobalPlan threw, 2 (0.1 m/s) when trajectorize returned false, 1 (init_cmds[0])
+    when the solve is not usable, 0 (cmds[0]) otherwise. Returns (cmd_vel [B,2], source [B])."""
+    B = len(status)
+    out, src = np.zeros((B, 2)), np.zeros(B, np.int32)
+    for s in range(B):
+        if window_error is not None and window_error[s] != 0:
+            src[s] = 3
+        elif traj_n[s] <= 0:
+            src[s], out[s] = 2, (0.1, 0.0)
+        elif not usable(status[s]):
+            src[s], out[s] = 1, traj_cmds[s, 0]
+        else:
+            src[s], out[s] = 0, cmds[s, 0]
+    return out, src

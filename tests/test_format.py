@@ -222,20 +222,22 @@ def test_gpu_fov_filter_matches_pyref(fov):
 def test_gpu_select_command_applies_the_reference_fallbacks():
     """computeVelocityCommands' returned command: optimised cmds[0], else the trajectorizer's first command
     (src/social_mpc_controller.cpp:241-245), else 0.1 m/s straight (:180-189); nothing when transformGlobalPlan threw
-    (src/path_handler.cpp:44-47, 100-103). A path shorter than the batch's horizon is NOT a fallback case."""
+    (src/path_handler.cpp:44-47, 100-103). A path shorter than the batch's horizon is NOT a fallback case. A scene the
+    solve's order left out (SMPC_NOT_SOLVED, -1) is not usable: its unspecified cmds[0] never goes out."""
     from nav2_social_mpc_controller_amd.params import OptimizerParams
     from nav2_social_mpc_controller_amd.solver import BatchSolver
     rng = np.random.default_rng(12)
     B, T, rows = 300, 28, 31
     traj_cmds, cmds = rng.normal(size=(B, rows, 2)), rng.normal(size=(B, T + 1, 2))
-    status = rng.integers(0, 3, size=B).astype(np.int32)
+    status = rng.integers(-1, 3, size=B).astype(np.int32)
     n = rng.choice([0, 5, T + 1, rows], size=B).astype(np.int32)
     s = BatchSolver(OptimizerParams.readme())
     got, src = s.select_command(n, traj_cmds, status, cmds)
-    want_src = np.where(n <= 0, 2, np.where(status == 2, 1, 0))
+    want_src = np.where(n <= 0, 2, np.where((status == 0) | (status == 1), 0, 1))
     want = np.where((want_src == 2)[:, None], np.array([0.1, 0.0]), np.where((want_src == 1)[:, None], traj_cmds[:, 0], cmds[:, 0]))
     assert np.array_equal(src, want_src) and np.array_equal(got, want)
     assert set(want_src.tolist()) == {0, 1, 2} and ((n == 5) & (src == 0)).any()
+    assert ((status == -1) & (n > 0) & (src == 1)).any() and ((status == 1) & (n > 0) & (src == 0)).any()
     werr = rng.choice([0, 0, 0, 1, 2], size=B).astype(np.int32)
     got2, src2 = s.select_command(n, traj_cmds, status, cmds, window_error=werr)
     assert np.array_equal(src2, np.where(werr != 0, 3, want_src))
@@ -293,7 +295,9 @@ def test_pyref_with_path_lengths_matches_host_adapter(hostlib):
 
 
 @pytest.mark.gpu
-def test_gpu_format_with_path_lengths_matches_pyref():
+def test_gpu_format_with_path_lengths_and_unseeded_short_paths_matches_pyref():
+    """Horizons per scene on the device against pyref_format, records included. A path of fewer than two poses leaves an
+    empty record empty: Optimizer::optimize returns before the seed (src/optimizer.cpp:158-162 ahead of :177-183)."""
     from nav2_social_mpc_controller_amd.params import OptimizerParams
     from nav2_social_mpc_controller_amd.solver import BatchSolver
     from oracle import pyref_format
@@ -312,6 +316,7 @@ def test_gpu_format_with_path_lengths_matches_pyref():
             mem["prev_path"][b, :plen[b]], mem["prev_cmds"][b, :plen[b]] = prev_path[b, :plen[b]], prev_cmds[b, :plen[b]]
             mem["valid"][b], mem["length"][b] = 1, (plen[b], plen[b])
     mem_ref = {k: v.copy() for k, v in mem.items()}
+    empty = mem["valid"] == 0
     got = s.format_to_optimize(path, cmds, speed, mem, 0.7, 0.4, n_poses=n, max_poses=max_poses, T=T)
     exp = pyref_format.format_to_optimize(path, cmds, speed, mem_ref, 0.7, 0.4, prm.time_step, nb, n_poses=n,
                                           max_poses=max_poses, T=T)
@@ -323,6 +328,9 @@ def test_gpu_format_with_path_lengths_matches_pyref():
         assert np.max(err) <= 1e-13, k
     for k in mem:
         assert np.array_equal(mem[k], mem_ref[k]), k
+    # a path of fewer than two poses does not seed an empty record (Optimizer::optimize returns first, :158-162)
+    assert (empty & (n < 2)).any() and not mem["valid"][empty & (n < 2)].any() and not mem["length"][empty & (n < 2)].any()
+    assert (mem["valid"][empty & (n >= 2)] == 1).all()
     # the store of a solve with those horizons, then a second format against records of mixed sizes
     status = rng.integers(0, 3, size=B).astype(np.int32)
     res_path, res_cmds, _ = make_inputs(44, B, T)

@@ -65,6 +65,24 @@ def test_device_order_entries_outside_the_batch_are_skipped():
     assert (st[skipped] == -1).all()
     assert np.array_equal(st[~skipped], base["status"][~skipped])
     assert np.array_equal(rt["cmds"].cpu().numpy()[~skipped], base["cmds"][~skipped])
+    # on through the memory store and the returned command: a left-out scene is not usable, so it keeps the record it
+    # had and its command is the trajectorizer's (source 1), not the unspecified cmds[0] of its result rows
+    T = sc.T
+    mem = s.new_memory(B, T, lengths=True)
+    rng = np.random.default_rng(6)
+    mem["prev_path"][:], mem["prev_cmds"][:] = rng.normal(size=(B, T + 1, 3)), rng.normal(size=(B, T + 1, 2))
+    mem["valid"][:], mem["length"][:] = 1, T + 1
+    mem0 = {k: v.copy() for k, v in mem.items()}
+    res_path, res_cmds = rt["path"].cpu().numpy(), rt["cmds"].cpu().numpy()
+    s.memory_store(st, res_path, res_cmds, mem)
+    for k in mem:
+        assert np.array_equal(mem[k][skipped], mem0[k][skipped]), k
+    assert np.array_equal(mem["prev_path"][~skipped & (st != 2)], res_path[~skipped & (st != 2)])
+    traj_cmds = rng.normal(size=(B, T + 1, 2))
+    cmd, src = s.select_command(None, traj_cmds, st, res_cmds)
+    assert (src[skipped] == 1).all() and np.array_equal(cmd[skipped], traj_cmds[skipped, 0])
+    usable = ~skipped & (st != 2)
+    assert usable.any() and (src[usable] == 0).all() and np.array_equal(cmd[usable], res_cmds[usable, 0])
 
 
 @pytest.mark.gpu
