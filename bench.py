@@ -306,6 +306,59 @@ def parity_sample(prm, scenes, out, n_sample, cores):
     return par, cpu_s
 
 
+SCENE_ARRAYS = ("pose0", "init_params", "path_pts", "goal_yaw", "people", "has_people", "costmap", "costmap_origin")
+_FILL = None   # (params, N, seed, [(first_scene, {name: shared array})]) of make_batches, inherited by its workers
+
+
+def _fill_chunk(task):
+    from nav2_social_mpc_controller_amd.scenes import make_scenes
+
+    params, N, seed, batches = _FILL
+    i, off, n = task
+    first, arrs = batches[i]
+    sc = make_scenes(params, n, N, seed=seed, first_scene=first + off)
+    for k, a in arrs.items():
+        a[off:off + n] = getattr(sc, k)
+
+
+def make_batches(params, B, N, seed, firsts, workers, chunk=512):
+    """[make_scenes(params, B, N, seed=seed, first_scene=f) for f in firsts], the same arrays, generated in chunks of
+    `chunk` scenes by `workers` forked processes into anonymous shared memory: a scene is a pure function of (seed,
+    scene id), and one process takes seconds per 8192-scene batch. Call it before the process initialises HIP."""
+    import concurrent.futures
+    import mmap
+    import multiprocessing
+
+    import numpy as np
+
+    from nav2_social_mpc_controller_amd.scenes import SceneBatch, make_scenes
+
+    global _FILL
+    proto = make_scenes(params, 1, N, seed=seed, first_scene=firsts[0])
+    shared = []
+    for _ in firsts:
+        arrs = {}
+        for k in SCENE_ARRAYS:
+            a = getattr(proto, k)
+            buf = mmap.mmap(-1, max(1, B * a.nbytes))
+            arrs[k] = np.frombuffer(buf, a.dtype, B * a.size).reshape((B,) + a.shape[1:])
+        shared.append(arrs)
+    _FILL = (params, N, seed, list(zip(firsts, shared)))
+    tasks = [(i, off, min(chunk, B - off)) for i in range(len(firsts)) for off in range(0, B, chunk)]
+    try:
+        with concurrent.futures.ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("fork")) as ex:
+            list(ex.map(_fill_chunk, tasks))
+    finally:
+        _FILL = None
+    P = proto.init_params.shape[1]
+    out = []
+    for arrs in shared:
+        sc = SceneBatch(proto.T, proto.N, proto.dt, *(arrs[k] for k in SCENE_ARRAYS), proto.resolution, False)
+        sc.validate(P)
+        out.append(sc)
+    return out
+
+
 DUMP_LIMIT_BYTES = 64 << 20
 
 
@@ -382,9 +435,14 @@ def main():
     ap.add_argument("--batch", type=int, default=8192, help="scenes per GPU")
     ap.add_argument("--people", type=int, default=8)
     ap.add_argument("--fixed-iterations", type=int, default=0, help="1: run exactly 40 LM iterations per scene")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also measure and check everything else: lone launches, parity "
+                         "against the CPU oracle and the CPU baseline, the K1 sweep and the roofline, the gather of all "
+                         "ranks' parameters, and the extras in `config`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the parity sample / CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra measurements in `config` (PCIe-inclusive, fixed-40, other shapes, closed loop): profiling runs")
+                    help="with --full: skip the extra measurements in `config` (PCIe-inclusive, fixed-40, other shapes, "
+                         "closed loop): profiling runs")
     ap.add_argument("--streams", type=int, default=4,
                     help="consecutive steps are issued round-robin on this many HIP streams (one solver handle and one "
                          "scene batch of its own each)")
@@ -418,11 +476,28 @@ def main():
         return
 
     import numpy as np
+
+    from nav2_social_mpc_controller_amd.params import OptimizerParams
+
+    prm = OptimizerParams.readme().replace(fixed_iterations=args.fixed_iterations)
+    B, N = args.batch, args.people
+    n_streams = max(1, args.streams)
+    # Consecutive steps (independent batches of a serving stream) are issued round-robin on a few HIP streams, one
+    # solver handle each: the persistent solve kernel ends with a tail of a few long scenes (per-scene LM iteration
+    # counts vary 5..40), and the next batch's waves fill the CUs that the tail leaves idle. Every stream solves a scene
+    # batch of its OWN (scene ids disjoint across streams and ranks: 4 x 424 MB of inputs per GPU, more than the
+    # 256 MiB Infinity Cache holds), so no step finds its costmaps or people blocks warm from the step before;
+    # results of the steps of stream i land in result set i. The batches are generated before HIP starts (fork).
+    lo, hi = D.weak_shard(B, rank)
+    batches = make_batches(prm, B, N, 0x5EED0001, [lo + i * B * world for i in range(n_streams)],
+                           workers=max(1, min(16, usable_cores() // world)))
+    scenes = batches[0]
+    T = scenes.T
+    CH, bl, nb, P, M, _ = prm.dims(T, True)
+
     import torch
     import torch.distributed as dist
 
-    from nav2_social_mpc_controller_amd.params import OptimizerParams
-    from nav2_social_mpc_controller_amd.scenes import make_scenes
     from nav2_social_mpc_controller_amd.solver import BatchSolver
 
     force_dist = os.environ.get("SMPC_BENCH_FORCE_DIST") == "1"   # rehearse the RCCL path with a single rank
@@ -437,21 +512,6 @@ def main():
             dist.init_process_group("nccl")
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)
-
-    prm = OptimizerParams.readme().replace(fixed_iterations=args.fixed_iterations)
-    B, N = args.batch, args.people
-    n_streams = max(1, args.streams)
-    # Consecutive steps (independent batches of a serving stream) are issued round-robin on a few HIP streams, one
-    # solver handle each: the persistent solve kernel ends with a tail of a few long scenes (per-scene LM iteration
-    # counts vary 5..40), and the next batch's waves fill the CUs that the tail leaves idle. Every stream solves a scene
-    # batch of its OWN (scene ids disjoint across streams and ranks: 4 x 424 MB of inputs per GPU, more than the
-    # 256 MiB Infinity Cache holds), so no step finds its costmaps or people blocks warm from the step before;
-    # results of the steps of stream i land in result set i.
-    lo, hi = D.weak_shard(B, rank)
-    batches = [make_scenes(prm, B, N, seed=0x5EED0001, first_scene=lo + i * B * world) for i in range(n_streams)]
-    scenes = batches[0]
-    T = scenes.T
-    CH, bl, nb, P, M, _ = prm.dims(T, True)
 
     solvers = [BatchSolver(prm, device=local_rank) for _ in range(n_streams)]
     from nav2_social_mpc_controller_amd.episode import concurrent_streams
@@ -487,22 +547,24 @@ def main():
     elapsed = time.perf_counter() - t0
     last_step = None
     if args.dump_outputs and rank == 0:
-        # a device copy now (the lone launches below write stream 0's result set again), written out after the measurements
+        # a device copy now (the lone launches of --full write stream 0's result set again), written out after the
+        # measurements
         last_step = {k: v.clone() for k, v in results[(args.steps - 1) % n_streams][1].items()}
-    step_ms = np.array([ev0[k].elapsed_time(ev1[k]) for k in range(args.steps)])
-    span_ms = max(ev0[0].elapsed_time(e) for e in ev1)
     # per-launch device time of the solve kernel alone (library-side HIP events around its last launch per handle)
     solve_ms_each = [sv.last_kernel_ms() for sv in solvers[:min(n_streams, args.steps)]]
     solve_ms = float(sum(solve_ms_each) / len(solve_ms_each))
-    # un-overlapped launches for reference (single stream, nothing else in flight): HIP events of the library around
-    # the solve kernel alone, the average over launches is what a `rocprofv3 --stats` of a one-stream run reports
-    solo = []
-    for _ in range(5):
-        solver.solve_device(sb, rb)
-        torch.cuda.synchronize(device)
-        solo.append(solver.last_kernel_ms())
-    solo_ms = float(np.mean(solo[1:]))
-    solo_min_ms = float(min(solo))
+    if args.full:
+        step_ms = np.array([ev0[k].elapsed_time(ev1[k]) for k in range(args.steps)])
+        span_ms = max(ev0[0].elapsed_time(e) for e in ev1)
+        # un-overlapped launches for reference (single stream, nothing else in flight): HIP events of the library around
+        # the solve kernel alone, the average over launches is what a `rocprofv3 --stats` of a one-stream run reports
+        solo = []
+        for _ in range(5):
+            solver.solve_device(sb, rb)
+            torch.cuda.synchronize(device)
+            solo.append(solver.last_kernel_ms())
+        solo_ms = float(np.mean(solo[1:]))
+        solo_min_ms = float(min(solo))
 
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if dist.is_initialized():
@@ -515,105 +577,64 @@ def main():
     status = out["status"].cpu().numpy()
     local = {"scenes": B, "sweeps": int(evals.sum()), "iterations": int(iters.sum()),
              "converged": int((status == 0).sum()), "no_convergence": int((status == 1).sum()),
-             "failed": int((status == 2).sum()), "max_solve_kernel_ms": solve_ms, "max_solo_kernel_ms": solo_ms}
+             "failed": int((status == 2).sum()), "max_solve_kernel_ms": solve_ms}
+    if args.full:
+        local["max_solo_kernel_ms"] = solo_ms
     summ = D.reduce_summary(local, device=device)
 
-    # ---- correctness evidence on EVERY rank: the oracle on a sample of this rank's own shard, reduced with
-    # MAX / SUM; the optimised parameters of all ranks gathered on rank 0
-    cores = usable_cores()
     par = None
-    cpu_s = None
-    n_sample = 0
-    if not args.no_cpu_baseline:
-        share = max(1, cores // max(1, world))
-        n_sample = min(B, 512 * share) if world == 1 else min(B, 512)
-        par, cpu_s = parity_sample(prm, scenes, out, n_sample, share)
     gathered = None
-    if dist.is_initialized():
-        if par is not None:
-            red = D.reduce_summary({"max_abs_dcmd": par["max_abs_dcmd"], "scenes": par["scenes"],
-                                    "scenes_with_firm_decisions": par["scenes_with_firm_decisions"],
-                                    "scenes_over_1e-5": par["scenes_over_1e-5"],
-                                    "scenes_over_1e-5_among_marginal": par["scenes_over_1e-5_among_marginal"]}, device=device)
-            par.update({k: (float(v) if k.startswith("max_") else int(v)) for k, v in red.items()})
-            par["reduced_over_ranks"] = world
-        gathered = D.gather_params(out["params"])      # [world][B][P] on every rank (all_gather over RCCL)
+    if args.full:
+        # ---- correctness evidence on EVERY rank: the oracle on a sample of this rank's own shard, reduced
+        # with MAX / SUM; the optimised parameters of all ranks gathered on rank 0
+        cores = usable_cores()
+        cpu_s = None
+        n_sample = 0
+        if not args.no_cpu_baseline:
+            share = max(1, cores // max(1, world))
+            n_sample = min(B, 512 * share) if world == 1 else min(B, 512)
+            par, cpu_s = parity_sample(prm, scenes, out, n_sample, share)
+        if dist.is_initialized():
+            if par is not None:
+                red = D.reduce_summary({"max_abs_dcmd": par["max_abs_dcmd"], "scenes": par["scenes"],
+                                        "scenes_with_firm_decisions": par["scenes_with_firm_decisions"],
+                                        "scenes_over_1e-5": par["scenes_over_1e-5"],
+                                        "scenes_over_1e-5_among_marginal": par["scenes_over_1e-5_among_marginal"]},
+                                       device=device)
+                par.update({k: (float(v) if k.startswith("max_") else int(v)) for k, v in red.items()})
+                par["reduced_over_ranks"] = world
+            gathered = D.gather_params(out["params"])      # [world][B][P] on every rank (all_gather over RCCL)
 
-    # K1 stand-alone sweep for the roofline line: staged people block, critic-major rows (the coalesced store path)
-    eo, eout = solver.alloc_eval(B, T, device, row_order=1)
-    solver.eval_device(sb, tens["init_params"].data_ptr(), eo)        # reference-layout people: staging pass + K1
-    k1_raw = []
-    for _ in range(3):
-        t1 = time.perf_counter()
-        solver.eval_device(sb, tens["init_params"].data_ptr(), eo)
-        torch.cuda.synchronize(device)
-        k1_raw.append((time.perf_counter() - t1) * 1e3)
-    keep = solver.stage_people_device(sb, device)
-    stage_ms = solver.last_kernel_ms()
-    k1 = []
-    for _ in range(10):
-        solver.eval_device(sb, tens["init_params"].data_ptr(), eo)
-        k1.append(solver.last_kernel_ms())
-    k1_ms = float(np.mean(k1[2:]))       # the average launch, as a rocprofv3 --stats summary reports it
-    k1_min_ms = float(min(k1[2:]))
-    eo.row_order = 0
-    k1r = []
-    for _ in range(5):
-        solver.eval_device(sb, tens["init_params"].data_ptr(), eo)
-        k1r.append(solver.last_kernel_ms())
-    k1_ref_order_ms = float(np.mean(k1r[1:]))
-    sb.people_records, sb.people_aux = None, None
-    del keep
+        # K1 stand-alone sweep for the roofline line: staged people block, critic-major rows (the coalesced store path)
+        eo, eout = solver.alloc_eval(B, T, device, row_order=1)
+        solver.eval_device(sb, tens["init_params"].data_ptr(), eo)        # reference-layout people: staging pass + K1
+        k1_raw = []
+        for _ in range(3):
+            t1 = time.perf_counter()
+            solver.eval_device(sb, tens["init_params"].data_ptr(), eo)
+            torch.cuda.synchronize(device)
+            k1_raw.append((time.perf_counter() - t1) * 1e3)
+        keep = solver.stage_people_device(sb, device)
+        stage_ms = solver.last_kernel_ms()
+        k1 = []
+        for _ in range(10):
+            solver.eval_device(sb, tens["init_params"].data_ptr(), eo)
+            k1.append(solver.last_kernel_ms())
+        k1_ms = float(np.mean(k1[2:]))       # the average launch, as a rocprofv3 --stats summary reports it
+        k1_min_ms = float(min(k1[2:]))
+        eo.row_order = 0
+        k1r = []
+        for _ in range(5):
+            solver.eval_device(sb, tens["init_params"].data_ptr(), eo)
+            k1r.append(solver.last_kernel_ms())
+        k1_ref_order_ms = float(np.mean(k1r[1:]))
+        sb.people_records, sb.people_aux = None, None
+        del keep
 
     if rank == 0:
         total_solves = summ["scenes"] * args.steps
         value = total_solves / elapsed_max
-        bytes_sweep = algorithmic_bytes_per_sweep(N, T, P, M)
-        sweeps_each = [int(e.sum()) for e in evals_each]
-        sweeps_per_launch = float(np.mean(sweeps_each))        # the streams solve different scenes: mean over them
         eff_ms = elapsed_max / args.steps * 1e3          # what one launch costs the timed region
-        measured_peak = solver.fp64_peak_tflops()
-        # ---- the binding resource of the dominant kernel: FP64 VALU work / VALU instruction issue. Instruction counts per
-        # launch come from the committed PMC passes (same scenes as stream 0 of rank 0), accepted only for the very
-        # device sources running now and scaled by the sweeps this run's launches made; times are this run's.
-        pmc, pmc_info = pmc_counters("smpc_solve_kernel")
-        k1pmc, _ = pmc_counters("smpc_eval_kernel")
-        fp64 = None
-        top = {"bound": "fp64_valu", "kernel": "smpc_solve_kernel", "achieved": None, "peak": FP64_PEAK_TFS,
-               "unit": "TFLOP/s", "frac": None, "traffic": None}
-        if all(k in pmc for k in ("SQ_INSTS_VALU_ADD_F64", "SQ_INSTS_VALU_MUL_F64", "SQ_INSTS_VALU_FMA_F64", "SQ_INSTS_VALU")):
-            scale = sweeps_per_launch / float(sweeps_each[0])   # PMC workload = stream 0's scenes
-            flop = 64.0 * (pmc["SQ_INSTS_VALU_ADD_F64"] + pmc["SQ_INSTS_VALU_MUL_F64"] + 2.0 * pmc["SQ_INSTS_VALU_FMA_F64"]) * scale
-            valu = pmc["SQ_INSTS_VALU"] * scale
-            f64_instr = (pmc["SQ_INSTS_VALU_ADD_F64"] + pmc["SQ_INSTS_VALU_MUL_F64"] + pmc["SQ_INSTS_VALU_FMA_F64"]) * scale
-            fp64 = {"flop_per_launch": flop, "valu_instructions_per_launch": valu,
-                    "fp64_arithmetic_share_of_valu_instructions": f64_instr / valu,
-                    "achieved_TFs_overlapped": flop / (eff_ms * 1e-3) / 1e12,
-                    "achieved_TFs_lone_launch": flop / (solo_ms * 1e-3) / 1e12,
-                    "frac_of_78.6_overlapped": flop / (eff_ms * 1e-3) / 1e12 / FP64_PEAK_TFS,
-                    "frac_of_78.6_lone_launch": flop / (solo_ms * 1e-3) / 1e12 / FP64_PEAK_TFS,
-                    "measured_peak_TFs": measured_peak,
-                    # every wave64 VALU instruction (FP64 or not) holds its SIMD for 4 cycles: the issue-slot view
-                    "valu_issue_frac_overlapped": valu * VALU_CYCLES / (SIMDS * 2.4e9 * eff_ms * 1e-3),
-                    "valu_issue_frac_lone_launch": valu * VALU_CYCLES / (SIMDS * 2.4e9 * solo_ms * 1e-3),
-                    "note": "counts: PMC passes committed in profiles/ for these very device sources (pmc.csrc_digest_*), scaled "
-                            "by sweeps; times: this run (overlapped = timed region / launches, lone = mean of lone launches "
-                            "by HIP events); issue fractions assume 2.4 GHz"}
-            top.update({"achieved": fp64["achieved_TFs_overlapped"], "frac": fp64["frac_of_78.6_overlapped"],
-                        "achieved_lone_launch": fp64["achieved_TFs_lone_launch"], "frac_lone_launch": fp64["frac_of_78.6_lone_launch"],
-                        "valu_issue_frac": fp64["valu_issue_frac_overlapped"],
-                        "valu_issue_frac_lone_launch": fp64["valu_issue_frac_lone_launch"]})
-        if "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc:
-            # HBM-side bytes per solve launch (KiB counters; the solve kernel's reads are 32-byte records and unaligned
-            # dwords, not the 16 B / lane streaming pattern the guide's x2 FETCH_SIZE correction is calibrated on: reported
-            # as counted)
-            top["traffic"] = (pmc["FETCH_SIZE"] + pmc["WRITE_SIZE"]) * 1024.0
-        k1_achieved = B * bytes_sweep / (k1_ms * 1e-3) / 1e9
-        k1_traffic = None
-        if "FETCH_SIZE" in k1pmc and "WRITE_SIZE" in k1pmc:
-            # K1 streams its inputs 16 B / lane: FETCH_SIZE x 2 per the guide's gfx950 correction, WRITE_SIZE as counted
-            k1_traffic = (2.0 * k1pmc["FETCH_SIZE"] + k1pmc["WRITE_SIZE"]) * 1024.0
-        bytes_launch = sweeps_per_launch * bytes_sweep
         line = {
             "metric": "MPC solves/sec (horizon=18, 8 agents, max 40 LM iterations, Ceres termination rules)",
             "value": value, "unit": "solves/s",
@@ -628,12 +649,59 @@ def main():
                                      f"scene batch of its own",
                        "scenes_per_gpu": B, "people": N, "T": T, "P": P, "M": M, "streams": n_streams,
                        "distinct_scene_batches": n_streams,
-                       "single_stream_solves_per_s_per_gpu": B / (summ["max_solo_kernel_ms"] * 1e-3),
                        "mean_lm_iterations": summ["iterations"] / summ["scenes"],
                        "mean_sweeps_per_solve": summ["sweeps"] / summ["scenes"],
                        "status": {"convergence": int(summ["converged"]), "no_convergence": int(summ["no_convergence"]),
                                   "failure": int(summ["failed"])}},
-            "roofline": dict(top, **{
+        }
+        if args.full:
+            bytes_sweep = algorithmic_bytes_per_sweep(N, T, P, M)
+            sweeps_each = [int(e.sum()) for e in evals_each]
+            sweeps_per_launch = float(np.mean(sweeps_each))        # the streams solve different scenes: mean over them
+            measured_peak = solver.fp64_peak_tflops()
+            # ---- the binding resource of the dominant kernel: FP64 VALU work / VALU instruction issue. Instruction counts per
+            # launch come from the committed PMC passes (same scenes as stream 0 of rank 0), accepted only for the very
+            # device sources running now and scaled by the sweeps this run's launches made; times are this run's.
+            pmc, pmc_info = pmc_counters("smpc_solve_kernel")
+            k1pmc, _ = pmc_counters("smpc_eval_kernel")
+            fp64 = None
+            top = {"bound": "fp64_valu", "kernel": "smpc_solve_kernel", "achieved": None, "peak": FP64_PEAK_TFS,
+                   "unit": "TFLOP/s", "frac": None, "traffic": None}
+            if all(k in pmc for k in ("SQ_INSTS_VALU_ADD_F64", "SQ_INSTS_VALU_MUL_F64", "SQ_INSTS_VALU_FMA_F64", "SQ_INSTS_VALU")):
+                scale = sweeps_per_launch / float(sweeps_each[0])   # PMC workload = stream 0's scenes
+                flop = 64.0 * (pmc["SQ_INSTS_VALU_ADD_F64"] + pmc["SQ_INSTS_VALU_MUL_F64"] + 2.0 * pmc["SQ_INSTS_VALU_FMA_F64"]) * scale
+                valu = pmc["SQ_INSTS_VALU"] * scale
+                f64_instr = (pmc["SQ_INSTS_VALU_ADD_F64"] + pmc["SQ_INSTS_VALU_MUL_F64"] + pmc["SQ_INSTS_VALU_FMA_F64"]) * scale
+                fp64 = {"flop_per_launch": flop, "valu_instructions_per_launch": valu,
+                        "fp64_arithmetic_share_of_valu_instructions": f64_instr / valu,
+                        "achieved_TFs_overlapped": flop / (eff_ms * 1e-3) / 1e12,
+                        "achieved_TFs_lone_launch": flop / (solo_ms * 1e-3) / 1e12,
+                        "frac_of_78.6_overlapped": flop / (eff_ms * 1e-3) / 1e12 / FP64_PEAK_TFS,
+                        "frac_of_78.6_lone_launch": flop / (solo_ms * 1e-3) / 1e12 / FP64_PEAK_TFS,
+                        "measured_peak_TFs": measured_peak,
+                        # every wave64 VALU instruction (FP64 or not) holds its SIMD for 4 cycles: the issue-slot view
+                        "valu_issue_frac_overlapped": valu * VALU_CYCLES / (SIMDS * 2.4e9 * eff_ms * 1e-3),
+                        "valu_issue_frac_lone_launch": valu * VALU_CYCLES / (SIMDS * 2.4e9 * solo_ms * 1e-3),
+                        "note": "counts: PMC passes committed in profiles/ for these very device sources (pmc.csrc_digest_*), scaled "
+                                "by sweeps; times: this run (overlapped = timed region / launches, lone = mean of lone launches "
+                                "by HIP events); issue fractions assume 2.4 GHz"}
+                top.update({"achieved": fp64["achieved_TFs_overlapped"], "frac": fp64["frac_of_78.6_overlapped"],
+                            "achieved_lone_launch": fp64["achieved_TFs_lone_launch"], "frac_lone_launch": fp64["frac_of_78.6_lone_launch"],
+                            "valu_issue_frac": fp64["valu_issue_frac_overlapped"],
+                            "valu_issue_frac_lone_launch": fp64["valu_issue_frac_lone_launch"]})
+            if "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc:
+                # HBM-side bytes per solve launch (KiB counters; the solve kernel's reads are 32-byte records and unaligned
+                # dwords, not the 16 B / lane streaming pattern the guide's x2 FETCH_SIZE correction is calibrated on: reported
+                # as counted)
+                top["traffic"] = (pmc["FETCH_SIZE"] + pmc["WRITE_SIZE"]) * 1024.0
+            k1_achieved = B * bytes_sweep / (k1_ms * 1e-3) / 1e9
+            k1_traffic = None
+            if "FETCH_SIZE" in k1pmc and "WRITE_SIZE" in k1pmc:
+                # K1 streams its inputs 16 B / lane: FETCH_SIZE x 2 per the guide's gfx950 correction, WRITE_SIZE as counted
+                k1_traffic = (2.0 * k1pmc["FETCH_SIZE"] + k1pmc["WRITE_SIZE"]) * 1024.0
+            bytes_launch = sweeps_per_launch * bytes_sweep
+            line["config"]["single_stream_solves_per_s_per_gpu"] = B / (summ["max_solo_kernel_ms"] * 1e-3)
+            line["roofline"] = dict(top, **{
                 "bound_note": "binding resource of the dominant kernel (the fused solve): FP64 VALU work under VALU instruction "
                               "issue; achieved = FP64 flop per launch / time per launch of THIS run (overlapped region; the "
                               "lone-launch figures beside it), peak = datasheet FP64 vector rate. The solve never writes J, so "
@@ -664,50 +732,49 @@ def main():
                     "solve_kernel_ms_last_launch_per_stream": solve_ms_each,
                     "note": "begin / end events of every step on its own stream: a step (staging pass + solve kernel) lasts "
                             "mean_step_ms while steps_in_flight of them overlap; launch_ms_effective = span / steps is what one "
-                            "launch costs the region (rocprofv3 kernel trace of the same command: profiles/r03_bench_trace_*)"}}),
-        }
-        if par is not None:
-            line["parity"] = par
-        if gathered is not None:
-            g = gathered.cpu().numpy()
-            line["gather"] = {"ranks_seen": int(g.shape[0]), "params_shape": list(g.shape),
-                              "all_finite": bool(np.isfinite(g).all()),
-                              "rank0_slice_equals_local": bool(np.array_equal(g[0], out["params"].cpu().numpy())),
-                              "distinct_rank_slices": int(len({hash(g[i].tobytes()) for i in range(g.shape[0])}))}
-        if world == 1 and not args.no_cpu_baseline and par is not None:
-            line["cpu_baseline"] = {"value": n_sample / cpu_s, "unit": "solves/s", "cores": max(1, cores), "kind": "port",
-                                    "sample": f"first {n_sample} scenes of the same workload, one solve per thread "
-                                              f"(CPU restatement oracle/smpc_oracle.cpp, not Ceres), {cpu_s:.1f} s"}
-        if world == 1 and not args.no_extras:
-            # extras of SURVEY §8(d): (ii) end-to-end including PCIe staging, (iii) fixed-40-iteration mode
-            t1 = time.perf_counter()
-            solver.solve(scenes)                      # host pointers: H2D of every input, solve, D2H of every output
-            line["config"]["pcie_inclusive_solves_per_s"] = B / (time.perf_counter() - t1)
-            fixed = BatchSolver(prm.replace(fixed_iterations=1), device=local_rank)
-            frb, fout = fixed.alloc_results(B, T, device)
-            fixed.solve_device(sb, frb)
-            fixed.solve_device(sb, frb)
-            torch.cuda.synchronize(device)
-            fms = fixed.last_kernel_ms()
-            line["config"]["fixed_40_iterations"] = {"launch_ms": fms, "solves_per_s": B / (fms * 1e-3),
-                                                     "mean_sweeps_per_solve": float(fout["evaluations"].float().mean().item())}
-            del fixed
-            # the other single-GPU BASELINE shapes, measured like the headline one but on one stream
-            cfg5 = OptimizerParams.readme().replace(control_horizon=30, max_time=2.0)
+                            "launch costs the region (rocprofv3 kernel trace of the same command: profiles/r03_bench_trace_*)"}})
+            if par is not None:
+                line["parity"] = par
+            if gathered is not None:
+                g = gathered.cpu().numpy()
+                line["gather"] = {"ranks_seen": int(g.shape[0]), "params_shape": list(g.shape),
+                                  "all_finite": bool(np.isfinite(g).all()),
+                                  "rank0_slice_equals_local": bool(np.array_equal(g[0], out["params"].cpu().numpy())),
+                                  "distinct_rank_slices": int(len({hash(g[i].tobytes()) for i in range(g.shape[0])}))}
+            if world == 1 and not args.no_cpu_baseline and par is not None:
+                line["cpu_baseline"] = {"value": n_sample / cpu_s, "unit": "solves/s", "cores": max(1, cores), "kind": "port",
+                                        "sample": f"first {n_sample} scenes of the same workload, one solve per thread "
+                                                  f"(CPU restatement oracle/smpc_oracle.cpp, not Ceres), {cpu_s:.1f} s"}
+            if world == 1 and not args.no_extras:
+                # extras of SURVEY §8(d): (ii) end-to-end including PCIe staging, (iii) fixed-40-iteration mode
+                t1 = time.perf_counter()
+                solver.solve(scenes)                      # host pointers: H2D of every input, solve, D2H of every output
+                line["config"]["pcie_inclusive_solves_per_s"] = B / (time.perf_counter() - t1)
+                fixed = BatchSolver(prm.replace(fixed_iterations=1), device=local_rank)
+                frb, fout = fixed.alloc_results(B, T, device)
+                fixed.solve_device(sb, frb)
+                fixed.solve_device(sb, frb)
+                torch.cuda.synchronize(device)
+                fms = fixed.last_kernel_ms()
+                line["config"]["fixed_40_iterations"] = {"launch_ms": fms, "solves_per_s": B / (fms * 1e-3),
+                                                         "mean_sweeps_per_solve": float(fout["evaluations"].float().mean().item())}
+                del fixed
+                # the other single-GPU BASELINE shapes, measured like the headline one but on one stream
+                cfg5 = OptimizerParams.readme().replace(control_horizon=30, max_time=2.0)
 
-            def extra(name, fn, *a, **kw):  # an extra that fails is reported, it does not cost the headline line
-                try:
-                    line["config"][name] = fn(*a, **kw)
-                except Exception as e:  # noqa: BLE001
-                    line["config"][name] = {"error": f"{type(e).__name__}: {e}"[:300]}
+                def extra(name, fn, *a, **kw):  # an extra that fails is reported, it does not cost the headline line
+                    try:
+                        line["config"][name] = fn(*a, **kw)
+                    except Exception as e:  # noqa: BLE001
+                        line["config"][name] = {"error": f"{type(e).__name__}: {e}"[:300]}
 
-            extra("cfg2", shape_record, OptimizerParams.readme(), 1024, 4, device, local_rank)
-            extra("cfg2_8192", shape_record, OptimizerParams.readme(), 8192, 4, device, local_rank)
-            extra("cfg5", shape_record, cfg5, 8192, 16, device, local_rank)
-            extra("params_yaml_n3", shape_record, OptimizerParams.params_yaml(), 8192, 3, device, local_rank)
-            extra("soc_work_obst_benchmark_n3", shape_record, OptimizerParams.soc_work_obst_benchmark(), 8192, 3, device,
-                  local_rank, map_cells=OptimizerParams.BENCHMARK_COSTMAP_CELLS)
-            extra("closed_loop", closed_loop_extras, prm, scenes, local_rank)
+                extra("cfg2", shape_record, OptimizerParams.readme(), 1024, 4, device, local_rank)
+                extra("cfg2_8192", shape_record, OptimizerParams.readme(), 8192, 4, device, local_rank)
+                extra("cfg5", shape_record, cfg5, 8192, 16, device, local_rank)
+                extra("params_yaml_n3", shape_record, OptimizerParams.params_yaml(), 8192, 3, device, local_rank)
+                extra("soc_work_obst_benchmark_n3", shape_record, OptimizerParams.soc_work_obst_benchmark(), 8192, 3, device,
+                      local_rank, map_cells=OptimizerParams.BENCHMARK_COSTMAP_CELLS)
+                extra("closed_loop", closed_loop_extras, prm, scenes, local_rank)
         real_stdout.write(json.dumps(line) + "\n")
         real_stdout.flush()
     if last_step is not None:

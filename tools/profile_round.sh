@@ -7,12 +7,13 @@ TAG=${1:-r02}
 OUT=gpurun_out/profile_$TAG
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
-# (1) the default bench (what the driver runs, minus the extras that launch other kernels): per-dispatch begin / end
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_trace" -- python3 bench.py --no-cpu-baseline --no-extras > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err"
+# (1) the default bench with --full, minus the extras that launch other kernels: the timed steps, then the lone
+# launches and K1 the roofline is taken from; per-dispatch begin / end
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_trace" -- python3 bench.py --full --no-cpu-baseline --no-extras > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err"
 cp $(find "$OUT/bench_trace" -name "*kernel_stats.csv" | head -1) "$OUT/${TAG}_bench_kernel_stats.csv"
 python3 tools/trace_extract.py $(find "$OUT/bench_trace" -name "*kernel_trace.csv" | head -1) > "$OUT/${TAG}_bench_trace_overlap.txt"
 # (2) the same bench on ONE stream (lone launches: what roofline.launch_ms_lone refers to)
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench1_trace" -- python3 bench.py --steps 10 --warmup 2 --streams 1 --no-cpu-baseline --no-extras > "$OUT/bench1_under_rocprof.json" 2> "$OUT/bench1_under_rocprof.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench1_trace" -- python3 bench.py --steps 10 --warmup 2 --streams 1 --full --no-cpu-baseline --no-extras > "$OUT/bench1_under_rocprof.json" 2> "$OUT/bench1_under_rocprof.err"
 cp $(find "$OUT/bench1_trace" -name "*kernel_stats.csv" | head -1) "$OUT/${TAG}_bench_streams1_kernel_stats.csv"
 # (3) the closed-loop chain (rows f1-f3 + solve + store) under the same tracer
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/episode_trace" -- python3 tools/gpu_episode.py 8192 8 10 window 0 > "$OUT/episode_under_rocprof.log" 2>&1
@@ -23,6 +24,6 @@ python3 tools/trace_extract.py $(find "$OUT/episode3_trace" -name "*kernel_trace
 # (4) PMC passes (separate runs, counters only)
 tools/prof_pmc.sh "$OUT/pmc" > /dev/null 2>&1
 cp "$OUT/pmc/pmc_summary.txt" "$OUT/${TAG}_pmc_summary.txt"
-# (5) the plain default bench of the same box
-python3 bench.py > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err"
+# (5) the default bench with everything it measures (--full) on the same box
+python3 bench.py --full > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err"
 head -c 1500 "$OUT/${TAG}_bench_kernel_stats.csv"; echo; head -30 "$OUT/${TAG}_bench_trace_overlap.txt"; cat "$OUT/${TAG}_pmc_summary.txt" | grep -E "==|FETCH|WRITE|SQ_INSTS_VALU |SQ_INSTS_MFMA|SQ_WAVES|GRBM"; cat "$OUT/${TAG}_bench.json"
