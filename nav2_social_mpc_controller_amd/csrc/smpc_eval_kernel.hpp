@@ -1,8 +1,21 @@
-// smpc_eval_kernel.inc — the body of the K1 kernels: included by smpc_lm.hpp once per kernel (no include guard),
-// with SMPC_KERNEL_HEAD the template head and name of the kernel and SMPC_KERNEL_FLAGS the constexpr flags (kSP, and kVT
-// where it is not a template parameter) it is compiled with.
-SMPC_KERNEL_HEAD {
-  SMPC_KERNEL_FLAGS
+// smpc_eval_kernel.hpp — smpc_eval_kernel, the stand-alone K1 kernel around sweep().
+#pragma once
+
+#include "smpc_sweep.hpp"
+
+namespace smpc {
+
+// K1 stand-alone: one sweep per scene at given parameters, rows written to HBM (parity checks, roofline runs).
+// Up to three parameter blocks the sweep fits the 168 registers that three waves per SIMD allow (the headline shapes;
+// K1 is a latency-bound streaming kernel, the third wave is worth 20 % of its time); beyond that the row buffers grow
+// with P and the allocator is left alone.
+#ifndef SMPC_EVAL_MIN_WAVES
+#define SMPC_EVAL_MIN_WAVES(NB) ((NB) <= 3 ? 3 : 1)
+#endif
+// smpc_eval_kernel<NB, W, kVT, kSP>: the variants are template parameters, as for the solve kernel (smpc_solve_kernel.hpp).
+template <int NB, int W, bool kVT = false, bool kSP = false>
+__global__ __launch_bounds__(64, SMPC_EVAL_MIN_WAVES(NB)) void smpc_eval_kernel(const KParams) {
+  static_assert(!kSP || kVT, "a kernel with per-scene weights and bounds reads its horizon per scene as well");
   const auto& k = *(KParamsK)__builtin_amdgcn_kernarg_segment_ptr();
   constexpr int P = 2 * NB;
   constexpr int S = kWave / W;
@@ -65,3 +78,5 @@ SMPC_KERNEL_HEAD {
   }
 #endif
 }
+
+}  // namespace smpc

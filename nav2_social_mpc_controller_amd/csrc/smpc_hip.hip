@@ -1,12 +1,15 @@
 // smpc_hip.hip — kernels + the C ABI of include/smpc.h (libsmpc_hip.so). gfx950 only, no CPU fallback.
 //
-// Kernels (one 64-lane wavefront per workgroup, split into 64/W scene slots; see smpc_device.hpp / smpc_lm.hpp):
-//   smpc_solve_kernel<NB,W>  persistent sweep engine: whole ceres::Solve-equivalent (reference
+// Kernels (one 64-lane wavefront per workgroup, split into 64/W scene slots; lane mapping and LDS layout: smpc_launch.hpp):
+//   smpc_solve_kernel<NB,W,kVT,kSP>  persistent sweep engine: whole ceres::Solve-equivalent (reference
 //                            src/optimizer.cpp:241-446) per scene, LM state resident in registers / LDS for all
-//                            <= max_iterations iterations, scenes pulled from a device-side queue;
-//   smpc_eval_kernel<NB,W>   K1: one residual + Jacobian sweep, rows written to HBM (parity + roofline runs);
-//   smpc_solve_sp_kernel<NB,W> / smpc_eval_sp_kernel<NB,W>: the same with per-scene weights and velocity bounds
-//                            (smpc_scene_batch.scene_params) and per-scene horizons.
+//                            <= max_iterations iterations, scenes pulled from a device-side queue (smpc_solve_kernel.hpp);
+//   smpc_eval_kernel<NB,W,kVT,kSP>   K1: one residual + Jacobian sweep, rows written to HBM (parity + roofline runs;
+//                            smpc_eval_kernel.hpp);
+//                            kVT: per-scene horizons; kSP (with kVT): per-scene weights and velocity bounds as well
+//                            (smpc_scene_batch.scene_params);
+//   smpc_stage_kernel<W>     the staging pass of the people block (smpc_stage.hpp);
+//   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -17,7 +20,11 @@
 #include <string>
 #include <vector>
 
+#include "smpc_eval_kernel.hpp"
+#include "smpc_launch.hpp"
 #include "smpc_lm.hpp"
+#include "smpc_solve_kernel.hpp"
+#include "smpc_stage.hpp"
 #include "smpc_project.hpp"
 #include "smpc_distance.hpp"
 #include "smpc_format.hpp"
@@ -136,18 +143,14 @@ using KernelFn = void (*)(const smpc::KParams);
 
 // vt: the batch carries a horizon per scene (smpc_scene_batch.T_scene): the instantiation that reads T, CH, bl of each
 // scene from LDS instead of taking them as launch constants. sp: the batch carries weights and bounds per scene
-// (smpc_scene_batch.scene_params): the sp kernels, which read the horizon per scene as well (T_scene or T).
+// (smpc_scene_batch.scene_params): kSP, which reads the horizon per scene as well (T_scene or T).
+template <int NB, int W, bool kVT, bool kSP> KernelFn pick_fn(bool eval) {
+  return eval ? smpc::smpc_eval_kernel<NB, W, kVT, kSP> : smpc::smpc_solve_kernel<NB, W, kVT, kSP>;
+}
+
 template <int NB> KernelFn pick_w(int W, bool eval, bool vt, bool sp) {
-  if (sp) {
-    if (W == 32) return eval ? smpc::smpc_eval_sp_kernel<NB, 32> : smpc::smpc_solve_sp_kernel<NB, 32>;
-    return eval ? smpc::smpc_eval_sp_kernel<NB, 64> : smpc::smpc_solve_sp_kernel<NB, 64>;
-  }
-  if (vt) {
-    if (W == 32) return eval ? smpc::smpc_eval_kernel<NB, 32, true> : smpc::smpc_solve_kernel<NB, 32, true>;
-    return eval ? smpc::smpc_eval_kernel<NB, 64, true> : smpc::smpc_solve_kernel<NB, 64, true>;
-  }
-  if (W == 32) return eval ? smpc::smpc_eval_kernel<NB, 32> : smpc::smpc_solve_kernel<NB, 32>;
-  return eval ? smpc::smpc_eval_kernel<NB, 64> : smpc::smpc_solve_kernel<NB, 64>;
+  if (W == 32) return sp ? pick_fn<NB, 32, true, true>(eval) : vt ? pick_fn<NB, 32, true, false>(eval) : pick_fn<NB, 32, false, false>(eval);
+  return sp ? pick_fn<NB, 64, true, true>(eval) : vt ? pick_fn<NB, 64, true, false>(eval) : pick_fn<NB, 64, false, false>(eval);
 }
 
 KernelFn pick(int nb, int W, bool eval, bool vt = false, bool sp = false) {

@@ -1,0 +1,176 @@
+// smpc_launch.hpp — what a launch of the sweep kernels (solve, K1, staging) is made of, for the host code that sizes and
+// issues it and for the kernels alike: the launch-parameter struct KParams, the lane mapping's constants, and the LDS
+// carve-up of a slot with the sizing functions behind it. Host and device; no device builtins.
+//
+// Lane mapping: a 64-lane wavefront is split into S = 64/W "slots" of W lanes (W = 32 when T+1 <= 32, else 64);
+// each slot works on its own scene, lane `sl` of a slot owns horizon step t = sl (pose after t+1 steps) for every
+// critic, and walks the N agents of that step in a register-resident loop (no cross-lane traffic for the social
+// terms). The horizon's cos/sin block and the staged people block live in LDS; per-step reductions over the slot
+// use wavefront shuffles.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/smpc.h"
+#include "smpc_math.hpp"
+
+namespace smpc {
+
+constexpr int kWave = 64;
+constexpr double kNoTarget = 1e300;  // agent-angle tag: no steering target at this step
+constexpr int kSoc = 15;  // sum F(2), sum dF/d{x,y,th,v}(8), sum |G|^2 (1), sum d|G|^2/d{x,y,th,v} (4)
+
+struct KParams {
+  int B, T, N, CH, bl, nb, P, nbounded, nfeas;
+  int size_x, size_y, costmap_shared;
+  double dt, resolution;
+  double inv_resolution;  // 1 / resolution, rounded once on the host
+  smpc_params prm;
+  const double* pose0;
+  const double* init_params;
+  const double* path_pts;
+  const double* goal_yaw;
+  const double* people;
+  const uint8_t* has_people;
+  const int32_t* T_scene;  // [B] rollout steps of each scene (<= T), or null: every scene has T (smpc_scene_batch.T_scene)
+  const uint8_t* costmap;
+  const double* costmap_origin;
+  // solve outputs
+  double* o_params;
+  double* o_cmds;
+  double* o_path;
+  int32_t* o_status;
+  int32_t* o_reason;
+  int32_t* o_iterations;
+  int32_t* o_evaluations;
+  double* o_initial_cost;
+  double* o_final_cost;
+  int* queue;  // scene work queue (one int, zeroed before every solve launch)
+  // staged people block (smpc_stage_people_batch / the library's own staging pass): what the sweep reads
+  const double* people_rec;  // [B][N][T][4]  px, py, vx, vy of people_proj[t + 1][a]
+  const double* people_aux;  // [B][T][2]     bit mask of valid agents (u64 bits), agent-angle target (kNoTarget: none)
+  const int32_t* order;      // [B] queue order of the solve kernel (null: index order)
+  int hp_A;                  // helper lanes (W = 64 kernels, see sweep()): agents the owner lane of a step walks itself;
+                             // == N: no helpers. Agents hp_A .. N-1 of every step are walked by the lanes beyond the horizon
+  int full_gram;             // != 0: every sweep of a solve forms the whole Gram (SMPC_FULL_GRAM: the check that stopping at
+                             // its last column changes nothing)
+  int prio_step;             // > 0: a wave whose oldest scene has made n sweeps runs at wave priority min(n / prio_step, 3)
+  double* stage_rec;         // staging kernel outputs (same layouts)
+  double* stage_aux;
+  unsigned long long* stamps;  // diagnostic builds only (SMPC_STAMPS): per-wave cycle sums per phase, [grid][8]
+  // eval (K1) inputs / outputs
+  const double* e_x;
+  double* e_residuals;
+  double* e_jacobian;
+  double* e_cost;
+  double* e_gradient;
+  int e_M;  // row stride of the eval outputs (M with people)
+  int e_row_order;  // 0: reference (step-major) row order, 1: critic-major (smpc_eval_batch_out.row_order)
+  MathTab mt;  // polynomial coefficients of smpc_math.hpp, read through scalar loads
+  AtanNodeTab an;  // nodes of atan2_unit(), copied into LDS by every wave (load_atan_nodes)
+  const smpc_scene_params* scene_params;  // [B] per-scene weights / bounds (smpc_scene_batch.scene_params): the sp kernels
+};
+
+// Kernel parameters are read through the kernel-argument segment (constant address space) instead of being held in
+// SGPRs for the whole kernel: the ~90 scalars of KParams otherwise overflow the SGPR file and come back as
+// v_readlane / v_writelane spill traffic on the VALU (1.4 k such instructions in the solve kernel before).
+typedef const KParams __attribute__((address_space(4))) * KParamsK;
+
+constexpr int kSensInRegsMaxBlocks = 6;  // K1 keeps a lane's sensitivities in registers up to this many parameter blocks
+// doubles of wave-shared LDS of the K1 kernel: two row staging blocks per slot, and the parked sensitivities
+__host__ __device__ constexpr int eval_extra_doubles(int T, int P, int W) {
+  return (64 / W) * (2 * T * P) + (P / 2 > kSensInRegsMaxBlocks ? (64 / W) * (5 * (P / 2) * W) : 0);
+}
+// The node table of atan2_unit() sits behind everything else in a wave's LDS (solve and K1 kernels).
+__host__ __device__ constexpr int atan_tab_offset(int slot_doubles, int extra_doubles) { return (slot_doubles + extra_doubles + 3) & ~3; }
+constexpr int kAtanTabDoubles = kAtanNodes * kAtanNodeStride;
+// Cross-lane sum of the per-lane Gram shares (solve kernel): values go through LDS in chunks of whole columns of the
+// packed upper triangle, at most kGramChunk values at a time; lane (part, v) of a slot then adds up value v of the 16
+// lanes of its part and the parts are combined by shuffles (W / 16 + 3 additions instead of 3 log2(W) shuffle
+// instructions per value). The buffer (W rows of kGramChunk + 1 doubles) lies over the sweep's own temporaries — the
+// cos / sin block and the scans are dead once the sensitivities are formed — plus a tail of its own; outside the
+// sweep the same area holds the temporaries of the LM algebra.
+constexpr int kGramChunk = 16;
+__host__ __device__ constexpr int gram_red_doubles(int W) { return W * (kGramChunk + 1); }
+// doubles of wave-shared LDS behind the per-slot blocks of the solve kernel: the feasibility rows of every slot
+__host__ __device__ constexpr int wave_extra_doubles(int P, int W) {
+  return (kWave / W) * ((P / 2 > 1 ? P / 2 - 1 : 1) * (P + 1));
+}
+
+// LDS carve-up (in doubles) of ONE slot.
+struct LdsLayout {
+  int ag;       // [N][T][4]  staged people block (px, py, vx, vy) — staging kernel only; the sweep reads the staged
+                //            records from global memory (HBM once in K1, L2 on the later sweeps of a solve)
+  int valid;    // [T]        bit a set = agent a valid at step t (64-bit words)
+  int cs;       // [2][T+1]   cos, sin of theta_j, j = 0..T
+  int inc;      // [4][T+1]   inclusive scans over j of cos, sin, j cos, j sin(theta_j) of the current sweep
+  int cst;      // [8]        x0, y0, yaw0, goal_yaw, origin x, origin y, final point x, y
+  int stepst;   // [4][T]     helper lanes only: robot x, y, velocity x, y at every step (what a pair evaluation needs of it)
+  int part;     // [T][kPart] helper lanes only: the partial sums a helper hands to the owner lane of a step
+  int hz;       // [4]        the scene's own horizon (kernels with per-scene T): ints T, CH, bl, last block, feasibility
+                //            rows, bounded blocks
+  int sp;       // [14]       sp kernels only: the scene's smpc_scene_params row (weights, target speed, bounds)
+  int lanec;    // [3][T]     per step: path point x, y (path_pts[t+1]) and agent-angle target (kNoTarget = none)
+  int lm;       // LM vectors / matrices / scalars
+  int gram;     // [(P+1)^2] Gram [J r]^T [J r] of the latest sweep, dense and symmetric
+  int scratch;  // polynomial scratch
+  int total;
+};
+
+// kLayoutSolve: LM state in LDS. kLayoutEval: the stand-alone K1 kernel, a single sweep. kLayoutStage: the staging
+// kernel, people block in LDS on its way to the staged records.
+enum LayoutKind { kLayoutEval = 0, kLayoutSolve = 1, kLayoutStage = 2 };
+
+constexpr int kPart = 18;  // 6 + 4 + 1 + 4 partial sums, nearest distance, its agent index, redo flag (+ 1 spare)
+
+// Helper lanes. With one scene per wave (W = 64) the lanes beyond the horizon (64 - T of them) idle through the agent loop,
+// the longest part of a sweep. They take over the tail of every step's agent list instead: the owner lane of step t walks
+// agents 0 .. A-1, one helper walks agents A .. N-1 of step t (a "unit"), helper h taking the units h, h + R, h + 2R, ...
+// (R = 64 - T helpers, U = ceil(T / R) units each) and handing the partial sums of each unit to its owner through LDS.
+// A is the smallest count with U (N - A) <= A: owners and helpers then finish together after A iterations instead of N
+// (BASELINE configs[4]: N = 16, T = 38 -> A = 11; params.yaml shape N = 3 -> A = 2). Returns N when helpers do not
+// pay (each unit costs a flush of ~30 instructions, the hand-over another ~40 per step).
+__host__ __device__ inline int helper_owner_agents(int T, int N, int W) {
+  const int R = W - T;
+  if (W != 64 || R < 1 || N < 2) return N;
+  const int U = (T + R - 1) / R;
+  const int A = (U * N + U) / (U + 1);            // ceil(U N / (U + 1))
+  if (A >= N) return N;
+  // instructions saved per sweep against the hand-over's, with a margin of two: measured, the params.yaml shape (N = 3:
+  // one pair saved, two units flushed) gained nothing, BASELINE configs[4] (five pairs saved) 14 %
+  return ((N - A) * 250 > 2 * (60 * U + 120)) ? A : N;
+}
+
+constexpr int kSceneParamDoubles = sizeof(smpc_scene_params) / sizeof(double);  // 14
+
+// W: the slot width of the kernel the layout is for (32: two scenes per wave, 64: one; slot_width() / solve_slot_width())
+// sp: the layout of the sp kernels (per-scene weights and bounds, smpc_scene_batch.scene_params): 14 doubles more per slot
+__host__ __device__ inline LdsLayout make_layout(int T, int N, int P, int kind, int W, bool sp = false) {
+  LdsLayout L;
+  const bool with_lm = kind == kLayoutSolve;
+  int o = 0;
+  L.ag = o; if (kind == kLayoutStage) o += 4 * T * (N > 0 ? N : 1);
+  L.valid = o; o += T;
+  L.cs = o; o += 2 * (T + 1);
+  L.inc = o; o += 4 * (T + 1);
+  if (with_lm) {  // tail of the Gram reduction buffer / LM temporaries, which start at L.cs
+    const int want = gram_red_doubles(W) > P * P + 7 * P + 96 ? gram_red_doubles(W) : P * P + 7 * P + 96;
+    if (want > 6 * (T + 1)) o += want - 6 * (T + 1);
+  }
+  L.cst = o; o += 8;
+  L.hz = o; o += 4;
+  L.sp = o; if (sp) o += kSceneParamDoubles;
+  L.stepst = o; L.part = o;
+  if (kind != kLayoutStage && helper_owner_agents(T, N, W) < N) { o += 4 * T; L.part = o; o += kPart * T; }
+  L.lanec = o; o += 3 * T;
+  L.lm = o; if (with_lm) o += P * P + 6 * P + 24;  // Hs, six vectors, scalars: what lives from trip to trip
+  L.gram = o; o += (P + 1) * (P + 1);  // dense symmetric [J r]^T [J r] of the latest sweep (VALU back-end)
+  L.scratch = o;  // (the generic line-search interpolation fallback borrows the wave's Gram reduction buffer)
+  L.total = (o + 3) & ~3;  // 32-byte multiple: records are moved as 4-double vectors
+  return L;
+}
+
+__host__ __device__ inline int slot_width(int T, int N) { return (T + 1 <= 32 && N <= 32) ? 32 : 64; }
+
+}  // namespace smpc

@@ -1,15 +1,12 @@
-// smpc_lm.hpp — per-slot Levenberg-Marquardt state machine (the ceres::Solve call of reference
-// src/optimizer.cpp:381, options :117-131) and the post-solve unpack (src/optimizer.cpp:390-446).
+// smpc_lm.hpp — the parts of the Levenberg-Marquardt solve the solve kernel (smpc_solve_kernel.hpp) is assembled from:
+// the small dense solves and polynomial root finders of the line search's interpolation, its register-resident fast
+// paths, the Armijo test, and the names of the state machine's phases, scalars and registers.
 // Algorithm = Ceres' trust-region minimizer with bounds as specified in SURVEY.md Appendix A (A.4 .. A.11).
-//
-// A wave is a persistent "sweep engine": every trip of the main loop runs ONE sweep() for all slots of the wave
-// at each slot's current trial point, then each slot advances its own LM state (phases below) and produces its
-// next trial point, or finishes its scene and pulls the next one from the global scene queue. Slots never wait for
-// each other: iteration counts and line-search lengths differ per scene, the sweep is the only shared code.
-// Every LM quantity is uniform across the W lanes of a slot (computed redundantly, LM vectors parked in LDS).
 #pragma once
 
-#include "smpc_device.hpp"
+#include <hip/hip_runtime.h>
+
+#include "smpc_math.hpp"
 
 namespace smpc {
 
@@ -457,97 +454,5 @@ struct LmRegs {  // slot-uniform integers / flags kept in registers
   int phase, iter, evals, num_invalid, ls_iters, n_samples, status, reason;
   bool step_successful, at_least_one, prev_vv, prev_gv, cur_vv, cur_gv, first_vv;
 };
-
-// waves per SIMD the solve kernel's register allocation must allow: three for the two-scenes-per-wave kernels up to three
-// parameter blocks (the headline shapes sit at 160-168 registers; stated so that an edit cannot silently cost the third
-// wave, which is what overlapped launches of several streams live on), two otherwise — the one-scene-per-wave kernels
-// serve small batches (the plugin's own B = 1 call) and long horizons, whose launches take at most eight waves per CU,
-// and their helper-lane loop needs the registers (held to 168 it spilled 14)
-#ifndef SMPC_SOLVE_MIN_WAVES
-#define SMPC_SOLVE_MIN_WAVES(NB, W) (((NB) <= 3 && (W) == 32) ? 3 : 2)
-#endif
-// The LM vectors and matrices of a slot are spread over its lanes: lane q < P owns parameter q (its entry of x, of the
-// trial point, of the step, row q of the scaled Gram and of its Cholesky factor). One instruction then updates all P
-// entries; sums over the parameters go through a few LDS words in index order (the same order a serial loop would
-// add them in). Nothing P x P lives in registers, so the P = 8..12 instantiations do not spill.
-//
-// Two kernels share this body (smpc_solve_kernel.inc, included once for each): smpc_solve_kernel<NB, W, kVT>, which takes
-// the handle's weights and bounds as launch constants, and smpc_solve_sp_kernel<NB, W>, whose scenes bring their own row of
-// smpc_scene_params (kSP: kept in the slot's LDS, see load_scene() and SMPC_SCENE_PRM) and always read their horizon per
-// scene (kVT; T for every scene when the batch gives no T_scene). The body is included rather than made a device function
-// the kernels call: behind a function boundary, always_inline included, the compiler optimises the body once on its own
-// before inlining it, which changed the register assignment and instruction order of the existing instantiations.
-#define SMPC_KERNEL_HEAD \
-  template <int NB, int W, bool kVT = false> \
-  __global__ __launch_bounds__(64, SMPC_SOLVE_MIN_WAVES(NB, W)) void smpc_solve_kernel(const KParams)
-#define SMPC_KERNEL_FLAGS constexpr bool kSP = false;
-#include "smpc_solve_kernel.inc"
-#undef SMPC_KERNEL_HEAD
-#undef SMPC_KERNEL_FLAGS
-#define SMPC_KERNEL_HEAD \
-  template <int NB, int W> __global__ __launch_bounds__(64, SMPC_SOLVE_MIN_WAVES(NB, W)) void smpc_solve_sp_kernel(const KParams)
-#define SMPC_KERNEL_FLAGS constexpr bool kVT = true, kSP = true;
-#include "smpc_solve_kernel.inc"
-#undef SMPC_KERNEL_HEAD
-#undef SMPC_KERNEL_FLAGS
-
-// K1 stand-alone: one sweep per scene at given parameters, rows written to HBM (parity checks, roofline runs).
-// Up to three parameter blocks the sweep fits the 168 registers that three waves per SIMD allow (the headline shapes;
-// K1 is a latency-bound streaming kernel, the third wave is worth 20 % of its time); beyond that the row buffers grow
-// with P and the allocator is left alone.
-#ifndef SMPC_EVAL_MIN_WAVES
-#define SMPC_EVAL_MIN_WAVES(NB) ((NB) <= 3 ? 3 : 1)
-#endif
-// smpc_eval_kernel<NB, W, kVT> and smpc_eval_sp_kernel<NB, W> share this body like the solve kernels (smpc_eval_kernel.inc).
-#define SMPC_KERNEL_HEAD \
-  template <int NB, int W, bool kVT = false> \
-  __global__ __launch_bounds__(64, SMPC_EVAL_MIN_WAVES(NB)) void smpc_eval_kernel(const KParams)
-#define SMPC_KERNEL_FLAGS constexpr bool kSP = false;
-#include "smpc_eval_kernel.inc"
-#undef SMPC_KERNEL_HEAD
-#undef SMPC_KERNEL_FLAGS
-#define SMPC_KERNEL_HEAD \
-  template <int NB, int W> __global__ __launch_bounds__(64, SMPC_EVAL_MIN_WAVES(NB)) void smpc_eval_sp_kernel(const KParams)
-#define SMPC_KERNEL_FLAGS constexpr bool kVT = true, kSP = true;
-#include "smpc_eval_kernel.inc"
-#undef SMPC_KERNEL_HEAD
-#undef SMPC_KERNEL_FLAGS
-
-// Staging pass: people block of the reference layout ([T+1][6][N] per scene) -> the records the sweep reads
-// ([N][T] x (px, py, vx, vy), written as whole 128-byte lines through LDS) + per-step valid mask and agent-angle tag.
-// One slot per scene like the sweep kernels; once per people block (a solve re-reads the records ~50 times).
-template <int W>
-__global__ __launch_bounds__(64) void smpc_stage_kernel(const KParams) {
-  SMPC_CHAIN_PRIORITY();
-  const auto& k = *(KParamsK)__builtin_amdgcn_kernarg_segment_ptr();
-  constexpr int S = kWave / W;
-  extern __shared__ __attribute__((aligned(32))) double lds_all[];
-  const int lane = threadIdx.x & 63;
-  const int slot = lane / W, sl = lane - slot * W;
-  const int T = k.T, N = k.N;
-  const LdsLayout L = make_layout(T, N, 2, kLayoutStage, W);
-  double* lds = lds_all + (size_t)slot * L.total;
-  const int scene_raw = blockIdx.x * S + slot;
-  const bool live = scene_raw < k.B;
-  const int scene = live ? scene_raw : k.B - 1;
-  const bool has_people = k.has_people ? k.has_people[scene] != 0 : true;
-  double* ag = lds + L.ag;
-  unsigned long long* vmask = reinterpret_cast<unsigned long long*>(lds + L.valid);
-  double* aa = lds + L.lanec;
-  if (has_people) stage_people<W>(&k, scene, sl, ag, vmask, aa);
-  wave_lds_fence();
-  if (live && has_people) {
-    const size_t s = scene;
-    const int nrec = N * T;
-    v4d* dst = reinterpret_cast<v4d*>(k.stage_rec + s * (size_t)4 * nrec);
-    const v4d* src = reinterpret_cast<const v4d*>(ag);
-    for (int q = sl; q < nrec; q += W) dst[q] = src[q];  // consecutive lanes, consecutive 32-byte records
-    if (sl < T) {
-      double* aux = k.stage_aux + (s * T + sl) * 2;
-      aux[0] = (lds + L.valid)[sl];
-      aux[1] = aa[sl];
-    }
-  }
-}
 
 }  // namespace smpc

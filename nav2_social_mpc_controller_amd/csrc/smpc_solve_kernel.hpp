@@ -1,8 +1,41 @@
-// smpc_solve_kernel.inc — the body of the solve kernels: included by smpc_lm.hpp once per kernel (no include guard),
-// with SMPC_KERNEL_HEAD the template head and name of the kernel and SMPC_KERNEL_FLAGS the constexpr flags (kSP, and kVT
-// where it is not a template parameter) it is compiled with.
-SMPC_KERNEL_HEAD {
-  SMPC_KERNEL_FLAGS
+// smpc_solve_kernel.hpp — the solve kernel: the per-slot Levenberg-Marquardt state machine (the ceres::Solve call of
+// reference src/optimizer.cpp:381, options :117-131) and the post-solve unpack (src/optimizer.cpp:390-446).
+//
+// A wave is a persistent "sweep engine": every trip of the main loop runs ONE sweep() for all slots of the wave
+// at each slot's current trial point, then each slot advances its own LM state (phases of smpc_lm.hpp) and produces its
+// next trial point, or finishes its scene and pulls the next one from the global scene queue. Slots never wait for
+// each other: iteration counts and line-search lengths differ per scene, the sweep is the only shared code.
+// Every LM quantity is uniform across the W lanes of a slot (computed redundantly, LM vectors parked in LDS).
+#pragma once
+
+#include "smpc_lm.hpp"
+#include "smpc_sweep.hpp"
+
+namespace smpc {
+
+// waves per SIMD the solve kernel's register allocation must allow: three for the two-scenes-per-wave kernels up to three
+// parameter blocks (the headline shapes sit at 160-168 registers; stated so that an edit cannot silently cost the third
+// wave, which is what overlapped launches of several streams live on), two otherwise — the one-scene-per-wave kernels
+// serve small batches (the plugin's own B = 1 call) and long horizons, whose launches take at most eight waves per CU,
+// and their helper-lane loop needs the registers (held to 168 it spilled 14)
+#ifndef SMPC_SOLVE_MIN_WAVES
+#define SMPC_SOLVE_MIN_WAVES(NB, W) (((NB) <= 3 && (W) == 32) ? 3 : 2)
+#endif
+// The LM vectors and matrices of a slot are spread over its lanes: lane q < P owns parameter q (its entry of x, of the
+// trial point, of the step, row q of the scaled Gram and of its Cholesky factor). One instruction then updates all P
+// entries; sums over the parameters go through a few LDS words in index order (the same order a serial loop would
+// add them in). Nothing P x P lives in registers, so the P = 8..12 instantiations do not spill.
+//
+// One template, four parameters: smpc_solve_kernel<NB, W, kVT, kSP>. Without kSP the handle's weights and bounds are launch
+// constants; with it every scene brings its own row of smpc_scene_params (kept in the slot's LDS, see load_scene() and
+// SMPC_SCENE_PRM) and the horizon is always read per scene (kVT; T for every scene when the batch gives no T_scene).
+// Variants of this kernel are template parameters, never a device function the kernel calls: behind a function boundary,
+// always_inline included, the compiler optimises the body once on its own before inlining it, which changes the register
+// assignment and instruction order of the existing instantiations. tools/isa_identity.py compares the machine code of
+// two trees function by function: run it on any edit that is meant to leave the generated code as it is.
+template <int NB, int W, bool kVT = false, bool kSP = false>
+__global__ __launch_bounds__(64, SMPC_SOLVE_MIN_WAVES(NB, W)) void smpc_solve_kernel(const KParams) {
+  static_assert(!kSP || kVT, "a kernel with per-scene weights and bounds reads its horizon per scene as well");
   const auto& k = *(KParamsK)__builtin_amdgcn_kernarg_segment_ptr();
   constexpr int P = 2 * NB;
   constexpr int S = kWave / W;
@@ -59,9 +92,8 @@ SMPC_KERNEL_HEAD {
   };
   // sums / maximum over the parameters: every active lane leaves its terms in the site's words, then every lane adds
   // them up in index order
-  auto reduce3 = [&](int site, double a, double b, double m, double& sa, double& sb, double& sm) {
+  auto reduce3 = [&](double a, double b, double m, double& sa, double& sb, double& sm) {
     double* w3 = rs;
-    (void)site;
     if (act) { w3[q] = a; w3[P + q] = b; w3[2 * P + q] = m; }
     wave_lds_fence();
     sa = 0.0; sb = 0.0; sm = 0.0;
@@ -146,7 +178,7 @@ SMPC_KERNEL_HEAD {
         }
         if (act) { xc[q] = v; xt[q] = v; }
         double xn, u0, u1;
-        reduce3(0, v * v, 0.0, 0.0, xn, u0, u1);
+        reduce3(v * v, 0.0, 0.0, xn, u0, u1);
         sv[S_XNORM] = fast_sqrt(xn);
         R.phase = PH_INIT;
         R.iter = 0; R.evals = 0; R.num_invalid = 0;
@@ -231,7 +263,7 @@ SMPC_KERNEL_HEAD {
         gm = fabs(xa - clampd(xa - g, lo_q, hi_q));
       }
       double xn, u0, gmax;
-      reduce3(1, xa * xa, 0.0, gm, xn, u0, gmax);
+      reduce3(xa * xa, 0.0, gm, xn, u0, gmax);
       sv[S_XNORM] = fast_sqrt(xn);
       sv[S_GMAX] = gmax;
     };
@@ -240,7 +272,7 @@ SMPC_KERNEL_HEAD {
       const double cand_cost = R.cur_vv ? sv[S_CUR_V] : 1.7976931348623157e308;
       const double d = act ? xc[q] - xt[q] : 0.0;
       double sn2, u0, u1;
-      reduce3(2, d * d, 0.0, 0.0, sn2, u0, u1);
+      reduce3(d * d, 0.0, 0.0, sn2, u0, u1);
       const double step_norm = fast_sqrt(sn2);
       const bool tol_allowed = !prm.fixed_iterations && (!prm.tol_needs_successful_step || R.at_least_one);
       if (tol_allowed && step_norm <= prm.param_tol * (sv[S_XNORM] + prm.param_tol)) {
@@ -291,7 +323,7 @@ SMPC_KERNEL_HEAD {
       // record the sample just evaluated (LineSearchFunction::Evaluate, A.8)
       const double dq = act ? dl[q] : 0.0;
       double gd, u0, u1;
-      reduce3(3, act ? dq * GH.base[q * GH.ld + P] : 0.0, 0.0, 0.0, gd, u0, u1);
+      reduce3(act ? dq * GH.base[q * GH.ld + P] : 0.0, 0.0, 0.0, gd, u0, u1);
       R.cur_vv = finite && isfinite(val);
       R.cur_gv = R.cur_vv && isfinite(gd);
       sv[S_CUR_V] = val; sv[S_CUR_G] = gd;
@@ -413,7 +445,7 @@ SMPC_KERNEL_HEAD {
 #pragma unroll
           for (int b = 0; b < P; ++b) rowv = fma(arow[b], bc[3 * P + b], rowv);
           double sg, sHs, u1;
-          reduce3(4, stepq * gsq, act ? stepq * rowv : 0.0, 0.0, sg, sHs, u1);
+          reduce3(stepq * gsq, act ? stepq * rowv : 0.0, 0.0, sg, sHs, u1);
           mcc = -sg - 0.5 * sHs;
           valid = mcc > 0.0;
         }
@@ -433,7 +465,7 @@ SMPC_KERNEL_HEAD {
           xt[q] = clampd(xc[q] + 1.0 * dq, lo_q, hi_q);
         }
         double gd0, u0, dirmax;
-        reduce3(5, gq, 0.0, fabs(dq), gd0, u0, dirmax);
+        reduce3(gq, 0.0, fabs(dq), gd0, u0, dirmax);
         sv[S_GD0] = gd0; sv[S_DIRMAX] = dirmax;
         sv[S_CUR_X] = 1.0;
         R.prev_vv = R.prev_gv = false;
@@ -508,3 +540,5 @@ SMPC_KERNEL_HEAD {
   }
 #endif
 }
+
+}  // namespace smpc

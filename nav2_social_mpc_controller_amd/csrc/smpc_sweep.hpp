@@ -1,6 +1,7 @@
-// smpc_device.hpp — gfx950 device code of the batched social-MPC solver: the residual/Jacobian sweep (K1).
+// smpc_sweep.hpp — the residual/Jacobian sweep of the batched social-MPC solver (the body of K1 and of every trip of
+// the solve kernel) and what it works on: the per-slot scene context, load_scene() and the per-scene horizon.
 //
-// What this restates, MI355X-first (reference files relative to /root/reference):
+// What this restates, MI355X-first (reference files relative to the reference repository's root):
 //   * rollout a1 (include/nav2_social_mpc_controller/update_state.hpp:37-63) as ONE shared rollout per sweep
 //     plus closed-form sensitivities S_t = d(x,y,theta)_{t+1}/d(params), instead of the reference's per-functor
 //     O(t) re-integration on ceres::Jet;
@@ -8,171 +9,20 @@
 //     state-space gradients (x, y, theta, v_block) chained with S_t — equal to Ceres autodiff in exact arithmetic;
 //   * the Gram contraction [J r]^T [J r] (gives J^T J, J^T r and the cost in one pass).
 //
-// Lane mapping: a 64-lane wavefront is split into S = 64/W "slots" of W lanes (W = 32 when T+1 <= 32, else 64);
-// each slot works on its own scene, lane `sl` of a slot owns horizon step t = sl (pose after t+1 steps) for every
-// critic, and walks the N agents of that step in a register-resident loop (no cross-lane traffic for the social
-// terms). The horizon's cos/sin block and the staged people block live in LDS; per-step reductions over the slot
-// use wavefront shuffles.
+// The lane mapping (slots, one lane per horizon step) is described in smpc_launch.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/smpc.h"
+#include "smpc_bicubic.hpp"
+#include "smpc_launch.hpp"
 #include "smpc_math.hpp"
+#include "smpc_social_force.hpp"
 
 namespace smpc {
-
-constexpr int kWave = 64;
-constexpr double kNoTarget = 1e300;  // agent-angle tag: no steering target at this step
-constexpr int kSoc = 15;  // sum F(2), sum dF/d{x,y,th,v}(8), sum |G|^2 (1), sum d|G|^2/d{x,y,th,v} (4)
-
-struct KParams {
-  int B, T, N, CH, bl, nb, P, nbounded, nfeas;
-  int size_x, size_y, costmap_shared;
-  double dt, resolution;
-  double inv_resolution;  // 1 / resolution, rounded once on the host
-  smpc_params prm;
-  const double* pose0;
-  const double* init_params;
-  const double* path_pts;
-  const double* goal_yaw;
-  const double* people;
-  const uint8_t* has_people;
-  const int32_t* T_scene;  // [B] rollout steps of each scene (<= T), or null: every scene has T (smpc_scene_batch.T_scene)
-  const uint8_t* costmap;
-  const double* costmap_origin;
-  // solve outputs
-  double* o_params;
-  double* o_cmds;
-  double* o_path;
-  int32_t* o_status;
-  int32_t* o_reason;
-  int32_t* o_iterations;
-  int32_t* o_evaluations;
-  double* o_initial_cost;
-  double* o_final_cost;
-  int* queue;  // scene work queue (one int, zeroed before every solve launch)
-  // staged people block (smpc_stage_people_batch / the library's own staging pass): what the sweep reads
-  const double* people_rec;  // [B][N][T][4]  px, py, vx, vy of people_proj[t + 1][a]
-  const double* people_aux;  // [B][T][2]     bit mask of valid agents (u64 bits), agent-angle target (kNoTarget: none)
-  const int32_t* order;      // [B] queue order of the solve kernel (null: index order)
-  int hp_A;                  // helper lanes (W = 64 kernels, see sweep()): agents the owner lane of a step walks itself;
-                             // == N: no helpers. Agents hp_A .. N-1 of every step are walked by the lanes beyond the horizon
-  int full_gram;             // != 0: every sweep of a solve forms the whole Gram (SMPC_FULL_GRAM: the check that stopping at
-                             // its last column changes nothing)
-  int prio_step;             // > 0: a wave whose oldest scene has made n sweeps runs at wave priority min(n / prio_step, 3)
-  double* stage_rec;         // staging kernel outputs (same layouts)
-  double* stage_aux;
-  unsigned long long* stamps;  // diagnostic builds only (SMPC_STAMPS): per-wave cycle sums per phase, [grid][8]
-  // eval (K1) inputs / outputs
-  const double* e_x;
-  double* e_residuals;
-  double* e_jacobian;
-  double* e_cost;
-  double* e_gradient;
-  int e_M;  // row stride of the eval outputs (M with people)
-  int e_row_order;  // 0: reference (step-major) row order, 1: critic-major (smpc_eval_batch_out.row_order)
-  MathTab mt;  // polynomial coefficients of smpc_math.hpp, read through scalar loads
-  AtanNodeTab an;  // nodes of atan2_unit(), copied into LDS by every wave (load_atan_nodes)
-  const smpc_scene_params* scene_params;  // [B] per-scene weights / bounds (smpc_scene_batch.scene_params): the sp kernels
-};
-
-// Cross-lane sum of the per-lane Gram shares (solve kernel): values go through LDS in chunks of whole columns of the
-// packed upper triangle, at most kGramChunk values at a time; lane (part, v) of a slot then adds up value v of the 16
-// lanes of its part and the parts are combined by shuffles (W / 16 + 3 additions instead of 3 log2(W) shuffle
-// instructions per value). The buffer (W rows of kGramChunk + 1 doubles) lies over the sweep's own temporaries — the
-// cos / sin block and the scans are dead once the sensitivities are formed — plus a tail of its own; outside the
-// sweep the same area holds the temporaries of the LM algebra.
-constexpr int kSensInRegsMaxBlocks = 6;  // K1 keeps a lane's sensitivities in registers up to this many parameter blocks
-// doubles of wave-shared LDS of the K1 kernel: two row staging blocks per slot, and the parked sensitivities
-__host__ __device__ constexpr int eval_extra_doubles(int T, int P, int W) {
-  return (64 / W) * (2 * T * P) + (P / 2 > kSensInRegsMaxBlocks ? (64 / W) * (5 * (P / 2) * W) : 0);
-}
-// The node table of atan2_unit() sits behind everything else in a wave's LDS (solve and K1 kernels).
-__host__ __device__ constexpr int atan_tab_offset(int slot_doubles, int extra_doubles) { return (slot_doubles + extra_doubles + 3) & ~3; }
-constexpr int kAtanTabDoubles = kAtanNodes * kAtanNodeStride;
-constexpr int kGramChunk = 16;
-__host__ __device__ constexpr int gram_red_doubles(int W) { return W * (kGramChunk + 1); }
-// doubles of wave-shared LDS behind the per-slot blocks of the solve kernel: the feasibility rows of every slot
-__host__ __device__ constexpr int wave_extra_doubles(int P, int W) {
-  return (kWave / W) * ((P / 2 > 1 ? P / 2 - 1 : 1) * (P + 1));
-}
-
-// LDS carve-up (in doubles) of ONE slot.
-struct LdsLayout {
-  int ag;       // [N][T][4]  staged people block (px, py, vx, vy) — staging kernel only; the sweep reads the staged
-                //            records from global memory (HBM once in K1, L2 on the later sweeps of a solve)
-  int valid;    // [T]        bit a set = agent a valid at step t (64-bit words)
-  int cs;       // [2][T+1]   cos, sin of theta_j, j = 0..T
-  int inc;      // [4][T+1]   inclusive scans over j of cos, sin, j cos, j sin(theta_j) of the current sweep
-  int cst;      // [8]        x0, y0, yaw0, goal_yaw, origin x, origin y, final point x, y
-  int stepst;   // [4][T]     helper lanes only: robot x, y, velocity x, y at every step (what a pair evaluation needs of it)
-  int part;     // [T][kPart] helper lanes only: the partial sums a helper hands to the owner lane of a step
-  int hz;       // [4]        the scene's own horizon (kernels with per-scene T): ints T, CH, bl, last block, feasibility
-                //            rows, bounded blocks
-  int sp;       // [14]       sp kernels only: the scene's smpc_scene_params row (weights, target speed, bounds)
-  int lanec;    // [3][T]     per step: path point x, y (path_pts[t+1]) and agent-angle target (kNoTarget = none)
-  int lm;       // LM vectors / matrices / scalars
-  int gram;     // [(P+1)^2] Gram [J r]^T [J r] of the latest sweep, dense and symmetric
-  int scratch;  // polynomial scratch
-  int total;
-};
-
-enum LayoutKind { kLayoutEval = 0, kLayoutSolve = 1, kLayoutStage = 2 };
-
-// kLayoutSolve: LM state in LDS. kLayoutEval: the stand-alone K1 kernel, a single sweep. kLayoutStage: the staging
-// kernel, people block in LDS on its way to the staged records.
-constexpr int kPart = 18;  // 6 + 4 + 1 + 4 partial sums, nearest distance, its agent index, redo flag (+ 1 spare)
-
-// Helper lanes. With one scene per wave (W = 64) the lanes beyond the horizon (64 - T of them) idle through the agent loop,
-// the longest part of a sweep. They take over the tail of every step's agent list instead: the owner lane of step t walks
-// agents 0 .. A-1, one helper walks agents A .. N-1 of step t (a "unit"), helper h taking the units h, h + R, h + 2R, ...
-// (R = 64 - T helpers, U = ceil(T / R) units each) and handing the partial sums of each unit to its owner through LDS.
-// A is the smallest count with U (N - A) <= A: owners and helpers then finish together after A iterations instead of N
-// (BASELINE configs[4]: N = 16, T = 38 -> A = 11; params.yaml shape N = 3 -> A = 2). Returns N when helpers do not
-// pay (each unit costs a flush of ~30 instructions, the hand-over another ~40 per step).
-__host__ __device__ inline int helper_owner_agents(int T, int N, int W) {
-  const int R = W - T;
-  if (W != 64 || R < 1 || N < 2) return N;
-  const int U = (T + R - 1) / R;
-  const int A = (U * N + U) / (U + 1);            // ceil(U N / (U + 1))
-  if (A >= N) return N;
-  // instructions saved per sweep against the hand-over's, with a margin of two: measured, the params.yaml shape (N = 3:
-  // one pair saved, two units flushed) gained nothing, BASELINE configs[4] (five pairs saved) 14 %
-  return ((N - A) * 250 > 2 * (60 * U + 120)) ? A : N;
-}
-
-constexpr int kSceneParamDoubles = sizeof(smpc_scene_params) / sizeof(double);  // 14
-
-// W: the slot width of the kernel the layout is for (32: two scenes per wave, 64: one; slot_width() / solve_slot_width())
-// sp: the layout of the sp kernels (per-scene weights and bounds, smpc_scene_batch.scene_params): 14 doubles more per slot
-__host__ __device__ inline LdsLayout make_layout(int T, int N, int P, int kind, int W, bool sp = false) {
-  LdsLayout L;
-  const bool with_lm = kind == kLayoutSolve;
-  int o = 0;
-  L.ag = o; if (kind == kLayoutStage) o += 4 * T * (N > 0 ? N : 1);
-  L.valid = o; o += T;
-  L.cs = o; o += 2 * (T + 1);
-  L.inc = o; o += 4 * (T + 1);
-  if (with_lm) {  // tail of the Gram reduction buffer / LM temporaries, which start at L.cs
-    const int want = gram_red_doubles(W) > P * P + 7 * P + 96 ? gram_red_doubles(W) : P * P + 7 * P + 96;
-    if (want > 6 * (T + 1)) o += want - 6 * (T + 1);
-  }
-  L.cst = o; o += 8;
-  L.hz = o; o += 4;
-  L.sp = o; if (sp) o += kSceneParamDoubles;
-  L.stepst = o; L.part = o;
-  if (kind != kLayoutStage && helper_owner_agents(T, N, W) < N) { o += 4 * T; L.part = o; o += kPart * T; }
-  L.lanec = o; o += 3 * T;
-  L.lm = o; if (with_lm) o += P * P + 6 * P + 24;  // Hs, six vectors, scalars: what lives from trip to trip
-  L.gram = o; o += (P + 1) * (P + 1);  // dense symmetric [J r]^T [J r] of the latest sweep (VALU back-end)
-  L.scratch = o;  // (the generic line-search interpolation fallback borrows the wave's Gram reduction buffer)
-  L.total = (o + 3) & ~3;  // 32-byte multiple: records are moved as 4-double vectors
-  return L;
-}
-
-__host__ __device__ inline int slot_width(int T, int N) { return (T + 1 <= 32 && N <= 32) ? 32 : 64; }
 
 // The workgroup is ONE wavefront: LDS operations of a wave execute in program order, so cross-lane hand-offs through
 // LDS only need the compiler not to reorder them — no s_barrier and, importantly, no s_waitcnt vmcnt(0) that a
@@ -189,15 +39,6 @@ template <int W> __device__ inline double slot_sum(double v) {
   return v;
 }
 
-__device__ inline double wrap_to_pi(double a) {  // critics/social_work_cost_function.hpp:39-46
-  // only ever called on a difference of two atan2 results (|a| <= 2 pi, or NaN): at most one trip per loop; the guard
-  // keeps the wave finite should that ever change
-  if (!(fabs(a) <= 8.0 * M_PI)) a = fmod(a, 2.0 * M_PI);
-  while (a > M_PI) a -= 2.0 * M_PI;
-  while (a <= -M_PI) a += 2.0 * M_PI;
-  return a;
-}
-
 // atan2(sin u, cos u) restated as a range reduction of u into (-pi, pi]; equal up to round-off
 // (critics/agent_angle_cost_function.hpp:156, critics/goal_align_cost_function.hpp:111-112).
 __device__ inline double wrap_angle(double u) {
@@ -207,295 +48,6 @@ __device__ inline double wrap_angle(double u) {
   return r;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Social force between one (me, other) pair and its derivatives with respect to diff = me_pos - other_pos and
-// u = me_vel - other_vel. Restates computeSocialForce (critics/social_work_cost_function.hpp:164-228) for a
-// single "other"; constants from src/critics/social_work_cost_function.cpp:38-43. F = k (fv i + fa i_perp).
-// ------------------------------------------------------------------------------------------------
-struct Force {
-  double fx, fy;
-  double dfx_dx, dfy_dx, dfx_dy, dfy_dy;      // wrt diff
-  double dfx_dux, dfy_dux, dfx_duy, dfy_duy;  // wrt u
-  bool special;  // pair_force() only: this pair needs social_force_general() (theta within 1e-6 of 0 or pi)
-};
-
-// 1/sqrt(x) for a normal positive x: hardware estimate + one cubic correction (what the library routine does, without
-// its zero / infinity / denormal cases, which cannot occur here: d2 >= 1e-12 after the coincident-pair clamp, and a
-// vanishing interaction vector is a singular configuration for the reference as well).
-__device__ inline double fast_rsqrt(double x) {
-  const double y = __builtin_amdgcn_rsq(x);
-  const double e = fma(-x * y, y, 1.0);
-  return fma(y * e, fma(e, 0.375, 0.5), y);
-}
-
-__device__ inline Force social_force_general(double dx, double dy, double ux, double uy) {
-  const double lambda = 2.0, gamma = 0.35, nPrime = 3.0, nn = 2.0, k = 2.1;
-  Force R;
-  double d2 = dx * dx + dy * dy;
-  const bool degenerate = d2 < 1e-12;  // |diff| < 1e-6 (:181-184): diff := (1e-6, 0), a constant: no dependence on positions
-  if (degenerate) { dx = 1e-6; dy = 0.0; d2 = 1e-12; }
-  const double inv_n = fast_rsqrt(d2);
-  const double n = d2 * inv_n;
-  const double ex = dx * inv_n, ey = dy * inv_n;  // diffDirection :185
-  const double ivx = fma(lambda, ux, ex), ivy = fma(lambda, uy, ey);  // :191-192 (lambda u is exact: lambda = 2)
-  const double L2 = ivx * ivx + ivy * ivy;
-  const double inv_L = fast_rsqrt(L2);
-  const double L = L2 * inv_L;  // :194
-  const double ix = ivx * inv_L, iy = ivy * inv_L;  // :195-196
-  // theta = wrapToPi(atan2(dir) - atan2(idir)) (:198-200) is the angle from idir to dir = atan2(idir x dir, idir . dir).
-  // One atan2 instead of two wherever that cannot change sign(theta): away from theta = 0 and |theta| = pi
-  // (|sin theta| >= 1e-6). Closer than that the reference's own two-atan2 form is evaluated, so that the last-bit
-  // behaviour next to the discontinuity of sign(theta) (:210) stays the reference's.
-  // Equal velocities (robot stopped beside a standing person): theta is mathematically 0 and the reference's value is
-  // 0 up to the last-bit noise of its own libm (which then decides sign(theta)). Take exactly 0.
-  const double cross = ix * ey - iy * ex, dot = ix * ex + iy * ey;
-  double phi;
-  if (ux == 0.0 && uy == 0.0) {
-    phi = 0.0;
-  } else if (fabs(cross) >= 1e-6) {
-    phi = atan2(cross, dot);
-  } else {
-    phi = wrap_to_pi(atan2(ey, ex) - atan2(iy, ix));
-  }
-  const double Bq = gamma * L;  // :203
-  const double inv_B = inv_L * (1.0 / gamma);
-  const double a1 = nPrime * Bq * phi, a2 = nn * Bq * phi;
-  const double base = -n * inv_B;
-  const double E1 = exp(base - a1 * a1);  // :205-207
-  const double E2 = exp(base - a2 * a2);  // :212-215
-  const double sgn = (phi > 0.0) ? 1.0 : -1.0;  // :210
-  const double fv = -E1, fa = -sgn * E2;
-  R.fx = k * (fv * ix - fa * iy);  // :218-224, i_perp = (-iy, ix)
-  R.fy = k * (fv * iy + fa * ix);
-  // The force depends on its inputs through (n, alpha = atan2(e), iv): dF = A_n dn + A_alpha dalpha + A_x d(iv_x) +
-  // A_y d(iv_y). With dL = i . d(iv), kappa = d atan2(i) = (i_perp . d(iv)) / L, dphi = dalpha - kappa, dB = gamma dL,
-  //   d(arg_m) = -dn/B + n dB/B^2 - 2 a_m c_m (dB phi + B dphi),   dF = k ((dfv - fa kappa) i + (dfa + fv kappa) i_perp),
-  // the four columns are evaluated once and every direction below is a linear combination of them.
-  const double nB2 = n * inv_B * inv_B;
-  // A_n: dn = 1 -> d(arg) = -1/B, no rotation: -F / B
-  const double anx = -inv_B * R.fx, any = -inv_B * R.fy;
-  // A_alpha: dalpha = 1 -> dphi = 1, d(arg_m) = -2 a_m c_m B
-  double aax, aay;
-  {
-    const double twoB = 2.0 * Bq;
-    const double dfv = E1 * (a1 * nPrime * twoB);
-    const double dfa = sgn * E2 * (a2 * nn * twoB);
-    aax = k * (dfv * ix - dfa * iy);
-    aay = k * (dfv * iy + dfa * ix);
-  }
-  // A_x, A_y: d(iv) = (1, 0) / (0, 1)
-  auto column = [&](double dL, double kappa, double& ofx, double& ofy) {
-    const double dB = gamma * dL;
-    const double dbase = nB2 * dB;
-    const double common = dB * phi - Bq * kappa;  // dphi = -kappa
-    const double dfv = -E1 * (dbase - 2.0 * a1 * nPrime * common);
-    const double dfa = -sgn * E2 * (dbase - 2.0 * a2 * nn * common);
-    const double ci = dfv - fa * kappa, cp = dfa + fv * kappa;
-    ofx = k * (ci * ix - cp * iy);
-    ofy = k * (ci * iy + cp * ix);
-  };
-  double axx, axy, ayx, ayy;
-  column(ix, -iy * inv_L, axx, axy);
-  column(iy, ix * inv_L, ayx, ayy);
-  R.dfx_dux = lambda * axx; R.dfy_dux = lambda * axy;  // u enters iv as lambda u
-  R.dfx_duy = lambda * ayx; R.dfy_duy = lambda * ayy;
-  if (degenerate) {
-    R.dfx_dx = R.dfy_dx = R.dfx_dy = R.dfy_dy = 0.0;
-  } else {
-    // moving diff by dd: dn = e . dd, dalpha = (e_perp . dd) / n, d(iv) = de = e_perp dalpha, e_perp = (-ey, ex);
-    // C = A_alpha + A_x (-ey) + A_y ex is what one unit of dalpha does in total
-    const double cx = aax - ey * axx + ex * ayx, cy = aay - ey * axy + ex * ayy;
-    const double da1 = -ey * inv_n, da2 = ex * inv_n;  // dd = (1, 0) / (0, 1)
-    R.dfx_dx = ex * anx + da1 * cx; R.dfy_dx = ex * any + da1 * cy;
-    R.dfx_dy = ey * anx + da2 * cx; R.dfy_dy = ey * any + da2 * cy;
-  }
-  return R;
-}
-
-// The same force for a regular pair (|diff| >= 1e-6, the overwhelmingly common case), built for instruction count:
-// table-driven exp / atan2 (smpc_math.hpp), no selects for the coincident-pair clamp, no branches. Two rare shapes
-// are only flagged, for the caller to redo the step's agents with social_force_general(): a coincident pair (flagged
-// by the caller) and a pair whose theta is within 1e-6 of 0 or pi while the velocities differ (Force::special: next
-// to the discontinuity of sign(theta) the reference's own two-atan2 form decides, :198-200).
-// pair_force(-d, -u) == -pair_force(d, u) bit for bit (every intermediate flips sign or stays exactly), with equal
-// derivatives: the force on an agent from the robot needs no evaluation of its own.
-// The constant factors are left to the caller, who applies them once to the sums over the agents of a step instead of
-// to every pair: the force and its diff-derivatives come WITHOUT the factor k (kPairForceK), the u-derivatives without
-// k * lambda (kPairForceLambda; u enters the interaction vector as lambda u).
-constexpr double kPairForceK = 2.1, kPairForceLambda = 2.0;
-__device__ inline Force pair_force(MathTabP mt, const double* atab, double dx, double dy, double ux, double uy) {
-  const double lambda = kPairForceLambda, gamma = 0.35, nPrime = 3.0, nn = 2.0;
-  Force R;
-  const double d2 = fma(dx, dx, dy * dy);
-  const double inv_n = rsqrt_pos(d2);
-  const double n = d2 * inv_n;
-  const double ex = dx * inv_n, ey = dy * inv_n;  // diffDirection :185
-  const double ivx = fma(lambda, ux, ex), ivy = fma(lambda, uy, ey);  // :191-192
-  const double L2 = fma(ivx, ivx, ivy * ivy);
-  const double inv_L = rsqrt_pos(L2);
-  const double L = L2 * inv_L;  // :194
-  const double ix = ivx * inv_L, iy = ivy * inv_L;  // :195-196
-  const double cross = fma(ix, ey, -(iy * ex)), dot = fma(ix, ex, iy * ey);
-  const bool zero_u = (ux == 0.0) & (uy == 0.0);  // equal velocities: theta := 0 (parity)
-  double phi = atan2_unit(mt, atab, cross, dot);  // (cross, dot) = (sin, cos) of theta: a unit vector
-  // keep the scheduler from interleaving the arctangent, the two exponentials and the derivative block: the extra
-  // overlap buys nothing with two or three waves per SIMD and costs ~15 VGPRs (the stand-alone K1 kernel would drop
-  // from three waves per SIMD to two)
-  __builtin_amdgcn_sched_barrier(0);
-  R.special = !zero_u & (fabs(cross) < 1e-6);
-  phi = zero_u ? 0.0 : phi;
-  const double Bq = gamma * L;  // :203
-  const double inv_B = inv_L * (1.0 / gamma);
-  const double a1 = nPrime * Bq * phi, a2 = nn * Bq * phi;
-  const double base = -n * inv_B;
-  const double E1 = exp_tab(mt, fma(-a1, a1, base));  // :205-207
-  const double E2 = exp_tab(mt, fma(-a2, a2, base));  // :212-215
-  __builtin_amdgcn_sched_barrier(0);
-  const double fv = -E1;
-  const double fa = (phi > 0.0) ? -E2 : E2;  // -sign(theta) E2, sign = -1 at theta == 0 (:210)
-  R.fx = fma(fv, ix, -(fa * iy));  // :218-224 without the factor k, i_perp = (-iy, ix)
-  R.fy = fma(fv, iy, fa * ix);
-  // derivative: see social_force_general(); dfa = sgn E2 (...) = -fa (...)
-  const double nB2 = n * inv_B * inv_B;
-  const double anx = -inv_B * R.fx, any = -inv_B * R.fy;
-  const double twoB = 2.0 * Bq;
-  const double g1 = a1 * nPrime, g2 = a2 * nn;
-  double aax, aay;
-  {
-    const double dfv = E1 * (g1 * twoB);
-    const double dfa = -fa * (g2 * twoB);
-    aax = fma(dfv, ix, -(dfa * iy));
-    aay = fma(dfv, iy, dfa * ix);
-  }
-  auto column = [&](double dL, double kappa, double& ofx, double& ofy) {
-    const double dB = gamma * dL;
-    const double dbase = nB2 * dB;
-    const double common = 2.0 * fma(dB, phi, -(Bq * kappa));  // dphi = -kappa
-    const double dfv = fv * fma(-g1, common, dbase);
-    const double dfa = fa * fma(-g2, common, dbase);
-    const double ci = fma(-fa, kappa, dfv), cp = fma(fv, kappa, dfa);
-    ofx = fma(ci, ix, -(cp * iy));
-    ofy = fma(ci, iy, cp * ix);
-  };
-  double axx, axy, ayx, ayy;
-  column(ix, -iy * inv_L, axx, axy);
-  column(iy, ix * inv_L, ayx, ayy);
-  R.dfx_dux = axx; R.dfy_dux = axy;  // without the factor k * lambda
-  R.dfx_duy = ayx; R.dfy_duy = ayy;
-  const double cx = aax - ey * axx + ex * ayx, cy = aay - ey * axy + ex * ayy;
-  const double da1 = -ey * inv_n, da2 = ex * inv_n;
-  R.dfx_dx = ex * anx + da1 * cx; R.dfy_dx = ex * any + da1 * cy;
-  R.dfx_dy = ey * anx + da2 * cx; R.dfy_dy = ey * any + da2 * cy;
-  return R;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Bicubic interpolation of the u8 costmap with clamp-to-edge, value and gradient
-// (ceres::BiCubicInterpolator<Grid2D<u_char>> semantics; used by
-// critics/obstacle_cost_function.hpp:161 as Evaluate(row = y_cell, col = x_cell)).
-// ------------------------------------------------------------------------------------------------
-__device__ inline void cubic_hermite(double p0, double p1, double p2, double p3, double x, double& f, double& df) {
-  const double a = 0.5 * (-p0 + 3.0 * p1 - 3.0 * p2 + p3);
-  const double b = 0.5 * (2.0 * p0 - 5.0 * p1 + 4.0 * p2 - p3);
-  const double c = 0.5 * (-p0 + p2);
-  f = p1 + x * (c + x * (b + x * a));
-  df = c + x * (2.0 * b + 3.0 * a * x);
-}
-
-// The same interpolation split in two, so that the sweep can request the 4 x 4 patch as soon as the pose is known and
-// consume it after the agent loop (the 16 dependent byte loads were 6 % of a lone solve launch): the patch is fetched
-// as four unaligned dwords, one per row, starting at column clamp(col - 1, 0, size_x - 4); the byte of clamped column
-// cc is then byte (cc - start) of its row's dword — also at the edges, where several taps share a cell.
-struct CostPatch {
-  uint32_t row[4];   // bytes start .. start + 3 of the four clamped rows
-};
-
-// Integer cell of a coordinate, kept defined for wild values (clamping below makes any far-outside index equivalent).
-__device__ inline int cell_index(double v, int size) { return (int)fmin(fmax(floor(v), -4.0), (double)size + 4.0); }
-
-// true when the whole 4 x 4 patch around (r, c) lies inside the map: no tap is clamped (NaN coordinates: false)
-__device__ inline bool bicubic_interior(int size_x, int size_y, double r, double c) {
-  const int row = cell_index(r, size_y), col = cell_index(c, size_x);
-  return (row >= 1) & (row <= size_y - 3) & (col >= 1) & (col <= size_x - 3);
-}
-
-// kInterior: the caller has established bicubic_interior() for EVERY lane of the wave (a wave-uniform decision: the
-// clamps, the per-tap bit offsets and their variable shifts — ~90 integer instructions per sweep — are then skipped;
-// the taps and the arithmetic on them are the same, so the result does not depend on which path a wave takes).
-template <bool kInterior>
-__device__ inline void bicubic_fetch(const uint8_t* __restrict__ map, int size_x, int size_y, double r, double c, CostPatch& p) {
-  const int row = cell_index(r, size_y), col = cell_index(c, size_x);
-  if (kInterior) {
-    const uint8_t* q = map + (size_t)(row - 1) * size_x + (col - 1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      uint32_t v;
-      __builtin_memcpy(&v, q + (size_t)i * size_x, 4);  // unaligned dword
-      p.row[i] = v;
-    }
-    return;
-  }
-  const int start = min(max(col - 1, 0), size_x - 4);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int rr = min(max(row - 1 + i, 0), size_y - 1);
-    uint32_t v;
-    __builtin_memcpy(&v, map + (size_t)rr * size_x + start, 4);  // unaligned dword
-    p.row[i] = v;
-  }
-}
-
-// (r, c) must be the coordinates the patch was fetched for. The bit offsets of the clamped taps inside a row dword are
-// derived here from c, not at the fetch: carried in the patch across the agent loop they were one register more than K1
-// <3,32> has (one spilled VGPR).
-template <bool kInterior>
-__device__ inline void bicubic_eval(const CostPatch& p, int size_x, double r, double c, double& f, double& dfdr,
-                                    double& dfdc) {
-  const double tr = r - floor(r), tc = c - floor(c);
-  uint32_t sh[4] = {0u, 8u, 16u, 24u};
-  if (!kInterior) {
-    const int col = cell_index(c, size_x);
-    const int start = min(max(col - 1, 0), size_x - 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sh[j] = (uint32_t)(8 * (min(max(col - 1 + j, 0), size_x - 1) - start));
-  }
-  double fv[4], dv[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    double t[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) t[j] = (double)((p.row[i] >> sh[j]) & 0xffu);
-    cubic_hermite(t[0], t[1], t[2], t[3], tc, fv[i], dv[i]);
-  }
-  double unused;
-  cubic_hermite(fv[0], fv[1], fv[2], fv[3], tr, f, dfdr);
-  cubic_hermite(dv[0], dv[1], dv[2], dv[3], tr, dfdc, unused);
-}
-
-__device__ inline void bicubic(const uint8_t* __restrict__ map, int size_x, int size_y, double r, double c,
-                               double& f, double& dfdr, double& dfdc) {
-  const double fr = floor(r), fc = floor(c);
-  // keep the int conversion defined for wild coordinates; clamping below makes any far-outside index equivalent
-  const double frc = fmin(fmax(fr, -4.0), (double)size_y + 4.0), fcc = fmin(fmax(fc, -4.0), (double)size_x + 4.0);
-  const int row = (int)frc, col = (int)fcc;
-  double fv[4], dv[4];
-  int cc[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) cc[j] = min(max(col - 1 + j, 0), size_x - 1);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int rr = min(max(row - 1 + i, 0), size_y - 1);
-    const uint8_t* p = map + (size_t)rr * size_x;
-    cubic_hermite((double)p[cc[0]], (double)p[cc[1]], (double)p[cc[2]], (double)p[cc[3]], c - fc, fv[i], dv[i]);
-  }
-  double unused;
-  cubic_hermite(fv[0], fv[1], fv[2], fv[3], r - fr, f, dfdr);
-  cubic_hermite(dv[0], dv[1], dv[2], dv[3], r - fr, dfdc, unused);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Per-slot scene context (registers; slot-uniform unless noted)
-// ------------------------------------------------------------------------------------------------
 // In-kernel phase stamps (diagnostic build -DSMPC_STAMPS only; the shipped kernel executes none of this).
 #ifdef SMPC_STAMPS
 #define SMPC_STAMP(ctx, phase) do { const unsigned long long _t = __builtin_amdgcn_s_memtime(); (ctx).acc[phase] += _t - (ctx).t_last; (ctx).t_last = _t; } while (0)
@@ -505,11 +57,9 @@ __device__ inline void bicubic(const uint8_t* __restrict__ map, int size_x, int 
 #define SMPC_STAMP(ctx, phase) do { } while (0)
 #endif
 
-// Kernel parameters are read through the kernel-argument segment (constant address space) instead of being held in
-// SGPRs for the whole kernel: the ~90 scalars of KParams otherwise overflow the SGPR file and come back as
-// v_readlane / v_writelane spill traffic on the VALU (1.4 k such instructions in the solve kernel before).
-typedef const KParams __attribute__((address_space(4))) * KParamsK;
-
+// ------------------------------------------------------------------------------------------------
+// Per-slot scene context (registers; slot-uniform unless noted)
+// ------------------------------------------------------------------------------------------------
 struct Ctx {
 #ifdef SMPC_STAMPS
   unsigned long long t_last;
@@ -544,85 +94,6 @@ struct GramView {
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
-
-// Staging pass (its own kernel, once per people block): gather the slot's people block, agent index fastest across
-// lanes (coalesced runs of one people row, 16 loads in flight per lane), convert to one 32-byte record (px, py, vx, vy)
-// per (agent, step) at record index a * T + t in LDS (ag), and compute per step the bit mask of valid agents (vmask)
-// and the agent-angle tag (aa). Executed by all W lanes of the slot.
-template <int W>
-__device__ inline void stage_people(KParamsK kp, int scene, int sl, double* ag, unsigned long long* vmask, double* aa) {
-  const auto& k = *kp;
-  const int T = k.T, N = k.N;
-  const size_t s = scene;
-  const double x0 = k.pose0[3 * s], y0 = k.pose0[3 * s + 1], yaw0 = k.pose0[3 * s + 2];
-  const double* ppl = k.people + s * (size_t)(T + 1) * 6 * N;
-  const int TN = T * N;
-  // people_proj[t+1] field f agent a is at ((t+1)*6 + f)*N + a. Element (a, t) lands at a*T + t.
-  for (int e0 = sl; e0 < TN; e0 += 4 * W) {
-    double gx[4], gy[4], gyaw[4], glv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int e = min(e0 + u * W, TN - 1);
-      const int t = e / N, a = e - t * N;
-      const double* f = ppl + (size_t)(t + 1) * 6 * N + a;
-      gx[u] = f[0]; gy[u] = f[N]; gyaw[u] = f[2 * N]; glv[u] = f[4 * N];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int e = e0 + u * W;
-      if (e < TN) {
-        const int t = e / N, a = e - t * N;
-        double sn, cs;
-        if (__builtin_expect(!(fabs(gyaw[u]) <= 1e5), 0)) sincos(gyaw[u], &sn, &cs);
-        else sincos_tab(&k.mt, gyaw[u], &sn, &cs);
-        const int q = a * T + t;
-        v4d rec = {gx[u], gy[u], glv[u] * cs, glv[u] * sn};  // aVel, social_work:187-188
-        reinterpret_cast<v4d*>(ag)[q] = rec;
-      }
-    }
-  }
-  if (sl < T) {
-    const double* f = ppl + (size_t)(sl + 1) * 6 * N;
-    unsigned long long m = 0;
-    double aa_target = kNoTarget;
-    // a7 AgentAngle tag: depends on constants only (critics/agent_angle_cost_function.hpp:130-190)
-    int closest = -1;
-    double best = INFINITY;
-    for (int a0 = 0; a0 < N; a0 += 4) {  // loads of four agents in flight at a time
-      double ft[4], fx[4], fy[4], fl[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int a = min(a0 + u, N - 1);
-        ft[u] = f[3 * N + a]; fx[u] = f[a]; fy[u] = f[N + a]; fl[u] = f[4 * N + a];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int a = a0 + u;
-        if (a < N) {
-          if (ft[u] != -1.0) m |= (1ull << a);  // social_work:175
-          const double ddx = fx[u] - x0, ddy = fy[u] - y0;
-          const double d2 = ddx * ddx + ddy * ddy;
-          if (d2 < best && fl[u] > 0.05) { best = d2; closest = a; }
-        }
-      }
-    }
-    if (closest >= 0 && !(best > 4.0)) {
-      const double ax = f[closest], ay = f[N + closest], ayaw = f[2 * N + closest];
-      const double agent_angle_initial = atan2(ay - y0, ax - x0);
-      // atan2(sin u, cos u) of the reference (:148-152) restated as the range reduction wrap_angle(u)
-      const double heading_diff = wrap_angle(ayaw - yaw0);
-      const double rel = wrap_angle(agent_angle_initial - yaw0);
-      const double kThr = M_PI / 6.0, kUp = 5 * M_PI / 6.0;
-      if (heading_diff <= -kUp || heading_diff >= kThr) {
-        if (!(rel < 0.0)) aa_target = yaw0 + (-(M_PI / 6.0));
-      } else {
-        if (!(rel > 0.0)) aa_target = yaw0 + (M_PI / 6.0);
-      }
-    }
-    vmask[sl] = m;
-    aa[sl] = aa_target;
-  }
-}
 
 // The horizon of the slot's scene: rollout steps T, control horizon CH = min(control_horizon, T), block length
 // bl = min(parameter_block_length, CH), index of the last parameter block, feasibility rows and bounded blocks

@@ -90,7 +90,7 @@ template <typename T> struct Agent6 { T x, y, yaw, t, lv, av; };
 thread_local long g_sign_noise_events = 0;
 // Test-infrastructure option (smpc_oracle_set_option): 0 = reference-literal (default); 1 = when both velocities
 // are exactly equal take theta == 0 exactly instead of the libm-noise value. This is the convention the HIP path
-// uses (csrc/smpc_device.hpp social_force); with it the oracle is a noise-free checker for every scene.
+// uses (csrc/smpc_social_force.hpp); with it the oracle is a noise-free checker for every scene.
 int g_opt_theta_zero_when_equal_velocities = 0;
 // Diagnostic only: number of accept / terminate / Armijo decisions of a solve whose margin was below 1e-12 of the
 // cost, i.e. inside the rounding noise of summing ~300 squared residuals in a different order (SURVEY Appendix A.12:

@@ -1,7 +1,7 @@
 """Cost of per-scene weights and bounds (smpc_scene_batch.scene_params) on the headline batch (BASELINE configs[2]:
 8192 scenes, N = 8, T = 28), lone solve launches on device-resident inputs, three variants alternated round by round:
-  (a) the per-scene-horizon kernel with every T_scene = T          smpc_solve_kernel<3,32,true>
-  (b) the sp kernel, every row equal to the handle's parameters    smpc_solve_sp_kernel<3,32>
+  (a) the per-scene-horizon kernel with every T_scene = T          smpc_solve_kernel<3,32,true,false>
+  (b) the sp kernel, every row equal to the handle's parameters    smpc_solve_kernel<3,32,true,true>
   (c) the sp kernel, the two benchmark presets alternating by scene
 The same for K1. Prints the median kernel time of each and (b) / (a)."""
 import sys

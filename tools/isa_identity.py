@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Do two source trees compile to the same gfx950 machine code? (CPU only: needs hipcc, no GPU.)
+
+usage: python tools/isa_identity.py <tree A> <tree B> [--nb N] [--out DIR]
+
+Builds the device assembly of both trees (csrc/build.sh --cuda-device-only -S; --nb N adds -DSMPC_ONLY_NB=N: seconds
+instead of a minute), splits it into functions and `.amdhsa_kernel` descriptors (register counts, LDS, scratch and
+kernarg sizes) and compares them name by name, whatever their order in the file. Exit status 1 on any difference or
+unpaired function; the normalised texts of a differing pair are left under --out for diff(1)."""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+BUILD = os.path.join("nav2_social_mpc_controller_amd", "csrc", "build.sh")
+
+# Names of tree A that tree B spells differently, applied to A's text before anything is compared (so a name inside a
+# body is compared under its new spelling too). Written out, not inferred from matching bodies.
+_TAIL = r"EEvNS_7KParamsE"
+RENAMES = [
+    # smpc_solve_sp_kernel<NB,W> -> smpc_solve_kernel<NB,W,true,true>; smpc_solve_kernel<NB,W,vt> -> <NB,W,vt,false>
+    (r"_ZN4smpc20smpc_solve_sp_kernelILi(\d+)ELi(\d+)E" + _TAIL, r"_ZN4smpc17smpc_solve_kernelILi\1ELi\2ELb1ELb1E" + _TAIL),
+    (r"_ZN4smpc17smpc_solve_kernelILi(\d+)ELi(\d+)ELb([01])E" + _TAIL, r"_ZN4smpc17smpc_solve_kernelILi\1ELi\2ELb\3ELb0E" + _TAIL),
+    # smpc_eval_sp_kernel<NB,W> -> smpc_eval_kernel<NB,W,true,true>; smpc_eval_kernel<NB,W,vt> -> <NB,W,vt,false>
+    (r"_ZN4smpc19smpc_eval_sp_kernelILi(\d+)ELi(\d+)E" + _TAIL, r"_ZN4smpc16smpc_eval_kernelILi\1ELi\2ELb1ELb1E" + _TAIL),
+    (r"_ZN4smpc16smpc_eval_kernelILi(\d+)ELi(\d+)ELb([01])E" + _TAIL, r"_ZN4smpc16smpc_eval_kernelILi\1ELi\2ELb\3ELb0E" + _TAIL),
+]
+# what cannot matter: the numbers the compiler gives basic blocks, temporaries, jump tables and function ends
+LABELS = [(r"\.LBB\d+_", ".LBB_"), (r"\.Ltmp\d+", ".Ltmp"), (r"\.LJTI\d+_", ".LJTI_"), (r"\.LCPI\d+_", ".LCPI_"),
+          (r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1")]
+
+
+def start_build(tree, nb, out):
+    cmd = ["bash", os.path.join(tree, BUILD), "--cuda-device-only", "-S"] + ([f"-DSMPC_ONLY_NB={nb}"] if nb else [])
+    return subprocess.Popen(cmd, env={**os.environ, "SMPC_OUT": out})
+
+
+def split(text):
+    """({symbol: normalised body lines}, {kernel symbol: descriptor lines}) of one assembly file."""
+    funcs, descs, name, desc, is_function = {}, {}, None, None, set()
+    for raw in text.splitlines():
+        line = raw.split(";")[0].rstrip()  # comments name basic blocks by their numbers
+        if not line:
+            continue
+        for pat, rep in LABELS:
+            line = re.sub(pat, rep, line)
+        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
+        if m:
+            desc = descs.setdefault(m.group(1), [])
+        if desc is not None:  # a descriptor may sit inside its function's text: it is compared on its own
+            desc.append(line.strip())
+            if line.strip() == ".end_amdhsa_kernel":
+                desc = None
+            continue
+        m = re.match(r"\s*\.type\s+(\S+),@function", line)
+        if m:
+            is_function.add(m.group(1))
+        m = re.match(r"([^\s:]+):", line)
+        if m and name is None and m.group(1) in is_function:  # (data labels and the metadata's keys are not code)
+            name = m.group(1)
+            funcs[name] = []
+        if name is not None:
+            funcs[name].append(line)
+            if line.startswith(".Lfunc_end"):
+                name = None
+    return funcs, descs
+
+
+def n_instructions(lines):
+    return sum(1 for l in lines if l[:1] in " \t" and not l.strip().startswith("."))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("tree_a"), ap.add_argument("tree_b"), ap.add_argument("--nb", type=int)
+    ap.add_argument("--out", default=None, help="directory for the texts of differing functions")
+    args = ap.parse_args()
+    with tempfile.TemporaryDirectory() as tmp:
+        files = [os.path.join(tmp, "a.s"), os.path.join(tmp, "b.s")]
+        jobs = [start_build(t, args.nb, f) for t, f in zip((args.tree_a, args.tree_b), files)]  # two compiler jobs
+        if any(j.wait() != 0 for j in jobs):
+            sys.exit("build failed")
+        text_a, text_b = (open(f).read() for f in files)
+    for pat, rep in RENAMES:
+        text_a = re.sub(pat, rep, text_a)
+    (fa, da), (fb, db) = split(text_a), split(text_b)
+    bad = 0
+    for kind, a, b in (("function", fa, fb), ("descriptor", da, db)):
+        for name in sorted(set(a) | set(b)):
+            if name not in a or name not in b:
+                verdict = "UNPAIRED (only in %s)" % ("A" if name in a else "B")
+            else:
+                verdict = "same" if a[name] == b[name] else "DIFFERENT"
+            lines = a.get(name) or b.get(name)
+            print(f"{kind} {name} {n_instructions(lines) if kind == 'function' else len(lines)} {verdict}")
+            if verdict != "same":
+                bad += 1
+                out = args.out or tempfile.mkdtemp(prefix="isa_identity_")
+                args.out = out
+                os.makedirs(out, exist_ok=True)
+                for side, d in (("a", a), ("b", b)):
+                    with open(os.path.join(out, f"{kind}.{name[:150]}.{side}.s"), "w") as f:
+                        f.write("\n".join(d.get(name, [])) + "\n")
+    print(f"{len(set(fa) | set(fb))} functions, {len(set(da) | set(db))} kernel descriptors: "
+          + ("all same" if not bad else f"{bad} DIFFERENT or unpaired, texts in {args.out}"))
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
