@@ -28,6 +28,9 @@
 extern "C" {
 #endif
 
+/* Bumped when an existing struct or entry point changes. A new struct with a new entry point of its own (as
+ * smpc_trace_out / smpc_solve_trace_batch) changes nothing a caller built against this version relies on and does not
+ * bump it. */
 #define SMPC_ABI_VERSION 6
 #define SMPC_MAX_BLOCKS 10 /* nb <= 10  => P <= 20; every nb in 1..10 is instantiated */
 #define SMPC_MAX_LM_ITERATIONS 100000 /* smpc_create refuses a larger max_iterations: a persistent wave must reach its exit */
@@ -254,6 +257,33 @@ int smpc_set_stream(smpc_handle* h, void* hip_stream);
  * on_device=1: asynchronous on the handle's stream. on_device=0: stages through device memory and
  * returns after the results are back in host memory. */
 int smpc_solve_batch(smpc_handle* h, const smpc_scene_batch* scenes, smpc_result_batch* out);
+
+/* The per-iteration record of a solve (the reference's optimizer.debug_optimizer, src/optimizer.cpp:122-126: Ceres'
+ * minimizer_progress_to_stdout / Solver::Summary::iterations as far as these columns go). One row of SMPC_TRACE_COLS
+ * doubles per LM iteration, row index == iteration number:
+ *   iter, cost, cost_change, gradient_max_norm, step_norm, rho, radius, ls_evals, accepted
+ * Row 0 (behind a finite initial evaluation): (0, initial cost, 0, gmax, 0, 0, 1e4, 0, 1). Row i >= 1:
+ *   invalid step:                  (i, cost, 0, gmax, 0, 0, halved radius, 0, 0);
+ *   parameter / function tolerance: (i, cost, cost - candidate cost, gmax, step_norm, 0, radius, ls_evals, 0);
+ *   otherwise:                     (i, cost, cost_change, gmax, step_norm, rho, radius, ls_evals, accepted) with cost,
+ *                                  gmax and radius behind the accept / reject update.
+ * ls_evals: sweeps of the iteration's projected line search. No row for a failed initial evaluation,
+ * SMPC_REASON_SHORT_PATH, the fifth consecutive invalid step, and the exits at the top of an iteration (cap, gradient
+ * tolerance, minimum radius). */
+#define SMPC_TRACE_COLS 9
+typedef struct smpc_trace_out {
+  double* rows;     /* [B][max_rows][SMPC_TRACE_COLS]; may be NULL when max_rows == 0. Rows of scene b from n_rows[b] on are
+                       left untouched (hand in a buffer filled with a value of your own to tell them apart) */
+  int32_t max_rows; /* capacity per scene; max_iterations + 1 holds every row */
+  int32_t* n_rows;  /* [B] rows the solve produced (can exceed max_rows: the rest were dropped); may be NULL */
+} smpc_trace_out;
+
+/* smpc_solve_batch that also records the per-iteration rows. `out` fields and every rule of smpc_solve_batch
+ * (order, T_scene, scene_params, host or device pointers) apply unchanged; trace buffers live in the batch's memory
+ * space. Results in `out` are bit-identical to smpc_solve_batch on the same batch. trace == NULL, max_rows < 0 or
+ * rows == NULL with max_rows > 0: SMPC_ERR_INVALID_ARG. */
+int smpc_solve_trace_batch(smpc_handle* h, const smpc_scene_batch* scenes, smpc_result_batch* out,
+                           const smpc_trace_out* trace);
 
 /* How many solve launches share the GPU at a time (this handle's and those of other handles on other streams, e.g.
  * the shards of a closed-loop batch: every shard's chain of small kernels must find free wave slots next to the other

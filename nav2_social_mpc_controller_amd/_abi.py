@@ -247,6 +247,17 @@ class SmpcResultBatch(C.Structure):
     ]
 
 
+SMPC_TRACE_COLS = 9
+
+
+class SmpcTraceOut(C.Structure):
+    _fields_ = [
+        ("rows", C.c_void_p),
+        ("max_rows", C.c_int32),
+        ("n_rows", C.c_void_p),
+    ]
+
+
 class SmpcEvalOut(C.Structure):
     _fields_ = [
         ("residuals", C.c_void_p),
@@ -267,6 +278,7 @@ EXPORTED_SYMBOLS = [
     "smpc_set_solve_share",
     "smpc_solve_slot_width",
     "smpc_solve_batch",
+    "smpc_solve_trace_batch",
     "smpc_eval_batch",
     "smpc_project_people_batch",
     "smpc_people_to_status_batch",

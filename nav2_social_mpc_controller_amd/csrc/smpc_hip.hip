@@ -4,6 +4,8 @@
 //   smpc_solve_kernel<NB,W,kVT,kSP>  persistent sweep engine: whole ceres::Solve-equivalent (reference
 //                            src/optimizer.cpp:241-446) per scene, LM state resident in registers / LDS for all
 //                            <= max_iterations iterations, scenes pulled from a device-side queue (smpc_solve_kernel.hpp);
+//   smpc_solve_trace_kernel<NB,W>    the same body as <NB,W,true,true>, leaving one row per LM iteration as well
+//                            (smpc_solve_trace_batch);
 //   smpc_eval_kernel<NB,W,kVT,kSP>   K1: one residual + Jacobian sweep, rows written to HBM (parity + roofline runs;
 //                            smpc_eval_kernel.hpp);
 //                            kVT: per-scene horizons; kSP (with kVT): per-scene weights and velocity bounds as well
@@ -118,6 +120,14 @@ __global__ __launch_bounds__(256) void smpc_fp64_peak_kernel(double* out, int it
 }
 }  // namespace smpc
 
+namespace smpc {
+// n rows of smpc_scene_params, all equal to `row` (neutral_rows(), below)
+__global__ void smpc_fill_scene_params_kernel(smpc_scene_params* rows, int n, const smpc_scene_params row) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) rows[i] = row;
+}
+}  // namespace smpc
+
 struct smpc_handle {
   smpc_params prm{};
   int device = 0;
@@ -133,6 +143,8 @@ struct smpc_handle {
   char* stage = nullptr;  // grow-only arena for host-pointer calls (the plugin's B = 1 use): no hipMalloc per call
   size_t stage_cap = 0;
   size_t stage_want = 0;  // high-water mark of the calls so far
+  double* neutral_sp = nullptr;  // smpc_solve_trace_batch on a batch without scene_params: the handle's own values as rows
+  size_t neutral_sp_bytes = 0;   // (grow-only; prm never changes, so rows once written stay valid)
   char* pin = nullptr;    // page-locked host mirror of the arena's first pin_cap bytes: the small arrays of a host-pointer call
   size_t pin_cap = 0;     // travel in ONE copy each way instead of one pageable hipMemcpy per array (Staging, below)
 };
@@ -168,6 +180,33 @@ KernelFn pick(int nb, int W, bool eval, bool vt = false, bool sp = false) {
     case 8: return pick_w<8>(W, eval, vt, sp);
     case 9: return pick_w<9>(W, eval, vt, sp);
     case 10: return pick_w<10>(W, eval, vt, sp);
+    default: return nullptr;
+  }
+#endif
+}
+
+// The trace kernels (smpc_solve_trace_batch): the most general solve variant only, kVT = kSP = true.
+// A batch without T_scene runs it as it is (the kernel takes T for every scene), one without scene_params with the
+// handle's own weights and bounds as every scene's row (neutral_rows()): both give the plain kernels' results bit for bit.
+template <int NB> KernelFn pick_trace_w(int W) {
+  return W == 32 ? smpc::smpc_solve_trace_kernel<NB, 32> : smpc::smpc_solve_trace_kernel<NB, 64>;
+}
+
+KernelFn pick_trace(int nb, int W) {
+#ifdef SMPC_ONLY_NB
+  return nb == SMPC_ONLY_NB ? pick_trace_w<SMPC_ONLY_NB>(W) : nullptr;
+#else
+  switch (nb) {
+    case 1: return pick_trace_w<1>(W);
+    case 2: return pick_trace_w<2>(W);
+    case 3: return pick_trace_w<3>(W);
+    case 4: return pick_trace_w<4>(W);
+    case 5: return pick_trace_w<5>(W);
+    case 6: return pick_trace_w<6>(W);
+    case 7: return pick_trace_w<7>(W);
+    case 8: return pick_trace_w<8>(W);
+    case 9: return pick_trace_w<9>(W);
+    case 10: return pick_trace_w<10>(W);
     default: return nullptr;
   }
 #endif
@@ -397,11 +436,12 @@ int solve_slot_width(const smpc_handle* h, const smpc::KParams& k) {
   return (k.B <= per_cu * h->num_cu / share) ? 64 : 32;
 }
 
-int launch(smpc_handle* h, Staging& st, bool eval, smpc::KParams& k) {
+// trace: the solve kernel that also writes k.o_trace / k.o_trace_n (k.scene_params is set by then)
+int launch(smpc_handle* h, Staging& st, bool eval, smpc::KParams& k, bool trace = false) {
   const int W = eval ? smpc::slot_width(k.T, k.N) : solve_slot_width(h, k);
   const int S = smpc::kWave / W;
   const bool sp = k.scene_params != nullptr;
-  KernelFn fn = pick(k.nb, W, eval, k.T_scene != nullptr, sp);
+  KernelFn fn = trace ? pick_trace(k.nb, W) : pick(k.nb, W, eval, k.T_scene != nullptr, sp);
   const smpc::LdsLayout L = smpc::make_layout(k.T, k.N, k.P, eval ? smpc::kLayoutEval : smpc::kLayoutSolve, W, sp);
   k.hp_A = smpc::helper_owner_agents(k.T, k.N, W);
   if (std::getenv("SMPC_NO_HELPERS")) k.hp_A = k.N;  // experiment knob (the LDS layout keeps the helper regions)
@@ -480,6 +520,26 @@ int check_scene_params(const smpc_scene_params* sp, size_t B) {
       set_error("scene_params[" + std::to_string(i) + "]: needs v_min <= v_max and w_min <= w_max"); return SMPC_ERR_INVALID_ARG;
     }
   }
+  return SMPC_OK;
+}
+
+// k.scene_params for a trace solve of a batch that brings none: B rows of the handle's own values in device memory.
+int neutral_rows(smpc_handle* h, smpc::KParams& k) {
+  const size_t have = h->neutral_sp_bytes, need = (size_t)k.B * sizeof(smpc_scene_params);
+  if (need > have) {
+    SMPC_TRY(grow(&h->neutral_sp, &h->neutral_sp_bytes, need + need / 4, h->stream));
+    const smpc_params& p = h->prm;
+    const smpc_scene_params row = {p.distance_w, p.socialwork_w, p.velocity_w, p.angle_w, p.agent_angle_w, p.proxemics_w,
+                                   p.velocity_feasibility_w, p.obstacle_w, p.goal_align_w, p.desired_linear_vel,
+                                   p.v_min, p.v_max, p.w_min, p.w_max};
+    const int n = (int)(h->neutral_sp_bytes / sizeof(smpc_scene_params));
+    hipLaunchKernelGGL(smpc::smpc_fill_scene_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
+                       reinterpret_cast<smpc_scene_params*>(h->neutral_sp), n, row);
+    SMPC_HIP_CHECK(hipGetLastError());
+    // the rows outlive this call, and a later one may run on another stream (smpc_set_stream): written before they are kept
+    SMPC_HIP_CHECK(hipStreamSynchronize(h->stream));
+  }
+  k.scene_params = reinterpret_cast<const smpc_scene_params*>(h->neutral_sp);
   return SMPC_OK;
 }
 
@@ -571,6 +631,7 @@ void smpc_destroy(smpc_handle* h) {
   if (h->queue) (void)hipFree(h->queue);
   if (h->stage_rec) (void)hipFree(h->stage_rec);
   if (h->stage_aux) (void)hipFree(h->stage_aux);
+  if (h->neutral_sp) (void)hipFree(h->neutral_sp);
   if (h->stage) (void)hipFree(h->stage);
   if (h->pin) (void)hipHostFree(h->pin);
   delete h;
@@ -604,7 +665,12 @@ int smpc_solve_slot_width(const smpc_handle* h, int32_t B, int32_t T, int32_t N)
   return solve_slot_width(h, k);
 }
 
-int smpc_solve_batch(smpc_handle* h, const smpc_scene_batch* sb, smpc_result_batch* out) {
+}  // extern "C"
+
+namespace {
+
+// smpc_solve_batch (trace == nullptr) and smpc_solve_trace_batch
+int solve_batch(smpc_handle* h, const smpc_scene_batch* sb, smpc_result_batch* out, const smpc_trace_out* trace) {
   Dims d;
   SMPC_TRY(validate(h, sb, &d));
   if (!out) { set_error("null result batch"); return SMPC_ERR_INVALID_ARG; }
@@ -636,8 +702,28 @@ int smpc_solve_batch(smpc_handle* h, const smpc_scene_batch* sb, smpc_result_bat
   // a device-side order cannot be checked here: should it not be a permutation, the scenes it leaves out must not keep
   // the status of an earlier call — every status starts as SMPC_NOT_SOLVED (-1) and is overwritten by the scene's solve
   if (sb->on_device && k.order && k.o_status && B > 0) SMPC_HIP_CHECK(hipMemsetAsync(k.o_status, 0xFF, B * sizeof(int32_t), h->stream));
-  SMPC_TRY(launch(h, st, false, k));
+  if (trace) {
+    k.trace_rows = trace->max_rows;
+    // read and written: the rows a solve does not produce keep the caller's bytes on the way through device memory too
+    SMPC_TRY(st.inout(k.o_trace, trace->rows, B * (size_t)trace->max_rows * SMPC_TRACE_COLS));
+    SMPC_TRY(st.out(k.o_trace_n, trace->n_rows, B));
+    if (!k.scene_params && B > 0) SMPC_TRY(neutral_rows(h, k));
+  }
+  SMPC_TRY(launch(h, st, false, k, trace != nullptr));
   return st.finish();
+}
+
+}  // namespace
+
+extern "C" {
+
+int smpc_solve_batch(smpc_handle* h, const smpc_scene_batch* sb, smpc_result_batch* out) { return solve_batch(h, sb, out, nullptr); }
+
+int smpc_solve_trace_batch(smpc_handle* h, const smpc_scene_batch* sb, smpc_result_batch* out, const smpc_trace_out* trace) {
+  if (!trace || trace->max_rows < 0 || (trace->max_rows > 0 && !trace->rows)) {
+    set_error("null trace, max_rows < 0 or null rows with max_rows > 0"); return SMPC_ERR_INVALID_ARG;
+  }
+  return solve_batch(h, sb, out, trace);
 }
 
 int smpc_project_people_batch(smpc_handle* h, const smpc_projection_batch* in, double* people_proj, int32_t* error) {

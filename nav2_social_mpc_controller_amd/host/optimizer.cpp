@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <iostream>
 #include <list>
 #include <stdexcept>
 
@@ -34,6 +35,30 @@ double yaw_from_quaternion(const geometry_msgs::msg::Quaternion & q)
   if (sarg <= -0.99999) return -2 * std::atan2(q.y, q.x);
   if (sarg >= 0.99999) return 2 * std::atan2(q.y, q.x);
   return std::atan2(2 * (q.x * q.y + q.w * q.z), sqw + sqx - sqy - sqz);
+}
+
+void format_trace(std::ostream & os, const double * rows, int n_rows)
+{
+  os << "iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius  ls_iter  ok\n";
+  char line[160];
+  for (int i = 0; i < n_rows; ++i) {
+    const double * r = rows + (size_t)i * SMPC_TRACE_COLS;
+    std::snprintf(line, sizeof(line), "% 4d % 8e   % 3.2e   % 3.2e  % 3.2e  % 3.2e % 3.2e     % 4d   %d\n",
+                  (int)r[0], r[1], r[2], r[3], r[4], r[5], r[6], (int)r[7], (int)r[8]);
+    os << line;
+  }
+}
+
+void format_trace_summary(std::ostream & os, int status, int reason, int iterations, double initial_cost, double final_cost)
+{
+  static const char * const kStatus[] = {"CONVERGENCE", "NO_CONVERGENCE", "FAILURE"};
+  static const char * const kReason[] = {"none", "gradient_tol", "parameter_tol", "function_tol", "min_radius", "max_iterations",
+                                         "invalid_steps", "eval_failed", "short_path"};
+  char line[200];
+  std::snprintf(line, sizeof(line), "%s (%s) after %d iterations, cost %.6e -> %.6e\n",
+                status >= 0 && status < 3 ? kStatus[status] : "NOT_SOLVED", reason >= 0 && reason < 9 ? kReason[reason] : "?",
+                iterations, initial_cost, final_cost);
+  os << line;
 }
 
 void OptimizerParams::validate() const
@@ -74,6 +99,7 @@ void Optimizer::initialize(const OptimizerParams params)  // src/optimizer.cpp:9
   current_path_w = params.current_path_w;
   current_cmds_w = params.current_cmds_w;
   device_ = params.device;
+  debug_ = params.debug;
   // options_.max_solver_time_in_seconds (:131) is a wall-clock cap of 1.5-2 s; a batched device solve takes
   // microseconds to milliseconds, the cap is not modelled.
   if (handle_) { smpc_destroy(handle_); handle_ = nullptr; }
@@ -357,11 +383,23 @@ bool Optimizer::optimize(
   sb.costmap_origin = origin; sb.resolution = costmap->getResolution();
 
   std::vector<double> out_cmds(2 * (T + 1)), out_path(3 * (T + 1));
-  int32_t status = SMPC_FAILURE, iterations = 0;
-  double final_cost = 0.0;
+  int32_t status = SMPC_FAILURE, iterations = 0, reason = SMPC_REASON_NONE;
+  double final_cost = 0.0, initial_cost = 0.0;
   smpc_result_batch rb{};
   rb.cmds = out_cmds.data(); rb.path = out_path.data(); rb.status = &status; rb.iterations = &iterations; rb.final_cost = &final_cost;
-  if (smpc_solve_batch(handle_, &sb, &rb) != SMPC_OK) throw std::runtime_error(std::string("smpc_solve_batch failed: ") + smpc_last_error());
+  if (!debug_) {
+    if (smpc_solve_batch(handle_, &sb, &rb) != SMPC_OK) throw std::runtime_error(std::string("smpc_solve_batch failed: ") + smpc_last_error());
+  } else {  // debug_optimizer: the same solve, with its per-iteration rows (src/optimizer.cpp:122-126)
+    std::vector<double> rows((size_t)(prm_.max_iterations + 1) * SMPC_TRACE_COLS);
+    int32_t n_rows = 0;
+    smpc_trace_out tr{};
+    tr.rows = rows.data(); tr.max_rows = prm_.max_iterations + 1; tr.n_rows = &n_rows;
+    rb.reason = &reason; rb.initial_cost = &initial_cost;
+    if (smpc_solve_trace_batch(handle_, &sb, &rb, &tr) != SMPC_OK) throw std::runtime_error(std::string("smpc_solve_trace_batch failed: ") + smpc_last_error());
+    format_trace(std::cout, rows.data(), n_rows < tr.max_rows ? n_rows : tr.max_rows);
+    format_trace_summary(std::cout, status, reason, iterations, initial_cost, final_cost);
+    std::cout.flush();
+  }
   last_status_ = status; last_iterations_ = iterations; last_final_cost_ = final_cost;
   if (const char * prefix = std::getenv("SMPC_HOST_DUMP")) {
     // test hook: raw dump of this solve's C-ABI inputs and outputs (replayed through the CPU oracle by tests/)

@@ -7,6 +7,7 @@
 
 #include <array>
 #include <map>
+#include <ostream>
 #include <string>
 #include <vector>
 
@@ -35,6 +36,8 @@ struct OptimizerParams
   double velocity_feasibility_w_ = 0.5, goal_align_w_ = 0.0, obstacle_w_ = 0.0, proxemics_w_ = 90.0;
   float current_path_w = 1.0f, current_cmds_w = 1.0f, max_time = 3.0f;
   int discretization_ = 1, control_horizon_ = 5, parameter_block_length_ = 5;
+  // optimizer.debug_optimizer (src/optimizer.cpp:59, :122-126: Ceres' minimizer_progress_to_stdout): Optimizer::optimize
+  // solves through smpc_solve_trace_batch and prints one line per LM iteration and a summary line to stdout
   bool debug = false;
   int max_iterations = 100;
   int device = 0;  // HIP device the solver binds to (no reference counterpart)
@@ -90,10 +93,18 @@ private:
   smpc_params prm_;
   smpc_handle * handle_ = nullptr;
   int device_ = 0;
+  bool debug_ = false;
   float max_time = 3.0f, current_path_w = 1.0f, current_cmds_w = 1.0f;
   int last_status_ = SMPC_FAILURE, last_iterations_ = 0;
   double last_final_cost_ = 0.0;
 };
+
+// What debug_optimizer prints. rows: n_rows rows of SMPC_TRACE_COLS doubles (smpc_trace_out: iter, cost, cost_change,
+// gradient_max_norm, step_norm, rho, radius, ls_evals, accepted). A header line, then one line per row in Ceres'
+// minimizer_progress_to_stdout layout as far as these columns go (no times; `ok` = step accepted).
+void format_trace(std::ostream & os, const double * rows, int n_rows);
+// The line behind them: status and reason by name, iterations, initial -> final cost.
+void format_trace_summary(std::ostream & os, int status, int reason, int iterations, double initial_cost, double final_cost);
 
 // tf2 helpers restated (tf2::Quaternion::setRPY(0,0,yaw) / tf2::getYaw) — used where the reference uses them
 geometry_msgs::msg::Quaternion quaternion_from_yaw(double yaw);

@@ -72,7 +72,7 @@ void SocialMPCController::configure(
   q.fn_tol = param(node, o + "fn_tol", 1e-7);
   q.gradient_tol = param(node, o + "gradient_tol", 1e-10);
   q.max_iterations = param(node, o + "max_iterations", 100);
-  q.debug = param(node, o + "debug_optimizer", false);
+  q.debug = param(node, o + "debug_optimizer", false);  // Optimizer::optimize then prints every LM iteration (optimizer.hpp)
   q.control_horizon_ = param(node, o + "control_horizon", 5);
   q.parameter_block_length_ = param(node, o + "parameter_block_length", 5);
   q.current_path_w = static_cast<float>(param(node, o + "current_path_weight", 1.0));

@@ -13,13 +13,17 @@ import numpy as np
 
 from . import _abi
 from ._abi import (SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcObstacleDistanceIn, SmpcObstacleDistanceOut,
-                   SmpcParams, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
+                   SmpcParams, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
+                   SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
 from .params import OptimizerParams, TrajectorizerParams
 from .scenes import SceneBatch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMPC_LIB_PATH", os.path.join(_HERE, "csrc", "libsmpc_hip.so"))  # env override: A/B builds
 _lib = None
+# columns of a trace row (smpc_trace_out, include/smpc.h): one row per LM iteration
+TRACE_COLS = ["iter", "cost", "cost_change", "gradient_max_norm", "step_norm", "rho", "radius", "ls_evals", "accepted"]
+assert len(TRACE_COLS) == _abi.SMPC_TRACE_COLS
 
 
 class SmpcError(RuntimeError):
@@ -60,6 +64,8 @@ def load_library():
     lib.smpc_solve_slot_width.restype = C.c_int
     lib.smpc_solve_batch.argtypes = [C.c_void_p, C.POINTER(SmpcSceneBatch), C.POINTER(SmpcResultBatch)]
     lib.smpc_solve_batch.restype = C.c_int
+    lib.smpc_solve_trace_batch.argtypes = [C.c_void_p, C.POINTER(SmpcSceneBatch), C.POINTER(SmpcResultBatch), C.POINTER(SmpcTraceOut)]
+    lib.smpc_solve_trace_batch.restype = C.c_int
     lib.smpc_eval_batch.argtypes = [C.c_void_p, C.POINTER(SmpcSceneBatch), C.c_void_p, C.POINTER(SmpcEvalOut)]
     lib.smpc_eval_batch.restype = C.c_int
     lib.smpc_project_people_batch.argtypes = [C.c_void_p, C.POINTER(SmpcProjectionBatch), C.c_void_p, C.c_void_p]
@@ -154,10 +160,9 @@ class BatchSolver:
         return float(self.lib.smpc_last_kernel_ms(self._h))
 
     # -- host-memory path (stages through HBM inside the library) ---------------------------------
-    def solve(self, scenes: SceneBatch, order: np.ndarray = None):
-        """Solve B scenes (host arrays in, host arrays out). order: optional queue order of the persistent kernel, a
-        permutation of 0..B-1 (smpc_scene_batch.order: longest scenes first shortens a lone launch; results do not
-        depend on it)."""
+    def _solve_call(self, scenes: SceneBatch, order):
+        """What solve() and solve_trace() hand to the library: (result dict of host arrays, SmpcSceneBatch, SmpcResultBatch,
+        the arrays the structs point into)."""
         CH, bl, nb, P, M, _ = self.params.dims(scenes.T, True)
         scenes.validate(P)
         B, T = scenes.B, scenes.T
@@ -174,7 +179,29 @@ class BatchSolver:
             order = np.ascontiguousarray(order, np.int32)
             assert order.shape == (B,)
             sb.order = order.ctypes.data
+        return out, sb, rb, order
+
+    def solve(self, scenes: SceneBatch, order: np.ndarray = None):
+        """Solve B scenes (host arrays in, host arrays out). order: optional queue order of the persistent kernel, a
+        permutation of 0..B-1 (smpc_scene_batch.order: longest scenes first shortens a lone launch; results do not
+        depend on it)."""
+        out, sb, rb, _keep = self._solve_call(scenes, order)
         _check(self.lib, self.lib.smpc_solve_batch(self._h, C.byref(sb), C.byref(rb)), "smpc_solve_batch")
+        return out
+
+    def solve_trace(self, scenes: SceneBatch, order: np.ndarray = None, max_rows: int = None):
+        """solve() that also returns the per-iteration record of every scene (optimizer.debug_optimizer; smpc_solve_trace_batch):
+        "trace" [B, max_rows, 9], columns TRACE_COLS, row i = LM iteration i, NaN where a scene has no row; "trace_rows" [B],
+        the rows each solve produced (more than max_rows: the rest were dropped). max_rows defaults to max_iterations + 1,
+        which holds every row. The other entries are those of solve(), bit for bit."""
+        max_rows = self.params.max_iterations + 1 if max_rows is None else int(max_rows)
+        if max_rows < 0:
+            raise SmpcError(f"max_rows must be >= 0, got {max_rows}")
+        out, sb, rb, _keep = self._solve_call(scenes, order)
+        out["trace"] = np.full((scenes.B, max_rows, _abi.SMPC_TRACE_COLS), np.nan)
+        out["trace_rows"] = np.zeros(scenes.B, np.int32)
+        to = SmpcTraceOut(out["trace"].ctypes.data if out["trace"].size else None, max_rows, out["trace_rows"].ctypes.data)
+        _check(self.lib, self.lib.smpc_solve_trace_batch(self._h, C.byref(sb), C.byref(rb), C.byref(to)), "smpc_solve_trace_batch")
         return out
 
     @staticmethod
@@ -529,6 +556,20 @@ class BatchSolver:
     def solve_device(self, sb: SmpcSceneBatch, rb: SmpcResultBatch):
         assert sb.on_device == 1
         _check(self.lib, self.lib.smpc_solve_batch(self._h, C.byref(sb), C.byref(rb)), "smpc_solve_batch")
+
+    def alloc_trace(self, B: int, max_rows: int = None, device="cuda:0"):
+        """(SmpcTraceOut, tensors) for solve_trace_device: "trace" [B, max_rows, 9] filled with NaN, "trace_rows" [B]."""
+        import torch
+
+        max_rows = self.params.max_iterations + 1 if max_rows is None else int(max_rows)
+        t = {"trace": torch.full((B, max_rows, _abi.SMPC_TRACE_COLS), float("nan"), dtype=torch.float64, device=device),
+             "trace_rows": torch.zeros(B, dtype=torch.int32, device=device)}
+        return SmpcTraceOut(t["trace"].data_ptr() if t["trace"].numel() else None, max_rows, t["trace_rows"].data_ptr()), t
+
+    def solve_trace_device(self, sb: SmpcSceneBatch, rb: SmpcResultBatch, to: SmpcTraceOut):
+        """solve_device that also records the per-iteration rows (alloc_trace); asynchronous on the handle's stream."""
+        assert sb.on_device == 1
+        _check(self.lib, self.lib.smpc_solve_trace_batch(self._h, C.byref(sb), C.byref(rb), C.byref(to)), "smpc_solve_trace_batch")
 
     def alloc_eval(self, B: int, T: int, device="cuda:0", row_order: int = 0):
         import torch

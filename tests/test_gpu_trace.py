@@ -1,0 +1,267 @@
+"""The per-iteration trace of every scene of a solve (`smpc_solve_trace_batch`, `BatchSolver.solve_trace`; `-m gpu`): the
+traced solve returns the untraced solve's results bit for bit, its rows obey the row rules (pinned on the oracle by
+tests/test_trace_oracle_rules.py), agree with the oracle's rows on the scenes whose LM path is firm, respect the caller's
+capacity, and depend on nothing but the scene."""
+import numpy as np
+import pytest
+
+from conftest import well_conditioned
+from test_gpu_instantiations import CASES, RESULT_KEYS, horizons, same, scenes_of, solver_for, sp_batch
+from test_trace_oracle_rules import COL, ROW_PER_ITERATION, check_radius_recurrence
+from nav2_social_mpc_controller_amd.params import OptimizerParams
+from nav2_social_mpc_controller_amd.scenes import make_scenes
+
+README = OptimizerParams.readme()
+TRACED = ["nb1_w32", "nb1_w64", "nb3_w32", "nb3_w64", "nb5_w32", "nb5_w64", "nb10_w32", "nb10_w64"]
+TRACE_KEYS = ("trace", "trace_rows")
+SHORT_PATH, EVAL_FAILED, INVALID_STEPS = 8, 7, 6
+
+
+@pytest.fixture(scope="module")
+def Solver():
+    from nav2_social_mpc_controller_amd.solver import BatchSolver
+    return BatchSolver
+
+
+def on_device(s, sc, short=(), max_rows=None):
+    """(untraced, traced) results of the device-pointer calls on one device copy of sc; scenes `short` get T_scene = 0 there
+    (a host array with such an entry is refused, a device array is not read by the host: SMPC_REASON_SHORT_PATH)."""
+    import torch
+
+    sb, keep = sc.to_device()
+    for b in short:
+        keep["T_scene"][b] = 0
+    rb0, t0 = s.alloc_results(sc.B, sc.T)
+    rb1, t1 = s.alloc_results(sc.B, sc.T)
+    to, tt = s.alloc_trace(sc.B, max_rows)
+    s.solve_device(sb, rb0)
+    s.solve_trace_device(sb, rb1, to)
+    torch.cuda.synchronize()
+    plain = {k: v.cpu().numpy() for k, v in t0.items()}
+    traced = {k: v.cpu().numpy() for k, v in {**t1, **tt}.items()}
+    return plain, traced
+
+
+def batches(c):
+    """the case's scenes as a plain batch, with a horizon per scene, with two parameter sets alternating"""
+    sc = scenes_of(c)
+    return {"plain": sc, "vt": sc.with_horizons(horizons(sc.B, c.T, c.seed + 1)), "sp": sp_batch(c, sc)[0]}
+
+
+def check_rows(res, max_iterations):
+    """What holds for the rows of every scene whatever its values (exact, but for the radius: the device divides through
+    its refined reciprocal, within 1 ulp, and cubes by two multiplications)."""
+    B = len(res["trace_rows"])
+    for b in range(B):
+        n, reason, iters = int(res["trace_rows"][b]), int(res["reason"][b]), int(res["iterations"][b])
+        if reason in ROW_PER_ITERATION:
+            assert n == iters + 1, (b, reason, n, iters)
+        elif reason in (SHORT_PATH, EVAL_FAILED):
+            assert n == 0, (b, reason, n)
+        else:
+            assert reason == INVALID_STEPS and n == iters, (b, reason, n, iters)
+        assert n <= max_iterations + 1
+        assert np.isnan(res["trace"][b, n:]).all(), b  # untouched: the wrapper's fill
+        if n == 0:
+            continue
+        tr = res["trace"][b, :n]
+        assert np.isfinite(tr).all(), b
+        assert np.array_equal(tr[:, COL["iter"]], np.arange(n)), b
+        assert np.array_equal(tr[0], [0, res["initial_cost"][b], 0, tr[0, COL["gradient_max_norm"]], 0, 0, 1e4, 0, 1]), b
+        acc = tr[:, COL["accepted"]] == 1
+        assert set(tr[:, COL["accepted"]]) <= {0.0, 1.0}
+        assert tr[acc, COL["cost"]].min() == res["final_cost"][b], b
+        # a step that is not accepted leaves the point, its cost and its gradient where they were
+        keep = np.where(~acc)[0]
+        assert np.array_equal(tr[keep, COL["cost"]], tr[keep - 1, COL["cost"]]), b
+        assert np.array_equal(tr[keep, COL["gradient_max_norm"]], tr[keep - 1, COL["gradient_max_norm"]]), b
+        assert (tr[acc, COL["rho"]][1:] > 1e-3).all() and (tr[acc, COL["cost_change"]][1:] > 0).all(), b
+        check_radius_recurrence(tr, reason, max_ulp=8)
+        # every sweep is a counted one: the initial point and the line-search samples. An accepted candidate is the last
+        # sample, whose Gram the slot has. (The re-sweep of smpc_solve_body.inc's PH_REEVAL would add one; its comments call
+        # it never seen, and a failure here would be its first sighting.)
+        assert res["evaluations"][b] == 1 + int(tr[:, COL["ls_evals"]].sum()), b
+        invalid = (tr[1:, COL["ls_evals"]] == 0)
+        assert not tr[1:][invalid][:, [COL["cost_change"], COL["step_norm"], COL["rho"], COL["accepted"]]].any(), b
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", TRACED)
+def test_results_are_those_of_the_untraced_solve(Solver, name, monkeypatch):
+    """Every key of solve()'s result, bit for bit, for the three kinds of batch, host and device pointers; and the rows of
+    the host call and the device call are the same rows."""
+    c = CASES[name]
+    s = solver_for(Solver, c, monkeypatch)
+    for kind, sc in batches(c).items():
+        plain, traced = s.solve(sc), s.solve_trace(sc)
+        same(plain, traced, RESULT_KEYS, what=(kind, "host"))
+        assert traced["trace"].shape == (sc.B, c.prm.max_iterations + 1, 9) and traced["trace_rows"].dtype == np.int32
+        dplain, dtraced = on_device(s, sc)
+        same(plain, dplain, RESULT_KEYS, what=(kind, "device untraced"))
+        same(plain, dtraced, RESULT_KEYS, what=(kind, "device"))
+        same(traced, dtraced, TRACE_KEYS, what=(kind, "device rows"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", TRACED)
+def test_rows_are_self_consistent(Solver, name, monkeypatch):
+    c = CASES[name]
+    s = solver_for(Solver, c, monkeypatch)
+    ended_by = set()
+    for kind, sc in batches(c).items():
+        res = s.solve_trace(sc)
+        check_rows(res, c.prm.max_iterations)
+        ended_by |= set(res["reason"].tolist())
+        if kind == "vt":  # some scenes without a path: no row, and the others' rows are what they were
+            short = [1, sc.B // 2, sc.B - 1]
+            dplain, dres = on_device(s, sc, short=short)
+            same(dplain, dres, RESULT_KEYS, what="short paths")
+            assert (dres["reason"][short] == SHORT_PATH).all() and (dres["trace_rows"][short] == 0).all()
+            check_rows(dres, c.prm.max_iterations)
+            rest = np.setdiff1d(np.arange(sc.B), short)
+            same(res, dres, TRACE_KEYS, where=rest, what="beside short paths")
+    assert ended_by & set(ROW_PER_ITERATION)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# against the oracle's rows
+
+INT_COLS = [COL[c] for c in ("iter", "ls_evals", "accepted")]
+REAL_COLS = [COL[c] for c in ("cost", "cost_change", "gradient_max_norm", "step_norm", "rho", "radius")]
+ORACLE_CASES = ["cfg2_n4", "cfg3_n8", "params_yaml_n3", "w32_five_blocks_valu_gram", "ten_blocks", "t32_first_one_slot_shape",
+                "obst_only_benchmark"]
+ORACLE_SCENES = 128  # the first scenes of each case: the oracle's traces come one scene at a time
+
+
+def rel(a, b):
+    return np.abs(a - b) / np.maximum(1.0, np.abs(b))
+
+
+def oracle_rows(oracle, prm, sc):
+    """The oracle's side of the comparison, no GPU: its rows per scene under the device's theta convention, the scenes
+    whose rows are determined by their inputs (firm decisions, well conditioned, and the same LM path when the start pose
+    moves by 1e-15 relative: conftest.well_conditioned's perturbation), and per real-valued column the largest move of a
+    row value, relative to max(1, |value|), under that perturbation."""
+    rz = oracle.solve(prm, sc, nthreads=16, theta_zero_convention=True)
+    stable = well_conditioned(oracle, prm, sc, rz, nthreads=16, theta_zero_convention=True)
+    usable = (rz["marginal_decisions"] == 0) & stable
+    moved = sc.select(np.arange(sc.B))
+    moved.pose0 = sc.pose0 * (1.0 + 1e-15 * np.random.default_rng(12345).standard_normal(sc.pose0.shape))
+    rows, spread = [], np.zeros(9)
+    oracle.set_theta_zero_convention(True)
+    try:
+        for b in range(sc.B):
+            tr = oracle.trace(prm, sc, b, max_rows=prm.max_iterations + 2)
+            rows.append(tr)
+            if not usable[b]:
+                continue
+            tm = oracle.trace(prm, moved, b, max_rows=prm.max_iterations + 2)
+            if tm.shape != tr.shape or not np.array_equal(tm[:, INT_COLS], tr[:, INT_COLS]):
+                usable[b] = False
+                continue
+            spread = np.maximum(spread, rel(tm, tr).max(axis=0))
+    finally:
+        oracle.set_theta_zero_convention(False)
+    return rz, rows, usable, spread
+
+
+def oracle_case(name):
+    from test_gpu_parity import SOLVE_CASES
+    prm, kw = SOLVE_CASES[name]
+    sc = make_scenes(prm, **kw)
+    return prm, sc.select(np.arange(min(sc.B, ORACLE_SCENES)))
+
+
+@pytest.mark.parametrize("name", ORACLE_CASES)
+def test_the_oracle_alone_leaves_few_scenes_out(oracle, name):
+    """(no GPU) the scenes the comparison below may use, before the device's iteration counts are known"""
+    prm, sc = oracle_case(name)
+    rz, rows, usable, spread = oracle_rows(oracle, prm, sc)
+    print(f"\n[trace oracle] {name}: {usable.sum()}/{sc.B} usable; oracle spread " +
+          " ".join(f"{c}={spread[COL[c]]:.1e}" for c in COL if COL[c] in REAL_COLS))
+    assert usable.mean() >= 0.85, (name, float(usable.mean()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ORACLE_CASES)
+def test_rows_match_the_oracles(Solver, oracle, name):
+    """On the firm, well-conditioned scenes whose iteration counts agree: the integer columns equal in every row, the six
+    real-valued ones within 10 x the move of the oracle's own rows under a 1e-15 perturbation of its input (measured per
+    column on the same scenes; the factor covers the device's table exp and reordered sums, 1e-14 .. 1e-13 against libm).
+
+    Measured (MI355X; oracle spread / device's worst difference per column): see DESIGN.md §4, "Per-iteration trace"."""
+    prm, sc = oracle_case(name)
+    rz, rows, usable, spread = oracle_rows(oracle, prm, sc)
+    res = Solver(prm).solve_trace(sc)
+    compared = usable & (res["iterations"] == rz["iterations"])
+    worst = np.zeros(9)
+    for b in np.where(compared)[0]:
+        want = rows[b]
+        got = res["trace"][b, :res["trace_rows"][b]]
+        assert got.shape == want.shape, (b, got.shape, want.shape)
+        assert np.array_equal(got[:, INT_COLS], want[:, INT_COLS]), b
+        worst = np.maximum(worst, rel(got, want).max(axis=0))
+    print(f"\n[trace parity] {name}: {compared.sum()}/{sc.B} compared; " +
+          " ".join(f"{c}: oracle {spread[COL[c]]:.1e} device {worst[COL[c]]:.1e}" for c in COL if COL[c] in REAL_COLS))
+    assert compared.mean() >= 0.85, (name, float(compared.mean()))
+    for j in REAL_COLS:
+        assert worst[j] <= 10.0 * spread[j], (name, list(COL)[j], worst[j], spread[j])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# capacity and independence
+
+
+@pytest.mark.gpu
+def test_capacity_is_respected(Solver):
+    import torch
+
+    sc = make_scenes(README, 96, 4, seed=811)
+    s = Solver(README)
+    full = s.solve_trace(sc)
+    assert (full["trace_rows"] > 5).any() and full["trace"].shape[1] == README.max_iterations + 1
+    five = s.solve_trace(sc, max_rows=5)
+    same(full, five, RESULT_KEYS + ("trace_rows",), what="max_rows = 5")
+    assert five["trace"].shape == (sc.B, 5, 9)
+    assert np.array_equal(five["trace"].view(np.uint8), np.ascontiguousarray(full["trace"][:, :5]).view(np.uint8))
+    # device pointers, a buffer with room behind the five rows of the last scene: nothing lands there, and nothing in the
+    # rows a scene does not have
+    canary = -12345.678
+    sb, keep = sc.to_device()
+    rb, rt = s.alloc_results(sc.B, sc.T)
+    to, tt = s.alloc_trace(sc.B, 5)
+    buf = torch.full((sc.B * 5 * 9 + 4096,), canary, dtype=torch.float64, device="cuda:0")
+    to.rows = buf.data_ptr()
+    s.solve_trace_device(sb, rb, to)
+    torch.cuda.synchronize()
+    got = buf.cpu().numpy()
+    assert (got[sc.B * 5 * 9:] == canary).all()
+    got = got[:sc.B * 5 * 9].reshape(sc.B, 5, 9)
+    n = np.minimum(full["trace_rows"], 5)
+    for b in range(sc.B):
+        assert np.array_equal(got[b, :n[b]], full["trace"][b, :n[b]]) and (got[b, n[b]:] == canary).all(), b
+    assert np.array_equal(tt["trace_rows"].cpu().numpy(), full["trace_rows"])
+    # the counts alone
+    none = s.solve_trace(sc, max_rows=0)
+    same(full, none, RESULT_KEYS + ("trace_rows",), what="max_rows = 0")
+    assert none["trace"].shape == (sc.B, 0, 9)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W", [32, 64])
+def test_rows_depend_on_the_scene_alone(Solver, W, monkeypatch):
+    """Under three queue orders, and solved alone at the same slot width (the pattern of tests/test_gpu_order.py)."""
+    if W == 32:
+        monkeypatch.setenv("SMPC_SOLVE_WIDTH", "32")
+    B = 333
+    sc = make_scenes(README, B, 8, seed=812)
+    s = Solver(README)
+    assert s.solve_slot_width(B, sc.T, sc.N) == W and s.solve_slot_width(1, sc.T, sc.N) == W
+    base = s.solve_trace(sc)
+    rng = np.random.default_rng(5)
+    for order in (np.argsort(-base["evaluations"], kind="stable"), rng.permutation(B), np.arange(B)[::-1]):
+        same(base, s.solve_trace(sc, order=order), RESULT_KEYS + TRACE_KEYS, what="order")
+    for b in (0, 1, 170, B - 1):
+        alone = s.solve_trace(sc.select([b]))
+        for k in RESULT_KEYS + TRACE_KEYS:
+            assert np.array_equal(alone[k][0:1].view(np.uint8), np.ascontiguousarray(base[k][b:b + 1]).view(np.uint8)), (b, k)

@@ -1,31 +1,50 @@
-"""Development probe: find the first LM iteration where HIP and oracle part ways for the worst scene of a case."""
+"""Development probe: find the first LM iteration where HIP and oracle part ways for the worst scene of a case.
+
+One traced launch (BatchSolver.solve_trace) gives the device's rows of every scene; the oracle's rows of the worst scene
+come from oracle_py.trace. Printed side by side from the first row that differs (integer columns unequal, or a real-valued
+column further apart than --rtol relative to max(1, |value|)).
+
+usage: python tools/gpu_trace_diff.py [--rtol 1e-9] [--scene B]"""
+import argparse
 import sys
+
 import numpy as np
+
 sys.path.insert(0, ".")
 from nav2_social_mpc_controller_amd.params import OptimizerParams
 from nav2_social_mpc_controller_amd.scenes import make_scenes
-from nav2_social_mpc_controller_amd.solver import BatchSolver
+from nav2_social_mpc_controller_amd.solver import TRACE_COLS, BatchSolver
 from oracle import oracle_py as O
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--rtol", type=float, default=1e-9)
+ap.add_argument("--scene", type=int, default=None, help="scene to print (default: the one with the largest command error)")
+args = ap.parse_args()
+
 README = OptimizerParams.readme()
 prm = README.replace(control_horizon=30, max_time=2.0)
 sc = make_scenes(prm, 128, 16, seed=204)
-rg = BatchSolver(prm).solve(sc)
+rg = BatchSolver(prm).solve_trace(sc)
 rz = O.solve(prm, sc, nthreads=16, theta_zero_convention=True)
-err = np.abs(rg["cmds"] - rz["cmds"]).reshape(128, -1).max(axis=1)
-b = int(np.argmax(err))
-print("worst scene", b, err[b], "iters gpu/oracle", rg["iterations"][b], rz["iterations"][b], "cost", rg["final_cost"][b], rz["final_cost"][b], "events", rz["sign_noise_events"][b])
-one = sc.select([b])
+err = np.abs(rg["cmds"] - rz["cmds"]).reshape(sc.B, -1).max(axis=1)
+b = int(np.argmax(err)) if args.scene is None else args.scene
+print("scene", b, "max|dcmd|", err[b], "iters gpu/oracle", rg["iterations"][b], rz["iterations"][b], "reason", rg["reason"][b],
+      rz["reason"][b], "cost", rg["final_cost"][b], rz["final_cost"][b], "events", rz["sign_noise_events"][b])
 O.set_theta_zero_convention(True)
-tr = O.trace(prm, one, 0)
+to = O.trace(prm, sc, b, max_rows=prm.max_iterations + 2)
 O.set_theta_zero_convention(False)
-np.set_printoptions(linewidth=220, precision=10)
-for k in range(0, 41):
-    p2 = prm.replace(max_iterations=k)
-    g = BatchSolver(p2).solve(one)
-    o = O.solve(p2, one, theta_zero_convention=True)
-    d = np.abs(g["params"] - o["params"]).max()
-    print(f"cap {k:2d}: max|dparams| {d:.3e} cost gpu {g['final_cost'][0]:.12e} oracle {o['final_cost'][0]:.12e} iters {g['iterations'][0]} {o['iterations'][0]} reason {g['reason'][0]} {o['reason'][0]} evals {g['evaluations'][0]} {o['evaluations'][0]}")
-    if d > 1e-6:
-        break
-print("oracle trace rows [iter, cost, cost_change, gmax, step_norm, rho, radius, ls_evals, accepted]:")
-print(tr[max(0, k - 3):k + 2])
+tg = rg["trace"][b, :min(rg["trace_rows"][b], rg["trace"].shape[1])]
+n = min(len(tg), len(to))
+ints = [TRACE_COLS.index(c) for c in ("iter", "ls_evals", "accepted")]
+differs = [i for i in range(n) if not np.array_equal(tg[i, ints], to[i, ints])
+           or np.any(np.abs(tg[i] - to[i]) > args.rtol * np.maximum(1.0, np.abs(to[i])))]
+first = differs[0] if differs else n
+if first == n and len(tg) == len(to):
+    print(f"all {n} rows agree within {args.rtol:g}")
+    sys.exit(0)
+print(f"first differing row: {first} (device has {len(tg)} rows, oracle {len(to)})")
+print("     " + " ".join(f"{c[:13]:>22s}" for c in TRACE_COLS))
+for i in range(max(0, first - 1), max(len(tg), len(to))):
+    for who, t in (("gpu", tg), ("cpu", to)):
+        if i < len(t):
+            print(f"{who:>4s} " + " ".join(f"{v:22.15e}" for v in t[i]))

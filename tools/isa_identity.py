@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """Do two source trees compile to the same gfx950 machine code? (CPU only: needs hipcc, no GPU.)
 
-usage: python tools/isa_identity.py <tree A> <tree B> [--nb N] [--out DIR]
+usage: python tools/isa_identity.py <tree A> <tree B> [--nb N] [--out DIR] [--allow-new] [--ignore-kernarg-size]
 
 Builds the device assembly of both trees (csrc/build.sh --cuda-device-only -S; --nb N adds -DSMPC_ONLY_NB=N: seconds
 instead of a minute), splits it into functions and `.amdhsa_kernel` descriptors (register counts, LDS, scratch and
 kernarg sizes) and compares them name by name, whatever their order in the file. Exit status 1 on any difference or
-unpaired function; the normalised texts of a differing pair are left under --out for diff(1)."""
+unpaired function; the normalised texts of a differing pair are left under --out for diff(1).
+
+--allow-new: a function or descriptor that only tree B has is listed as NEW and is no failure (B adds kernels, and A's
+must come out unchanged). --ignore-kernarg-size: `.amdhsa_kernarg_size` lines are left out of the descriptor comparison and
+the kernels whose size changed are counted (members appended to KParams, which every sweep kernel takes by value, grow the
+kernel-argument segment of all of them without moving an existing member)."""
 import argparse
 import os
 import re
@@ -76,6 +81,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("tree_a"), ap.add_argument("tree_b"), ap.add_argument("--nb", type=int)
     ap.add_argument("--out", default=None, help="directory for the texts of differing functions")
+    ap.add_argument("--allow-new", action="store_true", help="names only tree B has are no failure")
+    ap.add_argument("--ignore-kernarg-size", action="store_true", help="compare descriptors without .amdhsa_kernarg_size")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         files = [os.path.join(tmp, "a.s"), os.path.join(tmp, "b.s")]
@@ -86,16 +93,23 @@ def main():
     for pat, rep in RENAMES:
         text_a = re.sub(pat, rep, text_a)
     (fa, da), (fb, db) = split(text_a), split(text_b)
-    bad = 0
+    bad = new = resized = 0
+    if args.ignore_kernarg_size:
+        size = lambda d: [l for l in d if l.startswith(".amdhsa_kernarg_size")]
+        resized = sum(1 for n in set(da) & set(db) if size(da[n]) != size(db[n]))
+        da, db = ({n: [l for l in d if not l.startswith(".amdhsa_kernarg_size")] for n, d in x.items()} for x in (da, db))
     for kind, a, b in (("function", fa, fb), ("descriptor", da, db)):
         for name in sorted(set(a) | set(b)):
-            if name not in a or name not in b:
+            if args.allow_new and name not in a:
+                verdict = "NEW (only in B)"
+                new += 1
+            elif name not in a or name not in b:
                 verdict = "UNPAIRED (only in %s)" % ("A" if name in a else "B")
             else:
                 verdict = "same" if a[name] == b[name] else "DIFFERENT"
             lines = a.get(name) or b.get(name)
             print(f"{kind} {name} {n_instructions(lines) if kind == 'function' else len(lines)} {verdict}")
-            if verdict != "same":
+            if verdict not in ("same", "NEW (only in B)"):
                 bad += 1
                 out = args.out or tempfile.mkdtemp(prefix="isa_identity_")
                 args.out = out
@@ -104,7 +118,8 @@ def main():
                     with open(os.path.join(out, f"{kind}.{name[:150]}.{side}.s"), "w") as f:
                         f.write("\n".join(d.get(name, [])) + "\n")
     print(f"{len(set(fa) | set(fb))} functions, {len(set(da) | set(db))} kernel descriptors: "
-          + ("all same" if not bad else f"{bad} DIFFERENT or unpaired, texts in {args.out}"))
+          + ("all same" if not bad else f"{bad} DIFFERENT or unpaired, texts in {args.out}")
+          + (f"; {new} only in B" if new else "") + (f"; .amdhsa_kernarg_size (not compared) differs in {resized} descriptors" if resized else ""))
     sys.exit(1 if bad else 0)
 
 
