@@ -1,11 +1,10 @@
 // smpc_hip.hip — kernels + the C ABI of include/smpc.h (libsmpc_hip.so). gfx950 only, no CPU fallback.
 //
 // Kernels (one 64-lane wavefront per workgroup, split into 64/W scene slots; lane mapping and LDS layout: smpc_launch.hpp):
-//   smpc_solve_kernel<NB,W,kVT,kSP>  persistent sweep engine: whole ceres::Solve-equivalent (reference
+//   smpc_solve_kernel<NB,W,kVT,kSP,kTrace>  persistent sweep engine: whole ceres::Solve-equivalent (reference
 //                            src/optimizer.cpp:241-446) per scene, LM state resident in registers / LDS for all
 //                            <= max_iterations iterations, scenes pulled from a device-side queue (smpc_solve_kernel.hpp);
-//   smpc_solve_trace_kernel<NB,W>    the same body as <NB,W,true,true>, leaving one row per LM iteration as well
-//                            (smpc_solve_trace_batch);
+//                            kTrace (<NB,W,true,true,true> only): one row per LM iteration as well (smpc_solve_trace_batch);
 //   smpc_eval_kernel<NB,W,kVT,kSP>   K1: one residual + Jacobian sweep, rows written to HBM (parity + roofline runs;
 //                            smpc_eval_kernel.hpp);
 //                            kVT: per-scene horizons; kSP (with kVT): per-scene weights and velocity bounds as well
@@ -156,57 +155,37 @@ using KernelFn = void (*)(const smpc::KParams);
 // vt: the batch carries a horizon per scene (smpc_scene_batch.T_scene): the instantiation that reads T, CH, bl of each
 // scene from LDS instead of taking them as launch constants. sp: the batch carries weights and bounds per scene
 // (smpc_scene_batch.scene_params): kSP, which reads the horizon per scene as well (T_scene or T).
-template <int NB, int W, bool kVT, bool kSP> KernelFn pick_fn(bool eval) {
-  return eval ? smpc::smpc_eval_kernel<NB, W, kVT, kSP> : smpc::smpc_solve_kernel<NB, W, kVT, kSP>;
+// Sweep::Trace (smpc_solve_trace_batch): the solve that also leaves a row per LM iteration, compiled for the most general
+// variant only, kVT = kSP = true. A batch without T_scene runs it as it is (the kernel takes T for every scene), one
+// without scene_params with the handle's own weights and bounds as every scene's row (neutral_rows()): both give the
+// plain kernels' results bit for bit.
+enum class Sweep { Eval, Solve, Trace };
+
+template <int NB, int W, bool kVT, bool kSP> KernelFn pick_fn(Sweep kind) {
+  return kind == Sweep::Eval ? smpc::smpc_eval_kernel<NB, W, kVT, kSP> : smpc::smpc_solve_kernel<NB, W, kVT, kSP>;
 }
 
-template <int NB> KernelFn pick_w(int W, bool eval, bool vt, bool sp) {
-  if (W == 32) return sp ? pick_fn<NB, 32, true, true>(eval) : vt ? pick_fn<NB, 32, true, false>(eval) : pick_fn<NB, 32, false, false>(eval);
-  return sp ? pick_fn<NB, 64, true, true>(eval) : vt ? pick_fn<NB, 64, true, false>(eval) : pick_fn<NB, 64, false, false>(eval);
+template <int NB> KernelFn pick_w(int W, Sweep kind, bool vt, bool sp) {
+  if (kind == Sweep::Trace) return W == 32 ? smpc::smpc_solve_kernel<NB, 32, true, true, true> : smpc::smpc_solve_kernel<NB, 64, true, true, true>;
+  if (W == 32) return sp ? pick_fn<NB, 32, true, true>(kind) : vt ? pick_fn<NB, 32, true, false>(kind) : pick_fn<NB, 32, false, false>(kind);
+  return sp ? pick_fn<NB, 64, true, true>(kind) : vt ? pick_fn<NB, 64, true, false>(kind) : pick_fn<NB, 64, false, false>(kind);
 }
 
-KernelFn pick(int nb, int W, bool eval, bool vt = false, bool sp = false) {
+KernelFn pick(int nb, int W, Sweep kind, bool vt = false, bool sp = false) {
 #ifdef SMPC_ONLY_NB  // development builds: one instantiation only (seconds instead of a minute to compile)
-  return nb == SMPC_ONLY_NB ? pick_w<SMPC_ONLY_NB>(W, eval, vt, sp) : nullptr;
+  return nb == SMPC_ONLY_NB ? pick_w<SMPC_ONLY_NB>(W, kind, vt, sp) : nullptr;
 #else
   switch (nb) {
-    case 1: return pick_w<1>(W, eval, vt, sp);
-    case 2: return pick_w<2>(W, eval, vt, sp);
-    case 3: return pick_w<3>(W, eval, vt, sp);
-    case 4: return pick_w<4>(W, eval, vt, sp);
-    case 5: return pick_w<5>(W, eval, vt, sp);
-    case 6: return pick_w<6>(W, eval, vt, sp);
-    case 7: return pick_w<7>(W, eval, vt, sp);
-    case 8: return pick_w<8>(W, eval, vt, sp);
-    case 9: return pick_w<9>(W, eval, vt, sp);
-    case 10: return pick_w<10>(W, eval, vt, sp);
-    default: return nullptr;
-  }
-#endif
-}
-
-// The trace kernels (smpc_solve_trace_batch): the most general solve variant only, kVT = kSP = true.
-// A batch without T_scene runs it as it is (the kernel takes T for every scene), one without scene_params with the
-// handle's own weights and bounds as every scene's row (neutral_rows()): both give the plain kernels' results bit for bit.
-template <int NB> KernelFn pick_trace_w(int W) {
-  return W == 32 ? smpc::smpc_solve_trace_kernel<NB, 32> : smpc::smpc_solve_trace_kernel<NB, 64>;
-}
-
-KernelFn pick_trace(int nb, int W) {
-#ifdef SMPC_ONLY_NB
-  return nb == SMPC_ONLY_NB ? pick_trace_w<SMPC_ONLY_NB>(W) : nullptr;
-#else
-  switch (nb) {
-    case 1: return pick_trace_w<1>(W);
-    case 2: return pick_trace_w<2>(W);
-    case 3: return pick_trace_w<3>(W);
-    case 4: return pick_trace_w<4>(W);
-    case 5: return pick_trace_w<5>(W);
-    case 6: return pick_trace_w<6>(W);
-    case 7: return pick_trace_w<7>(W);
-    case 8: return pick_trace_w<8>(W);
-    case 9: return pick_trace_w<9>(W);
-    case 10: return pick_trace_w<10>(W);
+    case 1: return pick_w<1>(W, kind, vt, sp);
+    case 2: return pick_w<2>(W, kind, vt, sp);
+    case 3: return pick_w<3>(W, kind, vt, sp);
+    case 4: return pick_w<4>(W, kind, vt, sp);
+    case 5: return pick_w<5>(W, kind, vt, sp);
+    case 6: return pick_w<6>(W, kind, vt, sp);
+    case 7: return pick_w<7>(W, kind, vt, sp);
+    case 8: return pick_w<8>(W, kind, vt, sp);
+    case 9: return pick_w<9>(W, kind, vt, sp);
+    case 10: return pick_w<10>(W, kind, vt, sp);
     default: return nullptr;
   }
 #endif
@@ -223,7 +202,7 @@ int validate(const smpc_handle* h, const smpc_scene_batch* sb, Dims* d) {
   *d = make_dims(h->prm, sb->T, true);
   if (sb->T + 1 > smpc::kWave) { set_error("T + 1 > 64 rollout poses is not supported by the one-wave-per-scene mapping"); return SMPC_ERR_UNSUPPORTED; }
   if (sb->N > smpc::kWave) { set_error("N > 64 agents is not supported"); return SMPC_ERR_UNSUPPORTED; }
-  if (!pick(d->nb, 64, false)) { set_error("more than SMPC_MAX_BLOCKS parameter blocks (nb must be 1..10)"); return SMPC_ERR_UNSUPPORTED; }
+  if (!pick(d->nb, 64, Sweep::Solve)) { set_error("more than SMPC_MAX_BLOCKS parameter blocks (nb must be 1..10)"); return SMPC_ERR_UNSUPPORTED; }
   return SMPC_OK;
 }
 
@@ -436,12 +415,13 @@ int solve_slot_width(const smpc_handle* h, const smpc::KParams& k) {
   return (k.B <= per_cu * h->num_cu / share) ? 64 : 32;
 }
 
-// trace: the solve kernel that also writes k.o_trace / k.o_trace_n (k.scene_params is set by then)
-int launch(smpc_handle* h, Staging& st, bool eval, smpc::KParams& k, bool trace = false) {
+// Sweep::Trace: the solve kernel that also writes k.o_trace / k.o_trace_n (k.scene_params is set by then)
+int launch(smpc_handle* h, Staging& st, Sweep kind, smpc::KParams& k) {
+  const bool eval = kind == Sweep::Eval;
   const int W = eval ? smpc::slot_width(k.T, k.N) : solve_slot_width(h, k);
   const int S = smpc::kWave / W;
   const bool sp = k.scene_params != nullptr;
-  KernelFn fn = trace ? pick_trace(k.nb, W) : pick(k.nb, W, eval, k.T_scene != nullptr, sp);
+  KernelFn fn = pick(k.nb, W, kind, k.T_scene != nullptr, sp);
   const smpc::LdsLayout L = smpc::make_layout(k.T, k.N, k.P, eval ? smpc::kLayoutEval : smpc::kLayoutSolve, W, sp);
   k.hp_A = smpc::helper_owner_agents(k.T, k.N, W);
   if (std::getenv("SMPC_NO_HELPERS")) k.hp_A = k.N;  // experiment knob (the LDS layout keeps the helper regions)
@@ -709,7 +689,7 @@ int solve_batch(smpc_handle* h, const smpc_scene_batch* sb, smpc_result_batch* o
     SMPC_TRY(st.out(k.o_trace_n, trace->n_rows, B));
     if (!k.scene_params && B > 0) SMPC_TRY(neutral_rows(h, k));
   }
-  SMPC_TRY(launch(h, st, false, k, trace != nullptr));
+  SMPC_TRY(launch(h, st, trace ? Sweep::Trace : Sweep::Solve, k));
   return st.finish();
 }
 
@@ -1110,7 +1090,7 @@ int smpc_eval_batch(smpc_handle* h, const smpc_scene_batch* sb, const double* pa
   SMPC_TRY(st.out(k.e_jacobian, out->jacobian, B * d.M * d.P));
   SMPC_TRY(st.out(k.e_cost, out->cost, B));
   SMPC_TRY(st.out(k.e_gradient, out->gradient, B * d.P));
-  SMPC_TRY(launch(h, st, true, k));
+  SMPC_TRY(launch(h, st, Sweep::Eval, k));
   return st.finish();
 }
 

@@ -70,7 +70,7 @@ struct KParams {
   MathTab mt;  // polynomial coefficients of smpc_math.hpp, read through scalar loads
   AtanNodeTab an;  // nodes of atan2_unit(), copied into LDS by every wave (load_atan_nodes)
   const smpc_scene_params* scene_params;  // [B] per-scene weights / bounds (smpc_scene_batch.scene_params): the sp kernels
-  // trace kernels only (smpc_solve_trace_batch, smpc_solve_trace_kernel)
+  // trace kernels only (smpc_solve_trace_batch, kTrace)
   double* o_trace;      // [B][trace_rows][kTraceCols] one row per LM iteration; rows >= trace_rows are not stored
   int32_t* o_trace_n;   // [B] rows the solve produced (may exceed trace_rows), or null
   int trace_rows;

@@ -123,9 +123,9 @@ def planned_launches():
 def test_the_table_names_every_instantiation():
     src = open(os.path.join(ROOT, "include", "smpc.h")).read()
     max_blocks = int(re.search(r"#define SMPC_MAX_BLOCKS (\d+)", src).group(1))
-    # the variants pick() selects among: plain and one per flag of pick_w() after `eval`
+    # the variants pick() selects among: plain and one per flag of pick_w() after `kind`
     hip = open(os.path.join(ROOT, "nav2_social_mpc_controller_amd", "csrc", "smpc_hip.hip")).read()
-    flags = re.search(r"KernelFn pick_w\(int W, bool eval, ([^)]*)\)", hip).group(1)
+    flags = re.search(r"KernelFn pick_w\(int W, Sweep kind, ([^)]*)\)", hip).group(1)
     assert ("plain",) + tuple(f.split()[-1] for f in flags.split(",")) == VARIANTS
     want = set(itertools.product(("solve", "eval"), range(1, max_blocks + 1), (32, 64), VARIANTS))
     assert planned_launches() == want

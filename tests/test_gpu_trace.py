@@ -78,7 +78,7 @@ def check_rows(res, max_iterations):
         assert (tr[acc, COL["rho"]][1:] > 1e-3).all() and (tr[acc, COL["cost_change"]][1:] > 0).all(), b
         check_radius_recurrence(tr, reason, max_ulp=8)
         # every sweep is a counted one: the initial point and the line-search samples. An accepted candidate is the last
-        # sample, whose Gram the slot has. (The re-sweep of smpc_solve_body.inc's PH_REEVAL would add one; its comments call
+        # sample, whose Gram the slot has. (The re-sweep of smpc_solve_kernel.hpp's PH_REEVAL would add one; its comments call
         # it never seen, and a failure here would be its first sighting.)
         assert res["evaluations"][b] == 1 + int(tr[:, COL["ls_evals"]].sum()), b
         invalid = (tr[1:, COL["ls_evals"]] == 0)

@@ -16,7 +16,7 @@ HIPCC = "/opt/rocm/bin/hipcc"   # what build.sh invokes
 
 # the two-scenes-per-wave, fixed-horizon instantiations bench.py's workload runs: solve (timed) and K1 (roofline)
 KERNELS = {
-    "solve<3,32,false>": "_ZN4smpc17smpc_solve_kernelILi3ELi32ELb0ELb0EEEvNS_7KParamsE",
+    "solve<3,32,false>": "_ZN4smpc17smpc_solve_kernelILi3ELi32ELb0ELb0ELb0EEEvNS_7KParamsE",
     "K1<3,32,false>": "_ZN4smpc16smpc_eval_kernelILi3ELi32ELb0ELb0EEEvNS_7KParamsE",
 }
 MAX_VGPRS = 168   # 512 / 3, in the allocation granule: three waves per SIMD

@@ -101,10 +101,10 @@ def test_save_load_round_trip(tmp_path):
 
 # ---- register budget of the sp kernels (compile time, like tests/test_kernel_budget.py) ----------------------------
 SP_KERNELS = {
-    "solve_sp<3,32>": "_ZN4smpc17smpc_solve_kernelILi3ELi32ELb1ELb1EEEvNS_7KParamsE",
+    "solve_sp<3,32>": "_ZN4smpc17smpc_solve_kernelILi3ELi32ELb1ELb1ELb0EEEvNS_7KParamsE",
     "K1_sp<3,32>": "_ZN4smpc16smpc_eval_kernelILi3ELi32ELb1ELb1EEEvNS_7KParamsE",
 }
-VT_SOLVE = "_ZN4smpc17smpc_solve_kernelILi3ELi32ELb1ELb0EEEvNS_7KParamsE"  # the per-scene-horizon kernel the sp path extends
+VT_SOLVE = "_ZN4smpc17smpc_solve_kernelILi3ELi32ELb1ELb0ELb0EEEvNS_7KParamsE"  # the per-scene-horizon kernel the sp path extends
 
 
 @pytest.mark.parametrize("name", sorted(SP_KERNELS))

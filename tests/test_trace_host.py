@@ -39,8 +39,8 @@ def test_trace_out_layout_matches_the_c_header(tmp_path):
 
 
 # ---- register budget of the trace kernel (compile time, like tests/test_scene_params.py) --------------------------
-TRACE_SOLVE = "_ZN4smpc23smpc_solve_trace_kernelILi3ELi32EEEvNS_7KParamsE"
-SP_SOLVE = "_ZN4smpc17smpc_solve_kernelILi3ELi32ELb1ELb1EEEvNS_7KParamsE"  # the kernel whose body it shares
+TRACE_SOLVE = "_ZN4smpc17smpc_solve_kernelILi3ELi32ELb1ELb1ELb1EEEvNS_7KParamsE"
+SP_SOLVE = "_ZN4smpc17smpc_solve_kernelILi3ELi32ELb1ELb1ELb0EEEvNS_7KParamsE"  # the same template without kTrace
 
 
 def test_trace_kernel_costs_no_register_spill_or_private_segment(usage):
@@ -56,7 +56,7 @@ def test_trace_kernel_costs_no_register_spill_or_private_segment(usage):
 
 
 def test_one_scene_per_wave_trace_kernel_is_compiled(usage):
-    assert "_ZN4smpc23smpc_solve_trace_kernelILi3ELi64EEEvNS_7KParamsE" in usage
+    assert "_ZN4smpc17smpc_solve_kernelILi3ELi64ELb1ELb1ELb1EEEvNS_7KParamsE" in usage
 
 
 # ---- what debug_optimizer prints (host/optimizer.cpp: format_trace, format_trace_summary) --------------------------

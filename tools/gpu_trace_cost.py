@@ -1,7 +1,7 @@
 """Cost of the per-iteration trace (smpc_solve_trace_batch) on the headline batch (BASELINE configs[2]: 8192 scenes, N = 8,
 T = 28), lone solve launches on device-resident inputs, alternated round by round:
   (a) the sp kernel, every row equal to the handle's parameters    smpc_solve_kernel<3,32,true,true>
-  (b) the trace kernel on the plain batch (neutral rows filled by the library), every row kept   smpc_solve_trace_kernel<3,32>
+  (b) the trace kernel on the plain batch (neutral rows filled by the library), every row kept   smpc_solve_kernel<3,32,true,true,true>
   (c) the trace kernel with max_rows = 0: the counts alone
 Prints the median kernel time of each and (b) / (a), (c) / (a)."""
 import sys

@@ -31,6 +31,9 @@ RENAMES = [
     # smpc_eval_sp_kernel<NB,W> -> smpc_eval_kernel<NB,W,true,true>; smpc_eval_kernel<NB,W,vt> -> <NB,W,vt,false>
     (r"_ZN4smpc19smpc_eval_sp_kernelILi(\d+)ELi(\d+)E" + _TAIL, r"_ZN4smpc16smpc_eval_kernelILi\1ELi\2ELb1ELb1E" + _TAIL),
     (r"_ZN4smpc16smpc_eval_kernelILi(\d+)ELi(\d+)ELb([01])E" + _TAIL, r"_ZN4smpc16smpc_eval_kernelILi\1ELi\2ELb\3ELb0E" + _TAIL),
+    # smpc_solve_kernel<NB,W,vt,sp> -> <NB,W,vt,sp,false>; smpc_solve_trace_kernel<NB,W> -> smpc_solve_kernel<NB,W,true,true,true>
+    (r"_ZN4smpc17smpc_solve_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])E" + _TAIL, r"_ZN4smpc17smpc_solve_kernelILi\1ELi\2ELb\3ELb\4ELb0E" + _TAIL),
+    (r"_ZN4smpc23smpc_solve_trace_kernelILi(\d+)ELi(\d+)E" + _TAIL, r"_ZN4smpc17smpc_solve_kernelILi\1ELi\2ELb1ELb1ELb1E" + _TAIL),
 ]
 # what cannot matter: the numbers the compiler gives basic blocks, temporaries, jump tables and function ends
 LABELS = [(r"\.LBB\d+_", ".LBB_"), (r"\.Ltmp\d+", ".Ltmp"), (r"\.LJTI\d+_", ".LJTI_"), (r"\.LCPI\d+_", ".LCPI_"),
