@@ -522,6 +522,70 @@ int smpc_select_command_batch(smpc_handle* h, int32_t B, int32_t T, int32_t traj
                               int32_t* source /* [B]; may be NULL */,
                               const int32_t* window_error /* [B] enum smpc_window_error of this cycle; may be NULL */);
 
+/* ---- Per-robot navigation metrics of a closed-loop episode (csrc/smpc_metrics.hpp) ---------------------------------
+ * One call is one sample: the state of the world after a control period, folded into one row of SMPC_METRIC_COLS doubles
+ * per robot. The rows live with the caller (in / out, the memory space of the batch) and accumulate over the calls of an
+ * episode; a zero-filled buffer is a reset. Counters are doubles that hold whole numbers. */
+#define SMPC_METRIC_COLS 24
+enum smpc_metric_col {
+  SMPC_M_SAMPLES = 0,            /* calls folded into the row; 0 on entry: the row is empty and is initialised first */
+  SMPC_M_PATH_LENGTH,            /* sum of |position - previous sample's position| in metres */
+  SMPC_M_HEADING_CHANGE,         /* sum of |wrap(yaw - previous sample's yaw)| in radians, wrapped into (-pi, pi] */
+  SMPC_M_SUM_SPEED,              /* sum of robot_twist v */
+  SMPC_M_PEOPLE_SAMPLES,         /* samples with count[b] > 0; the next six columns move only in those */
+  SMPC_M_MIN_PERSON_DIST,        /* smallest distance to a person's centre so far; +inf before the first one */
+  SMPC_M_SUM_MIN_PERSON_DIST,    /* sum over the samples of the distance to the closest person */
+  SMPC_M_INTIMATE_SAMPLES,       /* samples with the closest person nearer than intimate_radius (strict) */
+  SMPC_M_PERSONAL_SAMPLES,       /* ... than personal_radius */
+  SMPC_M_SOCIAL_SAMPLES,         /* ... than social_radius */
+  SMPC_M_PERSON_COLLISION_SAMPLES, /* ... than robot_radius + person_radius */
+  SMPC_M_SOCIAL_WORK,            /* sum of SocialWorkCost's wr + wp (critics/social_work_cost_function.hpp:125-143, without
+                                    the weight and the + 1e-6) at the executed state: robot velocity v (cos yaw, sin yaw),
+                                    a person's velocity as given */
+  SMPC_M_MIN_CLEARANCE,          /* smallest od_distances entry under the robot so far; +inf before the first one */
+  SMPC_M_OBSTACLE_COLLISION_SAMPLES, /* samples with that entry < robot_radius */
+  SMPC_M_OFF_GRID_SAMPLES,       /* samples with the robot outside the distance grid */
+  SMPC_M_TIME_TO_GOAL,           /* -1 until the goal is within goal_tolerance, then SAMPLES * dt of that sample */
+  SMPC_M_GOAL_DIST,              /* distance to the goal at the latest sample */
+  SMPC_M_FALLBACK_SAMPLES,       /* samples with source[b] != 0 (smpc_select_command_batch) */
+  SMPC_M_UNUSABLE_SOLVES,        /* samples whose status is neither SMPC_CONVERGENCE nor SMPC_NO_CONVERGENCE */
+  SMPC_M_LAST_X, SMPC_M_LAST_Y, SMPC_M_LAST_YAW /* pose of the latest sample; columns 22, 23: reserved, kept 0 */
+};
+
+typedef struct smpc_metrics_batch {
+  int32_t B, Np, on_device, reserved; /* Np: row stride of `people` (1..SMPC_MAX_AGENTS); on_device as everywhere */
+  double dt;                  /* control period: TIME_TO_GOAL = SAMPLES * dt */
+  const double* robot_pose;   /* [B][3] x, y, yaw */
+  const double* robot_twist;  /* [B][2] v, w executed during the period that ended in this state */
+  const double* people;       /* [B][Np][5] smpc_people_batch.people rows */
+  const int32_t* count;       /* [B] persons of each robot, 0..Np (checked for host arrays, clamped for device arrays) */
+  const double* goal;         /* [B][2] or NULL: GOAL_DIST and TIME_TO_GOAL keep their initial values */
+  double goal_tolerance;      /* e.g. 0.25 */
+  double robot_radius, person_radius;                       /* e.g. 0.3, 0.3 */
+  double intimate_radius, personal_radius, social_radius;   /* e.g. 0.45, 1.2, 3.6 */
+  const float* od_distances;  /* [B or 1][od_height][od_width] smpc_obstacle_distance_out.distances, or NULL: the three
+                                 clearance columns keep their initial values */
+  int32_t od_shared, od_width, od_height; float od_resolution;
+  const double* od_origin;    /* [B or 1][2] */
+  const int32_t* status;      /* [B] of this tick's solve, or NULL */
+  const int32_t* source;      /* [B] of smpc_select_command_batch, or NULL */
+} smpc_metrics_batch;
+
+/* Folds one sample into acc [B][SMPC_METRIC_COLS]. Per robot, in this order: an empty row (SAMPLES == 0) is initialised
+ * (the two minima +inf, TIME_TO_GOAL -1, the rest 0); a row whose TIME_TO_GOAL is >= 0 after that test (the goal was
+ * reached in an earlier call) is left untouched bit for bit — the metrics describe the drive to the goal, not the waiting
+ * afterwards; motion (the first sample adds no length or heading); people (only with count[b] > 0); social work; the
+ * clearance cell (floor((x - origin x) / (double)od_resolution), floor((y - origin y) / (double)od_resolution)); the
+ * controller columns; LAST_* and SAMPLES; the goal test with the incremented SAMPLES. The social force follows the
+ * conventions of the solve: a pair closer than 1e-6 m takes diff = (1e-6, 0), exactly equal velocities take theta = 0.
+ * A robot's row depends on that robot's inputs alone, and the order of the sums over its persons on Np alone: not on B, the
+ * robot's place in the batch, the memory space or timing. One kernel on the handle's stream, no allocation and no host
+ * synchronisation for device pointers (capturable in a HIP graph). SMPC_ERR_INVALID_ARG (nothing launched, acc untouched):
+ * B < 1, Np < 1, dt <= 0, a negative radius or tolerance, NULL acc / robot_pose / robot_twist / people / count, a distance
+ * grid without origin or with a non-positive size or resolution, a host count outside 0..Np. SMPC_ERR_UNSUPPORTED:
+ * Np > SMPC_MAX_AGENTS. */
+int smpc_episode_metrics_batch(smpc_handle* h, const smpc_metrics_batch* in, double* acc);
+
 /* Diagnostic: evaluates the elementary functions the sweep uses (csrc/smpc_math.hpp: table-driven exp / atan2 /
  * sincos, refined reciprocal / rsqrt, and the raw hardware estimates behind them) on n host-side arguments, so that
  * tests can check them on the device against libm. fn: 0 exp(a) | 1 atan2(a, b) | 2 sin(a) -> out0, cos(a) -> out1 |

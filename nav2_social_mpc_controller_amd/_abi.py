@@ -258,6 +258,38 @@ class SmpcTraceOut(C.Structure):
     ]
 
 
+SMPC_METRIC_COLS = 24
+
+
+class SmpcMetricsBatch(C.Structure):
+    _fields_ = [
+        ("B", C.c_int32),
+        ("Np", C.c_int32),
+        ("on_device", C.c_int32),
+        ("reserved", C.c_int32),
+        ("dt", C.c_double),
+        ("robot_pose", C.c_void_p),
+        ("robot_twist", C.c_void_p),
+        ("people", C.c_void_p),
+        ("count", C.c_void_p),
+        ("goal", C.c_void_p),
+        ("goal_tolerance", C.c_double),
+        ("robot_radius", C.c_double),
+        ("person_radius", C.c_double),
+        ("intimate_radius", C.c_double),
+        ("personal_radius", C.c_double),
+        ("social_radius", C.c_double),
+        ("od_distances", C.c_void_p),
+        ("od_shared", C.c_int32),
+        ("od_width", C.c_int32),
+        ("od_height", C.c_int32),
+        ("od_resolution", C.c_float),
+        ("od_origin", C.c_void_p),
+        ("status", C.c_void_p),
+        ("source", C.c_void_p),
+    ]
+
+
 class SmpcEvalOut(C.Structure):
     _fields_ = [
         ("residuals", C.c_void_p),
@@ -288,6 +320,7 @@ EXPORTED_SYMBOLS = [
     "smpc_trajectorize_path_batch",
     "smpc_transform_global_plan_batch",
     "smpc_select_command_batch",
+    "smpc_episode_metrics_batch",
     "smpc_math_probe",
     "smpc_fp64_peak_probe",
     "smpc_stage_people_batch",

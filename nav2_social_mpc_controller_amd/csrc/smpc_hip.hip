@@ -31,6 +31,7 @@
 #include "smpc_format.hpp"
 #include "smpc_trajectorize.hpp"
 #include "smpc_path_window.hpp"
+#include "smpc_metrics.hpp"
 
 // ================================================================================================
 // Host side of the C ABI
@@ -997,6 +998,53 @@ int smpc_select_command_batch(smpc_handle* h, int32_t B_, int32_t T, int32_t tra
       return SMPC_OK;
     }));
   }
+  return st.finish();
+}
+
+int smpc_episode_metrics_batch(smpc_handle* h, const smpc_metrics_batch* in, double* acc) {
+  if (!h || !in || !acc) { set_error("null handle / input / acc"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B < 1 || in->Np < 1 || !(in->dt > 0.0)) { set_error("bad B / Np / dt"); return SMPC_ERR_INVALID_ARG; }
+  if (!(in->goal_tolerance >= 0.0) || !(in->robot_radius >= 0.0) || !(in->person_radius >= 0.0) || !(in->intimate_radius >= 0.0) ||
+      !(in->personal_radius >= 0.0) || !(in->social_radius >= 0.0)) {
+    set_error("negative radius or tolerance"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (!in->robot_pose || !in->robot_twist || !in->people || !in->count) { set_error("null input array"); return SMPC_ERR_INVALID_ARG; }
+  if (in->od_distances && (!in->od_origin || in->od_width < 1 || in->od_height < 1 || !(in->od_resolution > 0.0f))) {
+    set_error("distance grid without origin or with a non-positive size or resolution"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (in->Np > SMPC_MAX_AGENTS) { set_error("Np > 64 persons is not supported"); return SMPC_ERR_UNSUPPORTED; }
+  if (!in->on_device)
+    for (int32_t b = 0; b < in->B; ++b)
+      if (in->count[b] < 0 || in->count[b] > in->Np) { set_error("count outside 0..Np"); return SMPC_ERR_INVALID_ARG; }
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::MetricsParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.B = in->B; p.Np = in->Np;
+  int G = 1;
+  while (G < in->Np) G *= 2;
+  p.G = G;
+  p.dt = in->dt; p.goal_tolerance = in->goal_tolerance; p.robot_radius = in->robot_radius; p.person_radius = in->person_radius;
+  p.intimate_radius = in->intimate_radius; p.personal_radius = in->personal_radius; p.social_radius = in->social_radius;
+  const bool grid = in->od_distances != nullptr;
+  p.od_shared = in->od_shared ? 1 : 0; p.od_width = in->od_width; p.od_height = in->od_height; p.od_resolution = in->od_resolution;
+  const size_t B = in->B, Np = in->Np, ngrid = in->od_shared ? 1 : B;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.pose, in->robot_pose, B * 3));
+  SMPC_TRY(st.in(p.twist, in->robot_twist, B * 2));
+  SMPC_TRY(st.in(p.people, in->people, B * Np * 5));
+  SMPC_TRY(st.in(p.count, in->count, B));
+  SMPC_TRY(st.in(p.goal, in->goal, B * 2));
+  SMPC_TRY(st.in(p.od_distances, in->od_distances, grid ? ngrid * (size_t)in->od_width * in->od_height : 0));
+  SMPC_TRY(st.in(p.od_origin, grid ? in->od_origin : nullptr, ngrid * 2));
+  SMPC_TRY(st.in(p.status, in->status, B));
+  SMPC_TRY(st.in(p.source, in->source, B));
+  SMPC_TRY(st.inout(p.acc, acc, B * SMPC_METRIC_COLS));
+  const size_t per_block = smpc::kMetricsThreads / G;
+  SMPC_TRY(st.timed([&] {
+    hipLaunchKernelGGL(smpc::smpc_episode_metrics_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kMetricsThreads), 0,
+                       h->stream, p);
+    return SMPC_OK;
+  }));
   return st.finish();
 }
 

@@ -26,7 +26,7 @@ import numpy as np
 
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
-from .params import OptimizerParams, TrajectorizerParams, check_scene_param_rows
+from .params import MetricsParams, OptimizerParams, TrajectorizerParams, check_scene_param_rows
 from .scenes import SceneBatch
 from .solver import BatchSolver
 
@@ -58,6 +58,11 @@ class TickRecord:
     has_people: np.ndarray = None
     T_scene: np.ndarray = None      # [B] horizon every robot was solved with (plan episodes: from its own path length)
     window_err: np.ndarray = None   # [B] smpc_window_error of the tick's transformGlobalPlan (plan_window episodes)
+    # the world after the tick's move: what the tick's metrics sample is taken from (BatchEpisode(metrics=...))
+    pose_after: np.ndarray = None     # [B,3]
+    persons_after: np.ndarray = None  # [B,Np,5]
+    cmd_vel: np.ndarray = None        # [B,2] the executed command
+    cmd_source: np.ndarray = None     # [B]
 
 
 class BatchEpisode:
@@ -65,7 +70,8 @@ class BatchEpisode:
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
                  plan_len: np.ndarray = None, traj_params: TrajectorizerParams = None, fov_angle: float = None,
                  order_hint: bool = False, plan_window: tuple = None, obstacles_from_costmap: bool = False,
-                 obstacle_min_cost: int = 254, unknown_is_obstacle: bool = False, scene_params: np.ndarray = None):
+                 obstacle_min_cost: int = 254, unknown_is_obstacle: bool = False, scene_params: np.ndarray = None,
+                 metrics: MetricsParams = None, goal: np.ndarray = None, od_distances: np.ndarray = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -83,7 +89,15 @@ class BatchEpisode:
         (smpc_scene_batch.order; the results are the same, the lone launch is shorter).
         scene_params [B,14]: critic weights, target speed and velocity bounds of every robot (smpc_scene_batch.scene_params,
         e.g. params.scene_param_rows), handed to every tick's solve; None: `params`' values for every robot. Only the
-        solve takes them: the trajectorizer and the rest of the tick keep the episode-wide parameters."""
+        solve takes them: the trajectorizer and the rest of the tick keep the episode-wide parameters.
+        metrics: score every robot on the device (smpc_episode_metrics_batch): each tick ends with one sample of the world
+        after its move — the new pose, the executed command, the moved persons, the tick's solve status and command source —
+        folded into self.metrics_acc [B,24] (solver.METRIC_COLS; metrics() returns the host copy, solver.summarize_metrics
+        the derived values). goal [B,2]: where each robot is headed (default with global plans: the last pose of each plan;
+        otherwise none, and the goal columns stay unset); a robot's row is frozen once it is within metrics.goal_tolerance
+        of it. The clearance columns need the distances of the ObstacleDistance grid: with obstacles_from_costmap they are
+        computed along with the indexes, with host-given od_indexes they are fed only when od_distances (float32, shaped
+        like od_indexes) is passed too. None: nothing is allocated and nothing is launched."""
         import torch
 
         self.torch = torch
@@ -129,10 +143,13 @@ class BatchEpisode:
             self.od_resolution = float(np.float32(self.resolution))
             self.od_origin = self.costmap_origin
             self.od_indexes = torch.empty((grids, self.od_h, self.od_w), dtype=torch.int32, device=self.dev)
+            if metrics is not None:  # the clearance columns read the distances: one more array, once
+                self.od_distances = torch.empty((grids, self.od_h, self.od_w), dtype=torch.float32, device=self.dev)
             ob = BatchSolver.obstacle_distance_c(B, self.size_x, self.size_y, self.costmap_shared, self.resolution, 1,
                                                  obstacle_min_cost, unknown_is_obstacle)
             ob.costmap = self.costmap.data_ptr()
-            self.solver.obstacle_distance_device(ob, self.od_indexes.data_ptr())
+            self.solver.obstacle_distance_device(ob, self.od_indexes.data_ptr(),
+                                                 self.od_distances.data_ptr() if metrics is not None else 0)
         else:
             if od_indexes is None or od_origin is None or od_resolution is None:
                 raise ValueError("od_indexes, od_origin and od_resolution are needed unless obstacles_from_costmap=True")
@@ -145,6 +162,9 @@ class BatchEpisode:
             self.od_origin = torch.from_numpy(np.ascontiguousarray(od_origin, np.float64).reshape(-1 if per_scene else 1, 2)).to(self.dev)
             self.od_h, self.od_w = int(od_indexes.shape[-2]), int(od_indexes.shape[-1])
             self.od_resolution = float(od_resolution)
+            if metrics is not None and od_distances is not None:
+                assert np.shape(od_distances) == od_indexes.shape, "od_distances is shaped like od_indexes"
+                self.od_distances = torch.from_numpy(np.ascontiguousarray(od_distances, np.float32)).to(self.dev)
         # TrajectoryMemory, one record per scene
         self.mem_path = torch.zeros((B, T + 1, 3), **f64)
         self.mem_cmds = torch.zeros((B, T + 1, 2), **f64)
@@ -189,6 +209,16 @@ class BatchEpisode:
         if scene_params is not None:
             sp = check_scene_param_rows(scene_params, B)
             self.scene_params = torch.from_numpy(sp).to(self.dev)  # device rows: checked here, not by the library
+        self.metrics_params = metrics
+        if metrics is not None:
+            self.metrics_acc = torch.zeros((B, 24), **f64)  # zero rows: no samples yet
+            if goal is None and plan is not None:
+                L = np.asarray(plan_len).astype(np.int64)
+                goal = np.asarray(plan, np.float64)[np.arange(B), np.maximum(L, 1) - 1]
+            self.goal = None
+            if goal is not None:
+                assert np.shape(goal) == (B, 2), "goal [B,2]"
+                self.goal = torch.from_numpy(np.ascontiguousarray(goal, np.float64)).to(self.dev)
         self.graph = None
         self.gstream = None
         # queue order for the next solve (from the last solve's sweep counts; index order before the first one)
@@ -350,8 +380,35 @@ class BatchEpisode:
         self.speed.copy_(self.cmd_vel)
         self.persons[:, :, 0] += self.persons[:, :, 2] * dt
         self.persons[:, :, 1] += self.persons[:, :, 3] * dt
+        if self.metrics_params is not None:  # 6. one metrics sample of the world as the period leaves it
+            self._metrics_sample()
+            if timing is not None:
+                timing["metrics_ms"] = s.last_kernel_ms()
+        if record:
+            rec.update(pose_after=self.pose.cpu().numpy().copy(), persons_after=self.persons.cpu().numpy().copy(),
+                       cmd_vel=self.cmd_vel.cpu().numpy().copy(), cmd_source=self.cmd_source.cpu().numpy().copy())
         self.ticks += 1
         return TickRecord(**rec) if record else None
+
+    def _metrics_sample(self):
+        mb = BatchSolver.metrics_c(self.metrics_params, self.B, int(self.persons.shape[1]), self.params.dt, 1)
+        mb.robot_pose, mb.robot_twist = self.pose.data_ptr(), self.cmd_vel.data_ptr()
+        mb.people, mb.count = self.persons.data_ptr(), self.person_count.data_ptr()
+        if self.goal is not None:
+            mb.goal = self.goal.data_ptr()
+        od = getattr(self, "od_distances", None)
+        if od is not None:
+            mb.od_distances, mb.od_origin = od.data_ptr(), self.od_origin.data_ptr()
+            mb.od_shared, mb.od_width, mb.od_height, mb.od_resolution = self.od_shared, self.od_w, self.od_h, self.od_resolution
+        mb.status, mb.source = self.res["status"].data_ptr(), self.cmd_source.data_ptr()
+        self.solver.episode_metrics_device(mb, self.metrics_acc.data_ptr())
+
+    def metrics(self) -> np.ndarray:
+        """Host copy of the metrics rows [B,24] (columns solver.METRIC_COLS) accumulated so far."""
+        if self.metrics_params is None:
+            raise ValueError("this episode was built without metrics")
+        self.torch.cuda.synchronize()
+        return self.metrics_acc.cpu().numpy().copy()
 
     def capture_graph(self, stream=None):
         """Record one tick (every kernel of the chain and the torch ops of the world model) into a HIP graph on `stream`
@@ -363,6 +420,8 @@ class BatchEpisode:
         self.gstream.wait_stream(torch.cuda.current_stream(self.dev))
         self.solver.set_stream(self.gstream.cuda_stream)
         state = ("pose", "speed", "persons", "mem_path", "mem_cmds", "mem_valid", "mem_length", "order") + (("plan_start",) if self.plan_window is not None else ())
+        if self.metrics_params is not None:
+            state += ("metrics_acc",)  # the warm-up tick's sample does not count
         with torch.cuda.stream(self.gstream):
             saved = {k: getattr(self, k).clone() for k in state}
             ticks = self.ticks
@@ -446,7 +505,8 @@ class ShardedEpisode:
                  plan_len: np.ndarray = None, traj_params: TrajectorizerParams = None, fov_angle: float = None,
                  shards: int = 3, order_hint: bool = False, graphs: bool = True, solve_share: int = None,
                  plan_window: tuple = None, obstacles_from_costmap: bool = False, obstacle_min_cost: int = 254,
-                 unknown_is_obstacle: bool = False, scene_params: np.ndarray = None):
+                 unknown_is_obstacle: bool = False, scene_params: np.ndarray = None, metrics: MetricsParams = None,
+                 goal: np.ndarray = None, od_distances: np.ndarray = None):
         import torch
 
         self.torch = torch
@@ -461,6 +521,7 @@ class ShardedEpisode:
         for sl, st in zip(self.slices, self.streams):
             idx = np.arange(sl.start, sl.stop)
             odi, odo = (od_indexes[idx], np.asarray(od_origin)[idx]) if per_scene_od else (od_indexes, od_origin)
+            odd = np.asarray(od_distances)[idx] if per_scene_od and od_distances is not None else od_distances
             with torch.cuda.stream(st):  # the shard's solver handle binds to the stream current at construction
                 self.parts.append(BatchEpisode(
                     params, scenes.select(idx), np.asarray(w_ref)[idx], odi, odo, od_resolution, device=device,
@@ -468,7 +529,8 @@ class ShardedEpisode:
                     traj_params=traj_params, fov_angle=fov_angle, order_hint=order_hint, plan_window=plan_window,
                     obstacles_from_costmap=obstacles_from_costmap, obstacle_min_cost=obstacle_min_cost,
                     unknown_is_obstacle=unknown_is_obstacle,
-                    scene_params=None if scene_params is None else np.asarray(scene_params)[idx]))
+                    scene_params=None if scene_params is None else np.asarray(scene_params)[idx],
+                    metrics=metrics, goal=None if goal is None else np.asarray(goal)[idx], od_distances=odd))
         self.B = B
         self.graphs = graphs
         for part in self.parts:  # every shard's persistent solve grid takes its share of the resident wavefronts
@@ -490,7 +552,7 @@ class ShardedEpisode:
 
     def gather(self, name: str):
         """Concatenated per-robot tensor: a key of BatchEpisode.res ("status", "cmds", ...) or an attribute ("pose",
-        "cmd_vel", "cmd_source", "proj_error")."""
+        "cmd_vel", "cmd_source", "proj_error", "metrics_acc")."""
         self.synchronize()
         return self.torch.cat([p.res[name] if name in p.res else getattr(p, name) for p in self.parts], dim=0)
 

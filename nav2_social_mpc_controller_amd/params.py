@@ -34,6 +34,24 @@ class TrajectorizerParams:
 
 
 @dataclass
+class MetricsParams:
+    """What smpc_episode_metrics_batch compares a sample with (smpc_metrics_batch, include/smpc.h): the goal tolerance, the
+    robot's and a person's radius (a collision with a person: centres closer than their sum; with an obstacle: clearance
+    below the robot's), and the proxemic zones around a person's centre (Hall's intimate / personal / social distances)."""
+    goal_tolerance: float = 0.25
+    robot_radius: float = 0.3
+    person_radius: float = 0.3
+    intimate_radius: float = 0.45
+    personal_radius: float = 1.2
+    social_radius: float = 3.6
+
+    def __post_init__(self):
+        for f in fields(self):
+            if not getattr(self, f.name) >= 0.0:
+                raise ValueError(f"MetricsParams.{f.name} must be >= 0, got {getattr(self, f.name)}")
+
+
+@dataclass
 class OptimizerParams:
     # optimizer.* (src/optimizer.cpp:26-55, 76-83)
     linear_solver_type: str = "SPARSE_NORMAL_CHOLESKY"

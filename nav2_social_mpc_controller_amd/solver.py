@@ -12,10 +12,10 @@ import os
 import numpy as np
 
 from . import _abi
-from ._abi import (SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcObstacleDistanceIn, SmpcObstacleDistanceOut,
-                   SmpcParams, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
+from ._abi import (SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
+                   SmpcObstacleDistanceOut, SmpcParams, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
-from .params import OptimizerParams, TrajectorizerParams
+from .params import MetricsParams, OptimizerParams, TrajectorizerParams
 from .scenes import SceneBatch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -24,6 +24,12 @@ _lib = None
 # columns of a trace row (smpc_trace_out, include/smpc.h): one row per LM iteration
 TRACE_COLS = ["iter", "cost", "cost_change", "gradient_max_norm", "step_norm", "rho", "radius", "ls_evals", "accepted"]
 assert len(TRACE_COLS) == _abi.SMPC_TRACE_COLS
+# columns of a metrics row (enum smpc_metric_col, include/smpc.h): one row per robot, accumulated over an episode
+METRIC_COLS = ["samples", "path_length", "heading_change", "sum_speed", "people_samples", "min_person_dist",
+               "sum_min_person_dist", "intimate_samples", "personal_samples", "social_samples", "person_collision_samples",
+               "social_work", "min_clearance", "obstacle_collision_samples", "off_grid_samples", "time_to_goal", "goal_dist",
+               "fallback_samples", "unusable_solves", "last_x", "last_y", "last_yaw", "reserved0", "reserved1"]
+assert len(METRIC_COLS) == _abi.SMPC_METRIC_COLS
 
 
 class SmpcError(RuntimeError):
@@ -85,6 +91,8 @@ def load_library():
     lib.smpc_transform_global_plan_batch.restype = C.c_int
     lib.smpc_select_command_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7
     lib.smpc_select_command_batch.restype = C.c_int
+    lib.smpc_episode_metrics_batch.argtypes = [C.c_void_p, C.POINTER(SmpcMetricsBatch), C.c_void_p]
+    lib.smpc_episode_metrics_batch.restype = C.c_int
     lib.smpc_stage_people_batch.argtypes = [C.c_void_p, C.POINTER(SmpcSceneBatch), C.c_void_p, C.c_void_p]
     lib.smpc_stage_people_batch.restype = C.c_int
     lib.smpc_fp64_peak_probe.argtypes = [C.c_void_p, C.c_int32]
@@ -102,6 +110,41 @@ def load_library():
 def _check(lib, rc, what):
     if rc != 0:
         raise SmpcError(f"{what} failed ({rc}): {lib.smpc_last_error().decode()}")
+
+
+def summarize_metrics(acc: np.ndarray, dt: float) -> dict:
+    """Per-robot values derived from metrics rows acc [B,24] (columns METRIC_COLS) of an episode with control period dt:
+    success (goal reached), time_to_goal (NaN without success), duration (samples * dt), path_length, mean_speed,
+    min_person_dist, mean_min_person_dist (over the samples with people; NaN without any), social_work_per_metre (NaN for a
+    robot that did not move), intimate_share / personal_share / social_share (of the samples with people; 0 without any),
+    min_clearance, person_collision / obstacle_collision (any sample), fallback_share and unusable_share (of all
+    samples). A row without samples gives NaN shares and means."""
+    acc = np.asarray(acc, np.float64)
+    assert acc.ndim == 2 and acc.shape[1] == _abi.SMPC_METRIC_COLS
+    c = {name: acc[:, i] for i, name in enumerate(METRIC_COLS)}
+    n, npl = c["samples"], c["people_samples"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        per_sample = lambda v: np.where(n > 0, v / n, np.nan)
+        per_people = lambda v, empty: np.where(npl > 0, v / npl, np.where(n > 0, empty, np.nan))
+        success = (n > 0) & (c["time_to_goal"] >= 0)  # (a zero-filled row is an empty one, not an arrival at t = 0)
+        return {
+            "success": success,
+            "time_to_goal": np.where(success, c["time_to_goal"], np.nan),
+            "duration": n * float(dt),
+            "path_length": c["path_length"].copy(),
+            "mean_speed": per_sample(c["sum_speed"]),
+            "min_person_dist": c["min_person_dist"].copy(),
+            "mean_min_person_dist": per_people(c["sum_min_person_dist"], np.nan),
+            "social_work_per_metre": np.where(c["path_length"] > 0, c["social_work"] / c["path_length"], np.nan),
+            "intimate_share": per_people(c["intimate_samples"], 0.0),
+            "personal_share": per_people(c["personal_samples"], 0.0),
+            "social_share": per_people(c["social_samples"], 0.0),
+            "min_clearance": c["min_clearance"].copy(),
+            "person_collision": c["person_collision_samples"] > 0,
+            "obstacle_collision": c["obstacle_collision_samples"] > 0,
+            "fallback_share": per_sample(c["fallback_samples"]),
+            "unusable_share": per_sample(c["unusable_solves"]),
+        }
 
 
 class BatchSolver:
@@ -412,6 +455,62 @@ class BatchSolver:
                                                             out.ctypes.data, src.ctypes.data,
                                                             None if we is None else we.ctypes.data), "smpc_select_command_batch")
         return out, src
+
+    # -- per-robot navigation metrics of a closed-loop episode (smpc_episode_metrics_batch) ------------------------
+    @staticmethod
+    def metrics_c(mp: MetricsParams, B: int, Np: int, dt: float, on_device: int) -> SmpcMetricsBatch:
+        mb = SmpcMetricsBatch()
+        mb.B, mb.Np, mb.on_device, mb.dt = int(B), int(Np), int(on_device), float(dt)
+        mb.goal_tolerance, mb.robot_radius, mb.person_radius = mp.goal_tolerance, mp.robot_radius, mp.person_radius
+        mb.intimate_radius, mb.personal_radius, mb.social_radius = mp.intimate_radius, mp.personal_radius, mp.social_radius
+        return mb
+
+    def episode_metrics(self, mp: MetricsParams, dt: float, acc: np.ndarray, robot_pose: np.ndarray, robot_twist: np.ndarray,
+                        people: np.ndarray, count: np.ndarray, goal: np.ndarray = None, od_distances: np.ndarray = None,
+                        od_origin: np.ndarray = None, od_resolution: float = None, status: np.ndarray = None,
+                        source: np.ndarray = None) -> np.ndarray:
+        """One sample folded into the metrics rows (host arrays): acc [B,24] (zeros: empty rows), robot_pose [B,3],
+        robot_twist [B,2], people [B,Np,5], count [B]; optional goal [B,2], od_distances [h,w] (one shared grid, od_origin
+        [2]) or [B,h,w] (od_origin [B,2]) float32 with od_resolution, status [B] and source [B] of the tick. Returns the
+        updated copy of acc (columns METRIC_COLS)."""
+        acc = np.array(acc, dtype=np.float64, order="C")
+        robot_pose = np.ascontiguousarray(robot_pose, np.float64)
+        robot_twist = np.ascontiguousarray(robot_twist, np.float64)
+        people = np.ascontiguousarray(people, np.float64)
+        count = np.ascontiguousarray(count, np.int32)
+        B, Np, _ = people.shape
+        assert acc.shape == (B, _abi.SMPC_METRIC_COLS) and robot_pose.shape == (B, 3) and robot_twist.shape == (B, 2)
+        assert count.shape == (B,) and people.shape[2] == 5
+        mb = self.metrics_c(mp, B, Np, dt, 0)
+        mb.robot_pose, mb.robot_twist = robot_pose.ctypes.data, robot_twist.ctypes.data
+        mb.people, mb.count = people.ctypes.data, count.ctypes.data
+        keep = []
+        if goal is not None:
+            goal = np.ascontiguousarray(goal, np.float64)
+            assert goal.shape == (B, 2)
+            mb.goal = goal.ctypes.data
+        if od_distances is not None:
+            od_distances = np.ascontiguousarray(od_distances, np.float32)
+            shared = od_distances.ndim == 2
+            od_origin = np.ascontiguousarray(od_origin, np.float64).reshape(-1, 2)
+            assert od_distances.ndim == 2 or od_distances.shape[0] == B
+            assert od_origin.shape == ((1, 2) if shared else (B, 2))
+            mb.od_distances, mb.od_origin = od_distances.ctypes.data, od_origin.ctypes.data
+            mb.od_shared, mb.od_height, mb.od_width = 1 if shared else 0, int(od_distances.shape[-2]), int(od_distances.shape[-1])
+            mb.od_resolution = float(od_resolution)
+        for name, arr in (("status", status), ("source", source)):
+            if arr is not None:
+                arr = np.ascontiguousarray(arr, np.int32)
+                assert arr.shape == (B,)
+                keep.append(arr)
+                setattr(mb, name, arr.ctypes.data)
+        _check(self.lib, self.lib.smpc_episode_metrics_batch(self._h, C.byref(mb), acc.ctypes.data), "smpc_episode_metrics_batch")
+        return acc
+
+    def episode_metrics_device(self, mb: SmpcMetricsBatch, acc_ptr: int):
+        """Device pointers in mb (on_device == 1) and for acc; asynchronous on the handle's stream."""
+        assert mb.on_device == 1
+        _check(self.lib, self.lib.smpc_episode_metrics_batch(self._h, C.byref(mb), C.c_void_p(acc_ptr)), "smpc_episode_metrics_batch")
 
     def select_command_device(self, B, T, rows, traj_n_ptr, traj_cmds_ptr, status_ptr, cmds_ptr, cmd_vel_ptr, source_ptr,
                               window_error_ptr=0):

@@ -1,0 +1,180 @@
+"""Per-robot episode metrics (smpc_episode_metrics_batch), the parts that need no GPU: the CPU checker of the GPU tests
+(tests/metrics_ref.py) on hand-computed cases, its force against the oracle's, and the ABI additions."""
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import metrics_ref as R
+from nav2_social_mpc_controller_amd import _abi
+from nav2_social_mpc_controller_amd import solver as S
+from nav2_social_mpc_controller_amd.params import MetricsParams
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "smpc.h")
+I = R.I
+NOBODY = np.zeros((1, 5))
+
+
+def run(samples, mp=None, dt=0.05, **kw):
+    """samples: (x, y, yaw, v) of one robot without people; returns the row after all of them."""
+    row = np.zeros(R.NCOLS)
+    for x, y, yaw, v in samples:
+        row = R.update_row(row, mp or MetricsParams(), dt, (x, y, yaw), (v, 0.0), NOBODY, 0, **kw)
+    return row
+
+
+def test_three_collinear_samples_half_a_metre_apart():
+    row = run([(0.0, 0.25, 0.0, 0.5), (0.5, 0.25, 0.0, 0.5), (1.0, 0.25, 0.0, 0.25)])
+    assert row[I["path_length"]] == 1.0
+    assert row[I["samples"]] == 3 and row[I["sum_speed"]] == 1.25 and row[I["heading_change"]] == 0.0
+    assert (row[I["last_x"]], row[I["last_y"]], row[I["last_yaw"]]) == (1.0, 0.25, 0.0)
+    assert row[I["people_samples"]] == 0 and row[I["min_person_dist"]] == np.inf and row[I["social_work"]] == 0.0
+    assert row[I["time_to_goal"]] == -1.0 and row[I["min_clearance"]] == np.inf
+
+
+def test_heading_change_wraps_through_pi():
+    row = run([(0.0, 0.0, 3.1, 0.0), (0.0, 0.0, -3.1, 0.0)])
+    assert row[I["heading_change"]] == pytest.approx(2.0 * math.pi - 6.2, abs=1e-15)
+    assert R.wrap_to_pi(-math.pi) == math.pi and R.wrap_to_pi(math.pi) == math.pi   # (-pi, pi]
+
+
+def test_zone_comparisons_are_strict():
+    mp = MetricsParams(intimate_radius=0.5, personal_radius=1.25, social_radius=3.5, robot_radius=0.25, person_radius=0.25)
+    people = np.array([[1.5, 1.0, 0.0, 0.25, 0.0], [8.0, 8.0, 0.0, 0.0, 0.0]])   # the first one exactly 0.5 m away
+    row = R.update_row(np.zeros(R.NCOLS), mp, 0.05, (1.0, 1.0, 0.0), (0.5, 0.0), people, 2)
+    assert row[I["min_person_dist"]] == 0.5 == row[I["sum_min_person_dist"]]
+    assert row[I["intimate_samples"]] == 0          # 0.5 < 0.5 is false
+    assert row[I["person_collision_samples"]] == 0  # 0.5 < 0.25 + 0.25 is false
+    assert row[I["personal_samples"]] == 1 and row[I["social_samples"]] == 1 and row[I["people_samples"]] == 1
+    assert row[I["social_work"]] > 0.0
+    inside = R.update_row(np.zeros(R.NCOLS), mp, 0.05, (1.0078125, 1.0, 0.0), (0.5, 0.0), people, 2)
+    assert inside[I["intimate_samples"]] == 1 and inside[I["person_collision_samples"]] == 1
+
+
+def test_a_row_is_frozen_once_its_goal_was_reached():
+    goal = (1.0, 0.0)
+    mp = MetricsParams(goal_tolerance=0.25)
+    row = np.zeros(R.NCOLS)
+    for k, x in enumerate((0.0, 0.5, 0.75)):   # 0.75: exactly on the tolerance, which counts (<=)
+        row = R.update_row(row, mp, 0.05, (x, 0.0, 0.0), (0.5, 0.0), NOBODY, 0, goal=goal)
+        assert row[I["time_to_goal"]] == (-1.0 if k < 2 else 3 * 0.05)
+    assert row[I["goal_dist"]] == 0.25 and row[I["samples"]] == 3
+    later = R.update_row(row, mp, 0.05, (5.0, 5.0, 1.0), (0.5, 0.0), np.array([[5.0, 5.5, 0.0, 0.0, 0.0]]), 1, goal=goal,
+                         status=2, source=1)
+    assert later.tobytes() == row.tobytes()
+
+
+def test_a_zero_row_is_reinitialised():
+    junk = np.arange(R.NCOLS, dtype=np.float64)   # SAMPLES == 0 in front of stale values
+    row = R.update_row(junk, MetricsParams(), 0.05, (1.0, 2.0, 0.5), (0.25, 0.0), NOBODY, 0, status=2, source=3)
+    want = R.empty_row()
+    want[[I["samples"], I["sum_speed"], I["last_x"], I["last_y"], I["last_yaw"]]] = (1, 0.25, 1.0, 2.0, 0.5)
+    want[[I["fallback_samples"], I["unusable_solves"]]] = 1
+    assert np.array_equal(row, want)
+
+
+def test_clearance_cell_and_the_grid_edge():
+    grid = np.arange(12, dtype=np.float32).reshape(3, 4) * 0.25   # [h = 3][w = 4]
+    kw = dict(dist_grid=grid, origin=(-1.0, 0.0), resolution=0.5)
+    row = run([(0.25, 1.25, 0.0, 0.0)], MetricsParams(robot_radius=2.75), **kw)   # cell (2, 2): 10 * 0.25 = 2.5
+    assert row[I["min_clearance"]] == 2.5 and row[I["obstacle_collision_samples"]] == 1 and row[I["off_grid_samples"]] == 0
+    row = run([(0.25, 1.25, 0.0, 0.0)], MetricsParams(robot_radius=2.5), **kw)    # strict
+    assert row[I["obstacle_collision_samples"]] == 0
+    for x, y in ((1.0, 0.25), (-1.25, 0.25), (0.0, 1.5), (0.0, -0.125)):           # x = 1.0 is the first cell beyond
+        row = run([(x, y, 0.0, 0.0)], **kw)
+        assert row[I["off_grid_samples"]] == 1 and row[I["min_clearance"]] == np.inf, (x, y)
+
+
+def test_checker_force_equals_the_oracles():
+    torch = pytest.importorskip("torch")
+    from oracle import pyref
+
+    g = np.random.default_rng(20240611)
+    worst = 0.0
+    for _ in range(50):
+        a, b = g.uniform(-3, 3, 2), g.uniform(-3, 3, 2)
+        va, vb = g.uniform(-1, 1, 2), g.uniform(-1, 1, 2)
+        want = pyref._social_force(torch.tensor(a), torch.tensor(va), torch.tensor(b), torch.tensor(vb)).numpy()
+        got, theta = R.social_force(a, va, b, vb)
+        worst = max(worst, float(np.abs(got - want).max()))
+        back, theta_b = R.social_force(b, vb, a, va)   # the force on the other one from `me` alone: the exact negative
+        assert np.abs(back + got).max() <= 1e-15 and abs(theta - theta_b) <= 1e-12
+    assert worst <= 1e-12, worst
+
+
+def test_equal_velocities_take_theta_zero_and_a_coincident_pair_the_clamp():
+    f, theta = R.social_force((1.0, 1.0), (0.25, 0.5), (2.0, 1.5), (0.25, 0.5))
+    assert theta == 0.0 and np.isfinite(f).all()
+    f1, _ = R.social_force((1.0, 1.0), (0.25, 0.0), (1.0, 1.0), (0.0, 0.0))
+    f2, _ = R.social_force((1.0 + 1e-6, 1.0), (0.25, 0.0), (1.0, 1.0), (0.0, 0.0))
+    assert np.isfinite(f1).all() and np.abs(f1 - f2).max() <= 1e-9
+
+
+def _header():
+    return open(HEADER).read()
+
+
+def test_symbol_is_declared_listed_and_exported():
+    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    assert re.search(r"\bint\s+smpc_episode_metrics_batch\s*\(", src)
+    assert "smpc_episode_metrics_batch" in _abi.EXPORTED_SYMBOLS
+    assert os.path.exists(S.LIB_PATH), "run __graft_entry__.build() first"
+    out = subprocess.check_output(["nm", "-D", "--defined-only", S.LIB_PATH], text=True)
+    assert "smpc_episode_metrics_batch" in {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert hasattr(S.load_library(), "smpc_episode_metrics_batch")
+
+
+def test_metrics_struct_layout_matches_the_c_header(tmp_path):
+    late = ("od_resolution", "od_origin", "source")
+    body = 'printf("%zu\\n", sizeof(smpc_metrics_batch));\n' + "".join(
+        f'printf("%zu\\n", offsetof(smpc_metrics_batch, {f}));\n' for f in late)
+    body += 'printf("%d %d %d %d\\n", SMPC_METRIC_COLS, (int)SMPC_M_SOCIAL_WORK, (int)SMPC_M_TIME_TO_GOAL, (int)SMPC_M_LAST_YAW);\n'
+    prog = tmp_path / "layout_metrics.c"
+    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "smpc.h"\nint main(void){\n' + body + 'return 0;}\n')
+    exe = tmp_path / "layout_metrics"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
+    lines = subprocess.check_output([str(exe)], text=True).splitlines()
+    assert int(lines[0]) == C.sizeof(_abi.SmpcMetricsBatch)
+    for f, line in zip(late, lines[1:4]):
+        assert int(line) == getattr(_abi.SmpcMetricsBatch, f).offset, f
+    assert [int(v) for v in lines[4].split()] == [24, S.METRIC_COLS.index("social_work"), S.METRIC_COLS.index("time_to_goal"),
+                                                 S.METRIC_COLS.index("last_yaw")]
+
+
+def test_column_count_and_names():
+    assert int(re.search(r"#define SMPC_METRIC_COLS (\d+)", _header()).group(1)) == 24
+    assert _abi.SMPC_METRIC_COLS == 24 == len(S.METRIC_COLS) == R.NCOLS
+    assert S.METRIC_COLS == R.COLS
+    enum = re.search(r"enum smpc_metric_col \{(.*?)\};", _header(), flags=re.S).group(1)
+    names = re.findall(r"SMPC_M_([A-Z_]+)", re.sub(r"/\*.*?\*/", "", enum, flags=re.S))
+    assert [n.lower() for n in names] == S.METRIC_COLS[:22]
+
+
+def test_abi_version_is_still_6():
+    assert int(re.search(r"#define SMPC_ABI_VERSION (\d+)", _header()).group(1)) == 6 == _abi.SMPC_ABI_VERSION
+    assert S.load_library().smpc_abi_version() == 6
+
+
+def test_summarize_metrics():
+    mp = MetricsParams(goal_tolerance=0.25)
+    people = np.array([[0.5, 1.0, 0.0, 0.0, 0.0]])
+    acc = np.zeros((3, R.NCOLS))   # robot 0 drives 1 m to its goal past a person; robot 1 stands alone; robot 2: no samples
+    for x in (0.0, 0.5, 1.0):
+        acc[0] = R.update_row(acc[0], mp, 0.1, (x, 0.0, 0.0), (0.5, 0.0), people, 1, goal=(1.0, 0.0), status=0, source=0)
+        acc[1] = R.update_row(acc[1], mp, 0.1, (4.0, 4.0, 0.0), (0.0, 0.0), people, 0, goal=(9.0, 9.0), status=2, source=1)
+    s = S.summarize_metrics(acc, 0.1)
+    assert s["success"].tolist() == [True, False, False]
+    assert s["time_to_goal"][0] == pytest.approx(0.3) and np.isnan(s["time_to_goal"][1:]).all()
+    assert s["mean_speed"][0] == 0.5 and s["mean_speed"][1] == 0.0 and np.isnan(s["mean_speed"][2])
+    assert s["path_length"][0] == 1.0 and s["duration"].tolist() == pytest.approx([0.3, 0.3, 0.0])
+    assert s["mean_min_person_dist"][0] == pytest.approx((2 * math.hypot(0.5, 1.0) + 1.0) / 3) and np.isnan(s["mean_min_person_dist"][1])
+    assert s["social_work_per_metre"][0] == acc[0, I["social_work"]] / 1.0 and np.isnan(s["social_work_per_metre"][1])
+    assert s["intimate_share"][0] == 0.0 and s["personal_share"][0] == 1.0 and s["social_share"][0] == 1.0
+    assert s["personal_share"][1] == 0.0 and np.isnan(s["personal_share"][2])
+    assert not s["person_collision"].any() and not s["obstacle_collision"].any()
+    assert s["fallback_share"][:2].tolist() == [0.0, 1.0] and s["unusable_share"][:2].tolist() == [0.0, 1.0]

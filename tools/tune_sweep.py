@@ -1,0 +1,72 @@
+"""Worked example: compare a handful of controller tunings in closed loop, in ONE episode. Every parameter set drives the
+same --scenes scenes (same start poses, crowds, costmaps and global plans), as rows set * scenes .. (set + 1) * scenes - 1
+of a batch whose solve takes each robot's own critic weights and velocity bounds (params.scene_param_rows ->
+BatchEpisode(scene_params=...)); the device scores every robot as it drives (BatchEpisode(metrics=...)), and one line of
+summarize_metrics means is printed per set. Nothing but the final [B,24] metrics rows leaves the device.
+
+    python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120]
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def parameter_sets(base):
+    """name -> OptimizerParams. The sets may differ only in the values a scene can have of its own (the nine critic weights,
+    desired_linear_vel and the velocity bounds: params.SCENE_ROW_FIELDS); scene_param_rows refuses anything else."""
+    P = type(base)
+    return {
+        "readme": base,
+        "soc_work_obst_benchmark": P.soc_work_obst_benchmark(),
+        "obst_only_benchmark": P.obst_only_benchmark(),
+        "social_x4": base.replace(social_weight=4.0 * base.social_weight),
+        "slow_0.4": base.replace(desired_linear_vel=0.4, v_max=0.4),
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", type=int, default=256)
+    ap.add_argument("--agents", type=int, default=8)
+    ap.add_argument("--ticks", type=int, default=200)
+    ap.add_argument("--plan-poses", type=int, default=120, help="plan length in poses of 0.05 m (120: a 6 m drive)")
+    a = ap.parse_args()
+
+    import numpy as np
+
+    from nav2_social_mpc_controller_amd.episode import BatchEpisode, arc_plans
+    from nav2_social_mpc_controller_amd.params import MetricsParams, OptimizerParams, TrajectorizerParams, scene_param_rows
+    from nav2_social_mpc_controller_amd.scenes import make_scenes, uniform
+    from nav2_social_mpc_controller_amd.solver import summarize_metrics
+
+    prm = OptimizerParams.readme()
+    sets = parameter_sets(prm)
+    S, n = len(sets), a.scenes
+    one = make_scenes(prm, n, a.agents, map_cells=400)                      # 20 m maps: the drive stays inside
+    sc = one.select(np.tile(np.arange(n), S))                               # every set sees the same scenes
+    w_ref = np.tile((uniform(0x5EED0001, np.arange(n), 6)[:, 0] * 2.0 - 1.0) * 0.6, S)
+    plan, plan_len = arc_plans(sc.pose0, 0.1 * w_ref, L=a.plan_poses)
+    rows = scene_param_rows(list(sets.values()), np.repeat(np.arange(S), n))
+    tp = TrajectorizerParams(desired_linear_vel=prm.desired_linear_vel, max_time=prm.max_time, time_step=prm.time_step)
+    ep = BatchEpisode(prm, sc, w_ref, plan=plan, plan_len=plan_len, traj_params=tp, fov_angle=np.pi / 4,
+                      obstacles_from_costmap=True, scene_params=rows, metrics=MetricsParams())
+    ep.capture_graph()
+    for _ in range(a.ticks):
+        ep.replay()
+    m = summarize_metrics(ep.metrics(), prm.dt)
+    print(f"{S} parameter sets x {n} scenes, {a.agents} agents, {a.ticks} ticks of {prm.dt} s")
+    for k, name in enumerate(sets):
+        sl = slice(k * n, (k + 1) * n)
+        mean = lambda key: float(np.nanmean(m[key][sl])) if np.isfinite(m[key][sl]).any() else float("nan")
+        print(f"{name:24s} success {m['success'][sl].mean():.3f}  time_to_goal {mean('time_to_goal'):6.2f} s  "
+              f"mean_speed {mean('mean_speed'):.3f}  mean_min_person_dist {mean('mean_min_person_dist'):.3f}  "
+              f"intimate {mean('intimate_share'):.3f}  personal {mean('personal_share'):.3f}  "
+              f"social_work/m {mean('social_work_per_metre'):8.3f}  person_coll {m['person_collision'][sl].mean():.3f}  "
+              f"obstacle_coll {m['obstacle_collision'][sl].mean():.3f}  fallback {mean('fallback_share'):.3f}")
+
+
+if __name__ == "__main__":
+    main()
