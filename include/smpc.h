@@ -586,6 +586,58 @@ typedef struct smpc_metrics_batch {
  * Np > SMPC_MAX_AGENTS. */
 int smpc_episode_metrics_batch(smpc_handle* h, const smpc_metrics_batch* in, double* acc);
 
+/* ---- Reactive crowd of a closed-loop episode (csrc/smpc_crowd.hpp) --------------------------------------------------
+ * One call advances every robot's persons by one control period under the Social Force Model of
+ * include/nav2_social_mpc_controller/sfm.hpp (computeForces :462-485, updatePosition :525-572; group forces are out).
+ * The persons see the robot; the robot is not moved by this call. */
+#define SMPC_MAX_WAYPOINTS 8
+typedef struct smpc_crowd_batch {
+  int32_t B, Np, K, on_device;      /* Np: row stride of people (1..SMPC_MAX_AGENTS); K: waypoint slots per person (1..SMPC_MAX_WAYPOINTS) */
+  int32_t cyclic, robot_visible;    /* cyclic: sfm.hpp cyclicGoals for every person; robot_visible: the robot is a partner in every person's social force */
+  double dt;                        /* > 0 */
+  double goal_radius;               /* e.g. 0.25 */
+  double person_radius;             /* sfm.hpp Agent default 0.35; only the obstacle force reads it */
+  double desired_speed;             /* used where desired_speeds is NULL; sfm.hpp default 0.6 */
+  const double*  robot_pose;        /* [B][3] pose at the START of the period */
+  const double*  robot_twist;       /* [B][2] v, w being executed: robot velocity = v (cos yaw, sin yaw) */
+  const int32_t* count;             /* [B] 0..Np (checked for host arrays, clamped for device arrays) */
+  const double*  waypoints;         /* [B][Np][K][2] */
+  const int32_t* n_waypoints;       /* [B][Np] 0..K (clamped on the device) */
+  const double*  desired_speeds;    /* [B][Np] or NULL */
+  const uint32_t* od_indexes;       /* [B or 1][od_height][od_width] or NULL: no obstacle force */
+  int32_t od_shared, od_width, od_height; float od_resolution;
+  const double*  od_origin;         /* [B or 1][2] */
+} smpc_crowd_batch;
+
+/* Contract, per person i < count[b]; rows >= count[b] of `people` and their cursors are not written, bit for bit.
+ * Goal: the person has a goal while 0 <= cursor < n_waypoints; the goal is waypoints[cursor].
+ * Desired force (sfm.hpp:188-203): with a goal farther than goal_radius, 2.0 * (unit(goal - p) * des - v) / 0.5; otherwise
+ *   -v / 0.5. des is desired_speeds[b][i], or desired_speed when that array is NULL.
+ * Social force (sfm.hpp:237-281): the sum over every other person j < count[b], plus the robot when robot_visible, each term
+ *   with the reference's default constants (2.1, lambda 2, gamma 0.35, n 2, n' 3) and the library's two conventions: a pair
+ *   closer than 1e-6 m takes diff = (1e-6, 0) (each of the two persons does), exactly equal velocities take theta = 0 (so
+ *   thetaSign = 0). The order of the sum is a function of count[b] and robot_visible alone.
+ * Obstacle force (sfm.hpp:205-222), only with a grid: the nearest-obstacle entry of the person's cell
+ *   (floor((p - origin) / (double)od_resolution)) is turned into a position with computeObstacle's own float arithmetic
+ *   (src/optimizer.cpp:673-728); m = p - obstacle, force 20 * exp(-(|m| - person_radius) / 0.2) * unit(m). This is the model
+ *   as sfm.hpp means it, not project_people's difference-stored-as-position. A person off the grid, or on an entry
+ *   >= od_width * od_height, gets no obstacle force; it is not an error.
+ * Update (sfm.hpp:525-572), in this order: v += f dt; the speed is clamped to des; vz = wrap(atan2(v') - atan2(v_old)) / dt
+ *   with atan2(0, 0) = 0 and the wrap into (-pi, pi]; p += v' dt; if the person had a goal and is now within goal_radius of
+ *   it, cursor += 1; if cyclic and cursor >= n_waypoints, cursor = 0 (a non-cyclic cursor stops at n_waypoints).
+ * All persons of a robot are updated from the state at entry (a synchronous step). A robot's persons depend on that
+ * robot's inputs alone: not on B, the robot's place in the batch, the memory space, the stream or timing. A wave
+ * terminates whatever the input: non-finite values come back as non-finite values. For device pointers the call is one
+ * kernel on the handle's stream, no allocation and no host synchronisation (capturable in a HIP graph). Host pointers are
+ * staged like everywhere.
+ * SMPC_ERR_INVALID_ARG (nothing launched, people and cursor untouched): a NULL handle, input, people, cursor, robot_pose,
+ * robot_twist, count, waypoints or n_waypoints; B < 1, Np < 1, K < 1 or dt <= 0; a negative radius or a non-positive
+ * desired_speed; a grid without an origin or with a non-positive size or resolution; a host count outside 0..Np.
+ * SMPC_ERR_UNSUPPORTED: Np > SMPC_MAX_AGENTS or K > SMPC_MAX_WAYPOINTS. */
+int smpc_crowd_step_batch(smpc_handle* h, const smpc_crowd_batch* in,
+                          double* people  /* [B][Np][5] in/out: px, py, vx, vy, vz (smpc_people_batch.people rows) */,
+                          int32_t* cursor /* [B][Np] in/out: index of each person's current waypoint */);
+
 /* Diagnostic: evaluates the elementary functions the sweep uses (csrc/smpc_math.hpp: table-driven exp / atan2 /
  * sincos, refined reciprocal / rsqrt, and the raw hardware estimates behind them) on n host-side arguments, so that
  * tests can check them on the device against libm. fn: 0 exp(a) | 1 atan2(a, b) | 2 sin(a) -> out0, cos(a) -> out1 |

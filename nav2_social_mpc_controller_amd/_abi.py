@@ -290,6 +290,36 @@ class SmpcMetricsBatch(C.Structure):
     ]
 
 
+SMPC_MAX_WAYPOINTS = 8
+
+
+class SmpcCrowdBatch(C.Structure):
+    _fields_ = [
+        ("B", C.c_int32),
+        ("Np", C.c_int32),
+        ("K", C.c_int32),
+        ("on_device", C.c_int32),
+        ("cyclic", C.c_int32),
+        ("robot_visible", C.c_int32),
+        ("dt", C.c_double),
+        ("goal_radius", C.c_double),
+        ("person_radius", C.c_double),
+        ("desired_speed", C.c_double),
+        ("robot_pose", C.c_void_p),
+        ("robot_twist", C.c_void_p),
+        ("count", C.c_void_p),
+        ("waypoints", C.c_void_p),
+        ("n_waypoints", C.c_void_p),
+        ("desired_speeds", C.c_void_p),
+        ("od_indexes", C.c_void_p),
+        ("od_shared", C.c_int32),
+        ("od_width", C.c_int32),
+        ("od_height", C.c_int32),
+        ("od_resolution", C.c_float),
+        ("od_origin", C.c_void_p),
+    ]
+
+
 class SmpcEvalOut(C.Structure):
     _fields_ = [
         ("residuals", C.c_void_p),
@@ -321,6 +351,7 @@ EXPORTED_SYMBOLS = [
     "smpc_transform_global_plan_batch",
     "smpc_select_command_batch",
     "smpc_episode_metrics_batch",
+    "smpc_crowd_step_batch",
     "smpc_math_probe",
     "smpc_fp64_peak_probe",
     "smpc_stage_people_batch",

@@ -32,6 +32,7 @@
 #include "smpc_trajectorize.hpp"
 #include "smpc_path_window.hpp"
 #include "smpc_metrics.hpp"
+#include "smpc_crowd.hpp"
 
 // ================================================================================================
 // Host side of the C ABI
@@ -1042,6 +1043,52 @@ int smpc_episode_metrics_batch(smpc_handle* h, const smpc_metrics_batch* in, dou
   const size_t per_block = smpc::kMetricsThreads / G;
   SMPC_TRY(st.timed([&] {
     hipLaunchKernelGGL(smpc::smpc_episode_metrics_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kMetricsThreads), 0,
+                       h->stream, p);
+    return SMPC_OK;
+  }));
+  return st.finish();
+}
+
+int smpc_crowd_step_batch(smpc_handle* h, const smpc_crowd_batch* in, double* people, int32_t* cursor) {
+  if (!h || !in || !people || !cursor) { set_error("null handle / input / people / cursor"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B < 1 || in->Np < 1 || in->K < 1 || !(in->dt > 0.0)) { set_error("bad B / Np / K / dt"); return SMPC_ERR_INVALID_ARG; }
+  if (!(in->goal_radius >= 0.0) || !(in->person_radius >= 0.0) || !(in->desired_speed > 0.0)) {
+    set_error("negative radius or non-positive desired_speed"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (!in->robot_pose || !in->robot_twist || !in->count || !in->waypoints || !in->n_waypoints) { set_error("null input array"); return SMPC_ERR_INVALID_ARG; }
+  if (in->od_indexes && (!in->od_origin || in->od_width < 1 || in->od_height < 1 || !(in->od_resolution > 0.0f))) {
+    set_error("obstacle grid without origin or with a non-positive size or resolution"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (in->Np > SMPC_MAX_AGENTS) { set_error("Np > 64 persons is not supported"); return SMPC_ERR_UNSUPPORTED; }
+  if (in->K > SMPC_MAX_WAYPOINTS) { set_error("K > 8 waypoints is not supported"); return SMPC_ERR_UNSUPPORTED; }
+  if (!in->on_device)
+    for (int32_t b = 0; b < in->B; ++b)
+      if (in->count[b] < 0 || in->count[b] > in->Np) { set_error("count outside 0..Np"); return SMPC_ERR_INVALID_ARG; }
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::CrowdParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.B = in->B; p.Np = in->Np; p.K = in->K;
+  while ((1 << p.lgG) < in->Np) ++p.lgG;
+  p.cyclic = in->cyclic ? 1 : 0; p.robot_visible = in->robot_visible ? 1 : 0;
+  p.dt = in->dt; p.goal_radius = in->goal_radius; p.person_radius = in->person_radius; p.desired_speed = in->desired_speed;
+  smpc::fill_math_table(&p.mt);
+  const bool grid = in->od_indexes != nullptr;
+  p.od_shared = in->od_shared ? 1 : 0; p.od_width = in->od_width; p.od_height = in->od_height; p.od_resolution = in->od_resolution;
+  const size_t B = in->B, Np = in->Np, K = in->K, ngrid = in->od_shared ? 1 : B;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.pose, in->robot_pose, B * 3));
+  SMPC_TRY(st.in(p.twist, in->robot_twist, B * 2));
+  SMPC_TRY(st.in(p.count, in->count, B));
+  SMPC_TRY(st.in(p.waypoints, in->waypoints, B * Np * K * 2));
+  SMPC_TRY(st.in(p.n_waypoints, in->n_waypoints, B * Np));
+  SMPC_TRY(st.in(p.desired_speeds, in->desired_speeds, B * Np));
+  SMPC_TRY(st.in(p.od_indexes, in->od_indexes, grid ? ngrid * (size_t)in->od_width * in->od_height : 0));
+  SMPC_TRY(st.in(p.od_origin, grid ? in->od_origin : nullptr, ngrid * 2));
+  SMPC_TRY(st.inout(p.people, people, B * Np * 5));
+  SMPC_TRY(st.inout(p.cursor, cursor, B * Np));
+  const size_t per_block = smpc::kCrowdThreads >> p.lgG;
+  SMPC_TRY(st.timed([&] {
+    hipLaunchKernelGGL(smpc::smpc_crowd_step_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kCrowdThreads), 0,
                        h->stream, p);
     return SMPC_OK;
   }));

@@ -17,7 +17,12 @@ stood in for by the simplest thing that has the same shape:
   * the world: the robot executes the command computeVelocityCommands returns for one period — the first optimised
     command (it lands on the first pose of the optimised path), the trajectorizer's first command when the solve was
     not usable (src/social_mpc_controller.cpp:241-245), 0.1 m/s straight ahead when there is no trajectory (:180-189);
-    people move with constant velocity.
+    people move with constant velocity, walking through the robot, the walls and off the map, or, with
+    BatchEpisode(crowd=CrowdParams(...)), as a reactive crowd: every period smpc_crowd_step_batch moves every robot's
+    persons one step of the Social Force Model the controller itself predicts them with (sfm.hpp computeForces /
+    updatePosition): each person heads for its current waypoint (scenes.crowd_waypoints), gives way to the other persons
+    and to the robot as it was at the start of the period, is pushed back by the nearest obstacle of its cell of the
+    ObstacleDistance grid, and takes the next waypoint on arrival. The robot is seen but not pushed.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -26,7 +31,7 @@ import numpy as np
 
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
-from .params import MetricsParams, OptimizerParams, TrajectorizerParams, check_scene_param_rows
+from .params import CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams, check_scene_param_rows
 from .scenes import SceneBatch
 from .solver import BatchSolver
 
@@ -63,6 +68,9 @@ class TickRecord:
     persons_after: np.ndarray = None  # [B,Np,5]
     cmd_vel: np.ndarray = None        # [B,2] the executed command
     cmd_source: np.ndarray = None     # [B]
+    # the persons' waypoint cursors around the tick's crowd step (BatchEpisode(crowd=...))
+    cursor_before: np.ndarray = None  # [B,Np]
+    cursor_after: np.ndarray = None   # [B,Np]
 
 
 class BatchEpisode:
@@ -71,7 +79,9 @@ class BatchEpisode:
                  plan_len: np.ndarray = None, traj_params: TrajectorizerParams = None, fov_angle: float = None,
                  order_hint: bool = False, plan_window: tuple = None, obstacles_from_costmap: bool = False,
                  obstacle_min_cost: int = 254, unknown_is_obstacle: bool = False, scene_params: np.ndarray = None,
-                 metrics: MetricsParams = None, goal: np.ndarray = None, od_distances: np.ndarray = None):
+                 metrics: MetricsParams = None, goal: np.ndarray = None, od_distances: np.ndarray = None,
+                 crowd: CrowdParams = None, person_waypoints: np.ndarray = None, person_n_waypoints: np.ndarray = None,
+                 person_speed: np.ndarray = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -97,7 +107,13 @@ class BatchEpisode:
         otherwise none, and the goal columns stay unset); a robot's row is frozen once it is within metrics.goal_tolerance
         of it. The clearance columns need the distances of the ObstacleDistance grid: with obstacles_from_costmap they are
         computed along with the indexes, with host-given od_indexes they are fed only when od_distances (float32, shaped
-        like od_indexes) is passed too. None: nothing is allocated and nothing is launched."""
+        like od_indexes) is passed too. None: nothing is allocated and nothing is launched.
+        crowd: the persons move as a reactive crowd (smpc_crowd_step_batch, one launch per tick, in place of the
+        constant-velocity move): person_waypoints [B,Np,K,2] and person_n_waypoints [B,Np] (e.g. scenes.crowd_waypoints) are
+        each person's goals, self.person_cursor [B,Np] the index of its current one (0 at the start); person_speed [B,Np]:
+        desired speeds (default crowd.desired_speed for everybody). The step sees the pose the period started from and the
+        command being executed, and the episode's ObstacleDistance grid. None: nothing is allocated and the persons move
+        with constant velocity."""
         import torch
 
         self.torch = torch
@@ -219,6 +235,21 @@ class BatchEpisode:
             if goal is not None:
                 assert np.shape(goal) == (B, 2), "goal [B,2]"
                 self.goal = torch.from_numpy(np.ascontiguousarray(goal, np.float64)).to(self.dev)
+        self.crowd_params = crowd
+        if crowd is not None:
+            Np = int(self.persons.shape[1])
+            if person_waypoints is None or person_n_waypoints is None:
+                raise ValueError("crowd needs person_waypoints [B,Np,K,2] and person_n_waypoints [B,Np]")
+            wp = np.ascontiguousarray(person_waypoints, np.float64)
+            assert wp.ndim == 4 and wp.shape[:2] == (B, Np) and wp.shape[3] == 2, "person_waypoints [B,Np,K,2]"
+            assert np.shape(person_n_waypoints) == (B, Np), "person_n_waypoints [B,Np]"
+            self.person_wp = torch.from_numpy(wp).to(self.dev)
+            self.person_nwp = torch.from_numpy(np.ascontiguousarray(person_n_waypoints, np.int32)).to(self.dev)
+            self.person_cursor = torch.zeros((B, Np), dtype=torch.int32, device=self.dev)
+            self.person_speed = None
+            if person_speed is not None:
+                assert np.shape(person_speed) == (B, Np), "person_speed [B,Np]"
+                self.person_speed = torch.from_numpy(np.ascontiguousarray(person_speed, np.float64)).to(self.dev)
         self.graph = None
         self.gstream = None
         # queue order for the next solve (from the last solve's sweep counts; index order before the first one)
@@ -287,6 +318,8 @@ class BatchEpisode:
                                plan_start=self.plan_start.cpu().numpy().copy())
             rec.update(robot_pose=pose_before, persons=self.persons.cpu().numpy().copy(),
                        person_count=self.person_count.cpu().numpy().copy())
+            if self.crowd_params is not None:
+                rec.update(cursor_before=self.person_cursor.cpu().numpy().copy())
         # 0. field-of-view filter + people_to_status
         qb = SmpcPeopleBatch()
         qb.B, qb.Np, qb.N, qb.on_device = B, int(self.persons.shape[1]), N, 1
@@ -372,14 +405,19 @@ class BatchEpisode:
                                 self.cmd_vel.data_ptr(), self.cmd_source.data_ptr(),
                                 self.window_err.data_ptr() if self.plan_window is not None else 0)
         dt = prm.dt
+        if self.crowd_params is not None:  # the persons' period: they see the pose it starts from and the command executed
+            self._crowd_step()
+            if timing is not None:
+                timing["crowd_ms"] = s.last_kernel_ms()
         v, w, th = self.cmd_vel[:, 0], self.cmd_vel[:, 1], self.pose[:, 2]
         moved = torch.stack([self.pose[:, 0] + v * torch.cos(th) * dt, self.pose[:, 1] + v * torch.sin(th) * dt, th + w * dt], dim=1)
         optimised = (self.cmd_source == 0)[:, None]
         # state is updated in place: every buffer the kernels read keeps its address from tick to tick (capture_graph)
         self.pose.copy_(torch.where(optimised, self.res["path"][:, 0, :], moved))
         self.speed.copy_(self.cmd_vel)
-        self.persons[:, :, 0] += self.persons[:, :, 2] * dt
-        self.persons[:, :, 1] += self.persons[:, :, 3] * dt
+        if self.crowd_params is None:
+            self.persons[:, :, 0] += self.persons[:, :, 2] * dt
+            self.persons[:, :, 1] += self.persons[:, :, 3] * dt
         if self.metrics_params is not None:  # 6. one metrics sample of the world as the period leaves it
             self._metrics_sample()
             if timing is not None:
@@ -387,8 +425,21 @@ class BatchEpisode:
         if record:
             rec.update(pose_after=self.pose.cpu().numpy().copy(), persons_after=self.persons.cpu().numpy().copy(),
                        cmd_vel=self.cmd_vel.cpu().numpy().copy(), cmd_source=self.cmd_source.cpu().numpy().copy())
+            if self.crowd_params is not None:
+                rec.update(cursor_after=self.person_cursor.cpu().numpy().copy())
         self.ticks += 1
         return TickRecord(**rec) if record else None
+
+    def _crowd_step(self):
+        Np = int(self.persons.shape[1])
+        cb = BatchSolver.crowd_c(self.crowd_params, self.B, Np, int(self.person_wp.shape[2]), self.params.dt, 1)
+        cb.robot_pose, cb.robot_twist, cb.count = self.pose.data_ptr(), self.cmd_vel.data_ptr(), self.person_count.data_ptr()
+        cb.waypoints, cb.n_waypoints = self.person_wp.data_ptr(), self.person_nwp.data_ptr()
+        if self.person_speed is not None:
+            cb.desired_speeds = self.person_speed.data_ptr()
+        cb.od_indexes, cb.od_origin = self.od_indexes.data_ptr(), self.od_origin.data_ptr()
+        cb.od_shared, cb.od_width, cb.od_height, cb.od_resolution = self.od_shared, self.od_w, self.od_h, self.od_resolution
+        self.solver.crowd_step_device(cb, self.persons.data_ptr(), self.person_cursor.data_ptr())
 
     def _metrics_sample(self):
         mb = BatchSolver.metrics_c(self.metrics_params, self.B, int(self.persons.shape[1]), self.params.dt, 1)
@@ -422,6 +473,8 @@ class BatchEpisode:
         state = ("pose", "speed", "persons", "mem_path", "mem_cmds", "mem_valid", "mem_length", "order") + (("plan_start",) if self.plan_window is not None else ())
         if self.metrics_params is not None:
             state += ("metrics_acc",)  # the warm-up tick's sample does not count
+        if self.crowd_params is not None:
+            state += ("person_cursor",)
         with torch.cuda.stream(self.gstream):
             saved = {k: getattr(self, k).clone() for k in state}
             ticks = self.ticks
@@ -506,7 +559,8 @@ class ShardedEpisode:
                  shards: int = 3, order_hint: bool = False, graphs: bool = True, solve_share: int = None,
                  plan_window: tuple = None, obstacles_from_costmap: bool = False, obstacle_min_cost: int = 254,
                  unknown_is_obstacle: bool = False, scene_params: np.ndarray = None, metrics: MetricsParams = None,
-                 goal: np.ndarray = None, od_distances: np.ndarray = None):
+                 goal: np.ndarray = None, od_distances: np.ndarray = None, crowd: CrowdParams = None,
+                 person_waypoints: np.ndarray = None, person_n_waypoints: np.ndarray = None, person_speed: np.ndarray = None):
         import torch
 
         self.torch = torch
@@ -530,7 +584,10 @@ class ShardedEpisode:
                     obstacles_from_costmap=obstacles_from_costmap, obstacle_min_cost=obstacle_min_cost,
                     unknown_is_obstacle=unknown_is_obstacle,
                     scene_params=None if scene_params is None else np.asarray(scene_params)[idx],
-                    metrics=metrics, goal=None if goal is None else np.asarray(goal)[idx], od_distances=odd))
+                    metrics=metrics, goal=None if goal is None else np.asarray(goal)[idx], od_distances=odd, crowd=crowd,
+                    person_waypoints=None if person_waypoints is None else np.asarray(person_waypoints)[idx],
+                    person_n_waypoints=None if person_n_waypoints is None else np.asarray(person_n_waypoints)[idx],
+                    person_speed=None if person_speed is None else np.asarray(person_speed)[idx]))
         self.B = B
         self.graphs = graphs
         for part in self.parts:  # every shard's persistent solve grid takes its share of the resident wavefronts
@@ -552,7 +609,7 @@ class ShardedEpisode:
 
     def gather(self, name: str):
         """Concatenated per-robot tensor: a key of BatchEpisode.res ("status", "cmds", ...) or an attribute ("pose",
-        "cmd_vel", "cmd_source", "proj_error", "metrics_acc")."""
+        "cmd_vel", "cmd_source", "proj_error", "metrics_acc", "persons", "person_cursor")."""
         self.synchronize()
         return self.torch.cat([p.res[name] if name in p.res else getattr(p, name) for p in self.parts], dim=0)
 

@@ -52,6 +52,26 @@ class MetricsParams:
 
 
 @dataclass
+class CrowdParams:
+    """The reactive crowd of a closed-loop episode (smpc_crowd_batch, include/smpc.h): the Social Force Model step that
+    moves every robot's persons each control period. goal_radius: a waypoint counts as reached within it; person_radius:
+    a person's body in the obstacle force (sfm.hpp Agent default); desired_speed: of every person without a speed of its
+    own; cyclic: a person that reached its last waypoint heads for the first one again (sfm.hpp cyclicGoals), otherwise it
+    comes to rest there; robot_visible: the persons give way to the robot as they do to each other."""
+    goal_radius: float = 0.25
+    person_radius: float = 0.35
+    desired_speed: float = 0.6
+    cyclic: bool = True
+    robot_visible: bool = True
+
+    def __post_init__(self):
+        if not self.goal_radius >= 0.0 or not self.person_radius >= 0.0:
+            raise ValueError(f"CrowdParams radii must be >= 0, got {self.goal_radius}, {self.person_radius}")
+        if not self.desired_speed > 0.0:
+            raise ValueError(f"CrowdParams.desired_speed must be > 0, got {self.desired_speed}")
+
+
+@dataclass
 class OptimizerParams:
     # optimizer.* (src/optimizer.cpp:26-55, 76-83)
     linear_solver_type: str = "SPARSE_NORMAL_CHOLESKY"

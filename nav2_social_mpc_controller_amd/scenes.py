@@ -285,3 +285,60 @@ def make_scenes(params: OptimizerParams, B: int, N: int, seed: int = 0x5EED0001,
                     resolution, False)
     sb.validate(P)
     return sb
+
+
+def crowd_waypoints(scenes: SceneBatch, K: int = 2, seed: int = 0x5EED0002, first_scene: int = 0, margin: float = 0.5,
+                    tries: int = 16):
+    """Waypoint lists for the persons of `scenes` (BatchEpisode(crowd=..., person_waypoints=..., person_n_waypoints=...)):
+    (waypoints [B,N,K,2], n_waypoints [B,N]), a pure function of (seed, scene id, person, slot) through `uniform`.
+    Every waypoint lies inside the scene's costmap, at least `margin` from its border, on a free cell (cost 0). The first
+    one lies straight ahead of the person's initial velocity, 0.5 .. 6 m away, so an episode starts the way the
+    constant-velocity crowd does; the others are anywhere on the map. Each is the first of `tries` seeded candidates that
+    qualifies (the first one falls back to the candidates of the others, all of them to the free cell nearest the map's
+    centre). A person that stands at the start, or an invalid row, gets no waypoints: it stays where it is and only
+    gives way."""
+    B, N = scenes.B, scenes.N
+    ids = np.arange(first_scene, first_scene + B, dtype=np.int64)
+    res, sx, sy = scenes.resolution, scenes.size_x, scenes.size_y
+    cm = np.broadcast_to(scenes.costmap, (B, sy, sx)) if scenes.costmap_shared else scenes.costmap
+    origin = np.broadcast_to(scenes.costmap_origin, (B, 2)) if scenes.costmap_shared else scenes.costmap_origin
+    st0 = scenes.people[:, 0]                                             # [B,6,N]
+    rows = np.arange(B)[:, None, None]
+
+    def qualifies(x, y):                                                  # [B,N,tries] world points
+        inside = ((x >= origin[:, 0, None, None] + margin) & (x <= origin[:, 0, None, None] + sx * res - margin) &
+                  (y >= origin[:, 1, None, None] + margin) & (y <= origin[:, 1, None, None] + sy * res - margin))
+        cx = np.clip(np.floor((x - origin[:, 0, None, None]) / res).astype(np.int64), 0, sx - 1)
+        cy = np.clip(np.floor((y - origin[:, 1, None, None]) / res).astype(np.int64), 0, sy - 1)
+        return inside & (cm[rows, cy, cx] == 0)
+
+    def first_of(x, y, ok, fx, fy):                                       # the first qualifying candidate, else (fx, fy)
+        pick = np.argmax(ok, axis=2)[:, :, None]
+        any_ok = ok.any(axis=2)
+        return (np.where(any_ok, np.take_along_axis(x, pick, 2)[:, :, 0], fx),
+                np.where(any_ok, np.take_along_axis(y, pick, 2)[:, :, 0], fy))
+
+    # last resort: the free cell nearest the map's centre (its centre point)
+    jj, ii = np.meshgrid(np.arange(sy), np.arange(sx), indexing="ij")
+    d2 = (ii + 0.5 - 0.5 * sx) ** 2 + (jj + 0.5 - 0.5 * sy) ** 2
+    flat = np.argmin(np.where(cm == 0, d2[None], np.inf).reshape(B, -1), axis=1)
+    last_x = (origin[:, 0] + ((flat % sx) + 0.5) * res)[:, None]
+    last_y = (origin[:, 1] + ((flat // sx) + 0.5) * res)[:, None]
+
+    wp = np.zeros((B, N, K, 2))
+    anywhere = []
+    for k in range(K):
+        ux = uniform(seed, ids, 200 + 2 * k, N * tries).reshape(B, N, tries)
+        uy = uniform(seed, ids, 201 + 2 * k, N * tries).reshape(B, N, tries)
+        x = origin[:, 0, None, None] + margin + ux * (sx * res - 2.0 * margin)
+        y = origin[:, 1, None, None] + margin + uy * (sy * res - 2.0 * margin)
+        anywhere.append(first_of(x, y, qualifies(x, y), last_x, last_y))
+    dist = 0.5 + 5.5 * uniform(seed, ids, 199, N * tries).reshape(B, N, tries)
+    x = st0[:, 0, :, None] + dist * np.cos(st0[:, 2, :, None])
+    y = st0[:, 1, :, None] + dist * np.sin(st0[:, 2, :, None])
+    wp[:, :, 0, 0], wp[:, :, 0, 1] = first_of(x, y, qualifies(x, y), *anywhere[0])
+    for k in range(1, K):
+        wp[:, :, k, 0], wp[:, :, k, 1] = anywhere[k]
+    walking = (st0[:, 3, :] != -1.0) & (st0[:, 4, :] > 0.0)
+    n_wp = np.where(walking, K, 0).astype(np.int32)
+    return np.ascontiguousarray(wp), np.ascontiguousarray(n_wp)

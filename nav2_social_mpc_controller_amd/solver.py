@@ -12,10 +12,10 @@ import os
 import numpy as np
 
 from . import _abi
-from ._abi import (SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
+from ._abi import (SmpcCrowdBatch, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcParams, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
-from .params import MetricsParams, OptimizerParams, TrajectorizerParams
+from .params import CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams
 from .scenes import SceneBatch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -93,6 +93,8 @@ def load_library():
     lib.smpc_select_command_batch.restype = C.c_int
     lib.smpc_episode_metrics_batch.argtypes = [C.c_void_p, C.POINTER(SmpcMetricsBatch), C.c_void_p]
     lib.smpc_episode_metrics_batch.restype = C.c_int
+    lib.smpc_crowd_step_batch.argtypes = [C.c_void_p, C.POINTER(SmpcCrowdBatch), C.c_void_p, C.c_void_p]
+    lib.smpc_crowd_step_batch.restype = C.c_int
     lib.smpc_stage_people_batch.argtypes = [C.c_void_p, C.POINTER(SmpcSceneBatch), C.c_void_p, C.c_void_p]
     lib.smpc_stage_people_batch.restype = C.c_int
     lib.smpc_fp64_peak_probe.argtypes = [C.c_void_p, C.c_int32]
@@ -511,6 +513,60 @@ class BatchSolver:
         """Device pointers in mb (on_device == 1) and for acc; asynchronous on the handle's stream."""
         assert mb.on_device == 1
         _check(self.lib, self.lib.smpc_episode_metrics_batch(self._h, C.byref(mb), C.c_void_p(acc_ptr)), "smpc_episode_metrics_batch")
+
+    # -- the reactive crowd of a closed-loop episode (smpc_crowd_step_batch) -----------------------------------------
+    @staticmethod
+    def crowd_c(cp: CrowdParams, B: int, Np: int, K: int, dt: float, on_device: int) -> SmpcCrowdBatch:
+        cb = SmpcCrowdBatch()
+        cb.B, cb.Np, cb.K, cb.on_device, cb.dt = int(B), int(Np), int(K), int(on_device), float(dt)
+        cb.cyclic, cb.robot_visible = 1 if cp.cyclic else 0, 1 if cp.robot_visible else 0
+        cb.goal_radius, cb.person_radius, cb.desired_speed = cp.goal_radius, cp.person_radius, cp.desired_speed
+        return cb
+
+    def crowd_step(self, cp: CrowdParams, dt: float, people: np.ndarray, cursor: np.ndarray, robot_pose: np.ndarray,
+                   robot_twist: np.ndarray, count: np.ndarray, waypoints: np.ndarray, n_waypoints: np.ndarray,
+                   desired_speeds: np.ndarray = None, od_indexes: np.ndarray = None, od_origin: np.ndarray = None,
+                   od_resolution: float = None):
+        """One control period of the crowd (host arrays): people [B,Np,5], cursor [B,Np], robot_pose [B,3] at the start of
+        the period, robot_twist [B,2], count [B], waypoints [B,Np,K,2], n_waypoints [B,Np]; optional desired_speeds [B,Np],
+        od_indexes [h,w] (one shared grid, od_origin [2]) or [B,h,w] (od_origin [B,2]) uint32 with od_resolution.
+        Returns the updated copies (people, cursor)."""
+        people = np.array(people, dtype=np.float64, order="C")
+        cursor = np.array(cursor, dtype=np.int32, order="C")
+        robot_pose = np.ascontiguousarray(robot_pose, np.float64)
+        robot_twist = np.ascontiguousarray(robot_twist, np.float64)
+        count = np.ascontiguousarray(count, np.int32)
+        waypoints = np.ascontiguousarray(waypoints, np.float64)
+        n_waypoints = np.ascontiguousarray(n_waypoints, np.int32)
+        B, Np, _ = people.shape
+        K = waypoints.shape[2]
+        assert people.shape[2] == 5 and cursor.shape == (B, Np) and robot_pose.shape == (B, 3) and robot_twist.shape == (B, 2)
+        assert count.shape == (B,) and waypoints.shape == (B, Np, K, 2) and n_waypoints.shape == (B, Np)
+        cb = self.crowd_c(cp, B, Np, K, dt, 0)
+        cb.robot_pose, cb.robot_twist, cb.count = robot_pose.ctypes.data, robot_twist.ctypes.data, count.ctypes.data
+        cb.waypoints, cb.n_waypoints = waypoints.ctypes.data, n_waypoints.ctypes.data
+        if desired_speeds is not None:
+            desired_speeds = np.ascontiguousarray(desired_speeds, np.float64)
+            assert desired_speeds.shape == (B, Np)
+            cb.desired_speeds = desired_speeds.ctypes.data
+        if od_indexes is not None:
+            od_indexes = np.ascontiguousarray(od_indexes, np.uint32)
+            shared = od_indexes.ndim == 2
+            od_origin = np.ascontiguousarray(od_origin, np.float64).reshape(-1, 2)
+            assert od_indexes.ndim == 2 or od_indexes.shape[0] == B
+            assert od_origin.shape == ((1, 2) if shared else (B, 2))
+            cb.od_indexes, cb.od_origin = od_indexes.ctypes.data, od_origin.ctypes.data
+            cb.od_shared, cb.od_height, cb.od_width = 1 if shared else 0, int(od_indexes.shape[-2]), int(od_indexes.shape[-1])
+            cb.od_resolution = float(od_resolution)
+        _check(self.lib, self.lib.smpc_crowd_step_batch(self._h, C.byref(cb), people.ctypes.data, cursor.ctypes.data),
+               "smpc_crowd_step_batch")
+        return people, cursor
+
+    def crowd_step_device(self, cb: SmpcCrowdBatch, people_ptr: int, cursor_ptr: int):
+        """Device pointers in cb (on_device == 1) and for people and cursor; asynchronous on the handle's stream."""
+        assert cb.on_device == 1
+        _check(self.lib, self.lib.smpc_crowd_step_batch(self._h, C.byref(cb), C.c_void_p(people_ptr), C.c_void_p(cursor_ptr)),
+               "smpc_crowd_step_batch")
 
     def select_command_device(self, B, T, rows, traj_n_ptr, traj_cmds_ptr, status_ptr, cmds_ptr, cmd_vel_ptr, source_ptr,
                               window_error_ptr=0):
