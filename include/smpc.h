@@ -588,7 +588,7 @@ int smpc_episode_metrics_batch(smpc_handle* h, const smpc_metrics_batch* in, dou
 
 /* ---- Reactive crowd of a closed-loop episode (csrc/smpc_crowd.hpp) --------------------------------------------------
  * One call advances every robot's persons by one control period under the Social Force Model of
- * include/nav2_social_mpc_controller/sfm.hpp (computeForces :462-485, updatePosition :525-572; group forces are out).
+ * include/nav2_social_mpc_controller/sfm.hpp (computeForces :462-485, updatePosition :525-572; group forces: smpc_crowd_step_groups_batch below).
  * The persons see the robot; the robot is not moved by this call. */
 #define SMPC_MAX_WAYPOINTS 8
 typedef struct smpc_crowd_batch {
@@ -637,6 +637,43 @@ typedef struct smpc_crowd_batch {
 int smpc_crowd_step_batch(smpc_handle* h, const smpc_crowd_batch* in,
                           double* people  /* [B][Np][5] in/out: px, py, vx, vy, vz (smpc_people_batch.people rows) */,
                           int32_t* cursor /* [B][Np] in/out: index of each person's current waypoint */);
+
+/* ---- Reactive crowd with pedestrian groups: the crowd step plus sfm.hpp's group force (computeGroupForce :325-393, the
+ * branches without _PAPER_VERSION_). The groups exist in the world the controller is tested in only: the controller's
+ * own prediction (smpc_project_people_batch) has none, as people_msgs carries none. */
+typedef struct smpc_crowd_groups {
+  const int32_t* group_id;      /* [B][Np]; < 0: no group. Ids are compared within one robot only. Host or device as in->on_device says. */
+  double factor_gaze, factor_coherence, factor_repulsion;  /* sfm.hpp defaults 3.0, 2.0, 1.0; each >= 0 and finite */
+} smpc_crowd_groups;
+
+/* Everything smpc_crowd_step_batch specifies holds unchanged; one term is added to a person's force after the obstacle
+ * force (the reference's order: desired + social + obstacle + group). For person i < count[b] with gid = group_id[b][i]:
+ * Members: the persons j < count[b] with group_id[b][j] == gid >= 0, i included. Rows at or beyond count[b] are no members
+ *   whatever their id, the robot never is. Ids are arbitrary non-negative ints and need not be dense. With gid < 0 or
+ *   fewer than two members there is no group force.
+ * centre = mean of the members' positions at entry; size = their number; maxDistance = (size - 1) / 2.
+ * Gaze (:339-359): rel = (size * centre - p) / (size - 1) - p, the others' centre of mass seen from p. dd is the desired
+ *   direction computeDesiredForce returns: with a goal farther away than goal_radius the unit vector to the goal. Otherwise
+ *   the reference returns an uninitialised vector; the library's CONVENTION is dd = (0, 0), which gives no gaze force.
+ *   e = dd . rel, angle = acos(e / (|dd| |rel|)); if angle > pi / 2 the force is factor_gaze * (e / |dd|^2) * dd. A NaN
+ *   angle (rel = 0 or dd = 0) gives none. The device decides by the sign of e, which is the same test for a unit dd except
+ *   where |e| / |rel| is of the order of 1e-16.
+ * Coherence (:361-376): rel = centre - p; the force is rel * factor_coherence * (tanh(|rel| - maxDistance) + 1) / 2.
+ * Repulsion (:378-388): factor_repulsion * the sum over the OTHER members j with |p - p_j| < 2 * person_radius (strictly)
+ *   of (p - p_j).
+ * The order of every sum over members is a function of count[b] and robot b's group_id row alone (ascending j), so a
+ * robot's persons do not depend on B, the robot's place in the batch, the memory space, the stream or timing; two robots'
+ * coinciding ids never meet.
+ * No groups: with groups == NULL, groups->group_id == NULL or every id < 0 the result is smpc_crowd_step_batch's bit for
+ * bit (a person without a group force skips the addition: adding +0.0 would turn a -0.0 force component, and with it a
+ * zero velocity's sign, around). With a NULL group_id the plain kernel is launched.
+ * For device pointers the call is one kernel on the handle's stream, no allocation and no host synchronisation (capturable
+ * in a HIP graph); host pointers are staged like everywhere. A wave terminates whatever the input.
+ * SMPC_ERR_INVALID_ARG / SMPC_ERR_UNSUPPORTED (nothing launched, people and cursor untouched): every refusal of
+ * smpc_crowd_step_batch; SMPC_ERR_INVALID_ARG also for a negative or non-finite factor (with groups != NULL, whatever
+ * group_id is). */
+int smpc_crowd_step_groups_batch(smpc_handle* h, const smpc_crowd_batch* in, const smpc_crowd_groups* groups,
+                                 double* people, int32_t* cursor);
 
 /* Diagnostic: evaluates the elementary functions the sweep uses (csrc/smpc_math.hpp: table-driven exp / atan2 /
  * sincos, refined reciprocal / rsqrt, and the raw hardware estimates behind them) on n host-side arguments, so that

@@ -320,6 +320,15 @@ class SmpcCrowdBatch(C.Structure):
     ]
 
 
+class SmpcCrowdGroups(C.Structure):
+    _fields_ = [
+        ("group_id", C.c_void_p),
+        ("factor_gaze", C.c_double),
+        ("factor_coherence", C.c_double),
+        ("factor_repulsion", C.c_double),
+    ]
+
+
 class SmpcEvalOut(C.Structure):
     _fields_ = [
         ("residuals", C.c_void_p),
@@ -352,6 +361,7 @@ EXPORTED_SYMBOLS = [
     "smpc_select_command_batch",
     "smpc_episode_metrics_batch",
     "smpc_crowd_step_batch",
+    "smpc_crowd_step_groups_batch",
     "smpc_math_probe",
     "smpc_fp64_peak_probe",
     "smpc_stage_people_batch",

@@ -12,6 +12,11 @@
 // theta next to 0 and pi. The order of a person's sum is: robot, then per round its own term and the received one, a
 // function of count[b] and robot_visible alone. No LDS, no atomics, no private segment; the grid entry of a person's cell
 // is requested before the pair loop and consumed after it.
+// Groups (smpc_crowd_step_groups_batch, computeGroupForce :325-393): the same body with kGroups = true adds one pass over
+// the robot's grouped lanes after the pair rounds, in ascending lane order: three shuffles per grouped person (px, py, id)
+// give every member the position sum, the size and the repulsion sum of its group; no transcendental in the pass, one
+// exponential per member afterwards. A robot without a grouped person makes no trip. The plain kernel is the
+// instantiation with kGroups = false and compiles to the code it had before the template existed.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -58,9 +63,19 @@ __device__ inline double crowd_heading(MathTabP mt, double x, double y) {
   return proj_wrap((m > 1e-100 && m < 1e100) ? atan2_dir(mt, y, x) : atan2(y, x));
 }
 
-__global__ __launch_bounds__(kCrowdThreads) void smpc_crowd_step_kernel(const CrowdParams) {
+// the kernel arguments of the groups kernel: the plain step's, then what smpc_crowd_groups adds
+struct CrowdGroupsParams {
+  CrowdParams c;
+  const int32_t* group_id;  // [B][Np]
+  double factor_gaze, factor_coherence, factor_repulsion;
+};
+
+// kGroups: the kernel arguments P are CrowdGroupsParams (whose head is the plain step's), otherwise CrowdParams
+template <bool kGroups, class P>
+__global__ __launch_bounds__(kCrowdThreads) void smpc_crowd_step_kernel(const P) {
   SMPC_CHAIN_PRIORITY();
   const auto& p = *(const CrowdParams __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+  const auto* gp = (const CrowdGroupsParams __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
   const MathTabP mt = &p.mt;
   const int G = 1 << p.lgG;
   const int tid = blockIdx.x * kCrowdThreads + threadIdx.x;
@@ -81,7 +96,9 @@ __global__ __launch_bounds__(kCrowdThreads) void smpc_crowd_step_kernel(const Cr
   int cur = 0, nwp = 0;
   bool has_goal = false, on_grid = false;
   unsigned int ob = 0;
+  int gid = -1;
   if (act) {
+    if constexpr (kGroups) gid = gp->group_id[slot];
     const double* row = p.people + slot * 5;
     px = row[0]; py = row[1]; vx = row[2]; vy = row[3];
     cur = p.cursor[slot];
@@ -157,10 +174,30 @@ __global__ __launch_bounds__(kCrowdThreads) void smpc_crowd_step_kernel(const Cr
       }
     }
   }
+  // ---- the members of this person's group: position sum, size and repulsion sum (sfm.hpp:378-388), over the robot's
+  // grouped lanes in ascending order; every lane of the robot makes the same trips (the shuffles need their sources awake)
+  double gsx = 0.0, gsy = 0.0, grx = 0.0, gry = 0.0;
+  int gsize = 0;
+  if constexpr (kGroups) {
+    unsigned long long m = (__ballot(act && gid >= 0) >> base) & (G == 64 ? ~0ull : (1ull << G) - 1ull);
+    const double reach = 4.0 * p.person_radius * p.person_radius;
+    while (m) {
+      const int j = __builtin_ctzll(m);  // < n: only lanes with a person are in the mask
+      m &= m - 1ull;
+      const double qx = __shfl(px, base + j, 64), qy = __shfl(py, base + j, 64);
+      const int qid = __shfl(gid, base + j, 64);
+      if (qid == gid) {
+        gsx += qx; gsy += qy; ++gsize;
+        const double ux = px - qx, uy = py - qy;
+        if (j != g && ux * ux + uy * uy < reach) { grx += ux; gry += uy; }
+      }
+    }
+  }
   if (!has) return;
 
   // ---- computeDesiredForce (sfm.hpp:188-203)
   double fx, fy;
+  double dux = 0.0, duy = 0.0;  // the desired direction: the unit vector to the goal, or (0, 0)
   {
     const double ddx = gx - px, ddy = gy - py;
     const double z = ddx * ddx + ddy * ddy;
@@ -168,6 +205,7 @@ __global__ __launch_bounds__(kCrowdThreads) void smpc_crowd_step_kernel(const Cr
     if (has_goal && z * inv > p.goal_radius) {
       fx = kFd * ((z > 0 ? ddx * inv : ddx) * des - vx) / kRelax;
       fy = kFd * ((z > 0 ? ddy * inv : ddy) * des - vy) / kRelax;
+      if constexpr (kGroups) { dux = z > 0 ? ddx * inv : ddx; duy = z > 0 ? ddy * inv : ddy; }
     } else {
       fx = -vx / kRelax;
       fy = -vy / kRelax;
@@ -182,6 +220,26 @@ __global__ __launch_bounds__(kCrowdThreads) void smpc_crowd_step_kernel(const Cr
     const double e = kFo * exp_tab(mt, -(z * inv - p.person_radius) * (1.0 / kSig));
     fx += e * (z > 0 ? mx * inv : mx);
     fy += e * (z > 0 ? my * inv : my);
+  }
+  // ---- computeGroupForce (sfm.hpp:325-393) of a group of two or more: gaze + coherence + repulsion. A person without a
+  // group force skips the addition (adding +0.0 would turn a -0.0 component into +0.0).
+  if constexpr (kGroups) {
+    if (gsize >= 2) {
+      const double size = (double)gsize;
+      // gaze: the others' centre of mass lies behind the desired direction (angle > pi/2: e < 0 for a unit direction)
+      const double im = div_fast(1.0, size - 1.0);
+      const double e = dux * ((gsx - px) * im - px) + duy * ((gsy - py) * im - py);
+      double hx = 0.0, hy = 0.0;
+      if (e < 0.0) { hx = gp->factor_gaze * e * dux; hy = gp->factor_gaze * e * duy; }
+      // coherence: rel (tanh(|rel| - maxDistance) + 1) / 2 = rel / (1 + exp(-2 z)), the exponent kept non-positive
+      const double cx = div_fast(gsx, size) - px, cy = div_fast(gsy, size) - py;
+      const double z = proj_sqrt(cx * cx + cy * cy) - 0.5 * (size - 1.0);
+      const double t = exp_tab(mt, -2.0 * fabs(z));
+      const double s = gp->factor_coherence * div_fast(z >= 0.0 ? 1.0 : t, 1.0 + t);
+      hx += cx * s; hy += cy * s;
+      hx += gp->factor_repulsion * grx; hy += gp->factor_repulsion * gry;
+      fx += hx; fy += hy;
+    }
   }
   // ---- updatePosition (sfm.hpp:525-572)
   const double yaw_old = crowd_heading(mt, vx, vy);

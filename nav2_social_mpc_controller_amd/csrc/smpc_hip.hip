@@ -1049,7 +1049,9 @@ int smpc_episode_metrics_batch(smpc_handle* h, const smpc_metrics_batch* in, dou
   return st.finish();
 }
 
-int smpc_crowd_step_batch(smpc_handle* h, const smpc_crowd_batch* in, double* people, int32_t* cursor) {
+// smpc_crowd_step_batch (groups == nullptr) and smpc_crowd_step_groups_batch with a group_id array: one validation, one
+// staging path, the kernel by the presence of groups
+static int crowd_step(smpc_handle* h, const smpc_crowd_batch* in, const smpc_crowd_groups* groups, double* people, int32_t* cursor) {
   if (!h || !in || !people || !cursor) { set_error("null handle / input / people / cursor"); return SMPC_ERR_INVALID_ARG; }
   if (in->B < 1 || in->Np < 1 || in->K < 1 || !(in->dt > 0.0)) { set_error("bad B / Np / K / dt"); return SMPC_ERR_INVALID_ARG; }
   if (!(in->goal_radius >= 0.0) || !(in->person_radius >= 0.0) || !(in->desired_speed > 0.0)) {
@@ -1065,8 +1067,9 @@ int smpc_crowd_step_batch(smpc_handle* h, const smpc_crowd_batch* in, double* pe
     for (int32_t b = 0; b < in->B; ++b)
       if (in->count[b] < 0 || in->count[b] > in->Np) { set_error("count outside 0..Np"); return SMPC_ERR_INVALID_ARG; }
   SMPC_HIP_CHECK(hipSetDevice(h->device));
-  smpc::CrowdParams p;
-  std::memset(&p, 0, sizeof(p));
+  smpc::CrowdGroupsParams gp;
+  std::memset(&gp, 0, sizeof(gp));
+  smpc::CrowdParams& p = gp.c;
   p.B = in->B; p.Np = in->Np; p.K = in->K;
   while ((1 << p.lgG) < in->Np) ++p.lgG;
   p.cyclic = in->cyclic ? 1 : 0; p.robot_visible = in->robot_visible ? 1 : 0;
@@ -1086,13 +1089,32 @@ int smpc_crowd_step_batch(smpc_handle* h, const smpc_crowd_batch* in, double* pe
   SMPC_TRY(st.in(p.od_origin, grid ? in->od_origin : nullptr, ngrid * 2));
   SMPC_TRY(st.inout(p.people, people, B * Np * 5));
   SMPC_TRY(st.inout(p.cursor, cursor, B * Np));
+  if (groups) {
+    SMPC_TRY(st.in(gp.group_id, groups->group_id, B * Np));
+    gp.factor_gaze = groups->factor_gaze; gp.factor_coherence = groups->factor_coherence; gp.factor_repulsion = groups->factor_repulsion;
+  }
   const size_t per_block = smpc::kCrowdThreads >> p.lgG;
+  const dim3 blocks((unsigned)((B + per_block - 1) / per_block)), threads(smpc::kCrowdThreads);
   SMPC_TRY(st.timed([&] {
-    hipLaunchKernelGGL(smpc::smpc_crowd_step_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kCrowdThreads), 0,
-                       h->stream, p);
+    if (groups) hipLaunchKernelGGL((smpc::smpc_crowd_step_kernel<true, smpc::CrowdGroupsParams>), blocks, threads, 0, h->stream, gp);
+    else hipLaunchKernelGGL((smpc::smpc_crowd_step_kernel<false, smpc::CrowdParams>), blocks, threads, 0, h->stream, p);
     return SMPC_OK;
   }));
   return st.finish();
+}
+
+int smpc_crowd_step_batch(smpc_handle* h, const smpc_crowd_batch* in, double* people, int32_t* cursor) {
+  return crowd_step(h, in, nullptr, people, cursor);
+}
+
+int smpc_crowd_step_groups_batch(smpc_handle* h, const smpc_crowd_batch* in, const smpc_crowd_groups* groups, double* people,
+                                 int32_t* cursor) {
+  if (groups) {
+    const double f[3] = {groups->factor_gaze, groups->factor_coherence, groups->factor_repulsion};
+    for (double v : f)
+      if (!(v >= 0.0) || !std::isfinite(v)) { set_error("negative or non-finite group force factor"); return SMPC_ERR_INVALID_ARG; }
+  }
+  return crowd_step(h, in, groups && groups->group_id ? groups : nullptr, people, cursor);
 }
 
 int smpc_stage_people_batch(smpc_handle* h, const smpc_scene_batch* sb, double* records, double* aux) {

@@ -31,7 +31,7 @@ import numpy as np
 
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
-from .params import CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams, check_scene_param_rows
+from .params import CrowdGroupParams, CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams, check_scene_param_rows
 from .scenes import SceneBatch
 from .solver import BatchSolver
 
@@ -81,7 +81,8 @@ class BatchEpisode:
                  obstacle_min_cost: int = 254, unknown_is_obstacle: bool = False, scene_params: np.ndarray = None,
                  metrics: MetricsParams = None, goal: np.ndarray = None, od_distances: np.ndarray = None,
                  crowd: CrowdParams = None, person_waypoints: np.ndarray = None, person_n_waypoints: np.ndarray = None,
-                 person_speed: np.ndarray = None):
+                 person_speed: np.ndarray = None, person_groups: np.ndarray = None,
+                 crowd_groups: CrowdGroupParams = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -113,7 +114,11 @@ class BatchEpisode:
         each person's goals, self.person_cursor [B,Np] the index of its current one (0 at the start); person_speed [B,Np]:
         desired speeds (default crowd.desired_speed for everybody). The step sees the pose the period started from and the
         command being executed, and the episode's ObstacleDistance grid. None: nothing is allocated and the persons move
-        with constant velocity."""
+        with constant velocity.
+        person_groups [B,Np] int32 (with crowd; e.g. scenes.crowd_groups): the persons' group ids (< 0: none); companions
+        are held together by the Social Force Model's group force (smpc_crowd_step_groups_batch) with the factors of
+        crowd_groups (default CrowdGroupParams()). Uploaded once and constant over the episode. None: nothing is
+        allocated and the plain crowd step runs."""
         import torch
 
         self.torch = torch
@@ -250,6 +255,13 @@ class BatchEpisode:
             if person_speed is not None:
                 assert np.shape(person_speed) == (B, Np), "person_speed [B,Np]"
                 self.person_speed = torch.from_numpy(np.ascontiguousarray(person_speed, np.float64)).to(self.dev)
+        self.person_groups = None
+        if person_groups is not None:
+            if crowd is None:
+                raise ValueError("person_groups needs crowd=CrowdParams(...)")
+            assert np.shape(person_groups) == (B, int(self.persons.shape[1])), "person_groups [B,Np]"
+            self.person_groups = torch.from_numpy(np.ascontiguousarray(person_groups, np.int32)).to(self.dev)
+            self.crowd_group_params = crowd_groups if crowd_groups is not None else CrowdGroupParams()
         self.graph = None
         self.gstream = None
         # queue order for the next solve (from the last solve's sweep counts; index order before the first one)
@@ -430,7 +442,7 @@ class BatchEpisode:
         self.ticks += 1
         return TickRecord(**rec) if record else None
 
-    def _crowd_step(self):
+    def _crowd_step(self, groups: bool = True):
         Np = int(self.persons.shape[1])
         cb = BatchSolver.crowd_c(self.crowd_params, self.B, Np, int(self.person_wp.shape[2]), self.params.dt, 1)
         cb.robot_pose, cb.robot_twist, cb.count = self.pose.data_ptr(), self.cmd_vel.data_ptr(), self.person_count.data_ptr()
@@ -439,7 +451,10 @@ class BatchEpisode:
             cb.desired_speeds = self.person_speed.data_ptr()
         cb.od_indexes, cb.od_origin = self.od_indexes.data_ptr(), self.od_origin.data_ptr()
         cb.od_shared, cb.od_width, cb.od_height, cb.od_resolution = self.od_shared, self.od_w, self.od_h, self.od_resolution
-        self.solver.crowd_step_device(cb, self.persons.data_ptr(), self.person_cursor.data_ptr())
+        gb = None
+        if groups and self.person_groups is not None:
+            gb = BatchSolver.crowd_groups_c(self.crowd_group_params, self.person_groups.data_ptr())
+        self.solver.crowd_step_device(cb, self.persons.data_ptr(), self.person_cursor.data_ptr(), gb)
 
     def _metrics_sample(self):
         mb = BatchSolver.metrics_c(self.metrics_params, self.B, int(self.persons.shape[1]), self.params.dt, 1)
@@ -560,7 +575,8 @@ class ShardedEpisode:
                  plan_window: tuple = None, obstacles_from_costmap: bool = False, obstacle_min_cost: int = 254,
                  unknown_is_obstacle: bool = False, scene_params: np.ndarray = None, metrics: MetricsParams = None,
                  goal: np.ndarray = None, od_distances: np.ndarray = None, crowd: CrowdParams = None,
-                 person_waypoints: np.ndarray = None, person_n_waypoints: np.ndarray = None, person_speed: np.ndarray = None):
+                 person_waypoints: np.ndarray = None, person_n_waypoints: np.ndarray = None, person_speed: np.ndarray = None,
+                 person_groups: np.ndarray = None, crowd_groups: CrowdGroupParams = None):
         import torch
 
         self.torch = torch
@@ -587,7 +603,8 @@ class ShardedEpisode:
                     metrics=metrics, goal=None if goal is None else np.asarray(goal)[idx], od_distances=odd, crowd=crowd,
                     person_waypoints=None if person_waypoints is None else np.asarray(person_waypoints)[idx],
                     person_n_waypoints=None if person_n_waypoints is None else np.asarray(person_n_waypoints)[idx],
-                    person_speed=None if person_speed is None else np.asarray(person_speed)[idx]))
+                    person_speed=None if person_speed is None else np.asarray(person_speed)[idx],
+                    person_groups=None if person_groups is None else np.asarray(person_groups)[idx], crowd_groups=crowd_groups))
         self.B = B
         self.graphs = graphs
         for part in self.parts:  # every shard's persistent solve grid takes its share of the resident wavefronts

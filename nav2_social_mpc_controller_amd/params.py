@@ -72,6 +72,21 @@ class CrowdParams:
 
 
 @dataclass
+class CrowdGroupParams:
+    """The group force of the reactive crowd (smpc_crowd_groups, include/smpc.h; sfm.hpp forceFactorGroupGaze /
+    GroupCoherence / GroupRepulsion): companions look towards each other, stay together and do not overlap."""
+    factor_gaze: float = 3.0
+    factor_coherence: float = 2.0
+    factor_repulsion: float = 1.0
+
+    def __post_init__(self):
+        for f in fields(self):
+            v = getattr(self, f.name)
+            if not (v >= 0.0 and np.isfinite(v)):
+                raise ValueError(f"CrowdGroupParams.{f.name} must be finite and >= 0, got {v}")
+
+
+@dataclass
 class OptimizerParams:
     # optimizer.* (src/optimizer.cpp:26-55, 76-83)
     linear_solver_type: str = "SPARSE_NORMAL_CHOLESKY"

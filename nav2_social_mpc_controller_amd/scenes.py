@@ -342,3 +342,40 @@ def crowd_waypoints(scenes: SceneBatch, K: int = 2, seed: int = 0x5EED0002, firs
     walking = (st0[:, 3, :] != -1.0) & (st0[:, 4, :] > 0.0)
     n_wp = np.where(walking, K, 0).astype(np.int32)
     return np.ascontiguousarray(wp), np.ascontiguousarray(n_wp)
+
+
+def crowd_groups(scenes: SceneBatch, sizes=(2, 3), share: float = 0.5, K: int = 2, seed: int = 0x5EED0003,
+                 first_scene: int = 0, **waypoint_options):
+    """Pedestrian groups for the persons of `scenes` (BatchEpisode(crowd=..., person_groups=...)): (group_id [B,N] int32,
+    waypoints [B,N,K,2], n_waypoints [B,N]), a pure function of (seed, scene id) through `uniform`, so the result for a
+    slice of the scenes (first_scene) is the slice of the result. Of a scene's walking persons, taken in row order, the
+    first floor(share * their number) go into groups of consecutive rows whose sizes are drawn from `sizes` (a size
+    that no longer fits is replaced by the largest one that does; what is left below the smallest size stays alone).
+    A scene's groups are numbered 0, 1, ...; a standing person, an invalid row and everybody else get -1. The waypoints
+    are crowd_waypoints' (waypoint_options are passed on), except that a group's members share their first member's
+    list: companions head for the same places."""
+    B, N = scenes.B, scenes.N
+    sizes = sorted(int(s) for s in sizes)
+    if not sizes or sizes[0] < 2 or not 0.0 <= share <= 1.0:
+        raise ValueError("crowd_groups: sizes >= 2 and 0 <= share <= 1")
+    wp, n_wp = crowd_waypoints(scenes, K=K, first_scene=first_scene, **waypoint_options)
+    ids = np.arange(first_scene, first_scene + B, dtype=np.int64)
+    draw = uniform(seed, ids, 300, max(N, 1))
+    st0 = scenes.people[:, 0]
+    walking = (st0[:, 3, :] != -1.0) & (st0[:, 4, :] > 0.0)
+    gid = np.full((B, N), -1, np.int32)
+    for b in range(B):
+        rows = np.flatnonzero(walking[b])
+        quota, at, g = int(np.floor(share * len(rows))), 0, 0
+        while True:
+            fits = [s for s in sizes if s <= quota]
+            if not fits:
+                break
+            size = sizes[int(draw[b, g] * len(sizes))]
+            size = size if size <= quota else fits[-1]
+            members = rows[at:at + size]
+            gid[b, members] = g
+            wp[b, members] = wp[b, members[0]]
+            n_wp[b, members] = n_wp[b, members[0]]
+            quota, at, g = quota - size, at + size, g + 1
+    return gid, np.ascontiguousarray(wp), np.ascontiguousarray(n_wp)

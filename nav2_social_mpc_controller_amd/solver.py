@@ -12,10 +12,10 @@ import os
 import numpy as np
 
 from . import _abi
-from ._abi import (SmpcCrowdBatch, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
+from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcParams, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
-from .params import CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams
+from .params import CrowdGroupParams, CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams
 from .scenes import SceneBatch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -95,6 +95,8 @@ def load_library():
     lib.smpc_episode_metrics_batch.restype = C.c_int
     lib.smpc_crowd_step_batch.argtypes = [C.c_void_p, C.POINTER(SmpcCrowdBatch), C.c_void_p, C.c_void_p]
     lib.smpc_crowd_step_batch.restype = C.c_int
+    lib.smpc_crowd_step_groups_batch.argtypes = [C.c_void_p, C.POINTER(SmpcCrowdBatch), C.POINTER(SmpcCrowdGroups), C.c_void_p, C.c_void_p]
+    lib.smpc_crowd_step_groups_batch.restype = C.c_int
     lib.smpc_stage_people_batch.argtypes = [C.c_void_p, C.POINTER(SmpcSceneBatch), C.c_void_p, C.c_void_p]
     lib.smpc_stage_people_batch.restype = C.c_int
     lib.smpc_fp64_peak_probe.argtypes = [C.c_void_p, C.c_int32]
@@ -523,14 +525,22 @@ class BatchSolver:
         cb.goal_radius, cb.person_radius, cb.desired_speed = cp.goal_radius, cp.person_radius, cp.desired_speed
         return cb
 
+    @staticmethod
+    def crowd_groups_c(gp: CrowdGroupParams, group_id_ptr: int) -> SmpcCrowdGroups:
+        gb = SmpcCrowdGroups()
+        gb.group_id = group_id_ptr
+        gb.factor_gaze, gb.factor_coherence, gb.factor_repulsion = gp.factor_gaze, gp.factor_coherence, gp.factor_repulsion
+        return gb
+
     def crowd_step(self, cp: CrowdParams, dt: float, people: np.ndarray, cursor: np.ndarray, robot_pose: np.ndarray,
                    robot_twist: np.ndarray, count: np.ndarray, waypoints: np.ndarray, n_waypoints: np.ndarray,
                    desired_speeds: np.ndarray = None, od_indexes: np.ndarray = None, od_origin: np.ndarray = None,
-                   od_resolution: float = None):
+                   od_resolution: float = None, groups: np.ndarray = None, group_params: CrowdGroupParams = None):
         """One control period of the crowd (host arrays): people [B,Np,5], cursor [B,Np], robot_pose [B,3] at the start of
         the period, robot_twist [B,2], count [B], waypoints [B,Np,K,2], n_waypoints [B,Np]; optional desired_speeds [B,Np],
         od_indexes [h,w] (one shared grid, od_origin [2]) or [B,h,w] (od_origin [B,2]) uint32 with od_resolution.
-        Returns the updated copies (people, cursor)."""
+        groups [B,Np] int32 group ids (< 0: none) with group_params (default CrowdGroupParams()): the step with group forces
+        (smpc_crowd_step_groups_batch); None: the plain step. Returns the updated copies (people, cursor)."""
         people = np.array(people, dtype=np.float64, order="C")
         cursor = np.array(cursor, dtype=np.int32, order="C")
         robot_pose = np.ascontiguousarray(robot_pose, np.float64)
@@ -558,13 +568,25 @@ class BatchSolver:
             cb.od_indexes, cb.od_origin = od_indexes.ctypes.data, od_origin.ctypes.data
             cb.od_shared, cb.od_height, cb.od_width = 1 if shared else 0, int(od_indexes.shape[-2]), int(od_indexes.shape[-1])
             cb.od_resolution = float(od_resolution)
+        if groups is not None:
+            groups = np.ascontiguousarray(groups, np.int32)
+            assert groups.shape == (B, Np)
+            gb = self.crowd_groups_c(group_params if group_params is not None else CrowdGroupParams(), groups.ctypes.data)
+            _check(self.lib, self.lib.smpc_crowd_step_groups_batch(self._h, C.byref(cb), C.byref(gb), people.ctypes.data,
+                                                                   cursor.ctypes.data), "smpc_crowd_step_groups_batch")
+            return people, cursor
         _check(self.lib, self.lib.smpc_crowd_step_batch(self._h, C.byref(cb), people.ctypes.data, cursor.ctypes.data),
                "smpc_crowd_step_batch")
         return people, cursor
 
-    def crowd_step_device(self, cb: SmpcCrowdBatch, people_ptr: int, cursor_ptr: int):
-        """Device pointers in cb (on_device == 1) and for people and cursor; asynchronous on the handle's stream."""
+    def crowd_step_device(self, cb: SmpcCrowdBatch, people_ptr: int, cursor_ptr: int, groups: SmpcCrowdGroups = None):
+        """Device pointers in cb (on_device == 1), in groups (crowd_groups_c; None: the plain step) and for people and
+        cursor; asynchronous on the handle's stream."""
         assert cb.on_device == 1
+        if groups is not None:
+            _check(self.lib, self.lib.smpc_crowd_step_groups_batch(self._h, C.byref(cb), C.byref(groups), C.c_void_p(people_ptr),
+                                                                   C.c_void_p(cursor_ptr)), "smpc_crowd_step_groups_batch")
+            return
         _check(self.lib, self.lib.smpc_crowd_step_batch(self._h, C.byref(cb), C.c_void_p(people_ptr), C.c_void_p(cursor_ptr)),
                "smpc_crowd_step_batch")
 

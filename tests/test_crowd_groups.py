@@ -1,0 +1,233 @@
+"""Pedestrian groups in the crowd step (smpc_crowd_step_groups_batch) without a GPU: the plumbing of the entry point, the
+closed forms of the CPU checker (tests/crowd_groups_ref.py), scenes.crowd_groups, the refusals of CrowdGroupParams, and
+the margins of the seeded inputs that tests/test_gpu_crowd_groups.py runs on the device."""
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import crowd_cases as G
+import crowd_groups_cases as GC
+import crowd_groups_ref as GR
+import crowd_ref as R
+from nav2_social_mpc_controller_amd import _abi
+from nav2_social_mpc_controller_amd import solver as S
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "smpc.h")
+
+
+# ---- plumbing -------------------------------------------------------------------------------------------------------
+def test_entry_point_is_declared_listed_and_exported(tmp_path):
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    assert re.search(r"\bint\s+smpc_crowd_step_groups_batch\s*\(", src)
+    assert "smpc_crowd_step_groups_batch" in _abi.EXPORTED_SYMBOLS
+    assert os.path.exists(S.LIB_PATH), "run __graft_entry__.build() first"
+    out = subprocess.check_output(["nm", "-D", "--defined-only", S.LIB_PATH], text=True)
+    assert "smpc_crowd_step_groups_batch" in {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert _abi.SMPC_ABI_VERSION == 6 and int(re.search(r"#define SMPC_ABI_VERSION (\d+)", src).group(1)) == 6
+    fields = ("group_id", "factor_gaze", "factor_coherence", "factor_repulsion")
+    prog = tmp_path / "layout.c"
+    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "smpc.h"\nint main(void){\n'
+                    'printf("%zu %zu", sizeof(smpc_crowd_batch), sizeof(smpc_crowd_groups));\n'
+                    + "".join(f'printf(" %zu", offsetof(smpc_crowd_groups, {f}));\n' for f in fields) + 'return 0;}\n')
+    exe = tmp_path / "layout"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
+    batch, size, *offsets = (int(v) for v in subprocess.check_output([str(exe)], text=True).split())
+    assert batch == C.sizeof(_abi.SmpcCrowdBatch) == 136                       # the plain step's struct is unchanged
+    assert size == C.sizeof(_abi.SmpcCrowdGroups) == 32
+    assert offsets == [getattr(_abi.SmpcCrowdGroups, f).offset for f in fields] == [0, 8, 16, 24]
+
+
+def test_crowd_group_params_defaults_and_refusals():
+    from nav2_social_mpc_controller_amd.params import CrowdGroupParams
+    gp = CrowdGroupParams()
+    assert (gp.factor_gaze, gp.factor_coherence, gp.factor_repulsion) == GR.FACTORS == (3.0, 2.0, 1.0)
+    gb = S.BatchSolver.crowd_groups_c(CrowdGroupParams(0.0, 0.5, 0.25), 4096)
+    assert (gb.group_id, gb.factor_gaze, gb.factor_coherence, gb.factor_repulsion) == (4096, 0.0, 0.5, 0.25)
+    for name in ("factor_gaze", "factor_coherence", "factor_repulsion"):
+        for bad in (-1e-9, float("nan"), float("inf"), -float("inf")):
+            with pytest.raises(ValueError):
+                CrowdGroupParams(**{name: bad})
+
+
+# ---- closed forms of the checker --------------------------------------------------------------------------------------
+def _one(people, group_id, **kw):
+    people = np.asarray(people, np.float64)
+    n = people.shape[0]
+    args = dict(cursor=np.zeros(n, np.int32), pose=np.zeros(3), twist=np.zeros(2), count=n, waypoints=np.zeros((n, 1, 2)),
+                n_waypoints=np.zeros(n, np.int32), robot_visible=False)
+    args.update(kw)
+    return args, GR.step(G.DT, people, group_id=None if group_id is None else np.asarray(group_id, np.int32), **args)
+
+
+def _group_forces(people, group_id, dds=None, **kw):
+    people = np.asarray(people, np.float64)
+    n = people.shape[0]
+    return [GR.group_force(i, people, n, np.asarray(group_id, np.int32), (0.0, 0.0) if dds is None else dds[i], 0.35, **kw)
+            for i in range(n)]
+
+
+def test_a_standing_pair_two_metres_apart_gets_equal_and_opposite_coherence():
+    f = _group_forces([[0.0, 0.0, 0, 0, 0], [2.0, 0.0, 0, 0, 0]], [5, 5])
+    want = 1.0 * 2.0 * (math.tanh(1.0 - 0.5) + 1.0) / 2.0            # |rel| = 1 m, maxDistance = 0.5 m
+    assert abs(f[0][0] - want) <= 1e-15 and abs(f[1][0] + want) <= 1e-15 and f[0][1] == 0.0 and f[1][1] == 0.0
+    assert f[0][0] == -f[1][0]                                          # no gaze (no goals) and no repulsion (2 m >= 0.7 m)
+    # and through the whole step: only the social term and the coherence act, both along the axis
+    args, (got, _) = _one([[0.0, 0.0, 0, 0, 0], [2.0, 0.0, 0, 0, 0]], [5, 5])
+    plain, _ = R.step(G.DT, np.array([[0.0, 0.0, 0, 0, 0], [2.0, 0.0, 0, 0, 0]]), **args)
+    assert abs((got[0, 2] - plain[0, 2]) - want * G.DT) <= 1e-15 and got[0, 3] == plain[0, 3] == 0.0
+
+
+def test_a_pair_half_a_metre_apart_is_pushed_apart_by_the_repulsion():
+    people = [[1.0, 1.0, 0, 0, 0], [1.5, 1.0, 0, 0, 0]]
+    with_rep = _group_forces(people, [0, 0])
+    without = _group_forces(people, [0, 0], factors=(3.0, 2.0, 0.0))
+    assert with_rep[0][0] - without[0][0] == -0.5 and with_rep[1][0] - without[1][0] == 0.5
+    assert with_rep[0][1] == 0.0 and with_rep[1][1] == 0.0
+    # strictly inside 2 * person_radius only
+    at_reach = [[0.0, 0.0, 0, 0, 0], [0.75, 0.0, 0, 0, 0]]
+    a = [GR.group_force(i, np.array(at_reach), 2, np.array([1, 1]), (0.0, 0.0), 0.375, factors=(0.0, 0.0, 1.0)) for i in range(2)]
+    assert a == [(0.0, 0.0), (0.0, 0.0)]
+
+
+def test_a_person_walking_away_from_its_companion_is_held_back_by_the_gaze():
+    people = np.array([[0.0, 0.0, 0, 0, 0], [2.0, 0.0, 0, 0, 0]])
+    dd = (-0.6, -0.8)                                                   # away from the companion, and a unit vector
+    f = GR.group_force(0, people, 2, np.array([9, 9]), dd, 0.35, factors=(3.0, 0.0, 0.0))
+    e = dd[0] * 2.0                                                     # rel = (2, 0)
+    assert e < 0 and abs(f[0] - 3.0 * e * dd[0]) <= 1e-15 and abs(f[1] - 3.0 * e * dd[1]) <= 1e-15
+    assert abs(math.hypot(*f) - 3.0 * abs(e)) <= 1e-15 and f[0] * dd[1] - f[1] * dd[0] == pytest.approx(0.0, abs=1e-15)
+    assert f[0] * dd[0] + f[1] * dd[1] < 0                              # antiparallel to dd
+    # towards the companion, or without a desired direction: no gaze force
+    assert GR.group_force(0, people, 2, np.array([9, 9]), (0.6, 0.8), 0.35, factors=(3.0, 0.0, 0.0)) == (0.0, 0.0)
+    assert GR.group_force(0, people, 2, np.array([9, 9]), (0.0, 0.0), 0.35, factors=(3.0, 0.0, 0.0)) == (0.0, 0.0)
+    # the desired direction is the unit vector to a goal beyond goal_radius, (0, 0) otherwise
+    assert GR.desired_direction(1.0, 1.0, True, (4.0, 5.0), 0.25) == (0.6, 0.8)
+    assert GR.desired_direction(1.0, 1.0, True, (1.1, 1.0), 0.25) == (0.0, 0.0)
+    assert GR.desired_direction(1.0, 1.0, False, (4.0, 5.0), 0.25) == (0.0, 0.0)
+
+
+def test_a_group_of_one_and_negative_ids_are_the_plain_step_exactly():
+    d = G.case((3, 64))
+    pos, kw = G.arguments(d, G.CONFIGS[0])
+    rpos, one = G.robot_arguments(pos, kw, 1)
+    want = R.step(*rpos, **one)
+    n = d["Np"]
+    for gid in (np.full(n, -1), np.arange(n) * 1000 + 7, -1 - np.arange(n), np.where(np.arange(n) >= rpos[5], 7, -1)):
+        got = GR.step(*rpos, group_id=gid.astype(np.int32), **one)
+        assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
+    grouped = GR.step(*rpos, group_id=np.full(n, 7, np.int32), **one)
+    assert rpos[5] >= 2 and grouped[0].tobytes() != want[0].tobytes()
+
+
+def test_the_force_with_a_negative_zero_component_of_the_bit_exact_inputs():
+    """The person that tests/test_gpu_crowd_groups.py puts into its bit-exact cases: standing, without a goal, the robot
+    standing far away on the diagonal. Its social term underflows to -0.0 in y, and -v / 0.5 is -0.0 as well."""
+    d = GC.negative_zero_inputs()
+    forces = []
+    GR.step(G.DT, d["people"][0], d["cursor"][0], d["pose"][0], d["twist"][0], d["count"][0], d["waypoints"][0],
+            d["n_waypoints"][0], robot_visible=True, forces=forces, **G.PARAMS)
+    fx, fy = forces[0]
+    assert fy == 0.0 and math.copysign(1.0, fy) == -1.0 and d["people"][0, 0, 2:4].tolist() == [0.0, 0.0]
+    assert fy + 0.0 == 0.0 and math.copysign(1.0, fy + 0.0) == 1.0      # what adding a zero group force would do
+
+
+# ---- scenes.crowd_groups ----------------------------------------------------------------------------------------------
+def test_crowd_groups_are_seeded_slice_consistent_and_share_waypoints():
+    from nav2_social_mpc_controller_amd.params import OptimizerParams
+    from nav2_social_mpc_controller_amd.scenes import crowd_groups, crowd_waypoints, make_scenes
+    sc = make_scenes(OptimizerParams.readme(), 48, 8, n_valid=7)
+    gid, wp, n = crowd_groups(sc, K=2)
+    assert gid.shape == (48, 8) and gid.dtype == np.int32 and wp.shape == (48, 8, 2, 2) and n.shape == (48, 8) and n.dtype == np.int32
+    again = crowd_groups(sc, K=2)
+    assert all(np.array_equal(a, b) for a, b in zip(again, (gid, wp, n)))
+    part = crowd_groups(sc.select(np.arange(8, 16)), K=2, first_scene=8)
+    assert all(np.array_equal(a, b[8:16]) for a, b in zip(part, (gid, wp, n)))
+    other = crowd_groups(sc, K=2, seed=1234)
+    assert not np.array_equal(other[0], gid)
+    st0 = sc.people[:, 0]
+    walking = (st0[:, 3, :] != -1.0) & (st0[:, 4, :] > 0.0)
+    assert (gid[~walking] == -1).all() and (gid[:, 7] == -1).all() and (~walking).any()
+    plain_wp, plain_n = crowd_waypoints(sc, K=2)
+    assert np.array_equal(wp[gid < 0], plain_wp[gid < 0]) and np.array_equal(n[gid < 0], plain_n[gid < 0])
+    sizes = []
+    for b in range(48):
+        for g in sorted(set(gid[b][gid[b] >= 0].tolist())):
+            rows = np.flatnonzero(gid[b] == g)
+            sizes.append(len(rows))
+            assert (wp[b, rows] == wp[b, rows[0]]).all() and (n[b, rows] == 2).all()
+            assert np.array_equal(wp[b, rows[0]], plain_wp[b, rows[0]])
+        assert (gid[b] >= 0).sum() <= 0.5 * walking[b].sum()
+    assert set(sizes) == {2, 3}
+    assert (gid >= 0).sum() >= 0.3 * walking.sum()
+    none = crowd_groups(sc, share=0.0)
+    assert (none[0] == -1).all() and np.array_equal(none[1], plain_wp)
+    with pytest.raises(ValueError):
+        crowd_groups(sc, sizes=(1, 2))
+
+
+# ---- the inputs of the GPU tests stay clear of every decision ---------------------------------------------------------
+@pytest.mark.parametrize("shape", GC.SHAPES, ids=lambda s: f"B{s[0]}_Np{s[1]}")
+def test_generated_inputs_keep_their_margins(shape):
+    d = GC.case(shape)
+    B, Np = shape
+    gid = d["group_id"]
+    dead = np.arange(Np)[None, :] >= d["count"][:, None]
+    assert B == 1 or (gid[dead] >= 0).any()                              # rows beyond the count carry ids
+    if B >= 3:
+        live_ids = [gid[b, :d["count"][b]] for b in range(B)]
+        sizes = {int(c) for ids in live_ids for c in np.unique(ids[ids >= 0], return_counts=True)[1]}
+        assert {1, 2, 3} <= sizes and max(sizes) == Np and any((ids < 0).any() for ids in live_ids)
+        assert 7 in gid[1] and 1_000_000 in gid[1] and 7 in gid[2] and 1_000_000 in gid[2]
+    for ci, cfg in enumerate(G.CONFIGS):
+        pos, kw = G.arguments(d, cfg)
+        least = dict.fromkeys(GC.CONDITIONS, math.inf)
+        plain = dict.fromkeys(G.CONDITIONS, math.inf)
+        grouped = 0
+        for b in range(B):
+            rpos, one = G.robot_arguments(pos, kw, b)
+            m = GR.margins(*rpos, group_id=gid[b], **one)
+            grouped += m["grouped"]
+            for name in least:
+                least[name] = min(least[name], m[name])
+            m = R.margins(*rpos, **one)
+            for name in plain:
+                plain[name] = min(plain[name], m[name])
+        print(shape, cfg, least, plain, "grouped persons:", grouped)
+        for name, need in GC.CONDITIONS.items():
+            assert least[name] >= need, (shape, ci, name, least[name])
+        for name, need in G.CONDITIONS.items():
+            assert plain[name] >= need, (shape, ci, name, plain[name])
+        assert grouped > 0 or shape == (1, 1)
+
+
+def test_the_coinciding_ids_of_the_leak_test_keep_their_margins():
+    shape = (130, 8)
+    d = GC.case(shape)
+    gid = GC.coinciding_ids(*shape)
+    assert all(set(row.tolist()) == {0, 1} for row in gid)
+    pos, kw = G.arguments(d, G.CONFIGS[0])
+    least = dict.fromkeys(GC.CONDITIONS, math.inf)
+    for b in range(shape[0]):
+        rpos, one = G.robot_arguments(pos, kw, b)
+        m = GR.margins(*rpos, group_id=gid[b], **one)
+        for name in least:
+            least[name] = min(least[name], m[name])
+    print(least)
+    for name, need in GC.CONDITIONS.items():
+        assert least[name] >= need, (name, least[name])
+
+
+def test_checker_shows_that_companions_stay_together():
+    def stepper(people, cursor, d, group_id):
+        return GR.step_batch(G.DT, people, cursor, d["pose"], d["twist"], d["count"], d["waypoints"], d["n_waypoints"],
+                             robot_visible=False, cyclic=False, group_id=group_id, **G.PARAMS)
+    grouped, alone = GC.spread_after(stepper, True), GC.spread_after(stepper, False)
+    print(f"largest member-to-centre distance after {GC.BEHAVIOUR_STEPS} steps: grouped {grouped:.6f} m, alone {alone:.6f} m")
+    assert abs(grouped - GC.SPREAD_GROUPED) <= 1e-6 and abs(alone - GC.SPREAD_ALONE) <= 1e-6
+    assert alone - grouped >= 0.5 * (GC.SPREAD_ALONE - GC.SPREAD_GROUPED) > 0.0

@@ -1,7 +1,10 @@
-"""Cost of the reactive crowd (smpc_crowd_step_batch), two measurements, one JSON line:
+"""Cost of the reactive crowd (smpc_crowd_step_batch, smpc_crowd_step_groups_batch), two measurements, one JSON line:
   kernel: HIP-event time of the crowd kernel alone (smpc_last_kernel_ms) on device pointers, B robots with Np persons each
           on per-robot --cells x --cells ObstacleDistance grids computed from the scenes' costmaps, median of --reps
           launches; smpc_people_to_status_batch and smpc_episode_metrics_batch on the same state beside it, alternating.
+          The groups kernel (crowd_step_groups) runs in the same loop on the same inputs — the persons and cursors the
+          plain launch started from are put back first —, with half of the walking persons in pairs and triples
+          (scenes.crowd_groups).
   tick:   the closed-loop tick (arc stand-in, N = Np agents, grids from the costmaps) of two episodes on the same scenes,
           one with crowd=None (constant-velocity persons) and one with the crowd, each replayed from its HIP graph:
           --rounds blocks of --ticks ticks, alternating between the two; median ms per tick of each and the spread
@@ -35,7 +38,7 @@ def main():
     from nav2_social_mpc_controller_amd._abi import SmpcPeopleBatch
     from nav2_social_mpc_controller_amd.episode import BatchEpisode
     from nav2_social_mpc_controller_amd.params import CrowdParams, MetricsParams, OptimizerParams
-    from nav2_social_mpc_controller_amd.scenes import crowd_waypoints, make_scenes, uniform
+    from nav2_social_mpc_controller_amd.scenes import crowd_groups, crowd_waypoints, make_scenes, uniform
 
     B, Np = a.B, a.Np
     prm, cp, mp = OptimizerParams.readme(), CrowdParams(), MetricsParams()
@@ -46,24 +49,32 @@ def main():
     crowd = dict(crowd=cp, person_waypoints=wp, person_n_waypoints=n_wp)
 
     # ---- the kernel alone, on the state of an episode after a few ticks (its own buffers, its own grids)
-    ep = BatchEpisode(prm, sc, w_ref, obstacles_from_costmap=True, metrics=mp, **crowd)
+    gid, _, _ = crowd_groups(sc, K=2)   # the ids alone are used: both kernels run on the plain waypoints
+    ep = BatchEpisode(prm, sc, w_ref, obstacles_from_costmap=True, metrics=mp, person_groups=gid, **crowd)
+    out["grouped_persons"] = int((gid >= 0).sum())
     for _ in range(3):
         ep.tick()
     ep.synchronize()
+    persons0, cursor0 = ep.persons.clone(), ep.person_cursor.clone()
     s = ep.solver
     qb = SmpcPeopleBatch()
     qb.B, qb.Np, qb.N, qb.on_device = B, Np, Np, 1
     qb.people, qb.count = ep.persons.data_ptr(), ep.person_count.data_ptr()
-    ms = {"crowd_step": [], "people_to_status": [], "episode_metrics": []}
+    ms = {"crowd_step": [], "crowd_step_groups": [], "people_to_status": [], "episode_metrics": []}
     for r in range(a.reps + 2):
-        ep._crowd_step()
+        ep.persons.copy_(persons0), ep.person_cursor.copy_(cursor0)
+        ep._crowd_step(groups=False)
         t_c = s.last_kernel_ms()
+        ep.persons.copy_(persons0), ep.person_cursor.copy_(cursor0)
+        ep._crowd_step()
+        t_g = s.last_kernel_ms()
         s.people_to_status_device(qb, ep.people.data_ptr(), ep.has_people.data_ptr())
         t_p = s.last_kernel_ms()
         ep._metrics_sample()
         t_m = s.last_kernel_ms()
         if r >= 2:   # the first launches load the code object
             ms["crowd_step"].append(t_c)
+            ms["crowd_step_groups"].append(t_g)
             ms["people_to_status"].append(t_p)
             ms["episode_metrics"].append(t_m)
     out["kernel_us"] = {k: {"median": round(float(np.median(v)) * 1e3, 2), "min": round(min(v) * 1e3, 2), "max": round(max(v) * 1e3, 2)}

@@ -34,6 +34,8 @@ RENAMES = [
     # smpc_solve_kernel<NB,W,vt,sp> -> <NB,W,vt,sp,false>; smpc_solve_trace_kernel<NB,W> -> smpc_solve_kernel<NB,W,true,true,true>
     (r"_ZN4smpc17smpc_solve_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])E" + _TAIL, r"_ZN4smpc17smpc_solve_kernelILi\1ELi\2ELb\3ELb\4ELb0E" + _TAIL),
     (r"_ZN4smpc23smpc_solve_trace_kernelILi(\d+)ELi(\d+)E" + _TAIL, r"_ZN4smpc17smpc_solve_kernelILi\1ELi\2ELb1ELb1ELb1E" + _TAIL),
+    # smpc_crowd_step_kernel -> smpc_crowd_step_kernel<false, CrowdParams> (kGroups = true is the groups kernel)
+    (r"_ZN4smpc22smpc_crowd_step_kernelENS_11CrowdParamsE", r"_ZN4smpc22smpc_crowd_step_kernelILb0ENS_11CrowdParamsEEEvT0_"),
 ]
 # what cannot matter: the numbers the compiler gives basic blocks, temporaries, jump tables and function ends
 LABELS = [(r"\.LBB\d+_", ".LBB_"), (r"\.Ltmp\d+", ".Ltmp"), (r"\.LJTI\d+_", ".LJTI_"), (r"\.LCPI\d+_", ".LCPI_"),
@@ -51,6 +53,8 @@ def split(text):
     for raw in text.splitlines():
         line = raw.split(";")[0].rstrip()  # comments name basic blocks by their numbers
         if not line:
+            continue
+        if re.match(r"\s*\.(text|section)\b", line):  # a template's code goes to a section of its own (comdat): not code
             continue
         for pat, rep in LABELS:
             line = re.sub(pat, rep, line)

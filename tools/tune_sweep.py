@@ -4,10 +4,12 @@ of a batch whose solve takes each robot's own critic weights and velocity bounds
 BatchEpisode(scene_params=...)); the device scores every robot as it drives (BatchEpisode(metrics=...)), and one line of
 summarize_metrics means is printed per set. Nothing but the final [B,24] metrics rows leaves the device.
 
-    python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive]
+    python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]]
 
 --reactive: the persons are a reactive crowd (BatchEpisode(crowd=CrowdParams()), waypoints from scenes.crowd_waypoints)
-instead of walking straight on with constant velocity.
+instead of walking straight on with constant velocity. --groups (with --reactive): half of the walking persons go in pairs
+and triples (scenes.crowd_groups -> BatchEpisode(person_groups=...)): companions share their waypoints and are held
+together by the Social Force Model's group force.
 """
 import argparse
 import os
@@ -37,13 +39,16 @@ def main():
     ap.add_argument("--ticks", type=int, default=200)
     ap.add_argument("--plan-poses", type=int, default=120, help="plan length in poses of 0.05 m (120: a 6 m drive)")
     ap.add_argument("--reactive", action="store_true", help="persons react: Social Force Model crowd with seeded waypoints")
+    ap.add_argument("--groups", action="store_true", help="with --reactive: half of the walking persons go in pairs and triples")
     a = ap.parse_args()
+    if a.groups and not a.reactive:
+        ap.error("--groups needs --reactive")
 
     import numpy as np
 
     from nav2_social_mpc_controller_amd.episode import BatchEpisode, arc_plans
     from nav2_social_mpc_controller_amd.params import CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams, scene_param_rows
-    from nav2_social_mpc_controller_amd.scenes import crowd_waypoints, make_scenes, uniform
+    from nav2_social_mpc_controller_amd.scenes import crowd_groups, crowd_waypoints, make_scenes, uniform
     from nav2_social_mpc_controller_amd.solver import summarize_metrics
 
     prm = OptimizerParams.readme()
@@ -58,7 +63,10 @@ def main():
     crowd = {}
     if a.reactive:
         wp, n_wp = crowd_waypoints(one)                                     # every set meets the same crowd
-        crowd = dict(crowd=CrowdParams(), person_waypoints=np.tile(wp, (S, 1, 1, 1)), person_n_waypoints=np.tile(n_wp, (S, 1)))
+        if a.groups:
+            gid, wp, n_wp = crowd_groups(one)
+            crowd["person_groups"] = np.tile(gid, (S, 1))
+        crowd.update(crowd=CrowdParams(), person_waypoints=np.tile(wp, (S, 1, 1, 1)), person_n_waypoints=np.tile(n_wp, (S, 1)))
     ep = BatchEpisode(prm, sc, w_ref, plan=plan, plan_len=plan_len, traj_params=tp, fov_angle=np.pi / 4,
                       obstacles_from_costmap=True, scene_params=rows, metrics=MetricsParams(), **crowd)
     ep.capture_graph()
