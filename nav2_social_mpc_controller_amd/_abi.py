@@ -1,13 +1,15 @@
 """ctypes mirror of include/smpc.h (the C ABI of the HIP solver).
 
-Only plain C structs live here; the shared library itself is loaded by `solver.py`.
-Struct layouts must stay in lock-step with include/smpc.h (checked by tests/test_abi.py through
-`smpc_abi_version` and `sizeof` probes exported by the library).
+Only declarations live here: the constants, every struct (`c_name`: its C type) and FUNCTIONS, the signature of every
+exported function; the shared library itself is loaded by `solver.py`. All of it must stay in lock-step with
+include/smpc.h: tests/test_abi.py compiles a probe against the header and compares every sizeof, every field's offsetof
+and the constants, and refuses a header struct or function without a mirror here.
 """
 import ctypes as C
 
 SMPC_ABI_VERSION = 6
 SMPC_MAX_BLOCKS = 10
+SMPC_MAX_AGENTS = 64
 
 # enum smpc_linear_solver (mirrors OptimizerParams::solver_types, reference optimizer.hpp:71-77)
 LINEAR_SOLVER = {
@@ -28,6 +30,7 @@ c_uint8_p = C.POINTER(C.c_uint8)
 
 
 class SmpcParams(C.Structure):
+    c_name = "smpc_params"
     _fields_ = [
         ("distance_w", C.c_double),
         ("socialwork_w", C.c_double),
@@ -62,10 +65,12 @@ SCENE_PARAM_FIELDS = ("distance_w", "socialwork_w", "velocity_w", "angle_w", "ag
 
 
 class SmpcSceneParams(C.Structure):
+    c_name = "smpc_scene_params"
     _fields_ = [(f, C.c_double) for f in SCENE_PARAM_FIELDS]
 
 
 class SmpcSceneBatch(C.Structure):
+    c_name = "smpc_scene_batch"
     _fields_ = [
         ("B", C.c_int32),
         ("T", C.c_int32),
@@ -93,6 +98,7 @@ class SmpcSceneBatch(C.Structure):
 
 
 class SmpcProjectionBatch(C.Structure):
+    c_name = "smpc_projection_batch"
     _fields_ = [
         ("B", C.c_int32),
         ("T", C.c_int32),
@@ -112,6 +118,7 @@ class SmpcProjectionBatch(C.Structure):
 
 
 class SmpcPeopleBatch(C.Structure):
+    c_name = "smpc_people_batch"
     _fields_ = [
         ("B", C.c_int32),
         ("Np", C.c_int32),
@@ -130,6 +137,7 @@ class SmpcPeopleBatch(C.Structure):
 
 
 class SmpcObstacleDistanceIn(C.Structure):
+    c_name = "smpc_obstacle_distance_in"
     _fields_ = [
         ("B", C.c_int32),
         ("size_x", C.c_int32),
@@ -145,6 +153,7 @@ class SmpcObstacleDistanceIn(C.Structure):
 
 
 class SmpcObstacleDistanceOut(C.Structure):
+    c_name = "smpc_obstacle_distance_out"
     _fields_ = [
         ("indexes", C.c_void_p),
         ("distances", C.c_void_p),
@@ -153,6 +162,7 @@ class SmpcObstacleDistanceOut(C.Structure):
 
 
 class SmpcMemoryBatch(C.Structure):
+    c_name = "smpc_memory_batch"
     _fields_ = [
         ("prev_path", C.c_void_p),
         ("prev_cmds", C.c_void_p),
@@ -162,6 +172,7 @@ class SmpcMemoryBatch(C.Structure):
 
 
 class SmpcFormatBatch(C.Structure):
+    c_name = "smpc_format_batch"
     _fields_ = [
         ("B", C.c_int32),
         ("T", C.c_int32),
@@ -180,6 +191,7 @@ class SmpcFormatBatch(C.Structure):
 
 
 class SmpcFormatOut(C.Structure):
+    c_name = "smpc_format_out"
     _fields_ = [
         ("robot_status", C.c_void_p),
         ("pose0", C.c_void_p),
@@ -191,6 +203,7 @@ class SmpcFormatOut(C.Structure):
 
 
 class SmpcTrajectorizeBatch(C.Structure):
+    c_name = "smpc_trajectorize_batch"
     _fields_ = [
         ("B", C.c_int32),
         ("L", C.c_int32),
@@ -208,6 +221,7 @@ class SmpcTrajectorizeBatch(C.Structure):
 
 
 class SmpcPlanWindowBatch(C.Structure):
+    c_name = "smpc_plan_window_batch"
     _fields_ = [
         ("B", C.c_int32),
         ("L", C.c_int32),
@@ -224,6 +238,7 @@ class SmpcPlanWindowBatch(C.Structure):
 
 
 class SmpcTrajectorizeOut(C.Structure):
+    c_name = "smpc_trajectorize_out"
     _fields_ = [
         ("path", C.c_void_p),
         ("cmds", C.c_void_p),
@@ -234,6 +249,7 @@ class SmpcTrajectorizeOut(C.Structure):
 
 
 class SmpcResultBatch(C.Structure):
+    c_name = "smpc_result_batch"
     _fields_ = [
         ("params", C.c_void_p),
         ("cmds", C.c_void_p),
@@ -251,6 +267,7 @@ SMPC_TRACE_COLS = 9
 
 
 class SmpcTraceOut(C.Structure):
+    c_name = "smpc_trace_out"
     _fields_ = [
         ("rows", C.c_void_p),
         ("max_rows", C.c_int32),
@@ -262,6 +279,7 @@ SMPC_METRIC_COLS = 24
 
 
 class SmpcMetricsBatch(C.Structure):
+    c_name = "smpc_metrics_batch"
     _fields_ = [
         ("B", C.c_int32),
         ("Np", C.c_int32),
@@ -294,6 +312,7 @@ SMPC_MAX_WAYPOINTS = 8
 
 
 class SmpcCrowdBatch(C.Structure):
+    c_name = "smpc_crowd_batch"
     _fields_ = [
         ("B", C.c_int32),
         ("Np", C.c_int32),
@@ -321,6 +340,7 @@ class SmpcCrowdBatch(C.Structure):
 
 
 class SmpcCrowdGroups(C.Structure):
+    c_name = "smpc_crowd_groups"
     _fields_ = [
         ("group_id", C.c_void_p),
         ("factor_gaze", C.c_double),
@@ -330,6 +350,7 @@ class SmpcCrowdGroups(C.Structure):
 
 
 class SmpcEvalOut(C.Structure):
+    c_name = "smpc_eval_batch_out"
     _fields_ = [
         ("residuals", C.c_void_p),
         ("jacobian", C.c_void_p),
@@ -339,33 +360,41 @@ class SmpcEvalOut(C.Structure):
     ]
 
 
-# Every symbol include/smpc.h declares; tests/test_abi.py checks the built library exports all of them.
-EXPORTED_SYMBOLS = [
-    "smpc_params_default",
-    "smpc_dims",
-    "smpc_create",
-    "smpc_destroy",
-    "smpc_set_stream",
-    "smpc_set_solve_share",
-    "smpc_solve_slot_width",
-    "smpc_solve_batch",
-    "smpc_solve_trace_batch",
-    "smpc_eval_batch",
-    "smpc_project_people_batch",
-    "smpc_people_to_status_batch",
-    "smpc_obstacle_distance_batch",
-    "smpc_format_to_optimize_batch",
-    "smpc_memory_store_batch",
-    "smpc_trajectorize_path_batch",
-    "smpc_transform_global_plan_batch",
-    "smpc_select_command_batch",
-    "smpc_episode_metrics_batch",
-    "smpc_crowd_step_batch",
-    "smpc_crowd_step_groups_batch",
-    "smpc_math_probe",
-    "smpc_fp64_peak_probe",
-    "smpc_stage_people_batch",
-    "smpc_last_kernel_ms",
-    "smpc_last_error",
-    "smpc_abi_version",
-]
+def _p(struct):
+    return C.POINTER(struct)
+
+
+_h, _vp, _i32 = C.c_void_p, C.c_void_p, C.c_int32  # the handle, a buffer, an int32_t argument
+
+# Every function include/smpc.h declares: name -> (restype, argtypes). solver.load_library() binds the library from
+# this table; tests/test_abi.py holds it against the header and the built library.
+FUNCTIONS = {
+    "smpc_params_default": (None, [_p(SmpcParams)]),
+    "smpc_dims": (C.c_int, [_p(SmpcParams), C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 6),
+    "smpc_create": (_h, [_p(SmpcParams), C.c_int]),
+    "smpc_destroy": (None, [_h]),
+    "smpc_set_stream": (C.c_int, [_h, _vp]),
+    "smpc_set_solve_share": (C.c_int, [_h, _i32]),
+    "smpc_solve_slot_width": (C.c_int, [_h, _i32, _i32, _i32]),
+    "smpc_solve_batch": (C.c_int, [_h, _p(SmpcSceneBatch), _p(SmpcResultBatch)]),
+    "smpc_solve_trace_batch": (C.c_int, [_h, _p(SmpcSceneBatch), _p(SmpcResultBatch), _p(SmpcTraceOut)]),
+    "smpc_eval_batch": (C.c_int, [_h, _p(SmpcSceneBatch), _vp, _p(SmpcEvalOut)]),
+    "smpc_project_people_batch": (C.c_int, [_h, _p(SmpcProjectionBatch), _vp, _vp]),
+    "smpc_people_to_status_batch": (C.c_int, [_h, _p(SmpcPeopleBatch), _vp, _vp]),
+    "smpc_obstacle_distance_batch": (C.c_int, [_h, _p(SmpcObstacleDistanceIn), _p(SmpcObstacleDistanceOut)]),
+    "smpc_format_to_optimize_batch": (C.c_int, [_h, _p(SmpcFormatBatch), _p(SmpcFormatOut)]),
+    "smpc_memory_store_batch": (C.c_int, [_h, _i32, _i32, _i32, _vp, _vp, _vp, _p(SmpcMemoryBatch), _vp]),
+    "smpc_trajectorize_path_batch": (C.c_int, [_h, _p(SmpcTrajectorizeBatch), _p(SmpcTrajectorizeOut)]),
+    "smpc_transform_global_plan_batch": (C.c_int, [_h, _p(SmpcPlanWindowBatch), _vp, _vp, _vp]),
+    "smpc_select_command_batch": (C.c_int, [_h, _i32, _i32, _i32, _i32] + [_vp] * 7),
+    "smpc_episode_metrics_batch": (C.c_int, [_h, _p(SmpcMetricsBatch), _vp]),
+    "smpc_crowd_step_batch": (C.c_int, [_h, _p(SmpcCrowdBatch), _vp, _vp]),
+    "smpc_crowd_step_groups_batch": (C.c_int, [_h, _p(SmpcCrowdBatch), _p(SmpcCrowdGroups), _vp, _vp]),
+    "smpc_math_probe": (C.c_int, [_h, _i32, _i32] + [_vp] * 4),
+    "smpc_fp64_peak_probe": (C.c_double, [_h, _i32]),
+    "smpc_stage_people_batch": (C.c_int, [_h, _p(SmpcSceneBatch), _vp, _vp]),
+    "smpc_last_kernel_ms": (C.c_double, [_h]),
+    "smpc_last_error": (C.c_char_p, []),
+    "smpc_abi_version": (C.c_int, []),
+}
+EXPORTED_SYMBOLS = list(FUNCTIONS)

@@ -24,8 +24,8 @@ stood in for by the simplest thing that has the same shape:
     and to the robot as it was at the start of the period, is pushed back by the nearest obstacle of its cell of the
     ObstacleDistance grid, and takes the next waypoint on arrival. The robot is seen but not pushed.
 """
-import ctypes as C
 from dataclasses import dataclass
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -33,7 +33,7 @@ from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBa
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
 from .params import CrowdGroupParams, CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams, check_scene_param_rows
 from .scenes import SceneBatch
-from .solver import BatchSolver
+from .solver import BatchSolver, point, set_od_grid
 
 
 @dataclass
@@ -74,6 +74,16 @@ class TickRecord:
 
 
 class BatchEpisode:
+    # The keyword arguments of __init__, by what a shard of the robots gets of them (shard_kwargs, ShardedEpisode):
+    # one row per robot, sliced along axis 0
+    PER_ROBOT = ("plan", "plan_len", "scene_params", "goal", "person_waypoints", "person_n_waypoints", "person_speed",
+                 "person_groups")
+    # one row per robot exactly when the grids are per scene (od_indexes [B,h,w]), else shared by all shards
+    PER_GRID = ("od_indexes", "od_origin", "od_distances")
+    # the same object for every shard
+    FORWARDED = ("od_resolution", "device", "traj_params", "fov_angle", "order_hint", "plan_window", "obstacles_from_costmap",
+                 "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups")
+
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
                  plan_len: np.ndarray = None, traj_params: TrajectorizerParams = None, fov_angle: float = None,
@@ -127,50 +137,76 @@ class BatchEpisode:
         self.dev = f"cuda:{device}"
         # library kernels and the few torch ops of the world model share one stream, so they are ordered
         self.solver.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
-        B, T, N = scenes.B, scenes.T, scenes.N
+        self.B, self.T, self.N = scenes.B, scenes.T, scenes.N
         if plan is not None:
             # Plan mode: every robot is solved with the horizon its own trajectorized path gives it (smpc_format_batch.n_poses
             # -> T_scene). The arrays are sized for the longest one: a path of exactly max_poses = round(max_time / dt)
             # poses is not cut by format_to_optimize (src/optimizer.cpp:491-497) and so has one step more than the longer,
             # cut, paths: T = max_poses - 1 = rollout_steps + 1.
-            assert T == params.rollout_steps
-            T = T + 1
-        self.B, self.T, self.N = B, T, N
-        CH, bl, nb, P, M, _ = params.dims(T, True)
-        self.P = P
-        f64 = dict(dtype=torch.float64, device=self.dev)
-        self.pose = torch.from_numpy(scenes.pose0.copy()).to(self.dev)                 # [B,3] current robot pose
-        self.speed = torch.from_numpy(scenes.init_params[:, 0:2].copy()).to(self.dev)  # [B,2] current twist
-        self.w_ref = torch.from_numpy(np.ascontiguousarray(w_ref, np.float64)).to(self.dev)
+            assert self.T == params.rollout_steps
+            self.T += 1
+        self.P = params.dims(self.T, True)[3]
+        self._init_world(scenes, w_ref, fov_angle)
+        self._init_grid(od_indexes, od_origin, od_resolution, od_distances, obstacles_from_costmap, obstacle_min_cost,
+                        unknown_is_obstacle, distances=metrics is not None)
+        self._init_memory()
+        self._init_plan(plan, plan_len, traj_params, plan_window)
+        self._init_solve(order_hint, scene_params)
+        self._init_metrics(metrics, goal, plan, plan_len)
+        self._init_crowd(crowd, person_waypoints, person_n_waypoints, person_speed, person_groups, crowd_groups)
+        self._bind()
+        self.graph = None
+        self.gstream = None
+        self.ticks = 0
+
+    # -- construction, by concern: device buffers first, then (_bind) the structs that point into them -----------------
+    def _upload(self, a, dtype):
+        return self.torch.from_numpy(np.ascontiguousarray(a, dtype)).to(self.dev)
+
+    def _zeros(self, *shape, dtype=None):
+        return self.torch.zeros(shape, dtype=dtype or self.torch.float64, device=self.dev)
+
+    def _init_world(self, scenes, w_ref, fov_angle):
+        """The robots, the persons and the costmaps."""
+        i32 = self.torch.int32
+        self.pose = self._upload(scenes.pose0.copy(), np.float64)                 # [B,3] current robot pose
+        self.speed = self._upload(scenes.init_params[:, 0:2].copy(), np.float64)  # [B,2] current twist
+        self.w_ref = self._upload(w_ref, np.float64)
+        self.cmd_vel = self._zeros(self.B, 2)            # the command returned to the robot this tick
+        self.cmd_source = self._zeros(self.B, dtype=i32)  # 0 optimised, 1 trajectorizer, 2 creep, 3 none
         # world people as people_msgs::Person rows [B,Np,5]: position x, y, velocity x, y, z (scene people at step 0;
         # make_scenes keeps the invalid ones at the end, so the first `count` rows are the persons)
         st0 = scenes.people[:, 0].transpose(0, 2, 1)                                    # [B,N,6] x, y, yaw, t, lv, av
         persons = np.stack([st0[:, :, 0], st0[:, :, 1], st0[:, :, 4] * np.cos(st0[:, :, 2]), st0[:, :, 4] * np.sin(st0[:, :, 2]),
                             st0[:, :, 5]], axis=-1)
-        count = np.where(scenes.has_people != 0, (st0[:, :, 3] != -1.0).sum(axis=1), 0).astype(np.int32)
-        self.persons = torch.from_numpy(np.ascontiguousarray(persons)).to(self.dev)
-        self.person_count = torch.from_numpy(count).to(self.dev)
+        count = np.where(scenes.has_people != 0, (st0[:, :, 3] != -1.0).sum(axis=1), 0)
+        self.persons = self._upload(persons, np.float64)
+        self.person_count = self._upload(count, np.int32)
         self.fov_angle = fov_angle
-        self.people = torch.zeros((B, N, 6), **f64)                                     # people_to_status output
-        self.has_people = torch.zeros(B, dtype=torch.uint8, device=self.dev)
-        self.costmap = torch.from_numpy(scenes.costmap).to(self.dev)
-        self.costmap_origin = torch.from_numpy(scenes.costmap_origin).to(self.dev)
+        self.people = self._zeros(self.B, self.N, 6)                                    # people_to_status output
+        self.has_people = self._zeros(self.B, dtype=self.torch.uint8)
+        self.costmap = self.torch.from_numpy(scenes.costmap).to(self.dev)
+        self.costmap_origin = self.torch.from_numpy(scenes.costmap_origin).to(self.dev)
         self.costmap_shared = scenes.costmap_shared
         self.size_x, self.size_y, self.resolution = scenes.size_x, scenes.size_y, scenes.resolution
-        if obstacles_from_costmap:
-            grids = 1 if self.costmap_shared else B
+
+    def _init_grid(self, od_indexes, od_origin, od_resolution, od_distances, from_costmap, obstacle_min_cost,
+                   unknown_is_obstacle, distances):
+        """The ObstacleDistance grid(s): od_indexes, od_origin, od_shared, od_h, od_w, od_resolution and, when the metrics
+        read them (`distances`) and they are there, od_distances (else the attribute does not exist)."""
+        torch, B = self.torch, self.B
+        if from_costmap:
+            shape = (1 if self.costmap_shared else B, self.size_y, self.size_x)
             self.od_shared = 1 if self.costmap_shared else 0
-            self.od_h, self.od_w = self.size_y, self.size_x
             self.od_resolution = float(np.float32(self.resolution))
             self.od_origin = self.costmap_origin
-            self.od_indexes = torch.empty((grids, self.od_h, self.od_w), dtype=torch.int32, device=self.dev)
-            if metrics is not None:  # the clearance columns read the distances: one more array, once
-                self.od_distances = torch.empty((grids, self.od_h, self.od_w), dtype=torch.float32, device=self.dev)
+            self.od_indexes = torch.empty(shape, dtype=torch.int32, device=self.dev)
+            if distances:  # the clearance columns read the distances: one more array, once
+                self.od_distances = torch.empty(shape, dtype=torch.float32, device=self.dev)
             ob = BatchSolver.obstacle_distance_c(B, self.size_x, self.size_y, self.costmap_shared, self.resolution, 1,
                                                  obstacle_min_cost, unknown_is_obstacle)
             ob.costmap = self.costmap.data_ptr()
-            self.solver.obstacle_distance_device(ob, self.od_indexes.data_ptr(),
-                                                 self.od_distances.data_ptr() if metrics is not None else 0)
+            self.solver.obstacle_distance_device(ob, self.od_indexes.data_ptr(), self.od_distances.data_ptr() if distances else 0)
         else:
             if od_indexes is None or od_origin is None or od_resolution is None:
                 raise ValueError("od_indexes, od_origin and od_resolution are needed unless obstacles_from_costmap=True")
@@ -179,115 +215,171 @@ class BatchEpisode:
             if per_scene:
                 assert od_indexes.shape[0] == B and np.shape(od_origin) == (B, 2), "per-scene grids: od_indexes [B,h,w], od_origin [B,2]"
             self.od_shared = 0 if per_scene else 1
-            self.od_indexes = torch.from_numpy(np.ascontiguousarray(od_indexes, np.uint32).view(np.int32)).to(self.dev)
-            self.od_origin = torch.from_numpy(np.ascontiguousarray(od_origin, np.float64).reshape(-1 if per_scene else 1, 2)).to(self.dev)
-            self.od_h, self.od_w = int(od_indexes.shape[-2]), int(od_indexes.shape[-1])
+            self.od_indexes = self._upload(np.ascontiguousarray(od_indexes, np.uint32).view(np.int32), np.int32)
+            self.od_origin = self._upload(np.asarray(od_origin, np.float64).reshape(-1 if per_scene else 1, 2), np.float64)
             self.od_resolution = float(od_resolution)
-            if metrics is not None and od_distances is not None:
+            if distances and od_distances is not None:
                 assert np.shape(od_distances) == od_indexes.shape, "od_distances is shaped like od_indexes"
-                self.od_distances = torch.from_numpy(np.ascontiguousarray(od_distances, np.float32)).to(self.dev)
-        # TrajectoryMemory, one record per scene
-        self.mem_path = torch.zeros((B, T + 1, 3), **f64)
-        self.mem_cmds = torch.zeros((B, T + 1, 2), **f64)
-        self.mem_valid = torch.zeros(B, dtype=torch.int32, device=self.dev)
-        self.mem_length = torch.zeros((B, 2), dtype=torch.int32, device=self.dev)   # poses / commands of every record
-        self.T_scene = torch.full((B,), T, dtype=torch.int32, device=self.dev)      # horizon of every robot this tick
-        self.max_poses = int(np.round(np.float32(params.max_time) / np.float32(params.time_step)))
-        # per-tick buffers
+                self.od_distances = self._upload(od_distances, np.float32)
+        self.od_h, self.od_w = int(self.od_indexes.shape[-2]), int(self.od_indexes.shape[-1])
+
+    def _init_memory(self):
+        """TrajectoryMemory, one record per scene."""
+        B, T, i32 = self.B, self.T, self.torch.int32
+        self.mem_path = self._zeros(B, T + 1, 3)
+        self.mem_cmds = self._zeros(B, T + 1, 2)
+        self.mem_valid = self._zeros(B, dtype=i32)
+        self.mem_length = self._zeros(B, 2, dtype=i32)                              # poses / commands of every record
+        self.T_scene = self.torch.full((B,), T, dtype=i32, device=self.dev)         # horizon of every robot this tick
+        self.max_poses = int(np.round(np.float32(self.params.max_time) / np.float32(self.params.time_step)))
+
+    def _init_plan(self, plan, plan_len, traj_params, plan_window):
+        """The global plans with the trajectorizer's (and the plan window's) outputs, or the rows of the arc stand-in."""
+        B, i32 = self.B, self.torch.int32
         self.traj = traj_params
+        self.plan, self.plan_window, self.rows = None, None, self.T + 1
         if plan is not None:
-            assert traj_params is not None and traj_params.max_steps + 1 >= T + 1
-            self.plan = torch.from_numpy(np.ascontiguousarray(plan, np.float64)).to(self.dev)
-            self.plan_len = torch.from_numpy(np.ascontiguousarray(plan_len, np.int32)).to(self.dev)
+            assert traj_params is not None and traj_params.max_steps + 1 >= self.T + 1
+            self.plan = self._upload(plan, np.float64)
+            self.plan_len = self._upload(plan_len, np.int32)
             self.rows = traj_params.max_steps + 1
-            self.traj_n = torch.zeros(B, dtype=torch.int32, device=self.dev)
-            self.traj_err = torch.zeros(B, dtype=torch.int32, device=self.dev)
-            self.traj_vy = torch.zeros((B, self.rows), **f64)
+            self.traj_n = self._zeros(B, dtype=i32)
+            self.traj_err = self._zeros(B, dtype=i32)
+            self.traj_vy = self._zeros(B, self.rows)
             self.plan_window = plan_window
             if plan_window is not None:
-                self.plan_start = torch.zeros(B, dtype=torch.int32, device=self.dev)
-                self.window = torch.zeros_like(self.plan)
-                self.window_len = torch.zeros(B, dtype=torch.int32, device=self.dev)
-                self.window_err = torch.zeros(B, dtype=torch.int32, device=self.dev)
-        else:
-            self.plan = None
-            self.plan_window = None
-            self.rows = T + 1
-        self.plan_path = torch.zeros((B, self.rows, 3), **f64)
-        self.plan_cmds = torch.zeros((B, self.rows, 2), **f64)
-        self.robot_status = torch.zeros((B, T + 1, 6), **f64)
-        self.pose0 = torch.zeros((B, 3), **f64)
-        self.init_params = torch.zeros((B, P), **f64)
-        self.path_pts = torch.zeros((B, T + 1, 2), **f64)
-        self.goal_yaw = torch.zeros(B, **f64)
-        self.people_proj = torch.zeros((B, T + 1, 6, N), **f64)
-        self.proj_error = torch.zeros(B, dtype=torch.int32, device=self.dev)
+                self.plan_start = self._zeros(B, dtype=i32)
+                self.window = self.torch.zeros_like(self.plan)
+                self.window_len = self._zeros(B, dtype=i32)
+                self.window_err = self._zeros(B, dtype=i32)
+        self.plan_path = self._zeros(B, self.rows, 3)
+        self.plan_cmds = self._zeros(B, self.rows, 2)
+
+    def _init_solve(self, order_hint, scene_params):
+        """What format_to_optimize, project_people and the solve write every tick."""
+        B, T = self.B, self.T
+        self.robot_status = self._zeros(B, T + 1, 6)
+        self.pose0 = self._zeros(B, 3)
+        self.init_params = self._zeros(B, self.P)
+        self.path_pts = self._zeros(B, T + 1, 2)
+        self.goal_yaw = self._zeros(B)
+        self.people_proj = self._zeros(B, T + 1, 6, self.N)
+        self.proj_error = self._zeros(B, dtype=self.torch.int32)
         self.rb, self.res = self.solver.alloc_results(B, T, self.dev)
-        self.cmd_vel = torch.zeros((B, 2), **f64)                      # the command returned to the robot this tick
-        self.cmd_source = torch.zeros(B, dtype=torch.int32, device=self.dev)  # 0 optimised, 1 trajectorizer, 2 creep, 3 none
         self.order_hint = order_hint
-        self.scene_params = None
-        if scene_params is not None:
-            sp = check_scene_param_rows(scene_params, B)
-            self.scene_params = torch.from_numpy(sp).to(self.dev)  # device rows: checked here, not by the library
-        self.metrics_params = metrics
-        if metrics is not None:
-            self.metrics_acc = torch.zeros((B, 24), **f64)  # zero rows: no samples yet
-            if goal is None and plan is not None:
-                L = np.asarray(plan_len).astype(np.int64)
-                goal = np.asarray(plan, np.float64)[np.arange(B), np.maximum(L, 1) - 1]
-            self.goal = None
-            if goal is not None:
-                assert np.shape(goal) == (B, 2), "goal [B,2]"
-                self.goal = torch.from_numpy(np.ascontiguousarray(goal, np.float64)).to(self.dev)
-        self.crowd_params = crowd
-        if crowd is not None:
-            Np = int(self.persons.shape[1])
-            if person_waypoints is None or person_n_waypoints is None:
-                raise ValueError("crowd needs person_waypoints [B,Np,K,2] and person_n_waypoints [B,Np]")
-            wp = np.ascontiguousarray(person_waypoints, np.float64)
-            assert wp.ndim == 4 and wp.shape[:2] == (B, Np) and wp.shape[3] == 2, "person_waypoints [B,Np,K,2]"
-            assert np.shape(person_n_waypoints) == (B, Np), "person_n_waypoints [B,Np]"
-            self.person_wp = torch.from_numpy(wp).to(self.dev)
-            self.person_nwp = torch.from_numpy(np.ascontiguousarray(person_n_waypoints, np.int32)).to(self.dev)
-            self.person_cursor = torch.zeros((B, Np), dtype=torch.int32, device=self.dev)
-            self.person_speed = None
-            if person_speed is not None:
-                assert np.shape(person_speed) == (B, Np), "person_speed [B,Np]"
-                self.person_speed = torch.from_numpy(np.ascontiguousarray(person_speed, np.float64)).to(self.dev)
-        self.person_groups = None
-        if person_groups is not None:
-            if crowd is None:
-                raise ValueError("person_groups needs crowd=CrowdParams(...)")
-            assert np.shape(person_groups) == (B, int(self.persons.shape[1])), "person_groups [B,Np]"
-            self.person_groups = torch.from_numpy(np.ascontiguousarray(person_groups, np.int32)).to(self.dev)
-            self.crowd_group_params = crowd_groups if crowd_groups is not None else CrowdGroupParams()
-        self.graph = None
-        self.gstream = None
         # queue order for the next solve (from the last solve's sweep counts; index order before the first one)
-        self.order = torch.arange(B, dtype=torch.int32, device=self.dev)
-        self.ticks = 0
+        self.order = self.torch.arange(B, dtype=self.torch.int32, device=self.dev)
+        self.scene_params = None
+        if scene_params is not None:  # device rows: checked here, not by the library
+            self.scene_params = self.torch.from_numpy(check_scene_param_rows(scene_params, B)).to(self.dev)
+
+    def _init_metrics(self, metrics, goal, plan, plan_len):
+        self.metrics_params = metrics
+        if metrics is None:
+            return
+        B = self.B
+        self.metrics_acc = self._zeros(B, 24)  # zero rows: no samples yet
+        if goal is None and plan is not None:
+            L = np.asarray(plan_len).astype(np.int64)
+            goal = np.asarray(plan, np.float64)[np.arange(B), np.maximum(L, 1) - 1]
+        self.goal = None
+        if goal is not None:
+            assert np.shape(goal) == (B, 2), "goal [B,2]"
+            self.goal = self._upload(goal, np.float64)
+
+    def _init_crowd(self, crowd, person_waypoints, person_n_waypoints, person_speed, person_groups, crowd_groups):
+        B, Np = self.B, int(self.persons.shape[1])
+        self.crowd_params = crowd
+        self.person_groups = None
+        if person_groups is not None and crowd is None:
+            raise ValueError("person_groups needs crowd=CrowdParams(...)")
+        if crowd is None:
+            return
+        if person_waypoints is None or person_n_waypoints is None:
+            raise ValueError("crowd needs person_waypoints [B,Np,K,2] and person_n_waypoints [B,Np]")
+        wp = np.ascontiguousarray(person_waypoints, np.float64)
+        assert wp.ndim == 4 and wp.shape[:2] == (B, Np) and wp.shape[3] == 2, "person_waypoints [B,Np,K,2]"
+        assert np.shape(person_n_waypoints) == (B, Np), "person_n_waypoints [B,Np]"
+        self.person_wp = self._upload(wp, np.float64)
+        self.person_nwp = self._upload(person_n_waypoints, np.int32)
+        self.person_cursor = self._zeros(B, Np, dtype=self.torch.int32)
+        self.person_speed = None
+        if person_speed is not None:
+            assert np.shape(person_speed) == (B, Np), "person_speed [B,Np]"
+            self.person_speed = self._upload(person_speed, np.float64)
+        if person_groups is not None:
+            assert np.shape(person_groups) == (B, Np), "person_groups [B,Np]"
+            self.person_groups = self._upload(person_groups, np.int32)
+            self.crowd_group_params = crowd_groups if crowd_groups is not None else CrowdGroupParams()
+
+    def _bind(self):
+        """Every struct a tick hands to the library, built once: every buffer the kernels read keeps its address from tick
+        to tick (the state is updated in place), and the stream lives in the solver's handle, so nothing here changes
+        when capture_graph moves the episode to another stream."""
+        prm, B, T, N = self.params, self.B, self.T, self.N
+        Np, planned, od = int(self.persons.shape[1]), self.plan is not None, (self.od_shared, self.od_h, self.od_w)
+        c = self._c = SimpleNamespace()
+        if planned:
+            L = int(self.plan.shape[1])
+            c.traj = point(BatchSolver.trajectorize_c(self.traj, B, L, 1),
+                           {"plan": self.plan, "plan_len": self.plan_len, "robot_pose": self.pose})
+            if self.plan_window is not None:  # the trajectorizer sees the window of the plan around the robot
+                c.window = point(SmpcPlanWindowBatch(B=B, L=L, on_device=1, max_robot_pose_search_dist=float(self.plan_window[0]),
+                                                     dist_threshold=float(self.plan_window[1])),
+                                 {"plan": self.plan, "plan_len": self.plan_len, "plan_start": self.plan_start, "robot_pose": self.pose})
+                point(c.traj, {"plan": self.window, "plan_len": self.window_len})
+            c.traj_out = point(SmpcTrajectorizeOut(), {"path": self.plan_path, "cmds": self.plan_cmds, "cmds_vy": self.traj_vy,
+                                                       "n_poses": self.traj_n, "error": self.traj_err})
+        c.people = point(SmpcPeopleBatch(B=B, Np=Np, N=N, on_device=1), {"people": self.persons, "count": self.person_count})
+        if self.fov_angle is not None:
+            point(c.people, {"robot_pose": self.pose, "costmap_origin": self.costmap_origin})
+            c.people.fov_angle, c.people.costmap_shared = float(self.fov_angle), 1 if self.costmap_shared else 0
+            c.people.size_x, c.people.size_y, c.people.resolution = self.size_x, self.size_y, self.resolution
+        c.memory = point(SmpcMemoryBatch(), {"prev_path": self.mem_path, "prev_cmds": self.mem_cmds, "valid": self.mem_valid,
+                                             "length": self.mem_length})
+        c.format = point(SmpcFormatBatch(B=B, T=T, path_rows=self.rows, on_device=1, time_step=float(prm.dt),
+                                         current_path_w=float(prm.current_path_weight),
+                                         current_cmds_w=float(prm.current_cmds_weight), memory=c.memory),
+                         {"path": self.plan_path, "cmds": self.plan_cmds, "speed": self.speed})
+        if planned:  # every robot with the horizon of its own trajectorized path
+            c.format.n_poses, c.format.max_poses = self.traj_n.data_ptr(), self.max_poses
+        c.format_out = point(SmpcFormatOut(), {"robot_status": self.robot_status, "pose0": self.pose0, "init_params": self.init_params,
+                                               "path_pts": self.path_pts, "goal_yaw": self.goal_yaw, "T_scene": self.T_scene})
+        c.projection = point(SmpcProjectionBatch(B=B, T=T, N=N, on_device=1, max_time=float(prm.max_time), time_step=float(prm.time_step)),
+                             {"init_people": self.people, "robot_path": self.robot_status})
+        set_od_grid(c.projection, "od_indexes", self.od_indexes, self.od_origin, self.od_resolution, od)
+        c.scenes = point(SmpcSceneBatch(B=B, T=T, N=N, on_device=1, dt=prm.dt, costmap_shared=1 if self.costmap_shared else 0,
+                                        size_x=self.size_x, size_y=self.size_y, resolution=self.resolution),
+                         {"pose0": self.pose0, "init_params": self.init_params, "path_pts": self.path_pts, "goal_yaw": self.goal_yaw,
+                          "people": self.people_proj, "has_people": self.has_people, "costmap": self.costmap,
+                          "costmap_origin": self.costmap_origin,
+                          "order": self.order if self.order_hint else None,  # longest scenes of the previous period first
+                          "T_scene": self.T_scene if planned else None, "scene_params": self.scene_params})
+        if self.crowd_params is not None:
+            c.crowd = point(BatchSolver.crowd_c(self.crowd_params, B, Np, int(self.person_wp.shape[2]), prm.dt, 1),
+                            {"robot_pose": self.pose, "robot_twist": self.cmd_vel, "count": self.person_count,
+                             "waypoints": self.person_wp, "n_waypoints": self.person_nwp, "desired_speeds": self.person_speed})
+            set_od_grid(c.crowd, "od_indexes", self.od_indexes, self.od_origin, self.od_resolution, od)
+            c.groups = None
+            if self.person_groups is not None:
+                c.groups = BatchSolver.crowd_groups_c(self.crowd_group_params, self.person_groups.data_ptr())
+        if self.metrics_params is not None:
+            c.metrics = point(BatchSolver.metrics_c(self.metrics_params, B, Np, prm.dt, 1),
+                              {"robot_pose": self.pose, "robot_twist": self.cmd_vel, "people": self.persons,
+                               "count": self.person_count, "goal": self.goal, "status": self.res["status"],
+                               "source": self.cmd_source})
+            if hasattr(self, "od_distances"):  # the clearance columns
+                set_od_grid(c.metrics, "od_distances", self.od_distances, self.od_origin, self.od_resolution, od)
 
     # -- trajectorizer (row f3) on the global plans, or the arc stand-in: v = 0.6, w = w_ref from the current pose --
     def _plan(self, timing: dict = None):
-        torch = self.torch
+        torch, s, c = self.torch, self.solver, self._c
         if self.plan is not None:
-            tb = self.solver.trajectorize_c(self.traj, self.B, int(self.plan.shape[1]), 1)
-            tb.plan, tb.plan_len, tb.robot_pose = self.plan.data_ptr(), self.plan_len.data_ptr(), self.pose.data_ptr()
-            if self.plan_window is not None:  # the trajectorizer sees the window of the plan around the robot
-                wb = SmpcPlanWindowBatch()
-                wb.B, wb.L, wb.on_device = self.B, int(self.plan.shape[1]), 1
-                wb.max_robot_pose_search_dist, wb.dist_threshold = float(self.plan_window[0]), float(self.plan_window[1])
-                wb.plan, wb.plan_len, wb.plan_start = self.plan.data_ptr(), self.plan_len.data_ptr(), self.plan_start.data_ptr()
-                wb.robot_pose = self.pose.data_ptr()
-                self.solver.transform_global_plan_device(wb, self.window.data_ptr(), self.window_len.data_ptr(), self.window_err.data_ptr())
+            if self.plan_window is not None:
+                s.transform_global_plan_device(c.window, self.window.data_ptr(), self.window_len.data_ptr(), self.window_err.data_ptr())
                 if timing is not None:
-                    timing["window_ms"] = self.solver.last_kernel_ms()
-                tb.plan, tb.plan_len = self.window.data_ptr(), self.window_len.data_ptr()
-            to = SmpcTrajectorizeOut()
-            to.path, to.cmds, to.cmds_vy = self.plan_path.data_ptr(), self.plan_cmds.data_ptr(), self.traj_vy.data_ptr()
-            to.n_poses, to.error = self.traj_n.data_ptr(), self.traj_err.data_ptr()
-            self.solver.trajectorize_device(tb, to)
+                    timing["window_ms"] = s.last_kernel_ms()
+            s.trajectorize_device(c.traj, c.traj_out)
             return
         dt = self.params.dt
         k = torch.arange(self.T + 1, dtype=torch.float64, device=self.dev)[None, :]
@@ -299,15 +391,12 @@ class BatchEpisode:
         self.plan_cmds[:, :, 0] = 0.6
         self.plan_cmds[:, :, 1] = self.w_ref[:, None]
 
-    def _memory_c(self) -> SmpcMemoryBatch:
-        mb = SmpcMemoryBatch()
-        mb.prev_path, mb.prev_cmds, mb.valid = self.mem_path.data_ptr(), self.mem_cmds.data_ptr(), self.mem_valid.data_ptr()
-        mb.length = self.mem_length.data_ptr()
-        return mb
+    def _host(self, *names, **renamed) -> dict:
+        """Host copies of device buffers for a TickRecord: {name: self.<name>} and {key: self.<attribute>}."""
+        return {k: getattr(self, a).cpu().numpy().copy() for k, a in [(n, n) for n in names] + list(renamed.items())}
 
     def _memory_host(self) -> dict:
-        return {"prev_path": self.mem_path.cpu().numpy().copy(), "prev_cmds": self.mem_cmds.cpu().numpy().copy(),
-                "valid": self.mem_valid.cpu().numpy().copy(), "length": self.mem_length.cpu().numpy().copy()}
+        return self._host(prev_path="mem_path", prev_cmds="mem_cmds", valid="mem_valid", length="mem_length")
 
     def tick(self, record: bool = False, timing: dict = None):
         """One controller period for all B robots. Returns a TickRecord when `record`, else None. `timing`: a dict
@@ -316,158 +405,90 @@ class BatchEpisode:
         if self.gstream is not None and torch.cuda.current_stream(self.dev) != self.gstream:
             with torch.cuda.stream(self.gstream):  # after capture_graph the library's handle lives on the capture stream
                 return self.tick(record, timing)
-        s, prm, B, T, N = self.solver, self.params, self.B, self.T, self.N
-        pose_before = self.pose.cpu().numpy().copy() if record else None
-        self._plan(timing)
-        if timing is not None and self.plan is not None:
-            timing["trajectorize_ms"] = s.last_kernel_ms()
+        s, c, B, T = self.solver, self._c, self.B, self.T
+        planned, windowed, crowd = self.plan is not None, self.plan_window is not None, self.crowd_params is not None
+
+        def timed(stage):
+            if timing is not None:
+                timing[stage + "_ms"] = s.last_kernel_ms()
+
         rec = {}
         if record:
-            if self.plan is not None:
-                rec.update(traj_n_poses=self.traj_n.cpu().numpy().copy())
-                if self.plan_window is not None:
-                    rec.update(window=self.window.cpu().numpy().copy(), window_len=self.window_len.cpu().numpy().copy(),
-                               plan_start=self.plan_start.cpu().numpy().copy())
-            rec.update(robot_pose=pose_before, persons=self.persons.cpu().numpy().copy(),
-                       person_count=self.person_count.cpu().numpy().copy())
-            if self.crowd_params is not None:
-                rec.update(cursor_before=self.person_cursor.cpu().numpy().copy())
-        # 0. field-of-view filter + people_to_status
-        qb = SmpcPeopleBatch()
-        qb.B, qb.Np, qb.N, qb.on_device = B, int(self.persons.shape[1]), N, 1
-        qb.people, qb.count = self.persons.data_ptr(), self.person_count.data_ptr()
-        if self.fov_angle is not None:
-            qb.robot_pose, qb.fov_angle = self.pose.data_ptr(), float(self.fov_angle)
-            qb.costmap_origin, qb.costmap_shared = self.costmap_origin.data_ptr(), 1 if self.costmap_shared else 0
-            qb.size_x, qb.size_y, qb.resolution = self.size_x, self.size_y, self.resolution
-        s.people_to_status_device(qb, self.people.data_ptr(), self.has_people.data_ptr())
-        if timing is not None:
-            timing["people_ms"] = s.last_kernel_ms()
+            rec.update(self._host(robot_pose="pose"))
+        self._plan(timing)
+        if planned:
+            timed("trajectorize")
         if record:
-            rec.update(plan_path=self.plan_path.cpu().numpy().copy(), plan_cmds=self.plan_cmds.cpu().numpy().copy(),
-                       speed=self.speed.cpu().numpy().copy(), init_people=self.people.cpu().numpy().copy(),
-                       has_people=self.has_people.cpu().numpy().copy(), memory_before=self._memory_host())
+            if planned:
+                rec.update(self._host(traj_n_poses="traj_n"))
+                if windowed:
+                    rec.update(self._host("window", "window_len", "plan_start"))
+            rec.update(self._host("persons", "person_count"))
+            if crowd:
+                rec.update(self._host(cursor_before="person_cursor"))
+        # 0. field-of-view filter + people_to_status
+        s.people_to_status_device(c.people, self.people.data_ptr(), self.has_people.data_ptr())
+        timed("people")
+        if record:
+            rec.update(self._host("plan_path", "plan_cmds", "speed", "has_people", init_people="people"),
+                       memory_before=self._memory_host())
         # 1. format_to_optimize + memory
-        fb = SmpcFormatBatch()
-        fb.B, fb.T, fb.path_rows, fb.on_device = B, T, self.rows, 1
-        fb.time_step = float(prm.dt)
-        fb.current_path_w, fb.current_cmds_w = float(prm.current_path_weight), float(prm.current_cmds_weight)
-        fb.path, fb.cmds, fb.speed = self.plan_path.data_ptr(), self.plan_cmds.data_ptr(), self.speed.data_ptr()
-        fb.memory = self._memory_c()
-        if self.plan is not None:  # every robot with the horizon of its own trajectorized path
-            fb.n_poses, fb.max_poses = self.traj_n.data_ptr(), self.max_poses
-        fo = SmpcFormatOut()
-        fo.robot_status, fo.pose0, fo.init_params = self.robot_status.data_ptr(), self.pose0.data_ptr(), self.init_params.data_ptr()
-        fo.path_pts, fo.goal_yaw = self.path_pts.data_ptr(), self.goal_yaw.data_ptr()
-        fo.T_scene = self.T_scene.data_ptr()
-        s.format_device(fb, fo)
-        if timing is not None:
-            timing["format_ms"] = s.last_kernel_ms()
+        s.format_device(c.format, c.format_out)
+        timed("format")
         # 2. project_people
-        pb = SmpcProjectionBatch()
-        pb.B, pb.T, pb.N, pb.on_device = B, T, N, 1
-        pb.max_time, pb.time_step = float(prm.max_time), float(prm.time_step)
-        pb.init_people, pb.robot_path = self.people.data_ptr(), self.robot_status.data_ptr()
-        pb.od_indexes, pb.od_shared = self.od_indexes.data_ptr(), self.od_shared
-        pb.od_width, pb.od_height, pb.od_resolution = self.od_w, self.od_h, self.od_resolution
-        pb.od_origin = self.od_origin.data_ptr()
-        s.project_people_device(pb, self.people_proj.data_ptr(), self.proj_error.data_ptr())
-        if timing is not None:
-            timing["project_ms"] = s.last_kernel_ms()
+        s.project_people_device(c.projection, self.people_proj.data_ptr(), self.proj_error.data_ptr())
+        timed("project")
         # 3. solve
-        sb = SmpcSceneBatch()
-        sb.B, sb.T, sb.N, sb.on_device = B, T, N, 1
-        sb.dt = prm.dt
-        sb.pose0, sb.init_params, sb.path_pts = self.pose0.data_ptr(), self.init_params.data_ptr(), self.path_pts.data_ptr()
-        sb.goal_yaw, sb.people, sb.has_people = self.goal_yaw.data_ptr(), self.people_proj.data_ptr(), self.has_people.data_ptr()
-        sb.costmap, sb.costmap_shared = self.costmap.data_ptr(), 1 if self.costmap_shared else 0
-        sb.size_x, sb.size_y = self.size_x, self.size_y
-        sb.costmap_origin, sb.resolution = self.costmap_origin.data_ptr(), self.resolution
-        if self.order_hint:
-            sb.order = self.order.data_ptr()  # longest scenes of the previous period first
-        if self.plan is not None:
-            sb.T_scene = self.T_scene.data_ptr()
-        if self.scene_params is not None:
-            sb.scene_params = self.scene_params.data_ptr()
-        s.solve_device(sb, self.rb)
-        if timing is not None:
-            timing["solve_ms"] = s.last_kernel_ms()
+        s.solve_device(c.scenes, self.rb)
+        timed("solve")
         if self.order_hint:
             self.order.copy_(BatchSolver.longest_first(self.res["evaluations"]))
         # 4. memory store (usable solves only; T_scene + 1 poses and commands of each)
-        mb = self._memory_c()
-        s.memory_store_device(B, T, self.res["status"].data_ptr(), self.res["path"].data_ptr(), self.res["cmds"].data_ptr(), mb,
-                              self.T_scene.data_ptr() if self.plan is not None else 0)
-        if timing is not None:
-            timing["store_ms"] = s.last_kernel_ms()
+        s.memory_store_device(B, T, self.res["status"].data_ptr(), self.res["path"].data_ptr(), self.res["cmds"].data_ptr(),
+                              c.memory, self.T_scene.data_ptr() if planned else 0)
+        timed("store")
         if record:
-            rec.update(T_scene=self.T_scene.cpu().numpy().copy())
-            if self.plan_window is not None:
-                rec.update(window_err=self.window_err.cpu().numpy().copy())
-            rec.update(robot_status=self.robot_status.cpu().numpy().copy(), pose0=self.pose0.cpu().numpy().copy(),
-                       init_params=self.init_params.cpu().numpy().copy(), path_pts=self.path_pts.cpu().numpy().copy(),
-                       goal_yaw=self.goal_yaw.cpu().numpy().copy(), people_proj=self.people_proj.cpu().numpy().copy(),
-                       proj_error=self.proj_error.cpu().numpy().copy(),
-                       result={k: v.cpu().numpy().copy() for k, v in self.res.items()}, memory_after=self._memory_host())
+            rec.update(self._host("T_scene", "robot_status", "pose0", "init_params", "path_pts", "goal_yaw", "people_proj",
+                                  "proj_error"), result={k: v.cpu().numpy().copy() for k, v in self.res.items()},
+                       memory_after=self._memory_host())
+            if windowed:
+                rec.update(self._host("window_err"))
         # 5. the command computeVelocityCommands returns (fallbacks included), then the world moves one period with it:
         #    a usable solve lands the robot on the first optimised pose, a fallback command is integrated with the
         #    trajectorizer's own motion model (x, y with the old heading, then the heading)
-        s.select_command_device(B, T, self.rows, self.traj_n.data_ptr() if self.plan is not None else 0,
+        s.select_command_device(B, T, self.rows, self.traj_n.data_ptr() if planned else 0,
                                 self.plan_cmds.data_ptr(), self.res["status"].data_ptr(), self.res["cmds"].data_ptr(),
-                                self.cmd_vel.data_ptr(), self.cmd_source.data_ptr(),
-                                self.window_err.data_ptr() if self.plan_window is not None else 0)
-        dt = prm.dt
-        if self.crowd_params is not None:  # the persons' period: they see the pose it starts from and the command executed
+                                self.cmd_vel.data_ptr(), self.cmd_source.data_ptr(), self.window_err.data_ptr() if windowed else 0)
+        dt = self.params.dt
+        if crowd:  # the persons' period: they see the pose it starts from and the command executed
             self._crowd_step()
-            if timing is not None:
-                timing["crowd_ms"] = s.last_kernel_ms()
+            timed("crowd")
         v, w, th = self.cmd_vel[:, 0], self.cmd_vel[:, 1], self.pose[:, 2]
         moved = torch.stack([self.pose[:, 0] + v * torch.cos(th) * dt, self.pose[:, 1] + v * torch.sin(th) * dt, th + w * dt], dim=1)
         optimised = (self.cmd_source == 0)[:, None]
-        # state is updated in place: every buffer the kernels read keeps its address from tick to tick (capture_graph)
+        # state is updated in place: every buffer the kernels read keeps its address from tick to tick (_bind)
         self.pose.copy_(torch.where(optimised, self.res["path"][:, 0, :], moved))
         self.speed.copy_(self.cmd_vel)
-        if self.crowd_params is None:
+        if not crowd:
             self.persons[:, :, 0] += self.persons[:, :, 2] * dt
             self.persons[:, :, 1] += self.persons[:, :, 3] * dt
         if self.metrics_params is not None:  # 6. one metrics sample of the world as the period leaves it
             self._metrics_sample()
-            if timing is not None:
-                timing["metrics_ms"] = s.last_kernel_ms()
+            timed("metrics")
         if record:
-            rec.update(pose_after=self.pose.cpu().numpy().copy(), persons_after=self.persons.cpu().numpy().copy(),
-                       cmd_vel=self.cmd_vel.cpu().numpy().copy(), cmd_source=self.cmd_source.cpu().numpy().copy())
-            if self.crowd_params is not None:
-                rec.update(cursor_after=self.person_cursor.cpu().numpy().copy())
+            rec.update(self._host("cmd_vel", "cmd_source", pose_after="pose", persons_after="persons"))
+            if crowd:
+                rec.update(self._host(cursor_after="person_cursor"))
         self.ticks += 1
         return TickRecord(**rec) if record else None
 
     def _crowd_step(self, groups: bool = True):
-        Np = int(self.persons.shape[1])
-        cb = BatchSolver.crowd_c(self.crowd_params, self.B, Np, int(self.person_wp.shape[2]), self.params.dt, 1)
-        cb.robot_pose, cb.robot_twist, cb.count = self.pose.data_ptr(), self.cmd_vel.data_ptr(), self.person_count.data_ptr()
-        cb.waypoints, cb.n_waypoints = self.person_wp.data_ptr(), self.person_nwp.data_ptr()
-        if self.person_speed is not None:
-            cb.desired_speeds = self.person_speed.data_ptr()
-        cb.od_indexes, cb.od_origin = self.od_indexes.data_ptr(), self.od_origin.data_ptr()
-        cb.od_shared, cb.od_width, cb.od_height, cb.od_resolution = self.od_shared, self.od_w, self.od_h, self.od_resolution
-        gb = None
-        if groups and self.person_groups is not None:
-            gb = BatchSolver.crowd_groups_c(self.crowd_group_params, self.person_groups.data_ptr())
-        self.solver.crowd_step_device(cb, self.persons.data_ptr(), self.person_cursor.data_ptr(), gb)
+        """One crowd period; groups=False: the plain step even when the episode has groups."""
+        self.solver.crowd_step_device(self._c.crowd, self.persons.data_ptr(), self.person_cursor.data_ptr(),
+                                      self._c.groups if groups else None)
 
     def _metrics_sample(self):
-        mb = BatchSolver.metrics_c(self.metrics_params, self.B, int(self.persons.shape[1]), self.params.dt, 1)
-        mb.robot_pose, mb.robot_twist = self.pose.data_ptr(), self.cmd_vel.data_ptr()
-        mb.people, mb.count = self.persons.data_ptr(), self.person_count.data_ptr()
-        if self.goal is not None:
-            mb.goal = self.goal.data_ptr()
-        od = getattr(self, "od_distances", None)
-        if od is not None:
-            mb.od_distances, mb.od_origin = od.data_ptr(), self.od_origin.data_ptr()
-            mb.od_shared, mb.od_width, mb.od_height, mb.od_resolution = self.od_shared, self.od_w, self.od_h, self.od_resolution
-        mb.status, mb.source = self.res["status"].data_ptr(), self.cmd_source.data_ptr()
-        self.solver.episode_metrics_device(mb, self.metrics_acc.data_ptr())
+        self.solver.episode_metrics_device(self._c.metrics, self.metrics_acc.data_ptr())
 
     def metrics(self) -> np.ndarray:
         """Host copy of the metrics rows [B,24] (columns solver.METRIC_COLS) accumulated so far."""
@@ -512,6 +533,25 @@ class BatchEpisode:
 
     def synchronize(self):
         self.torch.cuda.synchronize()
+
+
+def shard_kwargs(kwargs: dict, idx: np.ndarray, B: int) -> dict:
+    """BatchEpisode's keyword arguments for the robots `idx` of a batch of B, from those for the whole batch: the rows idx
+    of the per-robot arrays (BatchEpisode.PER_ROBOT, and PER_GRID when there is a grid per scene: od_indexes [B,h,w] with
+    B > 1), every other one (FORWARDED) as it is. A name BatchEpisode declares in none of the three is refused."""
+    unknown = set(kwargs) - set(BatchEpisode.PER_ROBOT + BatchEpisode.PER_GRID + BatchEpisode.FORWARDED)
+    if unknown:
+        raise TypeError(f"BatchEpisode declares {sorted(unknown)} neither per robot nor forwarded")
+    od = kwargs.get("od_indexes")
+    per_scene = od is not None and np.ndim(od) == 3 and np.shape(od)[0] > 1
+    rows = BatchEpisode.PER_ROBOT + (BatchEpisode.PER_GRID if per_scene else ())
+    out = {}
+    for k, v in kwargs.items():
+        if k in rows and v is not None:
+            assert np.shape(v)[0] == B, f"{k}: one row per robot"
+            v = np.asarray(v)[idx]
+        out[k] = v
+    return out
 
 
 def concurrent_streams(n: int, device: str, candidates: int = 12):
@@ -569,14 +609,10 @@ class ShardedEpisode:
     are those of the one-stream episode bit for bit (kernels take every decision per scene / per lane)."""
 
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray,
-                 od_origin: np.ndarray, od_resolution: float, device: int = 0, plan: np.ndarray = None,
-                 plan_len: np.ndarray = None, traj_params: TrajectorizerParams = None, fov_angle: float = None,
-                 shards: int = 3, order_hint: bool = False, graphs: bool = True, solve_share: int = None,
-                 plan_window: tuple = None, obstacles_from_costmap: bool = False, obstacle_min_cost: int = 254,
-                 unknown_is_obstacle: bool = False, scene_params: np.ndarray = None, metrics: MetricsParams = None,
-                 goal: np.ndarray = None, od_distances: np.ndarray = None, crowd: CrowdParams = None,
-                 person_waypoints: np.ndarray = None, person_n_waypoints: np.ndarray = None, person_speed: np.ndarray = None,
-                 person_groups: np.ndarray = None, crowd_groups: CrowdGroupParams = None):
+                 od_origin: np.ndarray, od_resolution: float, device: int = 0, shards: int = 3, graphs: bool = True,
+                 solve_share: int = None, **episode_kw):
+        """episode_kw: the other keyword arguments of BatchEpisode, for all B robots; every shard gets its robots' part
+        of them (shard_kwargs)."""
         import torch
 
         self.torch = torch
@@ -586,25 +622,11 @@ class ShardedEpisode:
         self.slices = [slice(edges[k], edges[k + 1]) for k in range(shards) if edges[k + 1] > edges[k]]
         self.streams = concurrent_streams(len(self.slices), f"cuda:{device}")
         self.parts = []
-        od_indexes = None if od_indexes is None else np.asarray(od_indexes)
-        per_scene_od = od_indexes is not None and od_indexes.ndim == 3 and od_indexes.shape[0] > 1
+        kw = dict(episode_kw, od_indexes=od_indexes, od_origin=od_origin, od_resolution=od_resolution, device=device)
         for sl, st in zip(self.slices, self.streams):
             idx = np.arange(sl.start, sl.stop)
-            odi, odo = (od_indexes[idx], np.asarray(od_origin)[idx]) if per_scene_od else (od_indexes, od_origin)
-            odd = np.asarray(od_distances)[idx] if per_scene_od and od_distances is not None else od_distances
             with torch.cuda.stream(st):  # the shard's solver handle binds to the stream current at construction
-                self.parts.append(BatchEpisode(
-                    params, scenes.select(idx), np.asarray(w_ref)[idx], odi, odo, od_resolution, device=device,
-                    plan=None if plan is None else plan[idx], plan_len=None if plan_len is None else plan_len[idx],
-                    traj_params=traj_params, fov_angle=fov_angle, order_hint=order_hint, plan_window=plan_window,
-                    obstacles_from_costmap=obstacles_from_costmap, obstacle_min_cost=obstacle_min_cost,
-                    unknown_is_obstacle=unknown_is_obstacle,
-                    scene_params=None if scene_params is None else np.asarray(scene_params)[idx],
-                    metrics=metrics, goal=None if goal is None else np.asarray(goal)[idx], od_distances=odd, crowd=crowd,
-                    person_waypoints=None if person_waypoints is None else np.asarray(person_waypoints)[idx],
-                    person_n_waypoints=None if person_n_waypoints is None else np.asarray(person_n_waypoints)[idx],
-                    person_speed=None if person_speed is None else np.asarray(person_speed)[idx],
-                    person_groups=None if person_groups is None else np.asarray(person_groups)[idx], crowd_groups=crowd_groups))
+                self.parts.append(BatchEpisode(params, scenes.select(idx), np.asarray(w_ref)[idx], **shard_kwargs(kw, idx, B)))
         self.B = B
         self.graphs = graphs
         for part in self.parts:  # every shard's persistent solve grid takes its share of the resident wavefronts

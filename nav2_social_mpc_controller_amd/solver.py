@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
-                   SmpcObstacleDistanceOut, SmpcParams, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
+                   SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
 from .params import CrowdGroupParams, CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams
 from .scenes import SceneBatch
@@ -52,68 +52,60 @@ def load_library():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    lib.smpc_abi_version.restype = C.c_int
-    lib.smpc_last_error.restype = C.c_char_p
-    lib.smpc_params_default.argtypes = [C.POINTER(SmpcParams)]
-    lib.smpc_params_default.restype = None
-    lib.smpc_dims.restype = C.c_int
-    lib.smpc_dims.argtypes = [C.POINTER(SmpcParams), C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 6
-    lib.smpc_create.restype = C.c_void_p
-    lib.smpc_create.argtypes = [C.POINTER(SmpcParams), C.c_int]
-    lib.smpc_destroy.argtypes = [C.c_void_p]
-    lib.smpc_destroy.restype = None
-    lib.smpc_set_stream.argtypes = [C.c_void_p, C.c_void_p]
-    lib.smpc_set_stream.restype = C.c_int
-    lib.smpc_set_solve_share.argtypes = [C.c_void_p, C.c_int32]
-    lib.smpc_set_solve_share.restype = C.c_int
-    lib.smpc_solve_slot_width.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
-    lib.smpc_solve_slot_width.restype = C.c_int
-    lib.smpc_solve_batch.argtypes = [C.c_void_p, C.POINTER(SmpcSceneBatch), C.POINTER(SmpcResultBatch)]
-    lib.smpc_solve_batch.restype = C.c_int
-    lib.smpc_solve_trace_batch.argtypes = [C.c_void_p, C.POINTER(SmpcSceneBatch), C.POINTER(SmpcResultBatch), C.POINTER(SmpcTraceOut)]
-    lib.smpc_solve_trace_batch.restype = C.c_int
-    lib.smpc_eval_batch.argtypes = [C.c_void_p, C.POINTER(SmpcSceneBatch), C.c_void_p, C.POINTER(SmpcEvalOut)]
-    lib.smpc_eval_batch.restype = C.c_int
-    lib.smpc_project_people_batch.argtypes = [C.c_void_p, C.POINTER(SmpcProjectionBatch), C.c_void_p, C.c_void_p]
-    lib.smpc_project_people_batch.restype = C.c_int
-    lib.smpc_obstacle_distance_batch.argtypes = [C.c_void_p, C.POINTER(SmpcObstacleDistanceIn), C.POINTER(SmpcObstacleDistanceOut)]
-    lib.smpc_obstacle_distance_batch.restype = C.c_int
-    lib.smpc_people_to_status_batch.argtypes = [C.c_void_p, C.POINTER(SmpcPeopleBatch), C.c_void_p, C.c_void_p]
-    lib.smpc_people_to_status_batch.restype = C.c_int
-    lib.smpc_format_to_optimize_batch.argtypes = [C.c_void_p, C.POINTER(SmpcFormatBatch), C.POINTER(SmpcFormatOut)]
-    lib.smpc_format_to_optimize_batch.restype = C.c_int
-    lib.smpc_memory_store_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.POINTER(SmpcMemoryBatch), C.c_void_p]
-    lib.smpc_memory_store_batch.restype = C.c_int
-    lib.smpc_trajectorize_path_batch.argtypes = [C.c_void_p, C.POINTER(SmpcTrajectorizeBatch), C.POINTER(SmpcTrajectorizeOut)]
-    lib.smpc_trajectorize_path_batch.restype = C.c_int
-    lib.smpc_transform_global_plan_batch.argtypes = [C.c_void_p, C.POINTER(SmpcPlanWindowBatch), C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.smpc_transform_global_plan_batch.restype = C.c_int
-    lib.smpc_select_command_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7
-    lib.smpc_select_command_batch.restype = C.c_int
-    lib.smpc_episode_metrics_batch.argtypes = [C.c_void_p, C.POINTER(SmpcMetricsBatch), C.c_void_p]
-    lib.smpc_episode_metrics_batch.restype = C.c_int
-    lib.smpc_crowd_step_batch.argtypes = [C.c_void_p, C.POINTER(SmpcCrowdBatch), C.c_void_p, C.c_void_p]
-    lib.smpc_crowd_step_batch.restype = C.c_int
-    lib.smpc_crowd_step_groups_batch.argtypes = [C.c_void_p, C.POINTER(SmpcCrowdBatch), C.POINTER(SmpcCrowdGroups), C.c_void_p, C.c_void_p]
-    lib.smpc_crowd_step_groups_batch.restype = C.c_int
-    lib.smpc_stage_people_batch.argtypes = [C.c_void_p, C.POINTER(SmpcSceneBatch), C.c_void_p, C.c_void_p]
-    lib.smpc_stage_people_batch.restype = C.c_int
-    lib.smpc_fp64_peak_probe.argtypes = [C.c_void_p, C.c_int32]
-    lib.smpc_fp64_peak_probe.restype = C.c_double
-    lib.smpc_math_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4
-    lib.smpc_math_probe.restype = C.c_int
-    lib.smpc_last_kernel_ms.argtypes = [C.c_void_p]
-    lib.smpc_last_kernel_ms.restype = C.c_double
+    for name, (restype, argtypes) in _abi.FUNCTIONS.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
         raise SmpcError("libsmpc_hip.so ABI version mismatch")
     _lib = lib
     return lib
 
 
-def _check(lib, rc, what):
-    if rc != 0:
-        raise SmpcError(f"{what} failed ({rc}): {lib.smpc_last_error().decode()}")
+def _ptr(a):
+    """Address of a numpy array or a torch tensor; None (a NULL field) and plain addresses pass through."""
+    if a is None or isinstance(a, int):
+        return a or None
+    return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+
+
+def point(struct, arrays: dict):
+    """Point the fields of `struct` named by the keys of `arrays` at its numpy arrays or torch tensors."""
+    for k, v in arrays.items():
+        setattr(struct, k, _ptr(v))
+    return struct
+
+
+def _alloc(spec: dict, device=None) -> dict:
+    """The buffers `spec` declares, name -> (shape, dtype name, fill): host arrays (fill None: zeros) without `device`,
+    else torch tensors on it (fill None: uninitialised)."""
+    if device is None:
+        return {k: np.full(shape, 0 if fill is None else fill, dtype) for k, (shape, dtype, fill) in spec.items()}
+    import torch
+
+    return {k: torch.empty(shape, dtype=getattr(torch, dtype), device=device) if fill is None else
+            torch.full(shape, fill, dtype=getattr(torch, dtype), device=device) for k, (shape, dtype, fill) in spec.items()}
+
+
+_OD_DTYPE = {"od_indexes": np.uint32, "od_distances": np.float32}
+
+
+def set_od_grid(st, field: str, grid, origin, resolution: float, dims: tuple = None, B: int = None):
+    """Fill the ObstacleDistance-grid fields of `st` (SmpcProjectionBatch, SmpcMetricsBatch, SmpcCrowdBatch): `field`
+    ("od_indexes" or "od_distances"), od_origin, od_shared, od_height, od_width and od_resolution.
+    dims = (shared, h, w): grid and origin are addresses or device tensors of a grid of that shape.
+    dims = None: host arrays of a batch of B scenes, grid [h,w] + origin [2] one grid shared by all of them, grid [B,h,w] +
+    origin [B,2] one per scene. Returns the arrays `st` then points into (they must outlive the call)."""
+    if dims is None:
+        grid = np.ascontiguousarray(grid, _OD_DTYPE[field])
+        origin = np.ascontiguousarray(origin, np.float64).reshape(-1, 2)
+        shared = grid.ndim == 2
+        assert shared or grid.shape[0] == B
+        assert origin.shape == ((1, 2) if shared else (B, 2))
+        dims = (shared, grid.shape[-2], grid.shape[-1])
+    setattr(st, field, _ptr(grid) if dims[1] * dims[2] else None)
+    st.od_origin = _ptr(origin)
+    st.od_shared, st.od_height, st.od_width, st.od_resolution = int(dims[0]), int(dims[1]), int(dims[2]), float(resolution)
+    return grid, origin
 
 
 def summarize_metrics(acc: np.ndarray, dt: float) -> dict:
@@ -152,7 +144,10 @@ def summarize_metrics(acc: np.ndarray, dt: float) -> dict:
 
 
 class BatchSolver:
-    """One solver bound to one HIP device; mirrors Optimizer::initialize + Optimizer::optimize for B scenes."""
+    """One solver bound to one HIP device; mirrors Optimizer::initialize + Optimizer::optimize for B scenes.
+    Every entry point has a host method (numpy arrays in and out: it converts, allocates and sets on_device = 0) and a
+    `*_device` method (structs and addresses of device memory, asynchronous on the handle's stream); both end in the same
+    `_call` of the library function."""
 
     def __init__(self, params: OptimizerParams, device: int = 0):
         self.lib = load_library()
@@ -174,19 +169,24 @@ class BatchSolver:
         except Exception:
             pass
 
+    def _call(self, name: str, *args) -> int:
+        """lib.<name>(handle, *args), as _abi.FUNCTIONS declares it (a struct goes by reference, an int or None is an
+        address); a negative result code raises with the library's message. Returns the result (0, or a count)."""
+        rc = getattr(self.lib, name)(self._h, *args)
+        if rc < 0:
+            raise SmpcError(f"{name} failed ({rc}): {self.lib.smpc_last_error().decode()}")
+        return rc
+
     def set_stream(self, stream_ptr: int):
-        _check(self.lib, self.lib.smpc_set_stream(self._h, C.c_void_p(stream_ptr)), "smpc_set_stream")
+        self._call("smpc_set_stream", stream_ptr)
 
     def set_solve_share(self, n: int):
         """smpc_set_solve_share: this handle's solve launches leave room for n - 1 concurrent ones (other streams)."""
-        _check(self.lib, self.lib.smpc_set_solve_share(self._h, int(n)), "smpc_set_solve_share")
+        self._call("smpc_set_solve_share", int(n))
 
     def solve_slot_width(self, B: int, T: int, N: int) -> int:
         """smpc_solve_slot_width: 32 (two scenes per wave) or 64 (one) for a solve launch of this shape."""
-        w = self.lib.smpc_solve_slot_width(self._h, int(B), int(T), int(N))
-        if w < 0:
-            _check(self.lib, w, "smpc_solve_slot_width")
-        return w
+        return self._call("smpc_solve_slot_width", int(B), int(T), int(N))
 
     def math_probe(self, fn: int, a: np.ndarray, b: np.ndarray = None):
         """smpc_math_probe: the sweep's elementary functions evaluated on the device (see include/smpc.h)."""
@@ -195,8 +195,7 @@ class BatchSolver:
         bb = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
         o0 = np.empty(n)
         o1 = np.empty(n)
-        _check(self.lib, self.lib.smpc_math_probe(self._h, int(fn), n, a.ctypes.data, None if bb is None else bb.ctypes.data,
-                                                  o0.ctypes.data, o1.ctypes.data), "smpc_math_probe")
+        self._call("smpc_math_probe", int(fn), n, _ptr(a), _ptr(bb), _ptr(o0), _ptr(o1))
         return o0, o1
 
     def fp64_peak_tflops(self, iters: int = 20000) -> float:
@@ -206,25 +205,42 @@ class BatchSolver:
     def last_kernel_ms(self) -> float:
         return float(self.lib.smpc_last_kernel_ms(self._h))
 
+    # -- what the entry points write, declared once: name -> (shape, dtype, fill) for _alloc -------------------------
+    def _result_spec(self, B: int, T: int) -> dict:
+        """The arrays of SmpcResultBatch."""
+        P = self.params.dims(T, True)[3]
+        return {"params": ((B, P), "float64", None), "cmds": ((B, T + 1, 2), "float64", None),
+                "path": ((B, T + 1, 3), "float64", None), "status": ((B,), "int32", None), "reason": ((B,), "int32", None),
+                "iterations": ((B,), "int32", None), "evaluations": ((B,), "int32", None),
+                "initial_cost": ((B,), "float64", None), "final_cost": ((B,), "float64", None)}
+
+    def _eval_spec(self, B: int, T: int) -> dict:
+        """The arrays of SmpcEvalOut."""
+        CH, bl, nb, P, M, _ = self.params.dims(T, True)
+        return {"residuals": ((B, M), "float64", None), "jacobian": ((B, M, P), "float64", None),
+                "cost": ((B,), "float64", None), "gradient": ((B, P), "float64", None)}
+
+    def _trace_out(self, B: int, max_rows, device=None):
+        """(SmpcTraceOut, its buffers): "trace" [B, max_rows, 9] filled with NaN, "trace_rows" [B]; max_rows defaults to
+        max_iterations + 1, which holds every row."""
+        max_rows = self.params.max_iterations + 1 if max_rows is None else int(max_rows)
+        if max_rows < 0:
+            raise SmpcError(f"max_rows must be >= 0, got {max_rows}")
+        t = _alloc({"trace": ((B, max_rows, _abi.SMPC_TRACE_COLS), "float64", float("nan")),
+                    "trace_rows": ((B,), "int32", 0)}, device)
+        return SmpcTraceOut(_ptr(t["trace"]) if B * max_rows else None, max_rows, _ptr(t["trace_rows"])), t
+
     # -- host-memory path (stages through HBM inside the library) ---------------------------------
     def _solve_call(self, scenes: SceneBatch, order):
         """What solve() and solve_trace() hand to the library: (result dict of host arrays, SmpcSceneBatch, SmpcResultBatch,
         the arrays the structs point into)."""
-        CH, bl, nb, P, M, _ = self.params.dims(scenes.T, True)
-        scenes.validate(P)
-        B, T = scenes.B, scenes.T
-        out = {
-            "params": np.zeros((B, P)), "cmds": np.zeros((B, T + 1, 2)), "path": np.zeros((B, T + 1, 3)),
-            "status": np.zeros(B, np.int32), "reason": np.zeros(B, np.int32), "iterations": np.zeros(B, np.int32),
-            "evaluations": np.zeros(B, np.int32), "initial_cost": np.zeros(B), "final_cost": np.zeros(B),
-        }
-        rb = SmpcResultBatch()
-        for k, v in out.items():
-            setattr(rb, k, v.ctypes.data)
+        scenes.validate(self.params.dims(scenes.T, True)[3])
+        out = _alloc(self._result_spec(scenes.B, scenes.T))
+        rb = point(SmpcResultBatch(), out)
         sb = scenes.to_c()
         if order is not None:
             order = np.ascontiguousarray(order, np.int32)
-            assert order.shape == (B,)
+            assert order.shape == (scenes.B,)
             sb.order = order.ctypes.data
         return out, sb, rb, order
 
@@ -233,23 +249,36 @@ class BatchSolver:
         permutation of 0..B-1 (smpc_scene_batch.order: longest scenes first shortens a lone launch; results do not
         depend on it)."""
         out, sb, rb, _keep = self._solve_call(scenes, order)
-        _check(self.lib, self.lib.smpc_solve_batch(self._h, C.byref(sb), C.byref(rb)), "smpc_solve_batch")
+        self._call("smpc_solve_batch", sb, rb)
         return out
+
+    def solve_device(self, sb: SmpcSceneBatch, rb: SmpcResultBatch):
+        assert sb.on_device == 1
+        self._call("smpc_solve_batch", sb, rb)
+
+    def alloc_results(self, B: int, T: int, device="cuda:0"):
+        t = _alloc(self._result_spec(B, T), device)
+        return point(SmpcResultBatch(), t), t
 
     def solve_trace(self, scenes: SceneBatch, order: np.ndarray = None, max_rows: int = None):
         """solve() that also returns the per-iteration record of every scene (optimizer.debug_optimizer; smpc_solve_trace_batch):
         "trace" [B, max_rows, 9], columns TRACE_COLS, row i = LM iteration i, NaN where a scene has no row; "trace_rows" [B],
         the rows each solve produced (more than max_rows: the rest were dropped). max_rows defaults to max_iterations + 1,
         which holds every row. The other entries are those of solve(), bit for bit."""
-        max_rows = self.params.max_iterations + 1 if max_rows is None else int(max_rows)
-        if max_rows < 0:
-            raise SmpcError(f"max_rows must be >= 0, got {max_rows}")
+        to, trace = self._trace_out(scenes.B, max_rows)
         out, sb, rb, _keep = self._solve_call(scenes, order)
-        out["trace"] = np.full((scenes.B, max_rows, _abi.SMPC_TRACE_COLS), np.nan)
-        out["trace_rows"] = np.zeros(scenes.B, np.int32)
-        to = SmpcTraceOut(out["trace"].ctypes.data if out["trace"].size else None, max_rows, out["trace_rows"].ctypes.data)
-        _check(self.lib, self.lib.smpc_solve_trace_batch(self._h, C.byref(sb), C.byref(rb), C.byref(to)), "smpc_solve_trace_batch")
+        out.update(trace)
+        self._call("smpc_solve_trace_batch", sb, rb, to)
         return out
+
+    def alloc_trace(self, B: int, max_rows: int = None, device="cuda:0"):
+        """(SmpcTraceOut, tensors) for solve_trace_device: "trace" [B, max_rows, 9] filled with NaN, "trace_rows" [B]."""
+        return self._trace_out(B, max_rows, device)
+
+    def solve_trace_device(self, sb: SmpcSceneBatch, rb: SmpcResultBatch, to: SmpcTraceOut):
+        """solve_device that also records the per-iteration rows (alloc_trace); asynchronous on the handle's stream."""
+        assert sb.on_device == 1
+        self._call("smpc_solve_trace_batch", sb, rb, to)
 
     @staticmethod
     def longest_first(evaluations):
@@ -274,20 +303,43 @@ class BatchSolver:
         return perm
 
     def evaluate(self, scenes: SceneBatch, x: np.ndarray, row_order: int = 0):
-        CH, bl, nb, P, M, _ = self.params.dims(scenes.T, True)
+        P = self.params.dims(scenes.T, True)[3]
         scenes.validate(P)
-        B = scenes.B
         x = np.ascontiguousarray(x, dtype=np.float64)
-        assert x.shape == (B, P)
-        out = {"residuals": np.zeros((B, M)), "jacobian": np.zeros((B, M, P)), "cost": np.zeros(B),
-               "gradient": np.zeros((B, P))}
-        eo = SmpcEvalOut()
-        for k, v in out.items():
-            setattr(eo, k, v.ctypes.data)
-        eo.row_order = int(row_order)
-        sb = scenes.to_c()
-        _check(self.lib, self.lib.smpc_eval_batch(self._h, C.byref(sb), x.ctypes.data, C.byref(eo)), "smpc_eval_batch")
+        assert x.shape == (scenes.B, P)
+        out = _alloc(self._eval_spec(scenes.B, scenes.T))
+        eo = point(SmpcEvalOut(row_order=int(row_order)), out)
+        self._call("smpc_eval_batch", scenes.to_c(), _ptr(x), eo)
         return out
+
+    def alloc_eval(self, B: int, T: int, device="cuda:0", row_order: int = 0):
+        t = _alloc(self._eval_spec(B, T), device)
+        return point(SmpcEvalOut(row_order=int(row_order)), t), t
+
+    def eval_device(self, sb: SmpcSceneBatch, x_ptr: int, eo: SmpcEvalOut):
+        assert sb.on_device == 1
+        self._call("smpc_eval_batch", sb, x_ptr, eo)
+
+    def stage_people(self, scenes: SceneBatch):
+        """smpc_stage_people_batch on host arrays: (records [B,N,T,4], aux [B,T,2])."""
+        B, T, N = scenes.B, scenes.T, scenes.N
+        rec = np.zeros((B, N, T, 4))
+        aux = np.zeros((B, T, 2))
+        self._call("smpc_stage_people_batch", scenes.to_c(), _ptr(rec), _ptr(aux))
+        return rec, aux
+
+    def stage_people_device(self, sb: SmpcSceneBatch, device="cuda:0"):
+        """Stage the device-resident people block of `sb` once and attach the result to it: later solve_device /
+        eval_device calls with this batch read the staged records instead of running the staging pass again.
+        Returns the tensors that own the memory (keep them alive as long as `sb` is used)."""
+        import torch
+
+        assert sb.on_device == 1
+        rec = torch.zeros((sb.B, sb.N, sb.T, 4), dtype=torch.float64, device=device)
+        aux = torch.zeros((sb.B, sb.T, 2), dtype=torch.float64, device=device)
+        self._call("smpc_stage_people_batch", sb, rec.data_ptr(), aux.data_ptr())
+        sb.people_records, sb.people_aux = rec.data_ptr(), aux.data_ptr()
+        return rec, aux
 
     # -- people projection (SURVEY §8 row f1): Optimizer::project_people for B scenes -------------
     def project_people(self, init_people: np.ndarray, robot_path: np.ndarray, od_indexes: np.ndarray,
@@ -296,24 +348,22 @@ class BatchSolver:
         Returns (people_proj [B,T+1,6,N], error [B])."""
         init_people = np.ascontiguousarray(init_people, np.float64)
         robot_path = np.ascontiguousarray(robot_path, np.float64)
-        od_indexes = np.ascontiguousarray(od_indexes, np.uint32)
-        od_origin = np.ascontiguousarray(od_origin, np.float64)
         B, N, _ = init_people.shape
         T = robot_path.shape[1] - 1
-        pb = SmpcProjectionBatch()
-        pb.B, pb.T, pb.N, pb.on_device = B, T, N, 0
-        pb.max_time, pb.time_step = float(max_time), float(time_step)
+        pb = SmpcProjectionBatch(B=B, T=T, N=N, on_device=0, max_time=float(max_time), time_step=float(time_step))
         pb.init_people, pb.robot_path = init_people.ctypes.data, robot_path.ctypes.data
-        pb.od_indexes = od_indexes.ctypes.data if od_indexes.size else None
-        pb.od_shared = 1 if od_indexes.shape[0] == 1 else 0
-        pb.od_height, pb.od_width = (int(od_indexes.shape[1]), int(od_indexes.shape[2])) if od_indexes.ndim == 3 else (0, 0)
-        pb.od_resolution = float(od_resolution)
-        pb.od_origin = od_origin.ctypes.data
+        od_indexes = np.asarray(od_indexes)
+        if od_indexes.ndim == 3 and od_indexes.shape[0] == 1:  # [1,h,w]: the one grid of all scenes
+            od_indexes = od_indexes[0]
+        _keep = set_od_grid(pb, "od_indexes", od_indexes, od_origin, od_resolution, B=B)
         out = np.zeros((B, T + 1, 6, N))
         err = np.zeros(B, np.int32)
-        _check(self.lib, self.lib.smpc_project_people_batch(self._h, C.byref(pb), out.ctypes.data, err.ctypes.data),
-               "smpc_project_people_batch")
+        self._call("smpc_project_people_batch", pb, _ptr(out), _ptr(err))
         return out, err
+
+    def project_people_device(self, pb: SmpcProjectionBatch, out_ptr: int, err_ptr: int):
+        assert pb.on_device == 1
+        self._call("smpc_project_people_batch", pb, out_ptr, err_ptr)
 
     # -- the ObstacleDistance grid of the projection, from the costmaps (smpc_obstacle_distance_batch) -----------
     @staticmethod
@@ -341,10 +391,7 @@ class BatchSolver:
         ob.costmap = cm.ctypes.data if cm.size else None
         out = {"indexes": np.zeros(cm.shape, np.uint32), "distances": np.zeros(cm.shape, np.float32) if distances else None,
                "n_obstacles": np.zeros(G, np.int32)}
-        oo = SmpcObstacleDistanceOut()
-        oo.indexes, oo.n_obstacles = out["indexes"].ctypes.data, out["n_obstacles"].ctypes.data
-        oo.distances = out["distances"].ctypes.data if distances else None
-        _check(self.lib, self.lib.smpc_obstacle_distance_batch(self._h, C.byref(ob), C.byref(oo)), "smpc_obstacle_distance_batch")
+        self._call("smpc_obstacle_distance_batch", ob, point(SmpcObstacleDistanceOut(), out))
         if shared:
             out["indexes"] = out["indexes"][0]
             out["distances"] = None if out["distances"] is None else out["distances"][0]
@@ -354,9 +401,8 @@ class BatchSolver:
                                  n_obstacles_ptr: int = 0):
         """Device pointers in and out (ob.on_device == 1), asynchronous on the handle's stream."""
         assert ob.on_device == 1
-        oo = SmpcObstacleDistanceOut()
-        oo.indexes, oo.distances, oo.n_obstacles = indexes_ptr or None, distances_ptr or None, n_obstacles_ptr or None
-        _check(self.lib, self.lib.smpc_obstacle_distance_batch(self._h, C.byref(ob), C.byref(oo)), "smpc_obstacle_distance_batch")
+        oo = SmpcObstacleDistanceOut(indexes_ptr or None, distances_ptr or None, n_obstacles_ptr or None)
+        self._call("smpc_obstacle_distance_batch", ob, oo)
 
     # -- initial-guess generator (SURVEY §8 row f3): PathTrajectorizer::trajectorize for B plans ------------------
     @staticmethod
@@ -375,16 +421,16 @@ class BatchSolver:
         plan_len = np.ascontiguousarray(plan_len, np.int32)
         robot_pose = np.ascontiguousarray(robot_pose, np.float64)
         B, L, _ = plan.shape
-        tb = self.trajectorize_c(tp, B, L, 0)
-        tb.plan, tb.plan_len, tb.robot_pose = plan.ctypes.data, plan_len.ctypes.data, robot_pose.ctypes.data
+        tb = point(self.trajectorize_c(tp, B, L, 0), {"plan": plan, "plan_len": plan_len, "robot_pose": robot_pose})
         S1 = tp.max_steps + 1
         out = {"path": np.zeros((B, S1, 3)), "cmds": np.zeros((B, S1, 2)), "cmds_vy": np.zeros((B, S1)),
                "n_poses": np.zeros(B, np.int32), "error": np.zeros(B, np.int32)}
-        to = SmpcTrajectorizeOut()
-        for k, v in out.items():
-            setattr(to, k, v.ctypes.data)
-        _check(self.lib, self.lib.smpc_trajectorize_path_batch(self._h, C.byref(tb), C.byref(to)), "smpc_trajectorize_path_batch")
+        self._call("smpc_trajectorize_path_batch", tb, point(SmpcTrajectorizeOut(), out))
         return out
+
+    def trajectorize_device(self, tb: SmpcTrajectorizeBatch, to: SmpcTrajectorizeOut):
+        assert tb.on_device == 1
+        self._call("smpc_trajectorize_path_batch", tb, to)
 
     def transform_global_plan(self, plan: np.ndarray, plan_len: np.ndarray, plan_start: np.ndarray, robot_pose: np.ndarray,
                               max_robot_pose_search_dist: float, dist_threshold: float, to_local: np.ndarray = None):
@@ -395,29 +441,18 @@ class BatchSolver:
         plan_len = np.ascontiguousarray(plan_len, np.int32)
         assert plan_start.dtype == np.int32 and plan_start.flags.c_contiguous
         robot_pose = np.ascontiguousarray(robot_pose, np.float64)
+        to_local = None if to_local is None else np.ascontiguousarray(to_local, np.float64)
         B, L, _ = plan.shape
-        wb = SmpcPlanWindowBatch()
-        wb.B, wb.L, wb.on_device = B, L, 0
-        wb.max_robot_pose_search_dist, wb.dist_threshold = float(max_robot_pose_search_dist), float(dist_threshold)
-        wb.plan, wb.plan_len, wb.plan_start, wb.robot_pose = plan.ctypes.data, plan_len.ctypes.data, plan_start.ctypes.data, robot_pose.ctypes.data
-        if to_local is not None:
-            to_local = np.ascontiguousarray(to_local, np.float64)
-            wb.to_local = to_local.ctypes.data
+        wb = SmpcPlanWindowBatch(B=B, L=L, on_device=0, max_robot_pose_search_dist=float(max_robot_pose_search_dist),
+                                 dist_threshold=float(dist_threshold))
+        point(wb, {"plan": plan, "plan_len": plan_len, "plan_start": plan_start, "robot_pose": robot_pose, "to_local": to_local})
         out = {"window": np.zeros((B, L, 2)), "window_len": np.zeros(B, np.int32), "error": np.zeros(B, np.int32)}
-        _check(self.lib, self.lib.smpc_transform_global_plan_batch(self._h, C.byref(wb), out["window"].ctypes.data,
-                                                                   out["window_len"].ctypes.data, out["error"].ctypes.data),
-               "smpc_transform_global_plan_batch")
+        self._call("smpc_transform_global_plan_batch", wb, _ptr(out["window"]), _ptr(out["window_len"]), _ptr(out["error"]))
         return out
 
     def transform_global_plan_device(self, wb: "SmpcPlanWindowBatch", window_ptr: int, window_len_ptr: int, error_ptr: int = 0):
         assert wb.on_device == 1
-        _check(self.lib, self.lib.smpc_transform_global_plan_batch(self._h, C.byref(wb), C.c_void_p(window_ptr),
-                                                                   C.c_void_p(window_len_ptr), C.c_void_p(error_ptr)),
-               "smpc_transform_global_plan_batch")
-
-    def trajectorize_device(self, tb: SmpcTrajectorizeBatch, to: SmpcTrajectorizeOut):
-        assert tb.on_device == 1
-        _check(self.lib, self.lib.smpc_trajectorize_path_batch(self._h, C.byref(tb), C.byref(to)), "smpc_trajectorize_path_batch")
+        self._call("smpc_transform_global_plan_batch", wb, window_ptr, window_len_ptr, error_ptr)
 
     def people_to_status(self, people: np.ndarray, count: np.ndarray, N: int = 3, robot_pose: np.ndarray = None,
                          fov_angle: float = np.pi / 4, costmap_origin: np.ndarray = None, size_x: int = 0, size_y: int = 0,
@@ -428,9 +463,7 @@ class BatchSolver:
         people = np.ascontiguousarray(people, np.float64)
         count = np.ascontiguousarray(count, np.int32)
         B, Np, _ = people.shape
-        pb = SmpcPeopleBatch()
-        pb.B, pb.Np, pb.N, pb.on_device = B, Np, N, 0
-        pb.people, pb.count = people.ctypes.data, count.ctypes.data
+        pb = SmpcPeopleBatch(B=B, Np=Np, N=N, on_device=0, people=people.ctypes.data, count=count.ctypes.data)
         if robot_pose is not None:
             robot_pose = np.ascontiguousarray(robot_pose, np.float64)
             costmap_origin = np.ascontiguousarray(costmap_origin, np.float64).reshape(-1, 2)
@@ -438,9 +471,12 @@ class BatchSolver:
             pb.costmap_origin, pb.costmap_shared = costmap_origin.ctypes.data, 1 if costmap_origin.shape[0] == 1 else 0
             pb.size_x, pb.size_y, pb.resolution = int(size_x), int(size_y), float(resolution)
         out, has = np.zeros((B, N, 6)), np.zeros(B, np.uint8)
-        _check(self.lib, self.lib.smpc_people_to_status_batch(self._h, C.byref(pb), out.ctypes.data, has.ctypes.data),
-               "smpc_people_to_status_batch")
+        self._call("smpc_people_to_status_batch", pb, _ptr(out), _ptr(has))
         return out, has
+
+    def people_to_status_device(self, pb: SmpcPeopleBatch, out_ptr: int, has_people_ptr: int):
+        assert pb.on_device == 1
+        self._call("smpc_people_to_status_batch", pb, out_ptr, has_people_ptr)
 
     def select_command(self, traj_n_poses, traj_cmds: np.ndarray, status: np.ndarray, cmds: np.ndarray, window_error=None):
         """The command computeVelocityCommands returns for B robots (fallbacks included): traj_cmds [B,rows,2],
@@ -454,11 +490,14 @@ class BatchSolver:
         n = None if traj_n_poses is None else np.ascontiguousarray(traj_n_poses, np.int32)
         out, src = np.zeros((B, 2)), np.zeros(B, np.int32)
         we = None if window_error is None else np.ascontiguousarray(window_error, np.int32)
-        _check(self.lib, self.lib.smpc_select_command_batch(self._h, B, T, rows, 0, None if n is None else n.ctypes.data,
-                                                            traj_cmds.ctypes.data, status.ctypes.data, cmds.ctypes.data,
-                                                            out.ctypes.data, src.ctypes.data,
-                                                            None if we is None else we.ctypes.data), "smpc_select_command_batch")
+        self._call("smpc_select_command_batch", B, T, rows, 0, _ptr(n), _ptr(traj_cmds), _ptr(status), _ptr(cmds), _ptr(out),
+                   _ptr(src), _ptr(we))
         return out, src
+
+    def select_command_device(self, B, T, rows, traj_n_ptr, traj_cmds_ptr, status_ptr, cmds_ptr, cmd_vel_ptr, source_ptr,
+                              window_error_ptr=0):
+        self._call("smpc_select_command_batch", B, T, rows, 1, traj_n_ptr, traj_cmds_ptr, status_ptr, cmds_ptr, cmd_vel_ptr,
+                   source_ptr, window_error_ptr)
 
     # -- per-robot navigation metrics of a closed-loop episode (smpc_episode_metrics_batch) ------------------------
     @staticmethod
@@ -478,43 +517,26 @@ class BatchSolver:
         [2]) or [B,h,w] (od_origin [B,2]) float32 with od_resolution, status [B] and source [B] of the tick. Returns the
         updated copy of acc (columns METRIC_COLS)."""
         acc = np.array(acc, dtype=np.float64, order="C")
-        robot_pose = np.ascontiguousarray(robot_pose, np.float64)
-        robot_twist = np.ascontiguousarray(robot_twist, np.float64)
         people = np.ascontiguousarray(people, np.float64)
-        count = np.ascontiguousarray(count, np.int32)
         B, Np, _ = people.shape
-        assert acc.shape == (B, _abi.SMPC_METRIC_COLS) and robot_pose.shape == (B, 3) and robot_twist.shape == (B, 2)
-        assert count.shape == (B,) and people.shape[2] == 5
-        mb = self.metrics_c(mp, B, Np, dt, 0)
-        mb.robot_pose, mb.robot_twist = robot_pose.ctypes.data, robot_twist.ctypes.data
-        mb.people, mb.count = people.ctypes.data, count.ctypes.data
-        keep = []
-        if goal is not None:
-            goal = np.ascontiguousarray(goal, np.float64)
-            assert goal.shape == (B, 2)
-            mb.goal = goal.ctypes.data
+        f64, i32 = np.float64, np.int32
+        ins = {name: None if a is None else np.ascontiguousarray(a, dtype) for name, a, dtype in (
+            ("robot_pose", robot_pose, f64), ("robot_twist", robot_twist, f64), ("people", people, f64), ("count", count, i32),
+            ("goal", goal, f64), ("status", status, i32), ("source", source, i32))}
+        assert acc.shape == (B, _abi.SMPC_METRIC_COLS) and ins["robot_pose"].shape == (B, 3) and ins["robot_twist"].shape == (B, 2)
+        assert ins["count"].shape == (B,) and people.shape[2] == 5
+        assert goal is None or ins["goal"].shape == (B, 2)
+        assert all(ins[k] is None or ins[k].shape == (B,) for k in ("status", "source"))
+        mb = point(self.metrics_c(mp, B, Np, dt, 0), ins)
         if od_distances is not None:
-            od_distances = np.ascontiguousarray(od_distances, np.float32)
-            shared = od_distances.ndim == 2
-            od_origin = np.ascontiguousarray(od_origin, np.float64).reshape(-1, 2)
-            assert od_distances.ndim == 2 or od_distances.shape[0] == B
-            assert od_origin.shape == ((1, 2) if shared else (B, 2))
-            mb.od_distances, mb.od_origin = od_distances.ctypes.data, od_origin.ctypes.data
-            mb.od_shared, mb.od_height, mb.od_width = 1 if shared else 0, int(od_distances.shape[-2]), int(od_distances.shape[-1])
-            mb.od_resolution = float(od_resolution)
-        for name, arr in (("status", status), ("source", source)):
-            if arr is not None:
-                arr = np.ascontiguousarray(arr, np.int32)
-                assert arr.shape == (B,)
-                keep.append(arr)
-                setattr(mb, name, arr.ctypes.data)
-        _check(self.lib, self.lib.smpc_episode_metrics_batch(self._h, C.byref(mb), acc.ctypes.data), "smpc_episode_metrics_batch")
+            _keep = set_od_grid(mb, "od_distances", od_distances, od_origin, od_resolution, B=B)
+        self._call("smpc_episode_metrics_batch", mb, _ptr(acc))
         return acc
 
     def episode_metrics_device(self, mb: SmpcMetricsBatch, acc_ptr: int):
         """Device pointers in mb (on_device == 1) and for acc; asynchronous on the handle's stream."""
         assert mb.on_device == 1
-        _check(self.lib, self.lib.smpc_episode_metrics_batch(self._h, C.byref(mb), C.c_void_p(acc_ptr)), "smpc_episode_metrics_batch")
+        self._call("smpc_episode_metrics_batch", mb, acc_ptr)
 
     # -- the reactive crowd of a closed-loop episode (smpc_crowd_step_batch) -----------------------------------------
     @staticmethod
@@ -527,10 +549,7 @@ class BatchSolver:
 
     @staticmethod
     def crowd_groups_c(gp: CrowdGroupParams, group_id_ptr: int) -> SmpcCrowdGroups:
-        gb = SmpcCrowdGroups()
-        gb.group_id = group_id_ptr
-        gb.factor_gaze, gb.factor_coherence, gb.factor_repulsion = gp.factor_gaze, gp.factor_coherence, gp.factor_repulsion
-        return gb
+        return SmpcCrowdGroups(group_id_ptr, gp.factor_gaze, gp.factor_coherence, gp.factor_repulsion)
 
     def crowd_step(self, cp: CrowdParams, dt: float, people: np.ndarray, cursor: np.ndarray, robot_pose: np.ndarray,
                    robot_twist: np.ndarray, count: np.ndarray, waypoints: np.ndarray, n_waypoints: np.ndarray,
@@ -543,59 +562,37 @@ class BatchSolver:
         (smpc_crowd_step_groups_batch); None: the plain step. Returns the updated copies (people, cursor)."""
         people = np.array(people, dtype=np.float64, order="C")
         cursor = np.array(cursor, dtype=np.int32, order="C")
-        robot_pose = np.ascontiguousarray(robot_pose, np.float64)
-        robot_twist = np.ascontiguousarray(robot_twist, np.float64)
-        count = np.ascontiguousarray(count, np.int32)
-        waypoints = np.ascontiguousarray(waypoints, np.float64)
-        n_waypoints = np.ascontiguousarray(n_waypoints, np.int32)
+        f64, i32 = np.float64, np.int32
+        ins = {name: None if a is None else np.ascontiguousarray(a, dtype) for name, a, dtype in (
+            ("robot_pose", robot_pose, f64), ("robot_twist", robot_twist, f64), ("count", count, i32),
+            ("waypoints", waypoints, f64), ("n_waypoints", n_waypoints, i32), ("desired_speeds", desired_speeds, f64))}
         B, Np, _ = people.shape
-        K = waypoints.shape[2]
-        assert people.shape[2] == 5 and cursor.shape == (B, Np) and robot_pose.shape == (B, 3) and robot_twist.shape == (B, 2)
-        assert count.shape == (B,) and waypoints.shape == (B, Np, K, 2) and n_waypoints.shape == (B, Np)
-        cb = self.crowd_c(cp, B, Np, K, dt, 0)
-        cb.robot_pose, cb.robot_twist, cb.count = robot_pose.ctypes.data, robot_twist.ctypes.data, count.ctypes.data
-        cb.waypoints, cb.n_waypoints = waypoints.ctypes.data, n_waypoints.ctypes.data
-        if desired_speeds is not None:
-            desired_speeds = np.ascontiguousarray(desired_speeds, np.float64)
-            assert desired_speeds.shape == (B, Np)
-            cb.desired_speeds = desired_speeds.ctypes.data
+        K = ins["waypoints"].shape[2]
+        assert people.shape[2] == 5 and cursor.shape == (B, Np) and ins["robot_pose"].shape == (B, 3) and ins["robot_twist"].shape == (B, 2)
+        assert ins["count"].shape == (B,) and ins["waypoints"].shape == (B, Np, K, 2) and ins["n_waypoints"].shape == (B, Np)
+        assert desired_speeds is None or ins["desired_speeds"].shape == (B, Np)
+        cb = point(self.crowd_c(cp, B, Np, K, dt, 0), ins)
         if od_indexes is not None:
-            od_indexes = np.ascontiguousarray(od_indexes, np.uint32)
-            shared = od_indexes.ndim == 2
-            od_origin = np.ascontiguousarray(od_origin, np.float64).reshape(-1, 2)
-            assert od_indexes.ndim == 2 or od_indexes.shape[0] == B
-            assert od_origin.shape == ((1, 2) if shared else (B, 2))
-            cb.od_indexes, cb.od_origin = od_indexes.ctypes.data, od_origin.ctypes.data
-            cb.od_shared, cb.od_height, cb.od_width = 1 if shared else 0, int(od_indexes.shape[-2]), int(od_indexes.shape[-1])
-            cb.od_resolution = float(od_resolution)
+            _keep = set_od_grid(cb, "od_indexes", od_indexes, od_origin, od_resolution, B=B)
+        gb = None
         if groups is not None:
             groups = np.ascontiguousarray(groups, np.int32)
             assert groups.shape == (B, Np)
             gb = self.crowd_groups_c(group_params if group_params is not None else CrowdGroupParams(), groups.ctypes.data)
-            _check(self.lib, self.lib.smpc_crowd_step_groups_batch(self._h, C.byref(cb), C.byref(gb), people.ctypes.data,
-                                                                   cursor.ctypes.data), "smpc_crowd_step_groups_batch")
-            return people, cursor
-        _check(self.lib, self.lib.smpc_crowd_step_batch(self._h, C.byref(cb), people.ctypes.data, cursor.ctypes.data),
-               "smpc_crowd_step_batch")
+        self._crowd_call(cb, _ptr(people), _ptr(cursor), gb)
         return people, cursor
+
+    def _crowd_call(self, cb, people_ptr, cursor_ptr, groups):
+        if groups is not None:
+            self._call("smpc_crowd_step_groups_batch", cb, groups, people_ptr, cursor_ptr)
+        else:
+            self._call("smpc_crowd_step_batch", cb, people_ptr, cursor_ptr)
 
     def crowd_step_device(self, cb: SmpcCrowdBatch, people_ptr: int, cursor_ptr: int, groups: SmpcCrowdGroups = None):
         """Device pointers in cb (on_device == 1), in groups (crowd_groups_c; None: the plain step) and for people and
         cursor; asynchronous on the handle's stream."""
         assert cb.on_device == 1
-        if groups is not None:
-            _check(self.lib, self.lib.smpc_crowd_step_groups_batch(self._h, C.byref(cb), C.byref(groups), C.c_void_p(people_ptr),
-                                                                   C.c_void_p(cursor_ptr)), "smpc_crowd_step_groups_batch")
-            return
-        _check(self.lib, self.lib.smpc_crowd_step_batch(self._h, C.byref(cb), C.c_void_p(people_ptr), C.c_void_p(cursor_ptr)),
-               "smpc_crowd_step_batch")
-
-    def select_command_device(self, B, T, rows, traj_n_ptr, traj_cmds_ptr, status_ptr, cmds_ptr, cmd_vel_ptr, source_ptr,
-                              window_error_ptr=0):
-        _check(self.lib, self.lib.smpc_select_command_batch(self._h, B, T, rows, 1, C.c_void_p(traj_n_ptr), C.c_void_p(traj_cmds_ptr),
-                                                            C.c_void_p(status_ptr), C.c_void_p(cmds_ptr), C.c_void_p(cmd_vel_ptr),
-                                                            C.c_void_p(source_ptr), C.c_void_p(window_error_ptr)),
-               "smpc_select_command_batch")
+        self._crowd_call(cb, people_ptr, cursor_ptr, groups)
 
     # -- warm start / input formatting (SURVEY §8 row f2): format_to_optimize + TrajectoryMemory for B scenes -----
     def format_to_optimize(self, path: np.ndarray, cmds: np.ndarray, speed: np.ndarray, memory: dict,
@@ -613,35 +610,29 @@ class BatchSolver:
         Tp = T + 1
         assert cmds.shape == (B, rows, 2) and speed.shape == (B, 2) and rows >= Tp
         assert memory["prev_path"].shape == (B, Tp, 3) and memory["prev_cmds"].shape == (B, Tp, 2)
-        CH, bl, nb, P, M, _ = self.params.dims(T, True)
-        fb = SmpcFormatBatch()
-        fb.B, fb.T, fb.path_rows, fb.on_device = B, T, rows, 0
+        P = self.params.dims(T, True)[3]
+        fb = SmpcFormatBatch(B=B, T=T, path_rows=rows, on_device=0, time_step=float(self.params.dt))
         if n_poses is not None:
             n_poses = np.ascontiguousarray(n_poses, np.int32)
             assert n_poses.shape == (B,) and "length" in memory
             fb.n_poses, fb.max_poses = n_poses.ctypes.data, int(max_poses)
-        if "length" in memory:
-            fb.memory.length = memory["length"].ctypes.data
-        fb.time_step = float(self.params.dt)
         fb.current_path_w = float(self.params.current_path_weight if current_path_w is None else current_path_w)
         fb.current_cmds_w = float(self.params.current_cmds_weight if current_cmds_w is None else current_cmds_w)
-        fb.path, fb.cmds, fb.speed = path.ctypes.data, cmds.ctypes.data, speed.ctypes.data
-        fb.memory.prev_path = memory["prev_path"].ctypes.data
-        fb.memory.prev_cmds = memory["prev_cmds"].ctypes.data
-        fb.memory.valid = memory["valid"].ctypes.data
+        point(fb, {"path": path, "cmds": cmds, "speed": speed})
+        point(fb.memory, memory)
         out = {"robot_status": np.zeros((B, Tp, 6)), "pose0": np.zeros((B, 3)), "init_params": np.zeros((B, P)),
                "path_pts": np.zeros((B, Tp, 2)), "goal_yaw": np.zeros(B), "T_scene": np.zeros(B, np.int32)}
-        fo = SmpcFormatOut()
-        for k, v in out.items():
-            setattr(fo, k, v.ctypes.data)
-        _check(self.lib, self.lib.smpc_format_to_optimize_batch(self._h, C.byref(fb), C.byref(fo)),
-               "smpc_format_to_optimize_batch")
+        self._call("smpc_format_to_optimize_batch", fb, point(SmpcFormatOut(), out))
         return out
+
+    def format_device(self, fb: SmpcFormatBatch, fo: SmpcFormatOut):
+        assert fb.on_device == 1
+        self._call("smpc_format_to_optimize_batch", fb, fo)
 
     @staticmethod
     def new_memory(B: int, T: int, lengths: bool = False):
-        """An empty TrajectoryMemory record per scene (host arrays). lengths: with the per-record sizes that scenes with
-        horizons of their own need (smpc_memory_batch.length)."""
+        """An empty TrajectoryMemory record per scene (host arrays, named like the fields of SmpcMemoryBatch). lengths:
+        with the per-record sizes that scenes with horizons of their own need (smpc_memory_batch.length)."""
         m = {"prev_path": np.zeros((B, T + 1, 3)), "prev_cmds": np.zeros((B, T + 1, 2)), "valid": np.zeros(B, np.int32)}
         if lengths:
             m["length"] = np.zeros((B, 2), np.int32)
@@ -654,116 +645,10 @@ class BatchSolver:
         path = np.ascontiguousarray(path, np.float64)
         cmds = np.ascontiguousarray(cmds, np.float64)
         B, Tp, _ = path.shape
-        mb = SmpcMemoryBatch()
-        mb.prev_path, mb.prev_cmds, mb.valid = (memory["prev_path"].ctypes.data, memory["prev_cmds"].ctypes.data,
-                                                memory["valid"].ctypes.data)
-        if "length" in memory:
-            mb.length = memory["length"].ctypes.data
         ts = None if T_scene is None else np.ascontiguousarray(T_scene, np.int32)
-        _check(self.lib, self.lib.smpc_memory_store_batch(self._h, B, Tp - 1, 0, status.ctypes.data, path.ctypes.data,
-                                                          cmds.ctypes.data, C.byref(mb), None if ts is None else ts.ctypes.data),
-               "smpc_memory_store_batch")
-
-    def format_device(self, fb: SmpcFormatBatch, fo: SmpcFormatOut):
-        assert fb.on_device == 1
-        _check(self.lib, self.lib.smpc_format_to_optimize_batch(self._h, C.byref(fb), C.byref(fo)),
-               "smpc_format_to_optimize_batch")
+        self._call("smpc_memory_store_batch", B, Tp - 1, 0, _ptr(status), _ptr(path), _ptr(cmds),
+                   point(SmpcMemoryBatch(), memory), _ptr(ts))
 
     def memory_store_device(self, B: int, T: int, status_ptr: int, path_ptr: int, cmds_ptr: int, mb: SmpcMemoryBatch,
                             T_scene_ptr: int = 0):
-        _check(self.lib, self.lib.smpc_memory_store_batch(self._h, B, T, 1, C.c_void_p(status_ptr), C.c_void_p(path_ptr),
-                                                          C.c_void_p(cmds_ptr), C.byref(mb), C.c_void_p(T_scene_ptr)),
-               "smpc_memory_store_batch")
-
-    def people_to_status_device(self, pb: SmpcPeopleBatch, out_ptr: int, has_people_ptr: int):
-        assert pb.on_device == 1
-        _check(self.lib, self.lib.smpc_people_to_status_batch(self._h, C.byref(pb), C.c_void_p(out_ptr), C.c_void_p(has_people_ptr)),
-               "smpc_people_to_status_batch")
-
-    def project_people_device(self, pb: SmpcProjectionBatch, out_ptr: int, err_ptr: int):
-        assert pb.on_device == 1
-        _check(self.lib, self.lib.smpc_project_people_batch(self._h, C.byref(pb), C.c_void_p(out_ptr), C.c_void_p(err_ptr)),
-               "smpc_project_people_batch")
-
-    # -- device-resident path (inputs already in HBM; asynchronous on the handle's stream) -------
-    def alloc_results(self, B: int, T: int, device="cuda:0"):
-        import torch
-
-        CH, bl, nb, P, M, _ = self.params.dims(T, True)
-        t = {
-            "params": torch.empty((B, P), dtype=torch.float64, device=device),
-            "cmds": torch.empty((B, T + 1, 2), dtype=torch.float64, device=device),
-            "path": torch.empty((B, T + 1, 3), dtype=torch.float64, device=device),
-            "status": torch.empty(B, dtype=torch.int32, device=device),
-            "reason": torch.empty(B, dtype=torch.int32, device=device),
-            "iterations": torch.empty(B, dtype=torch.int32, device=device),
-            "evaluations": torch.empty(B, dtype=torch.int32, device=device),
-            "initial_cost": torch.empty(B, dtype=torch.float64, device=device),
-            "final_cost": torch.empty(B, dtype=torch.float64, device=device),
-        }
-        rb = SmpcResultBatch()
-        for k, v in t.items():
-            setattr(rb, k, v.data_ptr())
-        return rb, t
-
-    def stage_people(self, scenes: SceneBatch):
-        """smpc_stage_people_batch on host arrays: (records [B,N,T,4], aux [B,T,2])."""
-        B, T, N = scenes.B, scenes.T, scenes.N
-        rec = np.zeros((B, N, T, 4))
-        aux = np.zeros((B, T, 2))
-        sb = scenes.to_c()
-        _check(self.lib, self.lib.smpc_stage_people_batch(self._h, C.byref(sb), rec.ctypes.data, aux.ctypes.data),
-               "smpc_stage_people_batch")
-        return rec, aux
-
-    def stage_people_device(self, sb: SmpcSceneBatch, device="cuda:0"):
-        """Stage the device-resident people block of `sb` once and attach the result to it: later solve_device /
-        eval_device calls with this batch read the staged records instead of running the staging pass again.
-        Returns the tensors that own the memory (keep them alive as long as `sb` is used)."""
-        import torch
-
-        assert sb.on_device == 1
-        rec = torch.zeros((sb.B, sb.N, sb.T, 4), dtype=torch.float64, device=device)
-        aux = torch.zeros((sb.B, sb.T, 2), dtype=torch.float64, device=device)
-        _check(self.lib, self.lib.smpc_stage_people_batch(self._h, C.byref(sb), C.c_void_p(rec.data_ptr()),
-                                                          C.c_void_p(aux.data_ptr())), "smpc_stage_people_batch")
-        sb.people_records, sb.people_aux = rec.data_ptr(), aux.data_ptr()
-        return rec, aux
-
-    def solve_device(self, sb: SmpcSceneBatch, rb: SmpcResultBatch):
-        assert sb.on_device == 1
-        _check(self.lib, self.lib.smpc_solve_batch(self._h, C.byref(sb), C.byref(rb)), "smpc_solve_batch")
-
-    def alloc_trace(self, B: int, max_rows: int = None, device="cuda:0"):
-        """(SmpcTraceOut, tensors) for solve_trace_device: "trace" [B, max_rows, 9] filled with NaN, "trace_rows" [B]."""
-        import torch
-
-        max_rows = self.params.max_iterations + 1 if max_rows is None else int(max_rows)
-        t = {"trace": torch.full((B, max_rows, _abi.SMPC_TRACE_COLS), float("nan"), dtype=torch.float64, device=device),
-             "trace_rows": torch.zeros(B, dtype=torch.int32, device=device)}
-        return SmpcTraceOut(t["trace"].data_ptr() if t["trace"].numel() else None, max_rows, t["trace_rows"].data_ptr()), t
-
-    def solve_trace_device(self, sb: SmpcSceneBatch, rb: SmpcResultBatch, to: SmpcTraceOut):
-        """solve_device that also records the per-iteration rows (alloc_trace); asynchronous on the handle's stream."""
-        assert sb.on_device == 1
-        _check(self.lib, self.lib.smpc_solve_trace_batch(self._h, C.byref(sb), C.byref(rb), C.byref(to)), "smpc_solve_trace_batch")
-
-    def alloc_eval(self, B: int, T: int, device="cuda:0", row_order: int = 0):
-        import torch
-
-        CH, bl, nb, P, M, _ = self.params.dims(T, True)
-        t = {
-            "residuals": torch.empty((B, M), dtype=torch.float64, device=device),
-            "jacobian": torch.empty((B, M, P), dtype=torch.float64, device=device),
-            "cost": torch.empty(B, dtype=torch.float64, device=device),
-            "gradient": torch.empty((B, P), dtype=torch.float64, device=device),
-        }
-        eo = SmpcEvalOut()
-        for k, v in t.items():
-            setattr(eo, k, v.data_ptr())
-        eo.row_order = int(row_order)
-        return eo, t
-
-    def eval_device(self, sb: SmpcSceneBatch, x_ptr: int, eo: SmpcEvalOut):
-        assert sb.on_device == 1
-        _check(self.lib, self.lib.smpc_eval_batch(self._h, C.byref(sb), C.c_void_p(x_ptr), C.byref(eo)), "smpc_eval_batch")
+        self._call("smpc_memory_store_batch", B, T, 1, status_ptr, path_ptr, cmds_ptr, mb, T_scene_ptr)

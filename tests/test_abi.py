@@ -1,5 +1,5 @@
 """The C-ABI library loads, exports every symbol include/smpc.h declares, and its struct layouts match the
-ctypes mirror. No compute calls (no GPU needed)."""
+ctypes mirror: every struct, every field, every constant. No compute calls (no GPU needed)."""
 import ctypes as C
 import os
 import re
@@ -39,42 +39,57 @@ def test_library_loads_and_reports_abi_version():
     assert lib.smpc_abi_version() == _abi.SMPC_ABI_VERSION
 
 
-def test_struct_layouts_match_the_c_header(tmp_path):
+def _structs():
+    return [v for v in vars(_abi).values() if isinstance(v, type) and issubclass(v, C.Structure)]
+
+
+def _header_struct_typedefs():
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return sorted(re.findall(r"\btypedef\s+struct\s+\w+\s*\{.*?\}\s*(\w+)\s*;", src, flags=re.S))
+
+
+def test_function_table_is_the_symbol_list_and_what_the_library_is_bound_with():
+    assert _abi.EXPORTED_SYMBOLS == list(_abi.FUNCTIONS) and len(_abi.FUNCTIONS) == 27
+    lib = S.load_library()
+    for name, (restype, argtypes) in _abi.FUNCTIONS.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
+CONSTANTS = ("SMPC_ABI_VERSION", "SMPC_MAX_BLOCKS", "SMPC_TRACE_COLS", "SMPC_METRIC_COLS", "SMPC_MAX_WAYPOINTS", "SMPC_MAX_AGENTS")
+
+
+def test_every_struct_field_and_constant_matches_the_c_header(tmp_path):
+    """Every struct of _abi against include/smpc.h: one C program prints sizeof and the offsetof of every field (and the
+    header's constants and metric-column enumerators), and every value must be ctypes'. Every struct the header typedefs has
+    a mirror (smpc_handle is opaque), under the C name the mirror states."""
+    structs = _structs()
+    assert sorted(st.c_name for st in structs) == _header_struct_typedefs() and len(structs) == 19
+    probes = [(st, None) for st in structs] + [(st, f[0]) for st in structs for f in st._fields_]
+    enumerators = ["SMPC_M_" + n.upper() for n in S.METRIC_COLS[:22]]
+    body = "".join(f'printf("%zu\\n", sizeof({st.c_name}));\n' if f is None else f'printf("%zu\\n", offsetof({st.c_name}, {f}));\n'
+                   for st, f in probes)
+    body += "".join(f'printf("%d\\n", (int){name});\n' for name in CONSTANTS + tuple(enumerators))
     prog = tmp_path / "layout.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "smpc.h"\nint main(void){\n'
-                    'printf("%zu %zu %zu %zu\\n", sizeof(smpc_params), sizeof(smpc_scene_batch), sizeof(smpc_result_batch), sizeof(smpc_eval_batch_out));\n'
-                    'printf("%zu %zu %zu %zu\\n", offsetof(smpc_params, fn_tol), offsetof(smpc_params, fixed_iterations), offsetof(smpc_scene_batch, costmap_origin), offsetof(smpc_scene_batch, resolution));\n'
-                    'return 0;}\n')
+    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "smpc.h"\nint main(void){\n' + body + 'return 0;}\n')
     exe = tmp_path / "layout"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
-    l1, l2 = subprocess.check_output([str(exe)], text=True).splitlines()
-    sizes = [int(v) for v in l1.split()]
-    offs = [int(v) for v in l2.split()]
-    assert sizes == [C.sizeof(_abi.SmpcParams), C.sizeof(_abi.SmpcSceneBatch), C.sizeof(_abi.SmpcResultBatch), C.sizeof(_abi.SmpcEvalOut)]
-    assert offs == [_abi.SmpcParams.fn_tol.offset, _abi.SmpcParams.fixed_iterations.offset,
-                    _abi.SmpcSceneBatch.costmap_origin.offset, _abi.SmpcSceneBatch.resolution.offset]
-
-
-def test_next_row_struct_layouts_match_the_c_header(tmp_path):
-    """ctypes mirrors of the SURVEY §8(f) structs: sizes and a late field's offset each."""
-    probes = [("smpc_projection_batch", _abi.SmpcProjectionBatch, "od_origin"),
-              ("smpc_people_batch", _abi.SmpcPeopleBatch, "resolution"),
-              ("smpc_memory_batch", _abi.SmpcMemoryBatch, "valid"),
-              ("smpc_format_batch", _abi.SmpcFormatBatch, "memory"),
-              ("smpc_format_out", _abi.SmpcFormatOut, "goal_yaw"),
-              ("smpc_trajectorize_batch", _abi.SmpcTrajectorizeBatch, "robot_pose"),
-              ("smpc_trajectorize_out", _abi.SmpcTrajectorizeOut, "error"),
-              ("smpc_plan_window_batch", _abi.SmpcPlanWindowBatch, "to_local")]
-    body = "".join(f'printf("%zu %zu\\n", sizeof({c}), offsetof({c}, {f}));\n' for c, _, f in probes)
-    prog = tmp_path / "layout2.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "smpc.h"\nint main(void){\n' + body + 'return 0;}\n')
-    exe = tmp_path / "layout2"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    for (cname, py, field), line in zip(probes, lines):
-        size, off = (int(v) for v in line.split())
-        assert size == C.sizeof(py), cname
-        assert off == getattr(py, field).offset, (cname, field)
+    values = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
+    assert len(probes) == 19 + 217 and len(values) == len(probes) + len(CONSTANTS) + 22
+    print(f"{len(probes)} sizeof/offsetof probes of {len(structs)} structs, {len(values) - len(probes)} constants")
+    for (st, f), v in zip(probes, values):
+        assert v == (C.sizeof(st) if f is None else getattr(st, f).offset), (st.c_name, f)
+    consts = values[len(probes):]
+    assert consts[:len(CONSTANTS)] == [getattr(_abi, name) for name in CONSTANTS] == [6, 10, 9, 24, 8, 64]
+    # enum smpc_metric_col: a column's enumerator is its index in solver.METRIC_COLS (the last two columns are reserved)
+    assert consts[len(CONSTANTS):] == list(range(22))
+    # the literal sizes of the structs that were added beside unchanged ones, and the order inside them
+    size = {st.c_name: C.sizeof(st) for st in structs}
+    assert size["smpc_crowd_batch"] == 136 and size["smpc_crowd_groups"] == 32 and size["smpc_scene_params"] == 14 * 8
+    assert [getattr(_abi.SmpcCrowdGroups, f).offset for f, _ in _abi.SmpcCrowdGroups._fields_] == [0, 8, 16, 24]
+    assert [f for f, _ in _abi.SmpcCrowdGroups._fields_] == ["group_id", "factor_gaze", "factor_coherence", "factor_repulsion"]
+    assert _abi.SmpcSceneBatch._fields_[-1][0] == "scene_params"  # appended: every earlier offset is unchanged
+    assert [f for f, _ in _abi.SmpcSceneParams._fields_] == list(_abi.SCENE_PARAM_FIELDS)
 
 
 def test_params_default_matches_reference_code_defaults():

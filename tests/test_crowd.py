@@ -1,7 +1,6 @@
 """The crowd step (smpc_crowd_step_batch) without a GPU: the plumbing of the new entry point, the CPU checker
 (tests/crowd_ref.py) against the oracle's people projection on the one configuration where the two models coincide, the
 checker's closed forms, and the margins of the seeded inputs that tests/test_gpu_crowd.py runs on the device."""
-import ctypes as C
 import math
 import os
 import re
@@ -29,18 +28,6 @@ def test_entry_point_is_declared_listed_and_exported():
     assert "smpc_crowd_step_batch" in {line.split()[-1] for line in out.splitlines() if line.strip()}
     assert _abi.SMPC_ABI_VERSION == 6 and int(re.search(r"#define SMPC_ABI_VERSION (\d+)", src).group(1)) == 6
     assert int(re.search(r"#define SMPC_MAX_WAYPOINTS (\d+)", src).group(1)) == _abi.SMPC_MAX_WAYPOINTS == 8
-
-
-def test_struct_layout_matches_the_c_header(tmp_path):
-    prog = tmp_path / "layout.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "smpc.h"\nint main(void){\n'
-                    'printf("%zu %zu %zu\\n", sizeof(smpc_crowd_batch), offsetof(smpc_crowd_batch, od_origin), '
-                    'offsetof(smpc_crowd_batch, robot_pose));\nreturn 0;}\n')
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
-    size, od_origin, robot_pose = (int(v) for v in subprocess.check_output([str(exe)], text=True).split())
-    assert size == C.sizeof(_abi.SmpcCrowdBatch)
-    assert od_origin == _abi.SmpcCrowdBatch.od_origin.offset and robot_pose == _abi.SmpcCrowdBatch.robot_pose.offset
 
 
 def test_crowd_params_defaults_and_refusals():

@@ -1,7 +1,6 @@
 """Pedestrian groups in the crowd step (smpc_crowd_step_groups_batch) without a GPU: the plumbing of the entry point, the
 closed forms of the CPU checker (tests/crowd_groups_ref.py), scenes.crowd_groups, the refusals of CrowdGroupParams, and
 the margins of the seeded inputs that tests/test_gpu_crowd_groups.py runs on the device."""
-import ctypes as C
 import math
 import os
 import re
@@ -22,7 +21,7 @@ HEADER = os.path.join(ROOT, "include", "smpc.h")
 
 
 # ---- plumbing -------------------------------------------------------------------------------------------------------
-def test_entry_point_is_declared_listed_and_exported(tmp_path):
+def test_entry_point_is_declared_listed_and_exported():
     src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     assert re.search(r"\bint\s+smpc_crowd_step_groups_batch\s*\(", src)
     assert "smpc_crowd_step_groups_batch" in _abi.EXPORTED_SYMBOLS
@@ -30,17 +29,6 @@ def test_entry_point_is_declared_listed_and_exported(tmp_path):
     out = subprocess.check_output(["nm", "-D", "--defined-only", S.LIB_PATH], text=True)
     assert "smpc_crowd_step_groups_batch" in {line.split()[-1] for line in out.splitlines() if line.strip()}
     assert _abi.SMPC_ABI_VERSION == 6 and int(re.search(r"#define SMPC_ABI_VERSION (\d+)", src).group(1)) == 6
-    fields = ("group_id", "factor_gaze", "factor_coherence", "factor_repulsion")
-    prog = tmp_path / "layout.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "smpc.h"\nint main(void){\n'
-                    'printf("%zu %zu", sizeof(smpc_crowd_batch), sizeof(smpc_crowd_groups));\n'
-                    + "".join(f'printf(" %zu", offsetof(smpc_crowd_groups, {f}));\n' for f in fields) + 'return 0;}\n')
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
-    batch, size, *offsets = (int(v) for v in subprocess.check_output([str(exe)], text=True).split())
-    assert batch == C.sizeof(_abi.SmpcCrowdBatch) == 136                       # the plain step's struct is unchanged
-    assert size == C.sizeof(_abi.SmpcCrowdGroups) == 32
-    assert offsets == [getattr(_abi.SmpcCrowdGroups, f).offset for f in fields] == [0, 8, 16, 24]
 
 
 def test_crowd_group_params_defaults_and_refusals():

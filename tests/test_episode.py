@@ -295,3 +295,116 @@ def test_concurrent_streams_returns_distinct_streams():
         st = concurrent_streams(n, "cuda:0")
         assert len(st) == n and len({s.cuda_stream for s in st}) == n
         assert all(s.cuda_stream != torch.cuda.default_stream("cuda:0").cuda_stream for s in st)
+
+
+# ---- what a shard gets of the episode's arguments ---------------------------------------------------------------------
+def test_every_episode_argument_is_declared_per_robot_or_forwarded():
+    """ShardedEpisode hands BatchEpisode's keyword arguments on by declaration (episode.shard_kwargs): every one of them is
+    declared per robot, per grid or forwarded, so a new argument that is declared nowhere fails here, not on a GPU. Arrays
+    whose row i holds the value i come back as exactly the rows of the shard; everything else is the very same object."""
+    import inspect
+
+    from nav2_social_mpc_controller_amd.episode import BatchEpisode, shard_kwargs
+
+    E = BatchEpisode
+    sig = inspect.signature(E.__init__).parameters
+    keywords = [n for n, p in sig.items() if p.default is not inspect.Parameter.empty]
+    declared = E.PER_ROBOT + E.PER_GRID + E.FORWARDED
+    assert [n for n in sig if n not in keywords] == ["self", "params", "scenes", "w_ref"]
+    assert len(set(declared)) == len(declared) and sorted(declared) == sorted(keywords)
+    assert sorted(E.PER_ROBOT) == sorted(("plan", "plan_len", "scene_params", "goal", "person_waypoints", "person_n_waypoints",
+                                          "person_speed", "person_groups"))
+    assert E.PER_GRID == ("od_indexes", "od_origin", "od_distances")
+
+    B, idx = 7, np.array([2, 3, 4])
+
+    def rows(*tail):  # [B, *tail], row i filled with i
+        return np.broadcast_to(np.arange(B).reshape((B,) + (1,) * len(tail)), (B,) + tail).copy()
+
+    tails = dict(plan=(9, 2), plan_len=(), scene_params=(14,), goal=(2,), person_waypoints=(3, 2, 2), person_n_waypoints=(3,),
+                 person_speed=(3,), person_groups=(3,))
+    per_robot = {k: rows(*tails[k]) for k in E.PER_ROBOT}
+    forwarded = {k: object() for k in E.FORWARDED}
+    shared = dict(od_indexes=np.zeros((4, 5), np.uint32), od_origin=np.zeros(2), od_distances=np.zeros((4, 5), np.float32))
+    per_scene = dict(od_indexes=rows(4, 5).astype(np.uint32), od_origin=rows(2).astype(np.float64), od_distances=rows(4, 5).astype(np.float32))
+    one = dict(od_indexes=np.zeros((1, 4, 5), np.uint32), od_origin=np.zeros((1, 2)), od_distances=None)  # [1,h,w]: shared
+    for grid, sliced in ((shared, False), (per_scene, True), (one, False)):
+        kwargs = dict(per_robot, **forwarded, **grid)
+        got = shard_kwargs(kwargs, idx, B)
+        assert sorted(got) == sorted(kwargs)
+        for k in E.PER_ROBOT + (E.PER_GRID if sliced else ()):
+            assert got[k].shape == (3,) + kwargs[k].shape[1:] and got[k].dtype == kwargs[k].dtype, k
+            assert all((got[k][j] == i).all() for j, i in enumerate(idx)), k
+        for k in E.FORWARDED + (() if sliced else E.PER_GRID):
+            assert got[k] is kwargs[k], k
+    none = shard_kwargs(dict.fromkeys(declared), idx, B)     # nothing given: nothing to slice
+    assert sorted(none) == sorted(declared) and all(v is None for v in none.values())
+    with pytest.raises(TypeError, match="per_robot_extra"):
+        shard_kwargs(dict(per_robot, per_robot_extra=rows(2)), idx, B)
+    with pytest.raises(AssertionError, match="person_speed"):
+        shard_kwargs(dict(per_robot, person_speed=rows(3)[:5]), idx, B)
+
+
+def _every_option(B, N):
+    """(params, scenes, w_ref, keyword arguments) of an episode with every optional argument at once, every per-robot
+    array with a different row per robot."""
+    from nav2_social_mpc_controller_amd import _abi
+    from nav2_social_mpc_controller_amd.episode import arc_plans
+    from nav2_social_mpc_controller_amd.params import CrowdGroupParams, CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams
+    from nav2_social_mpc_controller_amd.scenes import crowd_groups, make_scenes, uniform
+
+    prm = OptimizerParams.readme()
+    tp = TrajectorizerParams(desired_linear_vel=0.6, lookahead_dist=0.4, max_angular_vel=1.0, time_step=0.05, max_time=1.5)
+    sc = make_scenes(prm, B, N, map_cells=80, standing_fraction=0.0)
+    assert not sc.costmap_shared and len({c.tobytes() for c in sc.costmap}) == B      # a costmap (so a grid) per scene
+    w_ref = (uniform(0x5EED0001, np.arange(B), 6)[:, 0] * 2.0 - 1.0) * 0.6
+    plan, plan_len = arc_plans(sc.pose0, 0.4 * w_ref)
+    plan_len = (plan_len - 10 * np.arange(B)).astype(np.int32)
+    gid, wp, n_wp = crowd_groups(sc, share=1.0, K=2)
+    assert (gid >= 0).any() and len({g.tobytes() + w.tobytes() for g, w in zip(gid, wp)}) == B
+    rows = np.tile(prm.scene_row(), (B, 1))
+    col = {f: i for i, f in enumerate(_abi.SCENE_PARAM_FIELDS)}
+    rows[:, col["desired_linear_vel"]] -= 0.02 * np.arange(B)
+    rows[:, col["distance_w"]] *= 1.0 + 0.1 * np.arange(B)
+    kw = dict(plan=plan, plan_len=plan_len, traj_params=tp, plan_window=(4.0, 10.0), fov_angle=2.0, order_hint=True,
+              scene_params=rows, metrics=MetricsParams(), goal=plan[np.arange(B), 40 + 5 * np.arange(B)],
+              crowd=CrowdParams(), person_waypoints=wp, person_n_waypoints=n_wp,
+              person_speed=0.4 + 0.05 * np.arange(B)[:, None] + 0.01 * np.arange(N)[None, :], person_groups=gid,
+              crowd_groups=CrowdGroupParams(2.0, 1.5, 0.5))
+    return prm, sc, w_ref, kw
+
+
+def _assert_two_shards_equal_the_single_chain(prm, sc, w_ref, od, kw, ticks=2):
+    from nav2_social_mpc_controller_amd.episode import BatchEpisode, ShardedEpisode
+
+    one = BatchEpisode(prm, sc, w_ref, *od, **kw)
+    two = ShardedEpisode(prm, sc, w_ref, *od, shards=2, graphs=True, **kw)
+    assert [p.B for p in two.parts] == [2, 3]
+    for _ in range(ticks):
+        one.tick()
+        two.tick()
+    one.synchronize()
+    for name in ("status", "iterations", "cmds", "path", "final_cost"):
+        assert np.array_equal(one.res[name].cpu().numpy(), two.gather(name).cpu().numpy()), name
+    for name in ("pose", "cmd_vel", "cmd_source", "persons", "person_cursor", "metrics_acc"):
+        assert np.array_equal(getattr(one, name).cpu().numpy(), two.gather(name).cpu().numpy()), name
+    return one
+
+
+@pytest.mark.gpu
+def test_two_shards_get_their_rows_of_every_optional_argument():
+    """Five robots (odd, so the shards differ in size) with plans and their window, the field-of-view filter, the order
+    hint, scene parameters, metrics with a goal, a crowd with speeds and groups, and grids from per-scene costmaps: the
+    two-shard graph episode returns the single chain's numbers robot by robot. Then the same with host-given grids per
+    scene, distances included."""
+    from nav2_social_mpc_controller_amd.solver import BatchSolver
+
+    B, N = 5, 3
+    prm, sc, w_ref, kw = _every_option(B, N)
+    one = _assert_two_shards_equal_the_single_chain(prm, sc, w_ref, (None, None, None), dict(kw, obstacles_from_costmap=True))
+    assert one.od_shared == 0 and one.od_distances is not None
+    grid = BatchSolver(prm).obstacle_distance(sc.costmap, sc.resolution)
+    assert grid["indexes"].shape == (B, 80, 80) and sc.costmap_origin.shape == (B, 2)
+    od = (grid["indexes"], sc.costmap_origin, float(np.float32(sc.resolution)))
+    host = _assert_two_shards_equal_the_single_chain(prm, sc, w_ref, od, dict(kw, od_distances=grid["distances"]))
+    assert host.od_shared == 0 and host.od_distances is not None

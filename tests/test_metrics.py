@@ -1,6 +1,5 @@
 """Per-robot episode metrics (smpc_episode_metrics_batch), the parts that need no GPU: the CPU checker of the GPU tests
 (tests/metrics_ref.py) on hand-computed cases, its force against the oracle's, and the ABI additions."""
-import ctypes as C
 import math
 import os
 import re
@@ -127,23 +126,6 @@ def test_symbol_is_declared_listed_and_exported():
     out = subprocess.check_output(["nm", "-D", "--defined-only", S.LIB_PATH], text=True)
     assert "smpc_episode_metrics_batch" in {line.split()[-1] for line in out.splitlines() if line.strip()}
     assert hasattr(S.load_library(), "smpc_episode_metrics_batch")
-
-
-def test_metrics_struct_layout_matches_the_c_header(tmp_path):
-    late = ("od_resolution", "od_origin", "source")
-    body = 'printf("%zu\\n", sizeof(smpc_metrics_batch));\n' + "".join(
-        f'printf("%zu\\n", offsetof(smpc_metrics_batch, {f}));\n' for f in late)
-    body += 'printf("%d %d %d %d\\n", SMPC_METRIC_COLS, (int)SMPC_M_SOCIAL_WORK, (int)SMPC_M_TIME_TO_GOAL, (int)SMPC_M_LAST_YAW);\n'
-    prog = tmp_path / "layout_metrics.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "smpc.h"\nint main(void){\n' + body + 'return 0;}\n')
-    exe = tmp_path / "layout_metrics"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    assert int(lines[0]) == C.sizeof(_abi.SmpcMetricsBatch)
-    for f, line in zip(late, lines[1:4]):
-        assert int(line) == getattr(_abi.SmpcMetricsBatch, f).offset, f
-    assert [int(v) for v in lines[4].split()] == [24, S.METRIC_COLS.index("social_work"), S.METRIC_COLS.index("time_to_goal"),
-                                                 S.METRIC_COLS.index("last_yaw")]
 
 
 def test_column_count_and_names():

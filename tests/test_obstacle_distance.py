@@ -103,21 +103,6 @@ def test_obstacle_distance_symbol_is_declared_and_exported():
     assert "smpc_obstacle_distance_batch" in {line.split()[-1] for line in out.splitlines() if line.strip()}
 
 
-def test_obstacle_distance_struct_layouts_match_the_c_header(tmp_path):
-    probes = [("smpc_obstacle_distance_in", _abi.SmpcObstacleDistanceIn, "costmap_shared"),
-              ("smpc_obstacle_distance_in", _abi.SmpcObstacleDistanceIn, "unknown_is_obstacle"),
-              ("smpc_obstacle_distance_in", _abi.SmpcObstacleDistanceIn, "resolution"),
-              ("smpc_obstacle_distance_out", _abi.SmpcObstacleDistanceOut, "n_obstacles")]
-    body = "".join(f'printf("%zu %zu\\n", sizeof({c}), offsetof({c}, {f}));\n' for c, _, f in probes)
-    prog = tmp_path / "layout_od.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "smpc.h"\nint main(void){\n' + body + 'return 0;}\n')
-    exe = tmp_path / "layout_od"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
-    for (cname, py, field), line in zip(probes, subprocess.check_output([str(exe)], text=True).splitlines()):
-        size, off = (int(v) for v in line.split())
-        assert size == C.sizeof(py) and off == getattr(py, field).offset, (cname, field)
-
-
 # ---- GPU: the kernel against the checker ----------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def solver():

@@ -25,19 +25,6 @@ def test_trace_entry_point_is_exported_and_the_version_stays():
     assert S.TRACE_COLS == ["iter", "cost", "cost_change", "gradient_max_norm", "step_norm", "rho", "radius", "ls_evals", "accepted"]
 
 
-def test_trace_out_layout_matches_the_c_header(tmp_path):
-    prog = tmp_path / "trace_layout.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "smpc.h"\nint main(void){\n'
-                    'printf("%zu %zu %zu %d %d\\n", sizeof(smpc_trace_out), offsetof(smpc_trace_out, max_rows), '
-                    'offsetof(smpc_trace_out, n_rows), SMPC_TRACE_COLS, SMPC_ABI_VERSION);\nreturn 0;}\n')
-    exe = tmp_path / "trace_layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
-    size, off_rows, off_n, cols, version = (int(v) for v in subprocess.check_output([str(exe)], text=True).split())
-    assert size == C.sizeof(_abi.SmpcTraceOut)
-    assert off_rows == _abi.SmpcTraceOut.max_rows.offset and off_n == _abi.SmpcTraceOut.n_rows.offset
-    assert cols == _abi.SMPC_TRACE_COLS == 9 and version == 6
-
-
 # ---- register budget of the trace kernel (compile time, like tests/test_scene_params.py) --------------------------
 TRACE_SOLVE = "_ZN4smpc17smpc_solve_kernelILi3ELi32ELb1ELb1ELb1EEEvNS_7KParamsE"
 SP_SOLVE = "_ZN4smpc17smpc_solve_kernelILi3ELi32ELb1ELb1ELb0EEEvNS_7KParamsE"  # the same template without kTrace
