@@ -398,3 +398,10 @@ FUNCTIONS = {
     "smpc_abi_version": (C.c_int, []),
 }
 EXPORTED_SYMBOLS = list(FUNCTIONS)
+
+# The functions include/smpc_fixed_shapes.h declares, bound by solver.load_library() like the table above.
+FIXED_SHAPE_FUNCTIONS = {
+    "smpc_set_fixed_shapes": (C.c_int, [_h, _i32]),
+    "smpc_solve_shape_is_fixed": (C.c_int, [_h, _i32, _i32, _i32]),
+    "smpc_eval_shape_is_fixed": (C.c_int, [_h, _i32, _i32]),
+}

@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/smpc_fixed_shapes.h"
 #include "smpc_eval_kernel.hpp"
 #include "smpc_launch.hpp"
 #include "smpc_lm.hpp"
@@ -138,6 +139,7 @@ struct smpc_handle {
   bool timed = false;
   int* queue = nullptr;  // device-side scene queue head
   int share = 1;         // smpc_set_solve_share: concurrent solve launches the persistent grid leaves room for
+  bool fixed_shapes = true;  // smpc_set_fixed_shapes: launches of a shape of SMPC_FIXED_SHAPES run that shape's kernels
   double* stage_rec = nullptr;  // staged people block of the latest call that did not bring its own (grow-only)
   double* stage_aux = nullptr;
   size_t stage_rec_bytes = 0, stage_aux_bytes = 0;
@@ -192,6 +194,33 @@ KernelFn pick(int nb, int W, Sweep kind, bool vt = false, bool sp = false) {
   }
 #endif
 }
+
+// The kernels of a shape of SMPC_FIXED_SHAPES (smpc_launch.hpp): T, N, CH, bl as literals instead of launch values, the
+// same results bit for bit. They stand in for the plain instantiation <NB, W, false, false> only: a launch with a horizon
+// or parameters per scene, a trace, or the other slot width (the one-scene-per-wave kernel of a small batch) runs the
+// run-time-shape kernel it always ran.
+template <class Shape> KernelFn fixed_fn(Sweep kind, int W) {
+#ifdef SMPC_ONLY_NB
+  if constexpr (Shape::kNB != SMPC_ONLY_NB) return nullptr; else
+#endif
+  if (W != Shape::kW) return nullptr;
+  else return kind == Sweep::Eval ? smpc::smpc_eval_fixed_kernel<Shape> : smpc::smpc_solve_fixed_kernel<Shape>;
+}
+
+KernelFn pick_fixed(const smpc::KParams& k, int W, Sweep kind, bool vt, bool sp) {
+  if (kind == Sweep::Trace || vt || sp) return nullptr;
+  const int want = smpc::fixed_shape_index(k.T, k.N, k.CH, k.bl);  // the rule; below only the index -> kernel table
+  int i = 0;
+#define SMPC_X(t, n, ch, b) \
+  if (want == i++) return fixed_fn<smpc::FixedShape<t, n, ch, b>>(kind, W);
+  SMPC_FIXED_SHAPES(SMPC_X)
+#undef SMPC_X
+  return nullptr;
+}
+
+// Whether this handle's launches may take a fixed-shape kernel at all: smpc_set_fixed_shapes, and not under the experiment
+// knob SMPC_NO_HELPERS, which works through the launch value k.hp_A that a fixed shape folds in.
+bool fixed_shapes_on(const smpc_handle* h) { return h->fixed_shapes && !std::getenv("SMPC_NO_HELPERS"); }
 
 int validate(const smpc_handle* h, const smpc_scene_batch* sb, Dims* d) {
   if (!h || !sb) { set_error("null handle or scene batch"); return SMPC_ERR_INVALID_ARG; }
@@ -423,7 +452,8 @@ int launch(smpc_handle* h, Staging& st, Sweep kind, smpc::KParams& k) {
   const int W = eval ? smpc::slot_width(k.T, k.N) : solve_slot_width(h, k);
   const int S = smpc::kWave / W;
   const bool sp = k.scene_params != nullptr;
-  KernelFn fn = pick(k.nb, W, kind, k.T_scene != nullptr, sp);
+  KernelFn fn = fixed_shapes_on(h) ? pick_fixed(k, W, kind, k.T_scene != nullptr, sp) : nullptr;
+  if (!fn) fn = pick(k.nb, W, kind, k.T_scene != nullptr, sp);
   const smpc::LdsLayout L = smpc::make_layout(k.T, k.N, k.P, eval ? smpc::kLayoutEval : smpc::kLayoutSolve, W, sp);
   k.hp_A = smpc::helper_owner_agents(k.T, k.N, W);
   if (std::getenv("SMPC_NO_HELPERS")) k.hp_A = k.N;  // experiment knob (the LDS layout keeps the helper regions)
@@ -645,6 +675,32 @@ int smpc_solve_slot_width(const smpc_handle* h, int32_t B, int32_t T, int32_t N)
   smpc::KParams k;
   k.B = B; k.T = T; k.N = N;
   return solve_slot_width(h, k);
+}
+
+int smpc_set_fixed_shapes(smpc_handle* h, int32_t enable) {
+  if (!h) { set_error("null handle"); return SMPC_ERR_INVALID_ARG; }
+  h->fixed_shapes = enable != 0;
+  return SMPC_OK;
+}
+
+int smpc_solve_shape_is_fixed(const smpc_handle* h, int32_t B, int32_t T, int32_t N) {
+  const int W = smpc_solve_slot_width(h, B, T, N);
+  if (W < 0) return W;
+  if (h->prm.control_horizon < 1 || h->prm.parameter_block_length < 1) { set_error("control_horizon and parameter_block_length must be >= 1"); return SMPC_ERR_INVALID_ARG; }
+  const Dims d = make_dims(h->prm, T, true);
+  smpc::KParams k;
+  k.T = T; k.N = N; k.CH = d.CH; k.bl = d.bl;
+  return (fixed_shapes_on(h) && pick_fixed(k, W, Sweep::Solve, false, false)) ? 1 : 0;
+}
+
+int smpc_eval_shape_is_fixed(const smpc_handle* h, int32_t T, int32_t N) {
+  if (!h || T < 1 || N < 0) { set_error("null handle or bad T/N"); return SMPC_ERR_INVALID_ARG; }
+  if (T + 1 > smpc::kWave || N > smpc::kWave) { set_error("T + 1 > 64 rollout poses or N > 64 agents"); return SMPC_ERR_UNSUPPORTED; }
+  if (h->prm.control_horizon < 1 || h->prm.parameter_block_length < 1) { set_error("control_horizon and parameter_block_length must be >= 1"); return SMPC_ERR_INVALID_ARG; }
+  const Dims d = make_dims(h->prm, T, true);
+  smpc::KParams k;
+  k.T = T; k.N = N; k.CH = d.CH; k.bl = d.bl;
+  return (fixed_shapes_on(h) && pick_fixed(k, smpc::slot_width(T, N), Sweep::Eval, false, false)) ? 1 : 0;
 }
 
 }  // extern "C"

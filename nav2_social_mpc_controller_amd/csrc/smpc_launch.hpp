@@ -136,7 +136,7 @@ constexpr int kPart = 18;  // 6 + 4 + 1 + 4 partial sums, nearest distance, its 
 // A is the smallest count with U (N - A) <= A: owners and helpers then finish together after A iterations instead of N
 // (BASELINE configs[4]: N = 16, T = 38 -> A = 11; params.yaml shape N = 3 -> A = 2). Returns N when helpers do not
 // pay (each unit costs a flush of ~30 instructions, the hand-over another ~40 per step).
-__host__ __device__ inline int helper_owner_agents(int T, int N, int W) {
+__host__ __device__ constexpr int helper_owner_agents(int T, int N, int W) {
   const int R = W - T;
   if (W != 64 || R < 1 || N < 2) return N;
   const int U = (T + R - 1) / R;
@@ -176,6 +176,65 @@ __host__ __device__ inline LdsLayout make_layout(int T, int N, int P, int kind, 
   return L;
 }
 
-__host__ __device__ inline int slot_width(int T, int N) { return (T + 1 <= 32 && N <= 32) ? 32 : 64; }
+__host__ __device__ constexpr int slot_width(int T, int N) { return (T + 1 <= 32 && N <= 32) ? 32 : 64; }
+
+// ------------------------------------------------------------------------------------------------
+// The shape of a launch: T, N, CH, bl and what follows from them (parameter blocks, feasibility rows, bounded blocks, the
+// slot width, every offset of make_layout()). sweep(), load_scene(), get_horizon() and the kernel bodies take it as a
+// template parameter and read it through these accessors, `k` being the launch parameters:
+//   RuntimeShape      the launch values k.T, k.N, ... : a kernel for every shape (smpc_solve_kernel, smpc_eval_kernel)
+//   FixedShape<...>   literals: the kernels of ONE shape (smpc_solve_fixed_kernel, smpc_eval_fixed_kernel). The values are
+//                     the controller's configuration (control_horizon, parameter_block_length, max_time / time_step, the
+//                     people cap), the same in every call of a handle's life; as constants they take no scalar registers,
+//                     no scalar loads, no sign extensions, and the counts of the rollout are folded.
+// Map size, resolution, dt, weights and bounds are launch values in both.
+// ------------------------------------------------------------------------------------------------
+struct RuntimeShape {
+  static constexpr bool kFixed = false;
+  template <class K> __host__ __device__ static inline int T(const K& k) { return k.T; }
+  template <class K> __host__ __device__ static inline int N(const K& k) { return k.N; }
+  template <class K> __host__ __device__ static inline int CH(const K& k) { return k.CH; }
+  template <class K> __host__ __device__ static inline int bl(const K& k) { return k.bl; }
+  template <class K> __host__ __device__ static inline int nfeas(const K& k) { return k.nfeas; }
+  template <class K> __host__ __device__ static inline int nbounded(const K& k) { return k.nbounded; }
+  template <class K> __host__ __device__ static inline int hp_A(const K& k) { return k.hp_A; }
+};
+
+// CH_ and BL_ as smpc_dims() reports them: CH = min(control_horizon, T), bl = min(parameter_block_length, CH)
+template <int T_, int N_, int CH_, int BL_> struct FixedShape {
+  static_assert(T_ >= 1 && T_ + 1 <= kWave && N_ >= 0 && N_ <= kWave, "a shape the sweep kernels take");
+  static_assert(CH_ >= 1 && CH_ <= T_ && BL_ >= 1 && BL_ <= CH_, "CH and bl are the clamped values of smpc_dims()");
+  static constexpr bool kFixed = true;
+  static constexpr int kNB = (CH_ - 1) / BL_ + 1;     // parameter blocks
+  static constexpr int kW = slot_width(T_, N_);       // the slot width its kernels are compiled for
+  static constexpr int kNbounded = CH_ / BL_;                                         // src/optimizer.cpp:373
+  static constexpr int kNfeas = (CH_ / BL_ < T_ ? CH_ / BL_ : T_) - 1 > 0 ? (CH_ / BL_ < T_ ? CH_ / BL_ : T_) - 1 : 0;  // :364
+  template <class K> __host__ __device__ static constexpr int T(const K&) { return T_; }
+  template <class K> __host__ __device__ static constexpr int N(const K&) { return N_; }
+  template <class K> __host__ __device__ static constexpr int CH(const K&) { return CH_; }
+  template <class K> __host__ __device__ static constexpr int bl(const K&) { return BL_; }
+  template <class K> __host__ __device__ static constexpr int nfeas(const K&) { return kNfeas; }
+  template <class K> __host__ __device__ static constexpr int nbounded(const K&) { return kNbounded; }
+  template <class K> __host__ __device__ static constexpr int hp_A(const K&) { return helper_owner_agents(T_, N_, kW); }
+};
+
+// The shapes that have fixed-shape kernels: X(T, N, CH, bl), one line per shape. The host picks a shape's kernels when a
+// launch has exactly these values and would otherwise run the plain <NB, W, false, false> instantiation of its slot width
+// (fixed_shape_index() below is the rule; pick_fixed() in smpc_hip.hip maps its index to the kernels).
+// (A shape whose slot width is 64 folds helper_owner_agents() in as well: the host takes no fixed-shape kernel while the
+// experiment knob SMPC_NO_HELPERS, which works through the launch value hp_A, is set.)
+#define SMPC_FIXED_SHAPES(X) \
+  X(28, 8, 18, 6) /* the headline configuration: H18 / bl6 at T = 28 with 8 people -> NB = 3, W = 32 */
+
+// index of (T, N, CH, bl) in SMPC_FIXED_SHAPES, or -1
+__host__ __device__ constexpr int fixed_shape_index(int T, int N, int CH, int bl) {
+  int i = 0;
+#define SMPC_X(t, n, ch, b) \
+  if (T == (t) && N == (n) && CH == (ch) && bl == (b)) return i; \
+  ++i;
+  SMPC_FIXED_SHAPES(SMPC_X)
+#undef SMPC_X
+  return -1;
+}
 
 }  // namespace smpc

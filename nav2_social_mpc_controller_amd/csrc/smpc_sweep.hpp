@@ -98,17 +98,18 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 // The horizon of the slot's scene: rollout steps T, control horizon CH = min(control_horizon, T), block length
 // bl = min(parameter_block_length, CH), index of the last parameter block, feasibility rows and bounded blocks
 // (src/optimizer.cpp:248-249, 364, 373). kVT = false: one T per batch, everything is a launch constant (scalar
-// registers) and the last block is NB - 1. kVT = true (smpc_scene_batch.T_scene): per scene, kept in LDS by load_scene();
+// registers; literals with a FixedShape, smpc_launch.hpp) and the last block is NB - 1. kVT = true (smpc_scene_batch.T_scene): per scene, kept in LDS by load_scene();
 // a scene with fewer blocks than the batch's NB keeps its surplus parameters at exactly zero — their Jacobian columns
 // are zero, the damped system is block diagonal and every sum gains exact zeros, so the iterates of the real
 // parameters are those of the smaller problem bit for bit.
 struct Horizon { int T, CH, bl, blast, nfeas, nbounded; };
 
-template <int NB, bool kVT> __device__ inline Horizon get_horizon(const Ctx& c) {
+template <int NB, bool kVT, class Shape = RuntimeShape> __device__ inline Horizon get_horizon(const Ctx& c) {
+  static_assert(!(kVT && Shape::kFixed), "a fixed shape has one horizon for every scene");
   Horizon h;
   if (!kVT) {
     const auto& k = *c.kp;
-    h.T = k.T; h.CH = k.CH; h.bl = k.bl; h.blast = NB - 1; h.nfeas = k.nfeas; h.nbounded = k.nbounded;
+    h.T = Shape::T(k); h.CH = Shape::CH(k); h.bl = Shape::bl(k); h.blast = NB - 1; h.nfeas = Shape::nfeas(k); h.nbounded = Shape::nbounded(k);
   } else {
     const int* z = reinterpret_cast<const int*>(c.lds + c.L.hz);
     h.T = z[0]; h.CH = z[1]; h.bl = z[2]; h.blast = z[3]; h.nfeas = z[4]; h.nbounded = z[5];
@@ -133,10 +134,10 @@ __device__ inline int block_end(int b, const Horizon& h) {
 // Load the slot's scene constants and the per-step side data of its staged people block (valid masks, agent-angle
 // tags) into LDS; the records themselves stay in global memory (c.ag). Executed by all W lanes of the slot (other
 // slots may be masked off).
-template <int W, bool kVT = false, bool kSP = false>
+template <int W, bool kVT = false, bool kSP = false, class Shape = RuntimeShape>
 __device__ inline void load_scene(Ctx& c, int scene) {
   const auto& k = *c.kp;
-  const int T = k.T, N = k.N, sl = c.sl;
+  const int T = Shape::T(k), N = Shape::N(k), sl = c.sl;
   if (kSP && sl < kSceneParamDoubles)  // the scene's row of smpc_scene_params, one value per lane
     (c.lds + c.L.sp)[sl] = reinterpret_cast<const double*>(k.scene_params + scene)[sl];
   int Th = T;  // the scene's own horizon
@@ -202,12 +203,14 @@ __device__ inline void load_scene(Ctx& c, int scene) {
 // and gradient there, LineSearchFunction::Evaluate), and most sweeps of a solve are such samples. c.gram_full tells
 // the caller what it got (wave-uniform). Every entry is summed in the same order whichever way it is produced.
 struct NeedAll { __device__ inline bool operator()() const { return true; } };
-template <int NB, int W, bool kRows, bool kVT = false, bool kSP = false, class NeedRest = NeedAll>
+// Shape: where T, N, CH, bl and what follows from them come from — the launch values (RuntimeShape) or the literals of a
+// FixedShape (smpc_launch.hpp). The arithmetic on doubles and the order of every sum are the same in both.
+template <int NB, int W, bool kRows, bool kVT = false, bool kSP = false, class Shape = RuntimeShape, class NeedRest = NeedAll>
 __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double* out_J, NeedRest need_rest = NeedRest()) {
   constexpr int P = 2 * NB;
   const auto& k = *c.kp;
-  const int T = k.T, N = k.N, sl = c.sl;  // T: the batch's T = the stride of every per-step array
-  const Horizon hz = get_horizon<NB, kVT>(c);
+  const int T = Shape::T(k), N = Shape::N(k), sl = c.sl;  // T: the batch's T = the stride of every per-step array
+  const Horizon hz = get_horizon<NB, kVT, Shape>(c);
   const int Th = hz.T, CH = hz.CH, bl = hz.bl;  // Th: the scene's own rollout steps (== T unless kVT)
   const double dt = k.dt;
   double* cs_ = c.lds + c.L.cs;
@@ -336,7 +339,7 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
       qh[2] = fma(F.fx, F.dfx_dux, fma(F.fy, F.dfy_dux, qh[2]));
       qh[3] = fma(F.fx, F.dfx_duy, fma(F.fy, F.dfy_duy, qh[3]));
     };
-    const int A = (W == 64) ? k.hp_A : N;  // agents the owner lane walks itself (helper_owner_agents(): N without helpers)
+    const int A = (W == 64) ? Shape::hp_A(k) : N;  // agents the owner lane walks itself (helper_owner_agents(): N without helpers)
     if (W == 64 && A < N) {
       // ---- with helper lanes (see helper_owner_agents()): lanes sl >= T walk agents A .. N-1 of the steps h, h + R, ...
       const int NA = N - A, R = W - T;
@@ -700,7 +703,7 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
   view.ld = Q;
   if (kRows) {
     // a9 velocity feasibility between blocks sl and sl-1 (src/optimizer.cpp:364-370); the row follows step sl
-    if (k.nfeas > 0) {
+    if (Shape::nfeas(k) > 0) {
       const bool live = lane_live && sl >= 1 && sl <= hz.nfeas;
       double row[P];
 #pragma unroll

@@ -52,7 +52,7 @@ def load_library():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in _abi.FUNCTIONS.items():
+    for name, (restype, argtypes) in {**_abi.FUNCTIONS, **_abi.FIXED_SHAPE_FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -187,6 +187,19 @@ class BatchSolver:
     def solve_slot_width(self, B: int, T: int, N: int) -> int:
         """smpc_solve_slot_width: 32 (two scenes per wave) or 64 (one) for a solve launch of this shape."""
         return self._call("smpc_solve_slot_width", int(B), int(T), int(N))
+
+    def set_fixed_shapes(self, enable: bool):
+        """smpc_set_fixed_shapes: whether launches of a listed shape run that shape's compile-time-shape kernels (default
+        on; the results are the same bit for bit either way)."""
+        self._call("smpc_set_fixed_shapes", 1 if enable else 0)
+
+    def solve_shape_is_fixed(self, B: int, T: int, N: int) -> bool:
+        """smpc_solve_shape_is_fixed: does a plain solve launch of this shape run a fixed-shape kernel?"""
+        return self._call("smpc_solve_shape_is_fixed", int(B), int(T), int(N)) == 1
+
+    def eval_shape_is_fixed(self, T: int, N: int) -> bool:
+        """smpc_eval_shape_is_fixed: does a plain K1 launch (evaluate / eval_device) of this shape run a fixed-shape kernel?"""
+        return self._call("smpc_eval_shape_is_fixed", int(T), int(N)) == 1
 
     def math_probe(self, fn: int, a: np.ndarray, b: np.ndarray = None):
         """smpc_math_probe: the sweep's elementary functions evaluated on the device (see include/smpc.h)."""

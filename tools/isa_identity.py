@@ -36,6 +36,8 @@ RENAMES = [
     (r"_ZN4smpc23smpc_solve_trace_kernelILi(\d+)ELi(\d+)E" + _TAIL, r"_ZN4smpc17smpc_solve_kernelILi\1ELi\2ELb1ELb1ELb1E" + _TAIL),
     # smpc_crowd_step_kernel -> smpc_crowd_step_kernel<false, CrowdParams> (kGroups = true is the groups kernel)
     (r"_ZN4smpc22smpc_crowd_step_kernelENS_11CrowdParamsE", r"_ZN4smpc22smpc_crowd_step_kernelILb0ENS_11CrowdParamsEEEvT0_"),
+    # (smpc_solve_fixed_kernel<FixedShape<T, N, CH, bl>> and smpc_eval_fixed_kernel<...> stand beside smpc_solve_kernel /
+    # smpc_eval_kernel, whose names did not change: against a tree without them they are NEW under --allow-new)
 ]
 # what cannot matter: the numbers the compiler gives basic blocks, temporaries, jump tables and function ends
 LABELS = [(r"\.LBB\d+_", ".LBB_"), (r"\.Ltmp\d+", ".Ltmp"), (r"\.LJTI\d+_", ".LJTI_"), (r"\.LCPI\d+_", ".LCPI_"),

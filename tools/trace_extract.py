@@ -14,7 +14,7 @@ with open(sys.argv[1]) as fh:
                      r.get("Queue_Id", "?")))
 rows.sort()
 t0 = rows[0][0]
-solve = [(a, b) for a, b, n, q in rows if "solve_kernel" in n]
+solve = [(a, b) for a, b, n, q in rows if "smpc_solve" in n]  # smpc_solve_kernel and smpc_solve_fixed_kernel
 print("# begin_us end_us dur_us queue kernel solve_kernels_in_flight_at_begin")
 for a, b, n, q in rows:
     inflight = sum(1 for (x, y) in solve if x <= a < y)
