@@ -690,7 +690,10 @@ int smpc_math_probe(smpc_handle* h, int32_t fn, int32_t n, const double* a, cons
 double smpc_fp64_peak_probe(smpc_handle* h, int32_t iters);
 
 /* Timing of the most recent kernel launched by this handle, measured with HIP events on the handle's
- * stream. Returns milliseconds, <0 if unavailable. Synchronises the stream. */
+ * stream. Returns milliseconds, <0 if unavailable. Synchronises the stream.
+ * After a solve on reference-layout people (people_records == NULL) that is the solve kernel alone where a staging kernel
+ * ran ahead of it, and the solve kernel with the staging inside it where the kernel stages every scene as it fetches it
+ * (the fixed-shape solve kernel: smpc_solve_shape_is_fixed). */
 double smpc_last_kernel_ms(smpc_handle* h);
 
 const char* smpc_last_error(void);

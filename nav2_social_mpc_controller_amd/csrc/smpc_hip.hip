@@ -9,7 +9,7 @@
 //                            smpc_eval_kernel.hpp);
 //                            kVT: per-scene horizons; kSP (with kVT): per-scene weights and velocity bounds as well
 //                            (smpc_scene_batch.scene_params);
-//   smpc_stage_kernel<W>     the staging pass of the people block (smpc_stage.hpp);
+//   smpc_stage_kernel<W>     the staging pass of the people block (smpc_stage_kernel.hpp);
 //   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window).
 #include <hip/hip_runtime.h>
 
@@ -26,7 +26,7 @@
 #include "smpc_launch.hpp"
 #include "smpc_lm.hpp"
 #include "smpc_solve_kernel.hpp"
-#include "smpc_stage.hpp"
+#include "smpc_stage_kernel.hpp"
 #include "smpc_project.hpp"
 #include "smpc_distance.hpp"
 #include "smpc_format.hpp"
@@ -199,20 +199,24 @@ KernelFn pick(int nb, int W, Sweep kind, bool vt = false, bool sp = false) {
 // same results bit for bit. They stand in for the plain instantiation <NB, W, false, false> only: a launch with a horizon
 // or parameters per scene, a trace, or the other slot width (the one-scene-per-wave kernel of a small batch) runs the
 // run-time-shape kernel it always ran.
-template <class Shape> KernelFn fixed_fn(Sweep kind, int W) {
+// *stages (if given): whether the kernel returned can stage the people block itself at the scene fetch (the solve kernel
+// of a Shape with kStageAtFetch; K1 never does)
+template <class Shape> KernelFn fixed_fn(Sweep kind, int W, bool* stages) {
 #ifdef SMPC_ONLY_NB
   if constexpr (Shape::kNB != SMPC_ONLY_NB) return nullptr; else
 #endif
   if (W != Shape::kW) return nullptr;
-  else return kind == Sweep::Eval ? smpc::smpc_eval_fixed_kernel<Shape> : smpc::smpc_solve_fixed_kernel<Shape>;
+  if (stages) *stages = kind == Sweep::Solve && Shape::kStageAtFetch;
+  return kind == Sweep::Eval ? smpc::smpc_eval_fixed_kernel<Shape> : smpc::smpc_solve_fixed_kernel<Shape>;
 }
 
-KernelFn pick_fixed(const smpc::KParams& k, int W, Sweep kind, bool vt, bool sp) {
+KernelFn pick_fixed(const smpc::KParams& k, int W, Sweep kind, bool vt, bool sp, bool* stages = nullptr) {
+  if (stages) *stages = false;
   if (kind == Sweep::Trace || vt || sp) return nullptr;
   const int want = smpc::fixed_shape_index(k.T, k.N, k.CH, k.bl);  // the rule; below only the index -> kernel table
   int i = 0;
 #define SMPC_X(t, n, ch, b) \
-  if (want == i++) return fixed_fn<smpc::FixedShape<t, n, ch, b>>(kind, W);
+  if (want == i++) return fixed_fn<smpc::FixedShape<t, n, ch, b>>(kind, W, stages);
   SMPC_FIXED_SHAPES(SMPC_X)
 #undef SMPC_X
   return nullptr;
@@ -403,23 +407,6 @@ int launch_stage(smpc_handle* h, smpc::KParams& k, double* rec, double* aux) {
   return SMPC_OK;
 }
 
-// Makes k.people_rec / k.people_aux valid: the caller's staged block, or the library's own staging pass into the
-// handle's buffers (timed separately: smpc_last_kernel_ms() reports the solve / sweep kernel alone).
-int bind_people(smpc_handle* h, const smpc_scene_batch* sb, smpc::KParams& k, Staging* st) {
-  if (sb->N == 0) return SMPC_OK;
-  const size_t nrec = (size_t)sb->B * sb->N * sb->T * 4, naux = (size_t)sb->B * sb->T * 2;
-  if (sb->people_records) {
-    SMPC_TRY(st->in(k.people_rec, sb->people_records, nrec));
-    return st->in(k.people_aux, sb->people_aux, naux);
-  }
-  SMPC_TRY(grow(&h->stage_rec, &h->stage_rec_bytes, nrec * sizeof(double), h->stream));
-  SMPC_TRY(grow(&h->stage_aux, &h->stage_aux_bytes, naux * sizeof(double), h->stream));
-  SMPC_TRY(st->flush_up());
-  SMPC_TRY(launch_stage(h, k, h->stage_rec, h->stage_aux));
-  k.people_rec = h->stage_rec; k.people_aux = h->stage_aux;
-  return SMPC_OK;
-}
-
 // Waves per CU a solve launch takes when it is sized for having the GPU to itself (launch(), below).
 int lone_waves_per_cu() {
   int lone_per_cu = 8;
@@ -446,14 +433,53 @@ int solve_slot_width(const smpc_handle* h, const smpc::KParams& k) {
   return (k.B <= per_cu * h->num_cu / share) ? 64 : 32;
 }
 
+// The kernel a launch runs: its slot width, the function, and whether that kernel stages the people block itself.
+struct Picked { int W; KernelFn fn; bool stages; };
+Picked pick_launch(const smpc_handle* h, const smpc::KParams& k, Sweep kind) {
+  Picked p;
+  p.W = kind == Sweep::Eval ? smpc::slot_width(k.T, k.N) : solve_slot_width(h, k);
+  p.stages = false;
+  const bool sp = k.scene_params != nullptr;
+  p.fn = fixed_shapes_on(h) ? pick_fixed(k, p.W, kind, k.T_scene != nullptr, sp, &p.stages) : nullptr;
+  if (!p.fn) p.fn = pick(k.nb, p.W, kind, k.T_scene != nullptr, sp);
+  return p;
+}
+
+// Makes the people block of a launch of `kind` readable by its kernel: the caller's staged block; or, where the kernel
+// picked for the launch stages each scene as it fetches it (pick_launch().stages: the fixed-shape solve kernel), room for
+// the records and k.stage_at_fetch — no staging kernel, no aux array, and smpc_last_kernel_ms() then covers the staging;
+// or the library's own staging pass into the handle's buffers (timed separately: smpc_last_kernel_ms() reports the
+// solve / sweep kernel alone).
+int bind_people(smpc_handle* h, const smpc_scene_batch* sb, smpc::KParams& k, Staging* st, Sweep kind) {
+  if (sb->N == 0) return SMPC_OK;
+  const size_t nrec = (size_t)sb->B * sb->N * sb->T * 4, naux = (size_t)sb->B * sb->T * 2;
+  if (sb->people_records) {
+    SMPC_TRY(st->in(k.people_rec, sb->people_records, nrec));
+    return st->in(k.people_aux, sb->people_aux, naux);
+  }
+  SMPC_TRY(grow(&h->stage_rec, &h->stage_rec_bytes, nrec * sizeof(double), h->stream));
+  if (pick_launch(h, k, kind).stages) {
+    k.stage_at_fetch = 1;  // (its own field: launch_stage() sets stage_rec for the staging kernel on this very struct)
+    k.stage_rec = h->stage_rec;
+    k.people_rec = h->stage_rec;
+    return SMPC_OK;
+  }
+  SMPC_TRY(grow(&h->stage_aux, &h->stage_aux_bytes, naux * sizeof(double), h->stream));
+  SMPC_TRY(st->flush_up());
+  SMPC_TRY(launch_stage(h, k, h->stage_rec, h->stage_aux));
+  k.people_rec = h->stage_rec; k.people_aux = h->stage_aux;
+  return SMPC_OK;
+}
+
 // Sweep::Trace: the solve kernel that also writes k.o_trace / k.o_trace_n (k.scene_params is set by then)
 int launch(smpc_handle* h, Staging& st, Sweep kind, smpc::KParams& k) {
   const bool eval = kind == Sweep::Eval;
-  const int W = eval ? smpc::slot_width(k.T, k.N) : solve_slot_width(h, k);
+  const Picked picked = pick_launch(h, k, kind);
+  const int W = picked.W;
   const int S = smpc::kWave / W;
   const bool sp = k.scene_params != nullptr;
-  KernelFn fn = fixed_shapes_on(h) ? pick_fixed(k, W, kind, k.T_scene != nullptr, sp) : nullptr;
-  if (!fn) fn = pick(k.nb, W, kind, k.T_scene != nullptr, sp);
+  KernelFn fn = picked.fn;
+  if (k.stage_at_fetch && !picked.stages) { set_error("internal: a launch without staged people on a kernel that stages none"); return SMPC_ERR_UNSUPPORTED; }
   const smpc::LdsLayout L = smpc::make_layout(k.T, k.N, k.P, eval ? smpc::kLayoutEval : smpc::kLayoutSolve, W, sp);
   k.hp_A = smpc::helper_owner_agents(k.T, k.N, W);
   if (std::getenv("SMPC_NO_HELPERS")) k.hp_A = k.N;  // experiment knob (the LDS layout keeps the helper regions)
@@ -717,7 +743,7 @@ int solve_batch(smpc_handle* h, const smpc_scene_batch* sb, smpc_result_batch* o
   fill_kparams(h, sb, d, &k);
   Staging st(h, sb->on_device);
   SMPC_TRY(bind_inputs(sb, d, &k, &st));
-  SMPC_TRY(bind_people(h, sb, k, &st));
+  SMPC_TRY(bind_people(h, sb, k, &st, trace ? Sweep::Trace : Sweep::Solve));
   const size_t B = sb->B, T = sb->T;
   if (sb->order && !sb->on_device) {  // queue order hint
     std::vector<uint8_t> seen(B, 0);
@@ -1255,7 +1281,7 @@ int smpc_eval_batch(smpc_handle* h, const smpc_scene_batch* sb, const double* pa
   fill_kparams(h, sb, d, &k);
   Staging st(h, sb->on_device);
   SMPC_TRY(bind_inputs(sb, d, &k, &st));
-  SMPC_TRY(bind_people(h, sb, k, &st));
+  SMPC_TRY(bind_people(h, sb, k, &st, Sweep::Eval));
   const size_t B = sb->B;
   k.e_row_order = out->row_order;
   SMPC_TRY(st.in(k.e_x, params, B * d.P));

@@ -21,6 +21,9 @@ constexpr int kWave = 64;
 constexpr double kNoTarget = 1e300;  // agent-angle tag: no steering target at this step
 constexpr int kSoc = 15;  // sum F(2), sum dF/d{x,y,th,v}(8), sum |G|^2 (1), sum d|G|^2/d{x,y,th,v} (4)
 
+typedef double v4d __attribute__((ext_vector_type(4)));  // one staged people record (px, py, vx, vy): 32 bytes, moved whole
+typedef double v2d __attribute__((ext_vector_type(2)));
+
 struct KParams {
   int B, T, N, CH, bl, nb, P, nbounded, nfeas;
   int size_x, size_y, costmap_shared;
@@ -74,6 +77,10 @@ struct KParams {
   double* o_trace;      // [B][trace_rows][kTraceCols] one row per LM iteration; rows >= trace_rows are not stored
   int32_t* o_trace_n;   // [B] rows the solve produced (may exceed trace_rows), or null
   int trace_rows;
+  // kernels that stage at the scene fetch only (Shape::kStageAtFetch; smpc_solve_fixed_kernel)
+  int stage_at_fetch;   // != 0: people_rec / people_aux hold nothing yet. The slot that fetches a scene turns its people
+                        // block (`people`) into records at stage_rec, masks and tags in its LDS (load_scene()); no
+                        // staging kernel ran and stage_aux is not used. 0: people_rec / people_aux are read as staged
 };
 constexpr int kTraceCols = SMPC_TRACE_COLS;
 
@@ -191,6 +198,7 @@ __host__ __device__ constexpr int slot_width(int T, int N) { return (T + 1 <= 32
 // ------------------------------------------------------------------------------------------------
 struct RuntimeShape {
   static constexpr bool kFixed = false;
+  static constexpr bool kStageAtFetch = false;  // its solve kernels read a people block the staging kernel has staged
   template <class K> __host__ __device__ static inline int T(const K& k) { return k.T; }
   template <class K> __host__ __device__ static inline int N(const K& k) { return k.N; }
   template <class K> __host__ __device__ static inline int CH(const K& k) { return k.CH; }
@@ -205,6 +213,10 @@ template <int T_, int N_, int CH_, int BL_> struct FixedShape {
   static_assert(T_ >= 1 && T_ + 1 <= kWave && N_ >= 0 && N_ <= kWave, "a shape the sweep kernels take");
   static_assert(CH_ >= 1 && CH_ <= T_ && BL_ >= 1 && BL_ <= CH_, "CH and bl are the clamped values of smpc_dims()");
   static constexpr bool kFixed = true;
+  // The solve kernel of a fixed shape may stage a scene's people block itself where it fetches the scene, instead of a
+  // staging kernel ahead of the launch (KParams::stage_at_fetch says whether a launch does; load_scene(), smpc_sweep.hpp).
+  // A property of the kernel, so that the kernels of RuntimeShape carry no test for it. K1 never stages.
+  static constexpr bool kStageAtFetch = true;
   static constexpr int kNB = (CH_ - 1) / BL_ + 1;     // parameter blocks
   static constexpr int kW = slot_width(T_, N_);       // the slot width its kernels are compiled for
   static constexpr int kNbounded = CH_ / BL_;                                         // src/optimizer.cpp:373

@@ -256,4 +256,13 @@ SMPC_MATH_FN void sincos_tab(TabP t, double theta, double* sn, double* cs) {
   *sn = us.d; *cs = uc.d;
 }
 
+// atan2(sin u, cos u) restated as a range reduction of u into (-pi, pi]; equal up to round-off
+// (critics/agent_angle_cost_function.hpp:156, critics/goal_align_cost_function.hpp:111-112).
+SMPC_MATH_FN double wrap_angle(double u) {
+  const double k = rint(u * (0.5 / M_PI));
+  double r = fma(-k, 2.0 * M_PI, u);
+  r = fma(-k, 2.4492935982947064e-16, r);  // 2*pi - (double)(2*pi)
+  return r;
+}
+
 }  // namespace smpc

@@ -143,7 +143,7 @@
       }
       scene = __shfl(scene, slot * W, 64);
       if (scene < k.B) {
-        load_scene<W, kVT, kSP, Shape>(c, scene);
+        load_scene<W, kVT, kSP, Shape, Shape::kStageAtFetch>(c, scene);
         ever_loaded = true;
         wave_lds_fence();
         const Horizon hz0 = get_horizon<NB, kVT, Shape>(c);
@@ -164,7 +164,7 @@
         R.step_successful = true; R.at_least_one = false;
       } else {
         if (!ever_loaded) {  // keep the sweep's memory accesses in bounds for a slot that never got a scene
-          load_scene<W, kVT, kSP, Shape>(c, 0);
+          load_scene<W, kVT, kSP, Shape, Shape::kStageAtFetch>(c, 0, false);  // (a kernel that stages at the fetch: not here)
           ever_loaded = true;
           if (act) xt[q] = 0.0;
         }

@@ -1,19 +1,23 @@
 // smpc_stage.hpp — the staging pass: the people block of the reference layout turned into the records, valid masks and
-// agent-angle tags the sweep reads (stage_people), and the kernel that runs it once per people block.
+// agent-angle tags the sweep reads (stage_people). Two callers, one text: the staging kernel (smpc_stage_kernel.hpp), once
+// per people block ahead of a launch, and load_scene() of a solve kernel that stages at the scene fetch (smpc_sweep.hpp).
+// Host and device: tests/native/stage_shim.hip runs it lane by lane on the host.
 #pragma once
 
-#include "smpc_sweep.hpp"
+#include "smpc_launch.hpp"
+#include "smpc_math.hpp"
 
 namespace smpc {
 
-// Staging pass (its own kernel, once per people block): gather the slot's people block, agent index fastest across
-// lanes (coalesced runs of one people row, 16 loads in flight per lane), convert to one 32-byte record (px, py, vx, vy)
-// per (agent, step) at record index a * T + t in LDS (ag), and compute per step the bit mask of valid agents (vmask)
-// and the agent-angle tag (aa). Executed by all W lanes of the slot.
-template <int W>
-__device__ inline void stage_people(KParamsK kp, int scene, int sl, double* ag, unsigned long long* vmask, double* aa) {
+// Gather the slot's people block, agent index fastest across lanes (coalesced runs of one people row, 16 loads in flight
+// per lane), convert to one 32-byte record (px, py, vx, vy) per (agent, step) at record index a * T + t of `ag` (the
+// staging kernel: LDS; at the scene fetch: the scene's records in global memory), and compute per step the bit mask of
+// valid agents (vmask) and the agent-angle tag (aa). Executed by all W lanes of the slot.
+// Shape: T and N as launch values or literals (smpc_launch.hpp). KP: the launch parameters where the caller has them.
+template <int W, class Shape = RuntimeShape, class KP = KParamsK>
+__host__ __device__ inline void stage_people(KP kp, int scene, int sl, double* ag, unsigned long long* vmask, double* aa) {
   const auto& k = *kp;
-  const int T = k.T, N = k.N;
+  const int T = Shape::T(k), N = Shape::N(k);
   const size_t s = scene;
   const double x0 = k.pose0[3 * s], y0 = k.pose0[3 * s + 1], yaw0 = k.pose0[3 * s + 2];
   const double* ppl = k.people + s * (size_t)(T + 1) * 6 * N;
@@ -82,43 +86,6 @@ __device__ inline void stage_people(KParamsK kp, int scene, int sl, double* ag, 
     }
     vmask[sl] = m;
     aa[sl] = aa_target;
-  }
-}
-
-// Staging pass: people block of the reference layout ([T+1][6][N] per scene) -> the records the sweep reads
-// ([N][T] x (px, py, vx, vy), written as whole 128-byte lines through LDS) + per-step valid mask and agent-angle tag.
-// One slot per scene like the sweep kernels; once per people block (a solve re-reads the records ~50 times).
-template <int W>
-__global__ __launch_bounds__(64) void smpc_stage_kernel(const KParams) {
-  SMPC_CHAIN_PRIORITY();
-  const auto& k = *(KParamsK)__builtin_amdgcn_kernarg_segment_ptr();
-  constexpr int S = kWave / W;
-  extern __shared__ __attribute__((aligned(32))) double lds_all[];
-  const int lane = threadIdx.x & 63;
-  const int slot = lane / W, sl = lane - slot * W;
-  const int T = k.T, N = k.N;
-  const LdsLayout L = make_layout(T, N, 2, kLayoutStage, W);
-  double* lds = lds_all + (size_t)slot * L.total;
-  const int scene_raw = blockIdx.x * S + slot;
-  const bool live = scene_raw < k.B;
-  const int scene = live ? scene_raw : k.B - 1;
-  const bool has_people = k.has_people ? k.has_people[scene] != 0 : true;
-  double* ag = lds + L.ag;
-  unsigned long long* vmask = reinterpret_cast<unsigned long long*>(lds + L.valid);
-  double* aa = lds + L.lanec;
-  if (has_people) stage_people<W>(&k, scene, sl, ag, vmask, aa);
-  wave_lds_fence();
-  if (live && has_people) {
-    const size_t s = scene;
-    const int nrec = N * T;
-    v4d* dst = reinterpret_cast<v4d*>(k.stage_rec + s * (size_t)4 * nrec);
-    const v4d* src = reinterpret_cast<const v4d*>(ag);
-    for (int q = sl; q < nrec; q += W) dst[q] = src[q];  // consecutive lanes, consecutive 32-byte records
-    if (sl < T) {
-      double* aux = k.stage_aux + (s * T + sl) * 2;
-      aux[0] = (lds + L.valid)[sl];
-      aux[1] = aa[sl];
-    }
   }
 }
 

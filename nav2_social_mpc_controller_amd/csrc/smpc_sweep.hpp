@@ -21,6 +21,7 @@
 #include "smpc_launch.hpp"
 #include "smpc_math.hpp"
 #include "smpc_social_force.hpp"
+#include "smpc_stage.hpp"
 
 namespace smpc {
 
@@ -37,15 +38,6 @@ template <int W> __device__ inline double slot_sum(double v) {
 #pragma unroll
   for (int off = W / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
-}
-
-// atan2(sin u, cos u) restated as a range reduction of u into (-pi, pi]; equal up to round-off
-// (critics/agent_angle_cost_function.hpp:156, critics/goal_align_cost_function.hpp:111-112).
-__device__ inline double wrap_angle(double u) {
-  const double k = rint(u * (0.5 / M_PI));
-  double r = fma(-k, 2.0 * M_PI, u);
-  r = fma(-k, 2.4492935982947064e-16, r);  // 2*pi - (double)(2*pi)
-  return r;
 }
 
 // In-kernel phase stamps (diagnostic build -DSMPC_STAMPS only; the shipped kernel executes none of this).
@@ -92,9 +84,6 @@ struct GramView {
   __device__ inline double operator()(int a, int b) const { return base[a * ld + b]; }
 };
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-typedef double v2d __attribute__((ext_vector_type(2)));
-
 // The horizon of the slot's scene: rollout steps T, control horizon CH = min(control_horizon, T), block length
 // bl = min(parameter_block_length, CH), index of the last parameter block, feasibility rows and bounded blocks
 // (src/optimizer.cpp:248-249, 364, 373). kVT = false: one T per batch, everything is a launch constant (scalar
@@ -134,8 +123,13 @@ __device__ inline int block_end(int b, const Horizon& h) {
 // Load the slot's scene constants and the per-step side data of its staged people block (valid masks, agent-angle
 // tags) into LDS; the records themselves stay in global memory (c.ag). Executed by all W lanes of the slot (other
 // slots may be masked off).
-template <int W, bool kVT = false, bool kSP = false, class Shape = RuntimeShape>
-__device__ inline void load_scene(Ctx& c, int scene) {
+// kStage (a solve kernel of a Shape with kStageAtFetch) and a launch with k.stage_at_fetch: no staging kernel ran. The
+// slot's lanes stage the scene's people block here, with stage_people() itself — the records to the scene's region of
+// k.stage_rec, masks and tags straight into the slot's LDS, nothing through k.people_aux. `stage` = false (the scene a
+// slot loads only to have addresses in bounds, its results never stored) stages nothing and walks no agents: that
+// scene's region belongs to the slot that fetched it from the queue.
+template <int W, bool kVT = false, bool kSP = false, class Shape = RuntimeShape, bool kStage = false>
+__device__ inline void load_scene(Ctx& c, int scene, bool stage = true) {
   const auto& k = *c.kp;
   const int T = Shape::T(k), N = Shape::N(k), sl = c.sl;
   if (kSP && sl < kSceneParamDoubles)  // the scene's row of smpc_scene_params, one value per lane
@@ -168,16 +162,36 @@ __device__ inline void load_scene(Ctx& c, int scene) {
   cst[6] = path_pts[2 * Th];  // final trajectorized point (src/optimizer.cpp:234-235)
   cst[7] = path_pts[2 * Th + 1];
   double* lanec = c.lds + c.L.lanec;
+  bool staged_here = false;  // masks and tags of this scene are in LDS already
+  if constexpr (kStage) {
+    if (k.stage_at_fetch) {
+      if (!stage) c.has_people = false;
+      if (c.has_people) {
+        double* rec = k.stage_rec + s * (size_t)4 * T * N;  // 32 T N bytes: whole 128-byte lines, none shared with a neighbour
+        stage_people<W, Shape>(c.kp, scene, sl, rec, reinterpret_cast<unsigned long long*>(c.lds + c.L.valid), lanec + 2 * T);
+        c.ag = rec;
+        // Lane l stored records (a, t) that lane t reads in every sweep, through global memory: program order within a
+        // lane says nothing about what another lane's load finds, and a wavefront-scope fence orders LDS traffic only. The
+        // release makes the wave's stores complete and visible at the device's L2 before anything behind it, the acquire
+        // drops what the CU's vector cache holds, so that no load of the sweeps can be served from a line cached before
+        // the stores (the region's previous contents: an earlier launch of this handle). Once per scene fetch; nothing
+        // waits on another wave, the records have one writer and one reader, this slot.
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        staged_here = true;
+      }
+    }
+  }
   if (sl < T) {
     double aa_target = kNoTarget;
-    if (c.has_people) {
+    if (c.has_people && !staged_here) {
       const double* aux = k.people_aux + (s * T + sl) * 2;
       (c.lds + c.L.valid)[sl] = aux[0];  // the mask's bits travel in a double-sized slot
       aa_target = aux[1];
     }
     lanec[sl] = path_pts[2 * (sl + 1)];
     lanec[T + sl] = path_pts[2 * (sl + 1) + 1];
-    lanec[2 * T + sl] = aa_target;
+    if (!staged_here) lanec[2 * T + sl] = aa_target;
   }
 }
 
