@@ -1,5 +1,8 @@
-// smpc_hip.hip — kernels + the C ABI of include/smpc.h (libsmpc_hip.so). gfx950 only, no CPU fallback.
+// smpc_hip.hip — the C ABI of include/smpc.h (libsmpc_hip.so): the entry points, one translation unit with the kernels
+// and the host code they include. gfx950 only, no CPU fallback.
 //
+// Host side: smpc_host.hpp (the handle, errors, the staging of host-pointer calls), smpc_plan.hpp (what a sweep launch
+// will be: width, variant, fixed shape, LDS; pure host code), smpc_sweep_host.hpp (checks, plan -> kernel, the launch).
 // Kernels (one 64-lane wavefront per workgroup, split into 64/W scene slots; lane mapping and LDS layout: smpc_launch.hpp):
 //   smpc_solve_kernel<NB,W,kVT,kSP,kTrace>  persistent sweep engine: whole ceres::Solve-equivalent (reference
 //                            src/optimizer.cpp:241-446) per scene, LM state resident in registers / LDS for all
@@ -10,23 +13,18 @@
 //                            kVT: per-scene horizons; kSP (with kVT): per-scene weights and velocity bounds as well
 //                            (smpc_scene_batch.scene_params);
 //   smpc_stage_kernel<W>     the staging pass of the people block (smpc_stage_kernel.hpp);
+//   the probe kernels (smpc_probes.hpp);
 //   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <string>
 #include <vector>
 
-#include "../../include/smpc_fixed_shapes.h"
-#include "smpc_eval_kernel.hpp"
-#include "smpc_launch.hpp"
-#include "smpc_lm.hpp"
-#include "smpc_solve_kernel.hpp"
-#include "smpc_stage_kernel.hpp"
+#include "smpc_host.hpp"
+#include "smpc_sweep_host.hpp"
+#include "smpc_probes.hpp"
 #include "smpc_project.hpp"
 #include "smpc_distance.hpp"
 #include "smpc_format.hpp"
@@ -34,575 +32,6 @@
 #include "smpc_path_window.hpp"
 #include "smpc_metrics.hpp"
 #include "smpc_crowd.hpp"
-
-// ================================================================================================
-// Host side of the C ABI
-// ================================================================================================
-namespace {
-
-thread_local std::string g_last_error;
-
-void set_error(const std::string& s) { g_last_error = s; }
-
-#define SMPC_HIP_CHECK(expr)                                                                   \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess) {                                                                    \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                            \
-      return SMPC_ERR_DEVICE;                                                                  \
-    }                                                                                          \
-  } while (0)
-
-struct Dims { int CH, bl, nb, P, M, nbounded, nfeas; };
-
-Dims make_dims(const smpc_params& p, int T, bool has_people) {
-  Dims d;
-  d.CH = p.control_horizon < T ? p.control_horizon : T;                 // src/optimizer.cpp:248
-  d.bl = p.parameter_block_length < d.CH ? p.parameter_block_length : d.CH;  // :249
-  if (d.bl < 1) d.bl = 1;
-  d.nb = (d.CH - 1) / d.bl + 1;
-  d.P = 2 * d.nb;
-  d.nbounded = d.CH / d.bl;                                             // :373
-  int nf = (d.CH / d.bl < T ? d.CH / d.bl : T) - 1;                      // :364
-  d.nfeas = nf > 0 ? nf : 0;
-  d.M = (has_people ? 8 : 5) * T + d.nfeas;
-  return d;
-}
-
-}  // namespace
-
-namespace smpc {
-struct ProbeParams { int fn, n; const double* a; const double* b; double* o0; double* o1; MathTab mt; AtanNodeTab an; };
-__global__ void smpc_math_probe_kernel(const ProbeParams) {
-  const auto& k = *(const ProbeParams __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
-  __shared__ double atab[kAtanTabDoubles];  // the LDS copy of the nodes, as in the sweep kernels
-  for (int j = threadIdx.x; j < kAtanTabDoubles; j += blockDim.x) atab[j] = k.an.v[j];
-  __syncthreads();
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k.n) return;
-  const double a = (k.fn == 7) ? 0.0 : k.a[i], b = k.b ? k.b[i] : 0.0;
-  double r0 = 0.0, r1 = 0.0;
-  switch (k.fn) {
-    case 0: r0 = exp_tab(&k.mt, a); break;
-    case 1: r0 = atan2_dir(&k.mt, a, b); break;
-    case 2: sincos_tab(&k.mt, a, &r0, &r1); break;
-    case 3: r0 = rsqrt_pos(a); break;
-    case 4: r0 = div_fast(a, b); break;
-    case 5: r0 = rcp_estimate(a); break;
-    case 8: r0 = atan2_unit(&k.mt, atab, a, b); break;
-    case 7: {  // a = [c4 c3 c2 c1 c0 lo hi _] per problem: the line search's bracketed root finder, trips in out1
-      const double q[5] = {k.a[8 * i], k.a[8 * i + 1], k.a[8 * i + 2], k.a[8 * i + 3], k.a[8 * i + 4]};
-      int trips = 0;
-      r0 = bracketed_root<4>(q, k.a[8 * i + 5], k.a[8 * i + 6], &trips);
-      r1 = (double)trips;
-      break;
-    }
-    default: r0 = rsq_estimate(a); break;
-  }
-  k.o0[i] = r0;
-  if (k.o1) k.o1[i] = r1;
-}
-}  // namespace smpc
-
-namespace smpc {
-// FP64 vector peak probe (SURVEY §7 asks for the denominator of the FP64 roofline to be measured, not assumed):
-// eight independent v_fma_f64 chains per lane, nothing else in the loop.
-__global__ __launch_bounds__(256) void smpc_fp64_peak_kernel(double* out, int iters) {
-  double a0 = 1.0 + threadIdx.x * 1e-9, a1 = a0 + 1e-9, a2 = a0 + 2e-9, a3 = a0 + 3e-9;
-  double a4 = a0 + 4e-9, a5 = a0 + 5e-9, a6 = a0 + 6e-9, a7 = a0 + 7e-9;
-  const double m = 0.999999999, c = 1e-9;
-  for (int i = 0; i < iters; ++i) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      a0 = fma(a0, m, c); a1 = fma(a1, m, c); a2 = fma(a2, m, c); a3 = fma(a3, m, c);
-      a4 = fma(a4, m, c); a5 = fma(a5, m, c); a6 = fma(a6, m, c); a7 = fma(a7, m, c);
-    }
-  }
-  out[blockIdx.x * blockDim.x + threadIdx.x] = ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7));
-}
-}  // namespace smpc
-
-namespace smpc {
-// n rows of smpc_scene_params, all equal to `row` (neutral_rows(), below)
-__global__ void smpc_fill_scene_params_kernel(smpc_scene_params* rows, int n, const smpc_scene_params row) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) rows[i] = row;
-}
-}  // namespace smpc
-
-struct smpc_handle {
-  smpc_params prm{};
-  int device = 0;
-  int num_cu = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
-  int* queue = nullptr;  // device-side scene queue head
-  int share = 1;         // smpc_set_solve_share: concurrent solve launches the persistent grid leaves room for
-  bool fixed_shapes = true;  // smpc_set_fixed_shapes: launches of a shape of SMPC_FIXED_SHAPES run that shape's kernels
-  double* stage_rec = nullptr;  // staged people block of the latest call that did not bring its own (grow-only)
-  double* stage_aux = nullptr;
-  size_t stage_rec_bytes = 0, stage_aux_bytes = 0;
-  char* stage = nullptr;  // grow-only arena for host-pointer calls (the plugin's B = 1 use): no hipMalloc per call
-  size_t stage_cap = 0;
-  size_t stage_want = 0;  // high-water mark of the calls so far
-  double* neutral_sp = nullptr;  // smpc_solve_trace_batch on a batch without scene_params: the handle's own values as rows
-  size_t neutral_sp_bytes = 0;   // (grow-only; prm never changes, so rows once written stay valid)
-  char* pin = nullptr;    // page-locked host mirror of the arena's first pin_cap bytes: the small arrays of a host-pointer call
-  size_t pin_cap = 0;     // travel in ONE copy each way instead of one pageable hipMemcpy per array (Staging, below)
-};
-
-namespace {
-
-using KernelFn = void (*)(const smpc::KParams);
-
-// vt: the batch carries a horizon per scene (smpc_scene_batch.T_scene): the instantiation that reads T, CH, bl of each
-// scene from LDS instead of taking them as launch constants. sp: the batch carries weights and bounds per scene
-// (smpc_scene_batch.scene_params): kSP, which reads the horizon per scene as well (T_scene or T).
-// Sweep::Trace (smpc_solve_trace_batch): the solve that also leaves a row per LM iteration, compiled for the most general
-// variant only, kVT = kSP = true. A batch without T_scene runs it as it is (the kernel takes T for every scene), one
-// without scene_params with the handle's own weights and bounds as every scene's row (neutral_rows()): both give the
-// plain kernels' results bit for bit.
-enum class Sweep { Eval, Solve, Trace };
-
-template <int NB, int W, bool kVT, bool kSP> KernelFn pick_fn(Sweep kind) {
-  return kind == Sweep::Eval ? smpc::smpc_eval_kernel<NB, W, kVT, kSP> : smpc::smpc_solve_kernel<NB, W, kVT, kSP>;
-}
-
-template <int NB> KernelFn pick_w(int W, Sweep kind, bool vt, bool sp) {
-  if (kind == Sweep::Trace) return W == 32 ? smpc::smpc_solve_kernel<NB, 32, true, true, true> : smpc::smpc_solve_kernel<NB, 64, true, true, true>;
-  if (W == 32) return sp ? pick_fn<NB, 32, true, true>(kind) : vt ? pick_fn<NB, 32, true, false>(kind) : pick_fn<NB, 32, false, false>(kind);
-  return sp ? pick_fn<NB, 64, true, true>(kind) : vt ? pick_fn<NB, 64, true, false>(kind) : pick_fn<NB, 64, false, false>(kind);
-}
-
-KernelFn pick(int nb, int W, Sweep kind, bool vt = false, bool sp = false) {
-#ifdef SMPC_ONLY_NB  // development builds: one instantiation only (seconds instead of a minute to compile)
-  return nb == SMPC_ONLY_NB ? pick_w<SMPC_ONLY_NB>(W, kind, vt, sp) : nullptr;
-#else
-  switch (nb) {
-    case 1: return pick_w<1>(W, kind, vt, sp);
-    case 2: return pick_w<2>(W, kind, vt, sp);
-    case 3: return pick_w<3>(W, kind, vt, sp);
-    case 4: return pick_w<4>(W, kind, vt, sp);
-    case 5: return pick_w<5>(W, kind, vt, sp);
-    case 6: return pick_w<6>(W, kind, vt, sp);
-    case 7: return pick_w<7>(W, kind, vt, sp);
-    case 8: return pick_w<8>(W, kind, vt, sp);
-    case 9: return pick_w<9>(W, kind, vt, sp);
-    case 10: return pick_w<10>(W, kind, vt, sp);
-    default: return nullptr;
-  }
-#endif
-}
-
-// The kernels of a shape of SMPC_FIXED_SHAPES (smpc_launch.hpp): T, N, CH, bl as literals instead of launch values, the
-// same results bit for bit. They stand in for the plain instantiation <NB, W, false, false> only: a launch with a horizon
-// or parameters per scene, a trace, or the other slot width (the one-scene-per-wave kernel of a small batch) runs the
-// run-time-shape kernel it always ran.
-// *stages (if given): whether the kernel returned can stage the people block itself at the scene fetch (the solve kernel
-// of a Shape with kStageAtFetch; K1 never does)
-template <class Shape> KernelFn fixed_fn(Sweep kind, int W, bool* stages) {
-#ifdef SMPC_ONLY_NB
-  if constexpr (Shape::kNB != SMPC_ONLY_NB) return nullptr; else
-#endif
-  if (W != Shape::kW) return nullptr;
-  if (stages) *stages = kind == Sweep::Solve && Shape::kStageAtFetch;
-  return kind == Sweep::Eval ? smpc::smpc_eval_fixed_kernel<Shape> : smpc::smpc_solve_fixed_kernel<Shape>;
-}
-
-KernelFn pick_fixed(const smpc::KParams& k, int W, Sweep kind, bool vt, bool sp, bool* stages = nullptr) {
-  if (stages) *stages = false;
-  if (kind == Sweep::Trace || vt || sp) return nullptr;
-  const int want = smpc::fixed_shape_index(k.T, k.N, k.CH, k.bl);  // the rule; below only the index -> kernel table
-  int i = 0;
-#define SMPC_X(t, n, ch, b) \
-  if (want == i++) return fixed_fn<smpc::FixedShape<t, n, ch, b>>(kind, W, stages);
-  SMPC_FIXED_SHAPES(SMPC_X)
-#undef SMPC_X
-  return nullptr;
-}
-
-// Whether this handle's launches may take a fixed-shape kernel at all: smpc_set_fixed_shapes, and not under the experiment
-// knob SMPC_NO_HELPERS, which works through the launch value k.hp_A that a fixed shape folds in.
-bool fixed_shapes_on(const smpc_handle* h) { return h->fixed_shapes && !std::getenv("SMPC_NO_HELPERS"); }
-
-int validate(const smpc_handle* h, const smpc_scene_batch* sb, Dims* d) {
-  if (!h || !sb) { set_error("null handle or scene batch"); return SMPC_ERR_INVALID_ARG; }
-  if (sb->B < 0 || sb->T < 1 || sb->N < 0) { set_error("bad B/T/N"); return SMPC_ERR_INVALID_ARG; }
-  if (h->prm.control_horizon < 1 || h->prm.parameter_block_length < 1) { set_error("control_horizon and parameter_block_length must be >= 1"); return SMPC_ERR_INVALID_ARG; }
-  if (!sb->pose0 || !sb->init_params || !sb->path_pts || !sb->goal_yaw || !sb->costmap || !sb->costmap_origin) { set_error("null input array"); return SMPC_ERR_INVALID_ARG; }
-  if ((sb->people_records != nullptr) != (sb->people_aux != nullptr)) { set_error("people_records and people_aux go together"); return SMPC_ERR_INVALID_ARG; }
-  if (sb->N > 0 && !sb->people && !sb->people_records) { set_error("people is null with N > 0"); return SMPC_ERR_INVALID_ARG; }
-  if (sb->size_x < 1 || sb->size_y < 1 || !(sb->resolution > 0.0)) { set_error("bad costmap geometry"); return SMPC_ERR_INVALID_ARG; }
-  *d = make_dims(h->prm, sb->T, true);
-  if (sb->T + 1 > smpc::kWave) { set_error("T + 1 > 64 rollout poses is not supported by the one-wave-per-scene mapping"); return SMPC_ERR_UNSUPPORTED; }
-  if (sb->N > smpc::kWave) { set_error("N > 64 agents is not supported"); return SMPC_ERR_UNSUPPORTED; }
-  if (!pick(d->nb, 64, Sweep::Solve)) { set_error("more than SMPC_MAX_BLOCKS parameter blocks (nb must be 1..10)"); return SMPC_ERR_UNSUPPORTED; }
-  return SMPC_OK;
-}
-
-void fill_kparams(const smpc_handle* h, const smpc_scene_batch* sb, const Dims& d, smpc::KParams* k) {
-  std::memset(k, 0, sizeof(*k));
-  k->B = sb->B; k->T = sb->T; k->N = sb->N;
-  k->CH = d.CH; k->bl = d.bl; k->nb = d.nb; k->P = d.P; k->nbounded = d.nbounded; k->nfeas = d.nfeas;
-  k->size_x = sb->size_x; k->size_y = sb->size_y; k->costmap_shared = sb->costmap_shared;
-  k->dt = sb->dt; k->resolution = sb->resolution; k->inv_resolution = 1.0 / sb->resolution;
-  k->prm = h->prm;
-  k->e_M = d.M;
-  k->hp_A = sb->N;  // set by launch() once the slot width is chosen
-  smpc::fill_math_table(&k->mt);
-  smpc::fill_atan_nodes(&k->an);
-}
-
-#define SMPC_TRY(expr) do { int _rc = (expr); if (_rc != SMPC_OK) return _rc; } while (0)
-
-// Every batch entry point takes host or device pointers (on_device) and names each of its arrays once, here: in(), out()
-// or inout(), with the kernel parameter to fill, the caller's pointer and the element count. Device pointers are passed
-// through. Host arrays are staged through device memory: sub-allocations of the handle's arena, which grows to the
-// high-water mark at the start of the next call (every host-pointer call ends with a stream synchronise, so nothing is
-// in flight then); what does not fit meanwhile comes from hipMalloc and is freed when the call returns.
-// The plugin's own call (B = 1: a dozen arrays of a few hundred bytes and one costmap) used to spend more time in its 16
-// pageable hipMemcpy calls than in its kernels. The head of the arena (kPinBytes) therefore has a page-locked mirror on
-// the host: inputs that land there are gathered in the mirror and cross in ONE asynchronous copy (flush_up(), before the
-// first kernel of the call), outputs that land there come back in one copy and are handed out from the mirror
-// (finish()). What lies beyond the mirror (large batches) is copied array by array.
-constexpr size_t kPinBytes = 8u << 20;
-class Staging {
- public:
-  Staging(smpc_handle* handle, bool on_device) : h(handle), host(!on_device) {
-    if (h->stage_want > h->stage_cap) {
-      if (h->stage) (void)hipFree(h->stage);
-      h->stage = nullptr; h->stage_cap = 0;
-      const size_t cap = h->stage_want + h->stage_want / 4;
-      void* p = nullptr;
-      if (hipMalloc(&p, cap) == hipSuccess) { h->stage = static_cast<char*>(p); h->stage_cap = cap; }
-    }
-    if (h->stage) {
-      const size_t want = h->stage_cap < kPinBytes ? h->stage_cap : kPinBytes;
-      if (h->pin_cap < want) {
-        if (h->pin) (void)hipHostFree(h->pin);
-        h->pin = nullptr; h->pin_cap = 0;
-        void* p = nullptr;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) == hipSuccess) { h->pin = static_cast<char*>(p); h->pin_cap = want; }
-      }
-    }
-  }
-  ~Staging() {
-    for (void* p : overflow) (void)hipFree(p);
-    if (need > h->stage_want) h->stage_want = need;
-  }
-  // n elements the kernel reads / writes / reads and updates in place
-  template <typename T> int in(const T*& dev, const T* src, size_t n) { return bind(dev, src, src, nullptr, n * sizeof(T)); }
-  template <typename T> int out(T*& dev, T* dst, size_t n) { return bind(dev, dst, nullptr, dst, n * sizeof(T)); }
-  template <typename T> int inout(T*& dev, T* buf, size_t n) { return bind(dev, buf, buf, buf, n * sizeof(T)); }
-  // the gathered inputs cross here (timed() does it before the kernels)
-  int flush_up() {
-    if (up_hi > up_lo) SMPC_HIP_CHECK(hipMemcpyAsync(h->stage + up_lo, h->pin + up_lo, up_hi - up_lo, hipMemcpyHostToDevice, h->stream));
-    up_lo = SIZE_MAX; up_hi = 0;
-    return SMPC_OK;
-  }
-  // The kernels of a call, between the events smpc_last_kernel_ms() reads: the inputs have crossed before ev0, so the
-  // time is the kernels' alone. `kernels` launches them on h->stream and returns SMPC_OK or an error code.
-  template <typename F> int timed(F&& kernels) {
-    SMPC_TRY(flush_up());
-    SMPC_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
-    SMPC_TRY(kernels());
-    SMPC_HIP_CHECK(hipGetLastError());
-    SMPC_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return SMPC_OK;
-  }
-  // End of the call. Host pointers: the outputs come back (those in the mirror in one copy), the stream is drained and
-  // the results are handed out. Device pointers: nothing to do, the call stays asynchronous.
-  int finish() {
-    if (!host) return SMPC_OK;
-    SMPC_TRY(flush_up());  // a call that launched nothing (empty batch)
-    size_t lo = SIZE_MAX, hi = 0;
-    for (const Back& b : backs) {
-      if (b.off == SIZE_MAX) { SMPC_HIP_CHECK(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, h->stream)); continue; }
-      if (b.off < lo) lo = b.off;
-      if (b.off + b.bytes > hi) hi = b.off + b.bytes;
-    }
-    if (hi > lo) SMPC_HIP_CHECK(hipMemcpyAsync(h->pin + lo, h->stage + lo, hi - lo, hipMemcpyDeviceToHost, h->stream));
-    SMPC_HIP_CHECK(hipStreamSynchronize(h->stream));
-    for (const Back& b : backs)
-      if (b.off != SIZE_MAX) std::memcpy(b.host, h->pin + b.off, b.bytes);
-    return SMPC_OK;
-  }
-
- private:
-  struct Back { void* host; const void* dev; size_t off, bytes; };  // off: in the mirror, or SIZE_MAX
-  smpc_handle* h;
-  bool host;
-  size_t off = 0, need = 0;
-  size_t up_lo = SIZE_MAX, up_hi = 0;  // arena bytes [up_lo, up_hi) wait in the mirror for flush_up()
-  std::vector<Back> backs;             // outputs, fetched by finish()
-  std::vector<void*> overflow;
-  int take(size_t bytes, void** out) {
-    const size_t sz = (bytes + 255) & ~(size_t)255;
-    need += sz;
-    if (h->stage && off + sz <= h->stage_cap) { *out = h->stage + off; off += sz; return SMPC_OK; }
-    void* p = nullptr;
-    SMPC_HIP_CHECK(hipMalloc(&p, sz));
-    overflow.push_back(p);
-    *out = p;
-    return SMPC_OK;
-  }
-  // offset of a device pointer inside the mirrored head of the arena, or SIZE_MAX
-  size_t mirrored(const void* dev, size_t bytes) const {
-    if (!h->stage || !h->pin) return SIZE_MAX;
-    const char* p = static_cast<const char*>(dev);
-    if (p < h->stage || p + bytes > h->stage + h->pin_cap) return SIZE_MAX;
-    return (size_t)(p - h->stage);
-  }
-  template <typename P> int bind(P& dev, P caller, const void* up, void* back, size_t bytes) {
-    if (!host) { dev = caller; return SMPC_OK; }
-    void* p = nullptr;
-    SMPC_TRY(stage(up, back, bytes, &p));
-    dev = static_cast<P>(p);
-    return SMPC_OK;
-  }
-  // Device room for a host array of `bytes`: `up` (if any) gathered in the mirror or copied now, `back` (if any) the
-  // host array finish() copies the result to. A null array or an empty one binds a null device pointer.
-  int stage(const void* up, void* back, size_t bytes, void** dev) {
-    *dev = nullptr;
-    if ((!up && !back) || bytes == 0) return SMPC_OK;
-    SMPC_TRY(take(bytes, dev));
-    const size_t o = mirrored(*dev, bytes);
-    if (up && o != SIZE_MAX) {
-      std::memcpy(h->pin + o, up, bytes);
-      if (o < up_lo) up_lo = o;
-      if (o + bytes > up_hi) up_hi = o + bytes;
-    } else if (up) {
-      SMPC_HIP_CHECK(hipMemcpyAsync(*dev, up, bytes, hipMemcpyHostToDevice, h->stream));
-    }
-    if (back) backs.push_back({back, *dev, o, bytes});
-    return SMPC_OK;
-  }
-};
-
-int grow(double** buf, size_t* have, size_t need, hipStream_t st) {
-  if (need <= *have) return SMPC_OK;
-  SMPC_HIP_CHECK(hipStreamSynchronize(st));  // nothing of an earlier call may still read the old buffer
-  if (*buf) SMPC_HIP_CHECK(hipFree(*buf));
-  *buf = nullptr; *have = 0;
-  SMPC_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(buf), need));
-  *have = need;
-  return SMPC_OK;
-}
-
-// The staging pass: k.people (+ pose0, has_people) -> records / aux at the given device pointers.
-int launch_stage(smpc_handle* h, smpc::KParams& k, double* rec, double* aux) {
-  if (k.B == 0 || k.N == 0) return SMPC_OK;
-  const int W = smpc::slot_width(k.T, k.N);
-  const int S = smpc::kWave / W;
-  const smpc::LdsLayout L = smpc::make_layout(k.T, k.N, 2, smpc::kLayoutStage, W);
-  const size_t shmem = (size_t)S * L.total * sizeof(double);
-  KernelFn fn = (W == 32) ? smpc::smpc_stage_kernel<32> : smpc::smpc_stage_kernel<64>;
-  if (shmem > 160 * 1024) { set_error("people block does not fit the 160 KiB LDS of one CU"); return SMPC_ERR_UNSUPPORTED; }
-  if (shmem > 64 * 1024) SMPC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  k.stage_rec = rec; k.stage_aux = aux;
-  hipLaunchKernelGGL(fn, dim3((k.B + S - 1) / S), dim3(smpc::kWave), shmem, h->stream, k);
-  SMPC_HIP_CHECK(hipGetLastError());
-  return SMPC_OK;
-}
-
-// Waves per CU a solve launch takes when it is sized for having the GPU to itself (launch(), below).
-int lone_waves_per_cu() {
-  int lone_per_cu = 8;
-  if (const char* v = std::getenv("SMPC_LONE_WAVES_PER_CU")) { const int c = std::atoi(v); if (c >= 1) lone_per_cu = c; }  // experiment knob
-  return lone_per_cu;
-}
-
-// Slot width of a solve launch. A shape that fits two scenes per wave (W = 32) still runs ONE scene per wave while the
-// batch is small: up to one scene per SIMD (4 x CUs), two scenes in the lockstep of one wave only make each other wait
-// (their LM phases differ from trip to trip; measured 4-17 % slower than a wave each, with bit-identical results); and
-// where the W = 64 kernel's helper lanes pay (helper_owner_agents(): the 64 - T lanes beyond the horizon take over half
-// of every step's agent list), up to the number of waves a lone launch takes anyway (8 per CU): every sweep of every
-// scene is shorter then — the plugin's own call (B = 1, 8 people) 1.24 -> 1.06 ms, 1024 scenes 1.60 -> 1.13 ms, equal at
-// 2048 (tools/gpu_width.py). Decided by the shape of the batch alone (B, T, N, the handle's share): a scene's result
-// never depends on timing. With helper lanes it differs from the W = 32 kernel's in the last bits (the order of the
-// sums over the agents).
-int solve_slot_width(const smpc_handle* h, const smpc::KParams& k) {
-  const int W = smpc::slot_width(k.T, k.N);
-  if (W == 64) return 64;
-  if (const char* v = std::getenv("SMPC_SOLVE_WIDTH")) { const int c = std::atoi(v); if (c == 32 || c == 64) return c; }  // experiment knob
-  const int share = h->share > 1 ? h->share : 1;
-  const bool helpers_pay = smpc::helper_owner_agents(k.T, k.N, 64) < k.N;
-  const int per_cu = helpers_pay ? lone_waves_per_cu() : 4;
-  return (k.B <= per_cu * h->num_cu / share) ? 64 : 32;
-}
-
-// The kernel a launch runs: its slot width, the function, and whether that kernel stages the people block itself.
-struct Picked { int W; KernelFn fn; bool stages; };
-Picked pick_launch(const smpc_handle* h, const smpc::KParams& k, Sweep kind) {
-  Picked p;
-  p.W = kind == Sweep::Eval ? smpc::slot_width(k.T, k.N) : solve_slot_width(h, k);
-  p.stages = false;
-  const bool sp = k.scene_params != nullptr;
-  p.fn = fixed_shapes_on(h) ? pick_fixed(k, p.W, kind, k.T_scene != nullptr, sp, &p.stages) : nullptr;
-  if (!p.fn) p.fn = pick(k.nb, p.W, kind, k.T_scene != nullptr, sp);
-  return p;
-}
-
-// Makes the people block of a launch of `kind` readable by its kernel: the caller's staged block; or, where the kernel
-// picked for the launch stages each scene as it fetches it (pick_launch().stages: the fixed-shape solve kernel), room for
-// the records and k.stage_at_fetch — no staging kernel, no aux array, and smpc_last_kernel_ms() then covers the staging;
-// or the library's own staging pass into the handle's buffers (timed separately: smpc_last_kernel_ms() reports the
-// solve / sweep kernel alone).
-int bind_people(smpc_handle* h, const smpc_scene_batch* sb, smpc::KParams& k, Staging* st, Sweep kind) {
-  if (sb->N == 0) return SMPC_OK;
-  const size_t nrec = (size_t)sb->B * sb->N * sb->T * 4, naux = (size_t)sb->B * sb->T * 2;
-  if (sb->people_records) {
-    SMPC_TRY(st->in(k.people_rec, sb->people_records, nrec));
-    return st->in(k.people_aux, sb->people_aux, naux);
-  }
-  SMPC_TRY(grow(&h->stage_rec, &h->stage_rec_bytes, nrec * sizeof(double), h->stream));
-  if (pick_launch(h, k, kind).stages) {
-    k.stage_at_fetch = 1;  // (its own field: launch_stage() sets stage_rec for the staging kernel on this very struct)
-    k.stage_rec = h->stage_rec;
-    k.people_rec = h->stage_rec;
-    return SMPC_OK;
-  }
-  SMPC_TRY(grow(&h->stage_aux, &h->stage_aux_bytes, naux * sizeof(double), h->stream));
-  SMPC_TRY(st->flush_up());
-  SMPC_TRY(launch_stage(h, k, h->stage_rec, h->stage_aux));
-  k.people_rec = h->stage_rec; k.people_aux = h->stage_aux;
-  return SMPC_OK;
-}
-
-// Sweep::Trace: the solve kernel that also writes k.o_trace / k.o_trace_n (k.scene_params is set by then)
-int launch(smpc_handle* h, Staging& st, Sweep kind, smpc::KParams& k) {
-  const bool eval = kind == Sweep::Eval;
-  const Picked picked = pick_launch(h, k, kind);
-  const int W = picked.W;
-  const int S = smpc::kWave / W;
-  const bool sp = k.scene_params != nullptr;
-  KernelFn fn = picked.fn;
-  if (k.stage_at_fetch && !picked.stages) { set_error("internal: a launch without staged people on a kernel that stages none"); return SMPC_ERR_UNSUPPORTED; }
-  const smpc::LdsLayout L = smpc::make_layout(k.T, k.N, k.P, eval ? smpc::kLayoutEval : smpc::kLayoutSolve, W, sp);
-  k.hp_A = smpc::helper_owner_agents(k.T, k.N, W);
-  if (std::getenv("SMPC_NO_HELPERS")) k.hp_A = k.N;  // experiment knob (the LDS layout keeps the helper regions)
-  // behind the slot blocks: the feasibility rows of every slot (solve) or the row staging blocks + parked sensitivities (K1)
-  const size_t extra = eval ? (size_t)smpc::eval_extra_doubles(k.T, k.P, W) : (size_t)smpc::wave_extra_doubles(k.P, W);
-  // ... and behind those the wave's copy of the arctangent's node table
-  const size_t shmem = ((size_t)smpc::atan_tab_offset(S * L.total, (int)extra) + smpc::kAtanTabDoubles) * sizeof(double);
-  if (shmem > 160 * 1024) { set_error("scene does not fit the 160 KiB LDS of one CU"); return SMPC_ERR_UNSUPPORTED; }
-  if (shmem > 64 * 1024) SMPC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  if (k.B == 0) return SMPC_OK;
-  int grid = (k.B + S - 1) / S;
-  if (!eval) {
-    // persistent sweep engine: no more waves than can be resident; scenes come from the queue
-    int per_cu = 0;
-    SMPC_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn), smpc::kWave, shmem));
-    if (h->share > 1) per_cu /= h->share;  // room for the other launches of smpc_set_solve_share
-    if (per_cu < 1) per_cu = 1;
-    if (const char* cap = std::getenv("SMPC_MAX_WAVES_PER_CU")) {  // experiment knob: limit resident waves per CU
-      const int c = std::atoi(cap);
-      if (c >= 1 && c < per_cu) per_cu = c;
-    }
-    if (std::getenv("SMPC_DEBUG_GRID")) std::fprintf(stderr, "[smpc] solve kernel: %zu B LDS per wave, %d waves per CU\n", shmem, per_cu);
-    const int resident = per_cu * h->num_cu;
-    // A launch alone on the GPU finishes soonest with two waves per SIMD (two scenes per slot at the headline batch:
-    // a third wave per SIMD lengthens every trip more than it shortens the queue, and the tail of long scenes grows);
-    // the third wave's registers and LDS then stay free for the launches of other streams, which is where the extra
-    // occupancy pays. Only a batch with many scenes per slot takes every resident wave for itself.
-    const int lone_per_cu = lone_waves_per_cu();
-    const int two_per_simd = lone_per_cu * h->num_cu < resident ? lone_per_cu * h->num_cu : resident;
-    if (grid > two_per_simd) grid = (grid >= 4 * resident) ? resident : two_per_simd;
-    k.queue = h->queue;
-    k.full_gram = std::getenv("SMPC_FULL_GRAM") ? 1 : 0;  // experiment / test knob
-    k.prio_step = 0;
-    if (const char* v = std::getenv("SMPC_PRIO_STEP")) { const int c = std::atoi(v); if (c >= 1) k.prio_step = c; }  // experiment knob
-    SMPC_HIP_CHECK(hipMemsetAsync(h->queue, 0, sizeof(int), h->stream));
-  }
-#ifdef SMPC_STAMPS
-  {  // diagnostic build: per-wave phase cycle sums, dumped to stderr after the launch
-    static unsigned long long* d_stamps = nullptr; static int cap = 0;
-    if (grid > cap) { if (d_stamps) (void)hipFree(d_stamps); SMPC_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_stamps), (size_t)grid * 12 * sizeof(unsigned long long))); cap = grid; }
-    k.stamps = d_stamps;
-  }
-#endif
-  SMPC_TRY(st.timed([&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(smpc::kWave), shmem, h->stream, k); return SMPC_OK; }));
-#ifdef SMPC_STAMPS
-  {
-    SMPC_HIP_CHECK(hipStreamSynchronize(h->stream));
-    std::vector<unsigned long long> hs((size_t)grid * 12);
-    SMPC_HIP_CHECK(hipMemcpy(hs.data(), k.stamps, hs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    double tot[12] = {0};
-    for (int g = 0; g < grid; ++g) for (int i = 0; i < 12; ++i) tot[i] += (double)hs[(size_t)g * 12 + i];
-    double all = 0; for (int i = 0; i < 8; ++i) all += tot[i];
-    static const char* names[8] = {"fetch+load_scene", "theta+sincos", "xy-loop", "agent-loop", "sens-loop", "critics+gram", "lm+output", "ls-interpolation"};
-    std::fprintf(stderr, "[stamps %s] grid=%d mean cycles/wave=%.0f:", eval ? "K1" : "solve", grid, all / grid);
-    for (int i = 0; i < 8; ++i) std::fprintf(stderr, " %s=%.1f%%", names[i], 100.0 * tot[i] / all);
-    std::fprintf(stderr, " | rows split: people-critics=%.1f%% vel/goal/dist=%.1f%% obstacle=%.1f%% (rest of rows = feas + gram out)\n",
-                 100.0 * tot[8] / all, 100.0 * tot[9] / all, 100.0 * tot[10] / all);
-    if (!eval) {
-      unsigned long long dbg[8] = {0};
-      (void)hipMemcpyFromSymbol(dbg, HIP_SYMBOL(smpc::g_ls_dbg), sizeof(dbg));
-      std::fprintf(stderr, "[ls counters, cumulative] root4 calls %llu trips %llu | root3 calls %llu trips %llu | cubic fits %llu quintic fits %llu "
-                   "(monotone shortcut %llu) generic fallback %llu\n", dbg[0], dbg[1], dbg[2], dbg[3], dbg[4], dbg[5], dbg[6], dbg[7]);
-    }
-  }
-#endif
-  return SMPC_OK;
-}
-
-// Host rows of smpc_scene_batch.scene_params: every value finite, v_min <= v_max, w_min <= w_max.
-int check_scene_params(const smpc_scene_params* sp, size_t B) {
-  for (size_t i = 0; i < B; ++i) {
-    const double* v = reinterpret_cast<const double*>(sp + i);
-    for (int j = 0; j < smpc::kSceneParamDoubles; ++j)
-      if (!std::isfinite(v[j])) { set_error("scene_params[" + std::to_string(i) + "]: every value must be finite"); return SMPC_ERR_INVALID_ARG; }
-    if (!(sp[i].v_min <= sp[i].v_max) || !(sp[i].w_min <= sp[i].w_max)) {
-      set_error("scene_params[" + std::to_string(i) + "]: needs v_min <= v_max and w_min <= w_max"); return SMPC_ERR_INVALID_ARG;
-    }
-  }
-  return SMPC_OK;
-}
-
-// k.scene_params for a trace solve of a batch that brings none: B rows of the handle's own values in device memory.
-int neutral_rows(smpc_handle* h, smpc::KParams& k) {
-  const size_t have = h->neutral_sp_bytes, need = (size_t)k.B * sizeof(smpc_scene_params);
-  if (need > have) {
-    SMPC_TRY(grow(&h->neutral_sp, &h->neutral_sp_bytes, need + need / 4, h->stream));
-    const smpc_params& p = h->prm;
-    const smpc_scene_params row = {p.distance_w, p.socialwork_w, p.velocity_w, p.angle_w, p.agent_angle_w, p.proxemics_w,
-                                   p.velocity_feasibility_w, p.obstacle_w, p.goal_align_w, p.desired_linear_vel,
-                                   p.v_min, p.v_max, p.w_min, p.w_max};
-    const int n = (int)(h->neutral_sp_bytes / sizeof(smpc_scene_params));
-    hipLaunchKernelGGL(smpc::smpc_fill_scene_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
-                       reinterpret_cast<smpc_scene_params*>(h->neutral_sp), n, row);
-    SMPC_HIP_CHECK(hipGetLastError());
-    // the rows outlive this call, and a later one may run on another stream (smpc_set_stream): written before they are kept
-    SMPC_HIP_CHECK(hipStreamSynchronize(h->stream));
-  }
-  k.scene_params = reinterpret_cast<const smpc_scene_params*>(h->neutral_sp);
-  return SMPC_OK;
-}
-
-int bind_inputs(const smpc_scene_batch* sb, const Dims& d, smpc::KParams* k, Staging* st) {
-  const size_t B = sb->B, T = sb->T, N = sb->N;
-  const size_t nmaps = sb->costmap_shared ? 1 : B;
-  // host rows are checked here; device arrays are trusted (the caller's responsibility, include/smpc.h: the kernel
-  // clamps every T_scene entry into 1..T)
-  if (!sb->on_device && sb->T_scene)
-    for (size_t i = 0; i < B; ++i)
-      if (sb->T_scene[i] < 1 || sb->T_scene[i] > sb->T) { set_error("T_scene entries must lie in 1..T"); return SMPC_ERR_INVALID_ARG; }
-  if (!sb->on_device && sb->scene_params) SMPC_TRY(check_scene_params(sb->scene_params, B));
-  SMPC_TRY(st->in(k->T_scene, sb->T_scene, B));
-  SMPC_TRY(st->in(k->scene_params, sb->scene_params, B));
-  SMPC_TRY(st->in(k->pose0, sb->pose0, B * 3));
-  SMPC_TRY(st->in(k->init_params, sb->init_params, B * d.P));
-  SMPC_TRY(st->in(k->path_pts, sb->path_pts, B * (T + 1) * 2));
-  SMPC_TRY(st->in(k->goal_yaw, sb->goal_yaw, B));
-  if (!sb->people_records) SMPC_TRY(st->in(k->people, sb->people, B * (T + 1) * 6 * N));  // else read by no kernel
-  SMPC_TRY(st->in(k->has_people, sb->has_people, B));
-  SMPC_TRY(st->in(k->costmap, sb->costmap, nmaps * (size_t)sb->size_x * sb->size_y));
-  return st->in(k->costmap_origin, sb->costmap_origin, nmaps * 2);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -695,12 +124,16 @@ int smpc_set_solve_share(smpc_handle* h, int32_t n) {
   return SMPC_OK;
 }
 
-int smpc_solve_slot_width(const smpc_handle* h, int32_t B, int32_t T, int32_t N) {
+// the arguments of the two queries about a solve launch
+static int check_solve_shape(const smpc_handle* h, int32_t B, int32_t T, int32_t N) {
   if (!h || B < 0 || T < 1 || N < 0) { set_error("null handle or bad B/T/N"); return SMPC_ERR_INVALID_ARG; }
   if (T + 1 > smpc::kWave || N > smpc::kWave) { set_error("T + 1 > 64 rollout poses or N > 64 agents"); return SMPC_ERR_UNSUPPORTED; }
-  smpc::KParams k;
-  k.B = B; k.T = T; k.N = N;
-  return solve_slot_width(h, k);
+  return SMPC_OK;
+}
+
+int smpc_solve_slot_width(const smpc_handle* h, int32_t B, int32_t T, int32_t N) {
+  SMPC_TRY(check_solve_shape(h, B, T, N));
+  return plan_for(h, Sweep::Solve, B, T, N, make_dims(h->prm, T, true), false, false, smpc::read_knobs()).W;
 }
 
 int smpc_set_fixed_shapes(smpc_handle* h, int32_t enable) {
@@ -710,23 +143,16 @@ int smpc_set_fixed_shapes(smpc_handle* h, int32_t enable) {
 }
 
 int smpc_solve_shape_is_fixed(const smpc_handle* h, int32_t B, int32_t T, int32_t N) {
-  const int W = smpc_solve_slot_width(h, B, T, N);
-  if (W < 0) return W;
+  SMPC_TRY(check_solve_shape(h, B, T, N));
   if (h->prm.control_horizon < 1 || h->prm.parameter_block_length < 1) { set_error("control_horizon and parameter_block_length must be >= 1"); return SMPC_ERR_INVALID_ARG; }
-  const Dims d = make_dims(h->prm, T, true);
-  smpc::KParams k;
-  k.T = T; k.N = N; k.CH = d.CH; k.bl = d.bl;
-  return (fixed_shapes_on(h) && pick_fixed(k, W, Sweep::Solve, false, false)) ? 1 : 0;
+  return plan_for(h, Sweep::Solve, B, T, N, make_dims(h->prm, T, true), false, false, smpc::read_knobs()).fixed >= 0 ? 1 : 0;
 }
 
 int smpc_eval_shape_is_fixed(const smpc_handle* h, int32_t T, int32_t N) {
   if (!h || T < 1 || N < 0) { set_error("null handle or bad T/N"); return SMPC_ERR_INVALID_ARG; }
   if (T + 1 > smpc::kWave || N > smpc::kWave) { set_error("T + 1 > 64 rollout poses or N > 64 agents"); return SMPC_ERR_UNSUPPORTED; }
   if (h->prm.control_horizon < 1 || h->prm.parameter_block_length < 1) { set_error("control_horizon and parameter_block_length must be >= 1"); return SMPC_ERR_INVALID_ARG; }
-  const Dims d = make_dims(h->prm, T, true);
-  smpc::KParams k;
-  k.T = T; k.N = N; k.CH = d.CH; k.bl = d.bl;
-  return (fixed_shapes_on(h) && pick_fixed(k, smpc::slot_width(T, N), Sweep::Eval, false, false)) ? 1 : 0;
+  return plan_for(h, Sweep::Eval, 0, T, N, make_dims(h->prm, T, true), false, false, smpc::read_knobs()).fixed >= 0 ? 1 : 0;
 }
 
 }  // extern "C"
@@ -735,46 +161,39 @@ namespace {
 
 // smpc_solve_batch (trace == nullptr) and smpc_solve_trace_batch
 int solve_batch(smpc_handle* h, const smpc_scene_batch* sb, smpc_result_batch* out, const smpc_trace_out* trace) {
-  Dims d;
-  SMPC_TRY(validate(h, sb, &d));
-  if (!out) { set_error("null result batch"); return SMPC_ERR_INVALID_ARG; }
-  SMPC_HIP_CHECK(hipSetDevice(h->device));
-  smpc::KParams k;
-  fill_kparams(h, sb, d, &k);
-  Staging st(h, sb->on_device);
-  SMPC_TRY(bind_inputs(sb, d, &k, &st));
-  SMPC_TRY(bind_people(h, sb, k, &st, trace ? Sweep::Trace : Sweep::Solve));
-  const size_t B = sb->B, T = sb->T;
-  if (sb->order && !sb->on_device) {  // queue order hint
-    std::vector<uint8_t> seen(B, 0);
-    for (size_t i = 0; i < B; ++i) {
-      const int32_t v = sb->order[i];
-      if (v < 0 || (size_t)v >= B || seen[v]) { set_error("order is not a permutation of 0..B-1"); return SMPC_ERR_INVALID_ARG; }
-      seen[v] = 1;
+  const Sweep kind = trace ? Sweep::Trace : Sweep::Solve;
+  return sweep_call(h, sb, kind, out ? nullptr : "null result batch", [&](const Dims& d, smpc::KParams& k, Staging& st) -> int {
+    const size_t B = sb->B, T = sb->T;
+    if (sb->order && !sb->on_device) {  // queue order hint
+      std::vector<uint8_t> seen(B, 0);
+      for (size_t i = 0; i < B; ++i) {
+        const int32_t v = sb->order[i];
+        if (v < 0 || (size_t)v >= B || seen[v]) { set_error("order is not a permutation of 0..B-1"); return SMPC_ERR_INVALID_ARG; }
+        seen[v] = 1;
+      }
     }
-  }
-  SMPC_TRY(st.in(k.order, sb->order, B));
-  SMPC_TRY(st.out(k.o_params, out->params, B * d.P));
-  SMPC_TRY(st.out(k.o_cmds, out->cmds, B * (T + 1) * 2));
-  SMPC_TRY(st.out(k.o_path, out->path, B * (T + 1) * 3));
-  SMPC_TRY(st.out(k.o_status, out->status, B));
-  SMPC_TRY(st.out(k.o_reason, out->reason, B));
-  SMPC_TRY(st.out(k.o_iterations, out->iterations, B));
-  SMPC_TRY(st.out(k.o_evaluations, out->evaluations, B));
-  SMPC_TRY(st.out(k.o_initial_cost, out->initial_cost, B));
-  SMPC_TRY(st.out(k.o_final_cost, out->final_cost, B));
-  // a device-side order cannot be checked here: should it not be a permutation, the scenes it leaves out must not keep
-  // the status of an earlier call — every status starts as SMPC_NOT_SOLVED (-1) and is overwritten by the scene's solve
-  if (sb->on_device && k.order && k.o_status && B > 0) SMPC_HIP_CHECK(hipMemsetAsync(k.o_status, 0xFF, B * sizeof(int32_t), h->stream));
-  if (trace) {
-    k.trace_rows = trace->max_rows;
-    // read and written: the rows a solve does not produce keep the caller's bytes on the way through device memory too
-    SMPC_TRY(st.inout(k.o_trace, trace->rows, B * (size_t)trace->max_rows * SMPC_TRACE_COLS));
-    SMPC_TRY(st.out(k.o_trace_n, trace->n_rows, B));
-    if (!k.scene_params && B > 0) SMPC_TRY(neutral_rows(h, k));
-  }
-  SMPC_TRY(launch(h, st, trace ? Sweep::Trace : Sweep::Solve, k));
-  return st.finish();
+    SMPC_TRY(st.in(k.order, sb->order, B));
+    SMPC_TRY(st.out(k.o_params, out->params, B * d.P));
+    SMPC_TRY(st.out(k.o_cmds, out->cmds, B * (T + 1) * 2));
+    SMPC_TRY(st.out(k.o_path, out->path, B * (T + 1) * 3));
+    SMPC_TRY(st.out(k.o_status, out->status, B));
+    SMPC_TRY(st.out(k.o_reason, out->reason, B));
+    SMPC_TRY(st.out(k.o_iterations, out->iterations, B));
+    SMPC_TRY(st.out(k.o_evaluations, out->evaluations, B));
+    SMPC_TRY(st.out(k.o_initial_cost, out->initial_cost, B));
+    SMPC_TRY(st.out(k.o_final_cost, out->final_cost, B));
+    // a device-side order cannot be checked here: should it not be a permutation, the scenes it leaves out must not keep
+    // the status of an earlier call — every status starts as SMPC_NOT_SOLVED (-1) and is overwritten by the scene's solve
+    if (sb->on_device && k.order && k.o_status && B > 0) SMPC_HIP_CHECK(hipMemsetAsync(k.o_status, 0xFF, B * sizeof(int32_t), h->stream));
+    if (trace) {
+      k.trace_rows = trace->max_rows;
+      // read and written: the rows a solve does not produce keep the caller's bytes on the way through device memory too
+      SMPC_TRY(st.inout(k.o_trace, trace->rows, B * (size_t)trace->max_rows * SMPC_TRACE_COLS));
+      SMPC_TRY(st.out(k.o_trace_n, trace->n_rows, B));
+      if (!k.scene_params && B > 0) SMPC_TRY(neutral_rows(h, k));
+    }
+    return SMPC_OK;
+  });
 }
 
 }  // namespace
@@ -1272,25 +691,18 @@ int smpc_math_probe(smpc_handle* h, int32_t fn, int32_t n, const double* a, cons
 }
 
 int smpc_eval_batch(smpc_handle* h, const smpc_scene_batch* sb, const double* params, smpc_eval_batch_out* out) {
-  Dims d;
-  SMPC_TRY(validate(h, sb, &d));
-  if (!out || !params) { set_error("null params / output"); return SMPC_ERR_INVALID_ARG; }
-  if (out->row_order != 0 && out->row_order != 1) { set_error("row_order must be 0 or 1"); return SMPC_ERR_INVALID_ARG; }
-  SMPC_HIP_CHECK(hipSetDevice(h->device));
-  smpc::KParams k;
-  fill_kparams(h, sb, d, &k);
-  Staging st(h, sb->on_device);
-  SMPC_TRY(bind_inputs(sb, d, &k, &st));
-  SMPC_TRY(bind_people(h, sb, k, &st, Sweep::Eval));
-  const size_t B = sb->B;
-  k.e_row_order = out->row_order;
-  SMPC_TRY(st.in(k.e_x, params, B * d.P));
-  SMPC_TRY(st.out(k.e_residuals, out->residuals, B * d.M));
-  SMPC_TRY(st.out(k.e_jacobian, out->jacobian, B * d.M * d.P));
-  SMPC_TRY(st.out(k.e_cost, out->cost, B));
-  SMPC_TRY(st.out(k.e_gradient, out->gradient, B * d.P));
-  SMPC_TRY(launch(h, st, Sweep::Eval, k));
-  return st.finish();
+  const char* bad = nullptr;
+  if (!out || !params) bad = "null params / output";
+  else if (out->row_order != 0 && out->row_order != 1) bad = "row_order must be 0 or 1";
+  return sweep_call(h, sb, Sweep::Eval, bad, [&](const Dims& d, smpc::KParams& k, Staging& st) -> int {
+    const size_t B = sb->B;
+    k.e_row_order = out->row_order;
+    SMPC_TRY(st.in(k.e_x, params, B * d.P));
+    SMPC_TRY(st.out(k.e_residuals, out->residuals, B * d.M));
+    SMPC_TRY(st.out(k.e_jacobian, out->jacobian, B * d.M * d.P));
+    SMPC_TRY(st.out(k.e_cost, out->cost, B));
+    return st.out(k.e_gradient, out->gradient, B * d.P);
+  });
 }
 
 }  // extern "C"

@@ -142,7 +142,7 @@ def test_block_limit_matches_the_header():
     nb = C.c_int()
     p.control_horizon, p.parameter_block_length = 33, 3
     assert lib.smpc_dims(C.byref(p), 40, 1, None, None, C.byref(nb), None, None, None) == 0 and nb.value == 11
-    hip_src = open(os.path.join(ROOT, "nav2_social_mpc_controller_amd", "csrc", "smpc_hip.hip")).read()
+    hip_src = open(os.path.join(ROOT, "nav2_social_mpc_controller_amd", "csrc", "smpc_sweep_host.hpp")).read()
     assert "case 10: return pick_w<10>" in hip_src and "case 11" not in hip_src
 
 

@@ -2,7 +2,7 @@
 time (CPU only, ~20 s): their register budget, the kernel names other tests pin, and the rule that picks a shape.
 
 Like test_kernel_budget.py this compiles the NB = 3 instantiations with the flags of `csrc/build.sh` and reads the
-compiler's kernel-resource-usage remarks. The picker rule is the constexpr function `pick_fixed()` of smpc_hip.hip
+compiler's kernel-resource-usage remarks. The picker rule is the constexpr function `plan_sweep()` of smpc_plan.hpp
 dispatches through (`smpc::fixed_shape_index`), called from a small host program: `smpc_solve_shape_is_fixed` itself
 needs a handle, and a handle needs a device. The functions of include/smpc_fixed_shapes.h stand outside the table
 tests/test_abi.py holds against include/smpc.h, so their declaration, export and binding are checked here."""
@@ -97,9 +97,13 @@ def test_picker_rule_lists_the_headline_shape_and_none_of_its_neighbours(tmp_pat
 
 
 def test_host_picker_dispatches_through_the_rule():
-    hip = open(os.path.join(CSRC, "smpc_hip.hip")).read()
-    body = hip[hip.index("KernelFn pick_fixed("):]
-    body = body[:body.index("\n}\n")]
+    def function(path, start):
+        text = open(os.path.join(CSRC, path)).read()
+        text = text[text.index(start):]
+        return text[:text.index("\n}\n")]
+
+    # the rule is asked where the launch is planned, its index is mapped to the kernels where the launch is issued
+    body = function("smpc_plan.hpp", "inline SweepPlan plan_sweep(") + function("smpc_sweep_host.hpp", "KernelFn pick_fixed(")
     assert "smpc::fixed_shape_index(k.T, k.N, k.CH, k.bl)" in body and "SMPC_FIXED_SHAPES(SMPC_X)" in body
     assert "k.T ==" not in body and "k.N ==" not in body   # no second copy of the comparison
 

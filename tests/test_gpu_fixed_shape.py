@@ -1,7 +1,7 @@
 """The fixed-shape kernels of the headline configuration (`-m gpu`): smpc_solve_fixed_kernel / smpc_eval_fixed_kernel
 <FixedShape<28, 8, 18, 6>> give, bit for bit, what the run-time-shape kernels <3, 32, false, false> give, and only the
-listed shape at the two-scenes-per-wave width runs them (csrc/smpc_launch.hpp SMPC_FIXED_SHAPES, smpc_hip.hip
-pick_fixed()).
+listed shape at the two-scenes-per-wave width runs them (csrc/smpc_launch.hpp SMPC_FIXED_SHAPES, smpc_plan.hpp
+plan_sweep()).
 
 Two batches. B = 5 on three waves of two slots: one wave runs with an empty slot, a scene without people sits beside
 scenes with people, one agent of every scene is invalid (a batch this small runs one scene per wave unless

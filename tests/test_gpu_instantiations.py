@@ -1,4 +1,4 @@
-"""Every solve and K1 instantiation the library compiles (pick() in csrc/smpc_hip.hip: parameter blocks NB = 1..10 x
+"""Every solve and K1 instantiation the library compiles (pick() in csrc/smpc_sweep_host.hpp: parameter blocks NB = 1..10 x
 slot width W = 32 / 64 x plain / per-scene horizon `vt` / per-scene weights and bounds `sp` x solve / K1), each launched
 on a shape of its own and checked against the CPU oracle, plus the identities between the variants that do not depend
 on the conditioning of a scene. The case table names the W each case takes; test_the_table_names_every_instantiation
@@ -124,7 +124,7 @@ def test_the_table_names_every_instantiation():
     src = open(os.path.join(ROOT, "include", "smpc.h")).read()
     max_blocks = int(re.search(r"#define SMPC_MAX_BLOCKS (\d+)", src).group(1))
     # the variants pick() selects among: plain and one per flag of pick_w() after `kind`
-    hip = open(os.path.join(ROOT, "nav2_social_mpc_controller_amd", "csrc", "smpc_hip.hip")).read()
+    hip = open(os.path.join(ROOT, "nav2_social_mpc_controller_amd", "csrc", "smpc_sweep_host.hpp")).read()
     flags = re.search(r"KernelFn pick_w\(int W, Sweep kind, ([^)]*)\)", hip).group(1)
     assert ("plain",) + tuple(f.split()[-1] for f in flags.split(",")) == VARIANTS
     want = set(itertools.product(("solve", "eval"), range(1, max_blocks + 1), (32, 64), VARIANTS))

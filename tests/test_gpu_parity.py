@@ -140,7 +140,7 @@ def test_solve_matches_oracle_on_seeded_scenes(Solver, oracle, name):
 
 
 # Batches this small run one scene per wave (the W = 64 kernel, helper lanes from four people up: solve_slot_width() in
-# csrc/smpc_hip.hip); the two-scenes-per-wave kernel that the large batches of the same shapes take is put through the
+# csrc/smpc_plan.hpp); the two-scenes-per-wave kernel that the large batches of the same shapes take is put through the
 # same cases here (SMPC_SOLVE_WIDTH is read at every launch), next to the full-size tests below.
 TWO_SLOT_CASES = ["cfg2_n4", "cfg3_n8", "single_block", "w32_five_blocks_valu_gram", "t31_last_two_slot_shape",
                   "n32_last_two_slot_shape"]
