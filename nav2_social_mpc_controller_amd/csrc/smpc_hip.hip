@@ -14,7 +14,8 @@
 //                            (smpc_scene_batch.scene_params);
 //   smpc_stage_kernel<W>     the staging pass of the people block (smpc_stage_kernel.hpp);
 //   the probe kernels (smpc_probes.hpp);
-//   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window).
+//   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window,
+//   metrics, crowd, local costmap).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -32,6 +33,8 @@
 #include "smpc_path_window.hpp"
 #include "smpc_metrics.hpp"
 #include "smpc_crowd.hpp"
+#include "smpc_local_costmap.hpp"
+#include "../../include/smpc_local_costmap.h"
 
 extern "C" {
 
@@ -616,6 +619,46 @@ int smpc_crowd_step_groups_batch(smpc_handle* h, const smpc_crowd_batch* in, con
       if (!(v >= 0.0) || !std::isfinite(v)) { set_error("negative or non-finite group force factor"); return SMPC_ERR_INVALID_ARG; }
   }
   return crowd_step(h, in, groups && groups->group_id ? groups : nullptr, people, cursor);
+}
+
+int smpc_local_costmap_batch(smpc_handle* h, const smpc_local_costmap_in* in, int32_t* cell, uint8_t* costmap, double* costmap_origin,
+                             int32_t* moved) {
+  if (!h || !in || !cell || !costmap || !costmap_origin) { set_error("null handle / input / cell / costmap / costmap_origin"); return SMPC_ERR_INVALID_ARG; }
+  if (!in->world || !in->world_origin || !in->pose) { set_error("null input array"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B < 0 || in->size_x < 1 || in->size_y < 1 || in->world_x < 1 || in->world_y < 1) {
+    set_error("bad B or a non-positive window / world size"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) { set_error("resolution must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  const int64_t cells = (int64_t)in->size_x * in->size_y, world_cells = (int64_t)in->world_x * in->world_y;
+  if (world_cells >= (int64_t)1 << 31 || cells >= (int64_t)1 << 31 || in->size_x >= 1 << 30 || in->size_y >= 1 << 30) {
+    set_error("world or window of 2^31 cells or more, or a window side of 2^30 cells or more, is not supported"); return SMPC_ERR_UNSUPPORTED;
+  }
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::LocalCostmapParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.B = in->B; p.size_x = in->size_x; p.size_y = in->size_y; p.world_x = in->world_x; p.world_y = in->world_y;
+  p.world_shared = in->world_shared ? 1 : 0; p.force = in->force ? 1 : 0; p.outside = 0x01010101u * in->outside_cost;
+  p.resolution = in->resolution;
+  const size_t B = in->B, nworld = in->world_shared ? 1 : B;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.world, in->world, nworld * (size_t)world_cells));
+  SMPC_TRY(st.in(p.world_origin, in->world_origin, nworld * 2));
+  SMPC_TRY(st.in(p.pose, in->pose, B * 3));
+  SMPC_TRY(st.inout(p.cell, cell, B * 2));
+  // read and written: the windows and origins of the robots that stay keep the caller's bytes on the way through device memory too
+  SMPC_TRY(st.inout(p.costmap, costmap, B * (size_t)cells));
+  SMPC_TRY(st.inout(p.costmap_origin, costmap_origin, B * 2));
+  SMPC_TRY(st.out(p.moved, moved, B));
+  if (B > 0) {
+    // 16-byte stores need every window to start on a 16-byte boundary and every 8-byte half to lie in one window row
+    p.wide = (in->size_x % 8 == 0 && cells % 16 == 0 && reinterpret_cast<uintptr_t>(p.costmap) % 16 == 0) ? 1 : 0;
+    const size_t grid = B < (size_t)h->num_cu * 8 ? B : (size_t)h->num_cu * 8;  // a fixed grid that strides over the robots
+    SMPC_TRY(st.timed([&] {
+      hipLaunchKernelGGL(smpc::smpc_local_costmap_kernel, dim3((unsigned)grid), dim3(smpc::kLcThreads), 0, h->stream, p);
+      return SMPC_OK;
+    }));
+  }
+  return st.finish();
 }
 
 int smpc_stage_people_batch(smpc_handle* h, const smpc_scene_batch* sb, double* records, double* aux) {

@@ -5,6 +5,7 @@
                                                                                    -> smpc_people_to_status_batch
     format_to_optimize + TrajectoryMemory   (src/optimizer.cpp:172-190, 484-551)  -> smpc_format_to_optimize_batch
     ObstacleDistance grid (optional, once)   (src/optimizer.cpp:593-605, 'TODO')   -> smpc_obstacle_distance_batch
+    rolling local costmap (optional)         (Nav2's LayeredCostmap::updateMap)    -> smpc_local_costmap_batch
     project_people                           (src/optimizer.cpp:554-728)           -> smpc_project_people_batch
     problem assembly + ceres::Solve + unpack (src/optimizer.cpp:197-446)           -> smpc_solve_batch
     memory store                             (src/optimizer.cpp:448-449)           -> smpc_memory_store_batch
@@ -23,6 +24,12 @@ stood in for by the simplest thing that has the same shape:
     updatePosition): each person heads for its current waypoint (scenes.crowd_waypoints), gives way to the other persons
     and to the robot as it was at the start of the period, is pushed back by the nearest obstacle of its cell of the
     ObstacleDistance grid, and takes the next waypoint on arrival. The robot is seen but not pushed.
+  * the ground: without a world map every robot keeps the local costmap it was created with, centred on its start pose,
+    and can be scored for the few metres that window covers. With BatchEpisode(world=World(...)) the robots drive on one
+    world map as the reference controller does on Nav2's rolling local costmap: every tick starts with
+    smpc_local_costmap_batch, which moves each robot's window to its pose by whole cells and cuts the windows that moved
+    out of the world map into the buffers the solve reads; the ObstacleDistance grid of the projection, the crowd and
+    the metrics is the world's, computed once.
 """
 from dataclasses import dataclass
 from types import SimpleNamespace
@@ -32,7 +39,7 @@ import numpy as np
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
 from .params import CrowdGroupParams, CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams, check_scene_param_rows
-from .scenes import SceneBatch
+from .scenes import SceneBatch, World
 from .solver import BatchSolver, point, set_od_grid
 
 
@@ -71,6 +78,10 @@ class TickRecord:
     # the persons' waypoint cursors around the tick's crowd step (BatchEpisode(crowd=...))
     cursor_before: np.ndarray = None  # [B,Np]
     cursor_after: np.ndarray = None   # [B,Np]
+    # the rolling local costmaps after the tick's roll (BatchEpisode(world=...)): what the tick's solve read
+    costmap_cell: np.ndarray = None    # [B,2] world cell of every window's cell (0,0)
+    costmap_origin: np.ndarray = None  # [B,2]
+    costmap_moved: np.ndarray = None   # [B] smpc_local_costmap_batch's moved
 
 
 class BatchEpisode:
@@ -82,7 +93,7 @@ class BatchEpisode:
     PER_GRID = ("od_indexes", "od_origin", "od_distances")
     # the same object for every shard
     FORWARDED = ("od_resolution", "device", "traj_params", "fov_angle", "order_hint", "plan_window", "obstacles_from_costmap",
-                 "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups")
+                 "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost")
 
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
@@ -92,13 +103,14 @@ class BatchEpisode:
                  metrics: MetricsParams = None, goal: np.ndarray = None, od_distances: np.ndarray = None,
                  crowd: CrowdParams = None, person_waypoints: np.ndarray = None, person_n_waypoints: np.ndarray = None,
                  person_speed: np.ndarray = None, person_groups: np.ndarray = None,
-                 crowd_groups: CrowdGroupParams = None):
+                 crowd_groups: CrowdGroupParams = None, world: World = None, outside_cost: int = 255):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
         are computed on the device from the scenes' costmaps once, here (smpc_obstacle_distance_batch with
-        obstacle_min_cost / unknown_is_obstacle; an episode's costmaps are fixed): one per scene, or one for a shared
-        costmap, with the costmap's origin and resolution. plan [B,L,2] + plan_len [B] + traj_params: global plans,
+        obstacle_min_cost / unknown_is_obstacle; without `world` an episode's costmaps are fixed): one per scene, or one for a
+        shared costmap, with the costmap's origin and resolution; with `world` the one grid of the world map.
+        plan [B,L,2] + plan_len [B] + traj_params: global plans,
         trajectorized on the device every tick (the plan must stay longer than the horizon for the whole episode).
         fov_angle: field-of-view half angle of the people filter (reference default pi/4); None = no filter.
         plan_window: (max_robot_pose_search_dist, dist_threshold): every tick starts with PathHandler::transformGlobalPlan
@@ -128,7 +140,16 @@ class BatchEpisode:
         person_groups [B,Np] int32 (with crowd; e.g. scenes.crowd_groups): the persons' group ids (< 0: none); companions
         are held together by the Social Force Model's group force (smpc_crowd_step_groups_batch) with the factors of
         crowd_groups (default CrowdGroupParams()). Uploaded once and constant over the episode. None: nothing is
-        allocated and the plain crowd step runs."""
+        allocated and the plain crowd step runs.
+        world: the map the robots drive on (scenes.World, e.g. scenes.make_world with scenes.scenes_in_world): the scenes'
+        costmaps (one per robot, of the world's resolution) become rolling windows of it. The world is uploaded once and
+        self.costmap_cell [B,2] holds the world cell of every window's cell (0,0); every tick starts, before the plan window
+        and the trajectorizer, with smpc_local_costmap_batch at the robots' current poses, which rewrites the windows (and
+        costmap_origin) of the robots whose window moved and leaves the others alone; window cells beyond the world read
+        outside_cost. The first tick, and the first replay of a captured graph, write every window (`force`). With
+        obstacles_from_costmap the ObstacleDistance grid is computed from the world map, once, shared by all robots, with
+        the world's origin (with distances when metrics ask for them); host-given od_* are taken as they are. None:
+        nothing is allocated and nothing is launched."""
         import torch
 
         self.torch = torch
@@ -147,6 +168,7 @@ class BatchEpisode:
             self.T += 1
         self.P = params.dims(self.T, True)[3]
         self._init_world(scenes, w_ref, fov_angle)
+        self._init_rolling(world, outside_cost)
         self._init_grid(od_indexes, od_origin, od_resolution, od_distances, obstacles_from_costmap, obstacle_min_cost,
                         unknown_is_obstacle, distances=metrics is not None)
         self._init_memory()
@@ -190,22 +212,41 @@ class BatchEpisode:
         self.costmap_shared = scenes.costmap_shared
         self.size_x, self.size_y, self.resolution = scenes.size_x, scenes.size_y, scenes.resolution
 
+    def _init_rolling(self, world, outside_cost):
+        """The world map the costmaps are rolling windows of, and where every window is."""
+        self.world = world
+        if world is None:
+            return
+        if self.costmap_shared:
+            raise ValueError("world needs a costmap per robot (costmap_shared = False, e.g. scenes.scenes_in_world)")
+        if float(world.resolution) != float(self.resolution):
+            raise ValueError("the world and the scenes' costmaps differ in resolution")
+        self.world_map = self._upload(world.map, np.uint8)                              # [Hy,Hx]
+        self.world_origin = self._upload(np.asarray(world.origin, np.float64).reshape(1, 2), np.float64)
+        self.outside_cost = int(outside_cost)
+        self.costmap_cell = self._zeros(self.B, 2, dtype=self.torch.int32)
+        self.costmap_moved = self._zeros(self.B, dtype=self.torch.int32)
+        self._force_roll = True  # the next roll writes every window: the first tick, the first replay of a graph
+
     def _init_grid(self, od_indexes, od_origin, od_resolution, od_distances, from_costmap, obstacle_min_cost,
                    unknown_is_obstacle, distances):
         """The ObstacleDistance grid(s): od_indexes, od_origin, od_shared, od_h, od_w, od_resolution and, when the metrics
         read them (`distances`) and they are there, od_distances (else the attribute does not exist)."""
         torch, B = self.torch, self.B
         if from_costmap:
-            shape = (1 if self.costmap_shared else B, self.size_y, self.size_x)
-            self.od_shared = 1 if self.costmap_shared else 0
+            # of the world map when the costmaps are rolling windows of it, else of the (fixed) costmaps themselves
+            rolling = self.world is not None
+            costmap, shared = (self.world_map, True) if rolling else (self.costmap, self.costmap_shared)
+            size_y, size_x = int(costmap.shape[-2]), int(costmap.shape[-1])
+            shape = (1 if shared else B, size_y, size_x)
+            self.od_shared = 1 if shared else 0
             self.od_resolution = float(np.float32(self.resolution))
-            self.od_origin = self.costmap_origin
+            self.od_origin = self.world_origin if rolling else self.costmap_origin
             self.od_indexes = torch.empty(shape, dtype=torch.int32, device=self.dev)
             if distances:  # the clearance columns read the distances: one more array, once
                 self.od_distances = torch.empty(shape, dtype=torch.float32, device=self.dev)
-            ob = BatchSolver.obstacle_distance_c(B, self.size_x, self.size_y, self.costmap_shared, self.resolution, 1,
-                                                 obstacle_min_cost, unknown_is_obstacle)
-            ob.costmap = self.costmap.data_ptr()
+            ob = BatchSolver.obstacle_distance_c(B, size_x, size_y, shared, self.resolution, 1, obstacle_min_cost, unknown_is_obstacle)
+            ob.costmap = costmap.data_ptr()
             self.solver.obstacle_distance_device(ob, self.od_indexes.data_ptr(), self.od_distances.data_ptr() if distances else 0)
         else:
             if od_indexes is None or od_origin is None or od_resolution is None:
@@ -319,6 +360,11 @@ class BatchEpisode:
         prm, B, T, N = self.params, self.B, self.T, self.N
         Np, planned, od = int(self.persons.shape[1]), self.plan is not None, (self.od_shared, self.od_h, self.od_w)
         c = self._c = SimpleNamespace()
+        if self.world is not None:  # two structs that differ in `force`: a captured graph keeps the one its tick was given
+            c.roll = {force: point(BatchSolver.local_costmap_c(B, self.size_x, self.size_y, self.world.cells_x, self.world.cells_y, True,
+                                                               self.resolution, 1, self.outside_cost, force),
+                                   {"world": self.world_map, "world_origin": self.world_origin, "pose": self.pose})
+                      for force in (False, True)}
         if planned:
             L = int(self.plan.shape[1])
             c.traj = point(BatchSolver.trajectorize_c(self.traj, B, L, 1),
@@ -391,6 +437,12 @@ class BatchEpisode:
         self.plan_cmds[:, :, 0] = 0.6
         self.plan_cmds[:, :, 1] = self.w_ref[:, None]
 
+    def _roll(self):
+        """The rolling costmaps follow the robots: one launch; every window is written when none has been yet."""
+        self.solver.local_costmap_device(self._c.roll[self._force_roll], self.costmap_cell.data_ptr(), self.costmap.data_ptr(),
+                                         self.costmap_origin.data_ptr(), self.costmap_moved.data_ptr())
+        self._force_roll = False
+
     def _host(self, *names, **renamed) -> dict:
         """Host copies of device buffers for a TickRecord: {name: self.<name>} and {key: self.<attribute>}."""
         return {k: getattr(self, a).cpu().numpy().copy() for k, a in [(n, n) for n in names] + list(renamed.items())}
@@ -415,6 +467,11 @@ class BatchEpisode:
         rec = {}
         if record:
             rec.update(self._host(robot_pose="pose"))
+        if self.world is not None:  # the ground first: everything below reads the windows where the robots are now
+            self._roll()
+            timed("local_costmap")
+            if record:
+                rec.update(self._host("costmap_cell", "costmap_origin", "costmap_moved"))
         self._plan(timing)
         if planned:
             timed("trajectorize")
@@ -523,11 +580,17 @@ class BatchEpisode:
             for k in state:
                 getattr(self, k).copy_(saved[k])
         self.ticks = ticks
+        if self.world is not None:
+            self._force_roll = True
         return self.graph
 
     def replay(self):
         """One control period through the captured graph (on the capture stream)."""
         with self.torch.cuda.stream(self.gstream):
+            if self.world is not None and self._force_roll:
+                # the first replay: every window is written from cell (0,0), as an eager episode's first tick does; the
+                # graph's own roll (captured without `force`) then finds every window in place
+                self._roll()
             self.graph.replay()
         self.ticks += 1
 

@@ -379,3 +379,133 @@ def crowd_groups(scenes: SceneBatch, sizes=(2, 3), share: float = 0.5, K: int = 
             n_wp[b, members] = n_wp[b, members[0]]
             quota, at, g = quota - size, at + size, g + 1
     return gid, np.ascontiguousarray(wp), np.ascontiguousarray(n_wp)
+
+
+# -- a world map and the rolling local costmaps cut out of it (include/smpc_local_costmap.h) ------------------------------
+@dataclass
+class World:
+    """The map a closed-loop episode's rolling local costmaps are cut out of (BatchEpisode(world=...))."""
+    map: np.ndarray        # [Hy,Hx] uint8 costs
+    origin: np.ndarray     # [2] world coordinates of the corner of cell (0,0)
+    resolution: float
+
+    @property
+    def cells_y(self) -> int:
+        return int(self.map.shape[0])
+
+    @property
+    def cells_x(self) -> int:
+        return int(self.map.shape[1])
+
+
+_CELL_LIMIT = 2.0 ** 30
+
+
+def window_cells(origin, resolution: float, cell, pose_xy, size_x: int, size_y: int, force: bool = False):
+    """The cell rule of smpc_local_costmap_batch on host arrays: origin [2] or [B,2] (the world's), cell [B,2] int32 (the
+    world cell of every window's cell (0,0); taken as zeros under `force`), pose_xy [B,2]. Returns (cell' [B,2] int32,
+    costmap_origin [B,2], moved [B] int32: 0 kept, 1 moved or forced, 2 pose not finite). numpy rounds every operation
+    on its own, which is the contract."""
+    res = np.float64(resolution)
+    w0 = np.broadcast_to(np.asarray(origin, np.float64).reshape(-1, 2), np.shape(pose_xy))
+    pose_xy = np.asarray(pose_xy, np.float64)
+    cell = np.zeros(pose_xy.shape, np.int32) if force else np.asarray(cell, np.int32)
+    size = np.array([size_x, size_y], np.float64)
+    finite = np.isfinite(pose_xy).all(axis=1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        o = w0 + cell.astype(np.float64) * res
+        want = pose_xy - ((size - 1.0 + 0.5) * res) / 2.0
+        d = np.trunc((want - o) / res)
+        c = cell.astype(np.float64) + d
+        c = np.where(c > _CELL_LIMIT, _CELL_LIMIT, c)
+        c = np.where(c >= -_CELL_LIMIT, c, -_CELL_LIMIT)
+    new = np.where(finite[:, None], c, cell).astype(np.int32)
+    changed = (new != cell).any(axis=1)
+    moved = np.where(finite, (changed | force).astype(np.int32), 2).astype(np.int32)
+    return new, w0 + new.astype(np.float64) * res, moved
+
+
+def crop_windows(world_map: np.ndarray, cell: np.ndarray, size_x: int, size_y: int, outside_cost: int = 255) -> np.ndarray:
+    """costmap [B,size_y,size_x]: window cell (y, x) of robot b is world_map[cell[b,1] + y, cell[b,0] + x] where that cell
+    exists, else outside_cost. world_map [Hy,Hx] (one for all) or [B,Hy,Hx]."""
+    world_map = np.asarray(world_map, np.uint8)
+    cell = np.asarray(cell, np.int64)
+    B = cell.shape[0]
+    Hy, Hx = world_map.shape[-2:]
+    wy = cell[:, 1, None] + np.arange(size_y)[None, :]   # [B,size_y]
+    wx = cell[:, 0, None] + np.arange(size_x)[None, :]   # [B,size_x]
+    inside = ((wy >= 0) & (wy < Hy))[:, :, None] & ((wx >= 0) & (wx < Hx))[:, None, :]
+    yy, xx = np.clip(wy, 0, Hy - 1)[:, :, None], np.clip(wx, 0, Hx - 1)[:, None, :]
+    got = world_map[yy, xx] if world_map.ndim == 2 else world_map[np.arange(B)[:, None, None], yy, xx]
+    return np.ascontiguousarray(np.where(inside, got, np.uint8(outside_cost)).astype(np.uint8))
+
+
+def make_world(cells_x: int, cells_y: int, resolution: float = 0.05, seed: int = 0x5EED0004, origin=(0.0, 0.0),
+               discs: Optional[int] = None, wall_cells: int = 2) -> World:
+    """A seeded floor of cells_x x cells_y cells: the discs of make_scenes' costmaps (cost 254, radius 0.15 .. 0.5 m, with
+    the exponential inflation 252 exp(-3 d) out to 0.7 m), `discs` of them anywhere on the floor (default: make_scenes'
+    mean density, 5.5 per 100 m^2), inside a lethal border wall of wall_cells cells, inflated the same way. A pure
+    function of its arguments through `uniform`."""
+    origin = np.asarray(origin, np.float64).reshape(2)
+    width, height = cells_x * resolution, cells_y * resolution
+    if discs is None:
+        discs = int(round(5.5 * width * height / 100.0))
+    ids = np.zeros(1, np.int64)
+    inflate = lambda d: np.where(d <= 0.0, 254.0, np.where(d <= 0.7, np.floor(252.0 * np.exp(-3.0 * d)), 0.0))
+    wx = origin[0] + (np.arange(cells_x) + 0.5) * resolution
+    wy = origin[1] + (np.arange(cells_y) + 0.5) * resolution
+    # the wall: cells within wall_cells of the border; d from a cell's centre to the wall's inner face
+    k = np.minimum(np.minimum(np.arange(cells_x), cells_x - 1 - np.arange(cells_x))[None, :],
+                   np.minimum(np.arange(cells_y), cells_y - 1 - np.arange(cells_y))[:, None]) - wall_cells
+    cost = np.where(k < 0, 254.0, inflate((k + 0.5) * resolution))
+    if discs > 0:
+        cr = 0.15 + uniform(seed, ids, 1, discs)[0] * 0.35
+        cx = origin[0] + uniform(seed, ids, 2, discs)[0] * width
+        cy = origin[1] + uniform(seed, ids, 3, discs)[0] * height
+        for r, x, y in zip(cr, cx, cy):
+            d = np.sqrt((wx[None, :] - x) ** 2 + (wy[:, None] - y) ** 2) - r
+            cost = np.maximum(cost, inflate(d))
+    return World(np.ascontiguousarray(cost.astype(np.uint8)), origin, float(resolution))
+
+
+def scenes_in_world(params: OptimizerParams, world: World, B: int, N: int, seed: int = 0x5EED0001, size_x: int = 200,
+                    size_y: int = 200, first_scene: int = 0, margin: float = 1.0, people_reach: float = 3.5, tries: int = 32,
+                    outside_cost: int = 255, **scene_options) -> SceneBatch:
+    """B robots on `world`, each with a rolling local costmap of size_x x size_y cells: make_scenes' robots, reference
+    paths and people (scene_options are passed on), moved as a whole to a seeded start position each: the first of `tries`
+    candidates, uniform over the floor at least `margin` from its border, that lies on a free cell (cost 0: beyond the
+    inflation of every disc and of the wall); without one, the centre of the free cell nearest the floor's centre.
+    people_reach: the largest start distance of a person from its robot: make_scenes' 0.8 .. 3.5 m are mapped linearly
+    onto 0.8 .. people_reach along each person's own bearing (a crowd that fits a small floor; the velocities stay). costmap / costmap_origin are the initial windows by
+    smpc_local_costmap_batch's contract (window_cells from cell (0,0), crop_windows), costmap_shared = 0: a one-shot solve
+    on the batch sees what the first tick of BatchEpisode(world=world) sees."""
+    sc = make_scenes(params, B, N, seed=seed, first_scene=first_scene, map_cells=2, resolution=world.resolution, **scene_options)
+    ids = np.arange(first_scene, first_scene + B, dtype=np.int64)
+    res, Hx, Hy = world.resolution, world.cells_x, world.cells_y
+    x = world.origin[0] + margin + uniform(seed, ids, 400, tries) * (Hx * res - 2.0 * margin)    # [B,tries]
+    y = world.origin[1] + margin + uniform(seed, ids, 401, tries) * (Hy * res - 2.0 * margin)
+    ci = np.clip(np.floor((x - world.origin[0]) / res).astype(np.int64), 0, Hx - 1)
+    cj = np.clip(np.floor((y - world.origin[1]) / res).astype(np.int64), 0, Hy - 1)
+    ok = world.map[cj, ci] == 0
+    jj, ii = np.meshgrid(np.arange(Hy), np.arange(Hx), indexing="ij")
+    flat = int(np.argmin(np.where(world.map == 0, (ii + 0.5 - 0.5 * Hx) ** 2 + (jj + 0.5 - 0.5 * Hy) ** 2, np.inf)))
+    pick = np.argmax(ok, axis=1)[:, None]
+    sx = np.where(ok.any(axis=1), np.take_along_axis(x, pick, 1)[:, 0], world.origin[0] + ((flat % Hx) + 0.5) * res)
+    sy = np.where(ok.any(axis=1), np.take_along_axis(y, pick, 1)[:, 0], world.origin[1] + ((flat // Hx) + 0.5) * res)
+    start = np.stack([sx, sy], axis=1)
+    old = sc.pose0[:, 0:2].copy()
+    sc.pose0[:, 0:2] = start
+    sc.path_pts += (start - old)[:, None, :]
+    if N > 0:
+        valid = sc.people[:, :, 3:4, :] != -1.0                                     # [B,T+1,1,N]
+        first = sc.people[:, 0:1, 0:2, :] - old[:, None, :, None]                   # offsets at step 0
+        r = np.hypot(first[:, :, 0:1, :], first[:, :, 1:2, :])
+        scale = np.where(r > 0.0, (0.8 + (r - 0.8) * ((float(people_reach) - 0.8) / 2.7)) / np.where(r > 0.0, r, 1.0), 1.0)
+        moved = start[:, None, :, None] + scale * first + (sc.people[:, :, 0:2, :] - sc.people[:, 0:1, 0:2, :])
+        sc.people[:, :, 0:2, :] = np.where(valid, moved, sc.people[:, :, 0:2, :])
+    cell, origin, _ = window_cells(world.origin, res, None, start, size_x, size_y, force=True)
+    sc.costmap = crop_windows(world.map, cell, size_x, size_y, outside_cost)
+    sc.costmap_origin = np.ascontiguousarray(origin)
+    sc.costmap_shared = False
+    sc.validate(sc.init_params.shape[1])
+    return sc

@@ -11,10 +11,11 @@ import os
 
 import numpy as np
 
-from . import _abi
+from . import _abi, _abi_local_costmap
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
+from ._abi_local_costmap import SmpcLocalCostmapIn
 from .params import CrowdGroupParams, CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams
 from .scenes import SceneBatch
 
@@ -52,7 +53,7 @@ def load_library():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_abi.FUNCTIONS, **_abi.FIXED_SHAPE_FUNCTIONS}.items():
+    for name, (restype, argtypes) in {**_abi.FUNCTIONS, **_abi.FIXED_SHAPE_FUNCTIONS, **_abi_local_costmap.FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -606,6 +607,50 @@ class BatchSolver:
         cursor; asynchronous on the handle's stream."""
         assert cb.on_device == 1
         self._crowd_call(cb, people_ptr, cursor_ptr, groups)
+
+    # -- rolling local costmaps of a closed-loop episode (smpc_local_costmap_batch, include/smpc_local_costmap.h) ------
+    @staticmethod
+    def local_costmap_c(B: int, size_x: int, size_y: int, world_x: int, world_y: int, world_shared: bool, resolution: float,
+                        on_device: int, outside_cost: int = 255, force: bool = False) -> SmpcLocalCostmapIn:
+        if not 0 <= int(outside_cost) <= 255:
+            raise SmpcError(f"outside_cost must be 0..255, got {outside_cost}")
+        lc = SmpcLocalCostmapIn()
+        lc.B, lc.on_device, lc.size_x, lc.size_y = int(B), int(on_device), int(size_x), int(size_y)
+        lc.world_x, lc.world_y, lc.world_shared = int(world_x), int(world_y), 1 if world_shared else 0
+        lc.outside_cost, lc.force, lc.resolution = int(outside_cost), 1 if force else 0, float(resolution)
+        return lc
+
+    def local_costmap(self, world: np.ndarray, world_origin: np.ndarray, resolution: float, pose: np.ndarray, cell: np.ndarray,
+                      costmap: np.ndarray, costmap_origin: np.ndarray, outside_cost: int = 255, force: bool = False,
+                      moved: bool = True):
+        """One roll of B robots' local costmaps (host arrays): world [Hy,Hx] uint8 with world_origin [2] (one map shared by
+        all) or [B,Hy,Hx] with [B,2], pose [B,3], cell [B,2] int32 (the world cell of every window's cell (0,0)), costmap
+        [B,size_y,size_x] uint8 and costmap_origin [B,2] as the last roll left them (a robot whose window does not move
+        keeps them bit for bit). force: the stored cells are taken as (0,0) and every window is written. Returns the
+        updated copies (cell, costmap, costmap_origin, moved [B] int32: 0 kept, 1 moved, 2 pose not finite; None with
+        moved=False, which passes a NULL array)."""
+        world = np.ascontiguousarray(world, np.uint8)
+        shared = world.ndim == 2
+        world_origin = np.ascontiguousarray(world_origin, np.float64).reshape(-1, 2)
+        pose = np.ascontiguousarray(pose, np.float64)
+        cell = np.array(cell, dtype=np.int32, order="C")
+        costmap = np.array(costmap, dtype=np.uint8, order="C")
+        costmap_origin = np.array(costmap_origin, dtype=np.float64, order="C")
+        B, size_y, size_x = costmap.shape
+        assert pose.shape == (B, 3) and cell.shape == (B, 2) and costmap_origin.shape == (B, 2)
+        assert shared or world.shape[0] == B
+        assert world_origin.shape == ((1, 2) if shared else (B, 2))
+        lc = point(self.local_costmap_c(B, size_x, size_y, world.shape[-1], world.shape[-2], shared, resolution, 0, outside_cost, force),
+                   {"world": world, "world_origin": world_origin, "pose": pose})
+        mv = np.zeros(B, np.int32) if moved else None
+        self._call("smpc_local_costmap_batch", lc, _ptr(cell), _ptr(costmap), _ptr(costmap_origin), _ptr(mv))
+        return cell, costmap, costmap_origin, mv
+
+    def local_costmap_device(self, lc: SmpcLocalCostmapIn, cell_ptr: int, costmap_ptr: int, origin_ptr: int, moved_ptr: int = 0):
+        """Device pointers in lc (on_device == 1) and for cell, costmap, costmap_origin and moved (0: none); asynchronous on
+        the handle's stream."""
+        assert lc.on_device == 1
+        self._call("smpc_local_costmap_batch", lc, cell_ptr, costmap_ptr, origin_ptr, moved_ptr or None)
 
     # -- warm start / input formatting (SURVEY §8 row f2): format_to_optimize + TrajectoryMemory for B scenes -----
     def format_to_optimize(self, path: np.ndarray, cmds: np.ndarray, speed: np.ndarray, memory: dict,
