@@ -90,7 +90,7 @@ smpc_handle* smpc_create(const smpc_params* p, int device) {
   if (hipGetDeviceProperties(&prop, device) != hipSuccess) { set_error("hipGetDeviceProperties failed"); delete h; return nullptr; }
   h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) { set_error("hipEventCreate failed"); delete h; return nullptr; }
-  if (hipMalloc(reinterpret_cast<void**>(&h->queue), sizeof(int)) != hipSuccess) { set_error("hipMalloc(queue) failed"); delete h; return nullptr; }
+  if (hipMalloc(reinterpret_cast<void**>(&h->queue), smpc::kQueueWords * sizeof(int)) != hipSuccess) { set_error("hipMalloc(queue) failed"); delete h; return nullptr; }
   return h;
 }
 

@@ -18,7 +18,7 @@ struct smpc_handle {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
-  int* queue = nullptr;  // device-side scene queue head
+  int* queue = nullptr;  // device-side scene queue head and trip counters (KParams::queue)
   int share = 1;         // smpc_set_solve_share: concurrent solve launches the persistent grid leaves room for
   bool fixed_shapes = true;  // smpc_set_fixed_shapes: launches of a shape of SMPC_FIXED_SHAPES run that shape's kernels
   double* stage_rec = nullptr;  // staged people block of the latest call that did not bring its own (grow-only)

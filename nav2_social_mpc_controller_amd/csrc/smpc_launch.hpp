@@ -49,7 +49,10 @@ struct KParams {
   int32_t* o_evaluations;
   double* o_initial_cost;
   double* o_final_cost;
-  int* queue;  // scene work queue (one int, zeroed before every solve launch)
+  int* queue;  // [kQueueWords]: [0] the scene work queue, zeroed before every solve launch; behind it what the kernels with
+               // lone trips count (lone_trip_kernel()): [1] trips with exactly one slot idle for good, [2] all trips,
+               // [3] the trips of [1] that took the helped agent loop — running sums, zeroed by a launch under
+               // SMPC_DEBUG_GRID, which reports them
   // staged people block (smpc_stage_people_batch / the library's own staging pass): what the sweep reads
   const double* people_rec;  // [B][N][T][4]  px, py, vx, vy of people_proj[t + 1][a]
   const double* people_aux;  // [B][T][2]     bit mask of valid agents (u64 bits), agent-angle target (kNoTarget: none)
@@ -59,6 +62,8 @@ struct KParams {
   int full_gram;             // != 0: every sweep of a solve forms the whole Gram (SMPC_FULL_GRAM: the check that stopping at
                              // its last column changes nothing)
   int prio_step;             // > 0: a wave whose oldest scene has made n sweeps runs at wave priority min(n / prio_step, 3)
+  int lone_help;             // != 0: a trip with one slot idle for good is a lone trip, its idle half evaluates every other
+                             // agent (sweep()); 0 (SMPC_NO_LONE_HELP): every trip is paired. Results are the same bit for bit
   double* stage_rec;         // staging kernel outputs (same layouts)
   double* stage_aux;
   unsigned long long* stamps;  // diagnostic builds only (SMPC_STAMPS): per-wave cycle sums per phase, [grid][8]
@@ -83,6 +88,11 @@ struct KParams {
                         // staging kernel ran and stage_aux is not used. 0: people_rec / people_aux are read as staged
 };
 constexpr int kTraceCols = SMPC_TRACE_COLS;
+constexpr int kQueueWords = 4;  // KParams::queue
+
+// The solve kernels that know lone trips (sweep(), kLone): two scenes per wave, launch-constant horizon and weights, no
+// trace. Every other kernel is compiled without a line of it.
+__host__ __device__ constexpr bool lone_trip_kernel(int W, bool vt, bool sp, bool trace) { return W == 32 && !vt && !sp && !trace; }
 
 // Kernel parameters are read through the kernel-argument segment (constant address space) instead of being held in
 // SGPRs for the whole kernel: the ~90 scalars of KParams otherwise overflow the SGPR file and come back as

@@ -22,7 +22,9 @@ struct Knobs {
   int max_waves_per_cu = 0;   // SMPC_MAX_WAVES_PER_CU >= 1: limit on the resident waves per CU a solve launch counts on
   int prio_step = 0;          // SMPC_PRIO_STEP >= 1: KParams::prio_step
   bool full_gram = false;     // SMPC_FULL_GRAM: KParams::full_gram
-  bool debug_grid = false;    // SMPC_DEBUG_GRID: a solve launch reports its LDS bytes and waves per CU on stderr
+  bool debug_grid = false;    // SMPC_DEBUG_GRID: a solve launch reports its LDS bytes and waves per CU on stderr and, once it has
+                              // finished, its trips: all, those with one slot idle for good, those that took the helped loop
+  bool no_lone_help = false;  // SMPC_NO_LONE_HELP: KParams::lone_help = 0, every trip of a solve is paired
 };
 
 inline Knobs read_knobs() {
@@ -35,6 +37,7 @@ inline Knobs read_knobs() {
   if (const int c = number("SMPC_PRIO_STEP"); c >= 1) kn.prio_step = c;
   kn.full_gram = std::getenv("SMPC_FULL_GRAM") != nullptr;
   kn.debug_grid = std::getenv("SMPC_DEBUG_GRID") != nullptr;
+  kn.no_lone_help = std::getenv("SMPC_NO_LONE_HELP") != nullptr;
   return kn;
 }
 

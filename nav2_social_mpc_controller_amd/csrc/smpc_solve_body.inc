@@ -6,6 +6,7 @@
   const auto& k = *(KParamsK)__builtin_amdgcn_kernarg_segment_ptr();
   constexpr int P = 2 * NB;
   constexpr int S = kWave / W;
+  constexpr bool kLone = lone_trip_kernel(W, kVT, kSP, kTrace);
   extern __shared__ __attribute__((aligned(32))) double lds_all[];
   const int lane = threadIdx.x & 63;
   Ctx c;
@@ -101,6 +102,9 @@
     R.cur_vv = f & 16; R.cur_gv = f & 32; R.first_vv = f & 64;
   };
   bool ever_loaded = false;
+  // kLone: this wave's trips, those with one slot idle for good and those helped, 21 bits each in one word of LDS behind
+  // the state machine's parked integers (each slot keeps the wave's count; a wave makes far fewer than 2^21 trips)
+  if constexpr (kLone) *reinterpret_cast<unsigned long long*>(rw + 8) = 0ull;
 #ifdef SMPC_STAMPS
   for (int i = 0; i < 8; ++i) c.acc[i] = 0;
   for (int i = 0; i < 4; ++i) c.acc2[i] = 0;
@@ -173,6 +177,17 @@
     }
     if (__all(R.phase == PH_IDLE)) break;
     SMPC_STAMP(c, 0);  // fetch + load_scene
+    if constexpr (kLone) {
+      // A lone trip: one slot is idle — for good, PH_IDLE is final — and the other works on a scene with people and
+      // N >= 2. Its agent loop is shared between the halves (sweep(), trip_mode()). Decided for the wave; a paired trip pays two
+      // ballots and a scalar branch.
+      const bool idle = R.phase == PH_IDLE;
+      const unsigned long long ib = __ballot(idle);
+      const bool half = ((ib ^ (ib >> 32)) & 1ull) != 0ull;  // (the phase is uniform over a slot)
+      const bool lone = half && k.lone_help != 0 && Shape::N(k) >= 2 && __ballot(!idle && c.has_people) != 0ull;
+      *trip_mode(c) = !lone ? kTripPaired : idle ? kTripHelper : kTripOwner;
+      *reinterpret_cast<unsigned long long*>(rw + 8) += 1ull + (half ? 1ull << 21 : 0ull) + (lone ? 1ull << 42 : 0ull);
+    }
     if (k.prio_step > 0) {
       // Attained-service priority: the launch ends when its longest scene does, and a scene's sweeps are a dependent
       // chain — so the longer a scene has been running, the more of the SIMD's issue slots its wave gets against the
@@ -204,7 +219,7 @@
       const bool col_finite = (__ballot(c.sl <= P && !isfinite(gt[min(c.sl, P) * (P + 1) + P])) & slot_bits) == 0ull;
       return !col_finite || armijo_holds(0.5 * gt[P * (P + 1) + P], svp[S_COST], svp[S_GD0], svp[S_CUR_X]);
     };
-    sweep<NB, W, false, kVT, kSP, Shape>(c, xt, nullptr, nullptr, need_rest);  // [J r]^T [J r] of this slot, left in LDS
+    sweep<NB, W, false, kVT, kSP, Shape, kLone>(c, xt, nullptr, nullptr, need_rest);  // [J r]^T [J r] of this slot, left in LDS
     {
       int lane_t = lane;
       asm volatile("" : "+v"(lane_t));
@@ -526,6 +541,18 @@
         }
       }
       R.phase = PH_FETCH;
+    }
+  }
+  if constexpr (kLone) {
+    // (through the loop's copy of the argument pointer and with an address of its own: the prologue's pointer or the loop's
+    // LDS pointers, live to here, were four scalar registers spilled in the line search)
+    const auto& ke = *c.kp;
+    const LdsLayout Lx = make_layout(Shape::T(ke), Shape::N(ke), P, kLayoutSolve, W, kSP);
+    if (threadIdx.x == 0) {
+      const unsigned long long n = *reinterpret_cast<const unsigned long long*>(lds_all + Lx.lm + P * P + 6 * P + S_COUNT + 4);
+      atomicAdd(ke.queue + 1, (int)((n >> 21) & 0x1fffffull));
+      atomicAdd(ke.queue + 2, (int)(n & 0x1fffffull));
+      atomicAdd(ke.queue + 3, (int)(n >> 42));
     }
   }
 #ifdef SMPC_STAMPS

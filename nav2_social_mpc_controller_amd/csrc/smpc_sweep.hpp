@@ -40,6 +40,16 @@ template <int W> __device__ inline double slot_sum(double v) {
   return v;
 }
 
+// What lane ^ 32 holds: the same lane of the wave's other half (the other slot of a two-scenes-per-wave kernel). One LDS
+// crossbar operation per 32 bits, nothing on the VALU but the address, which is the same at every call.
+__device__ inline int other_half(int v) { return __builtin_amdgcn_ds_bpermute(((int)__lane_id() ^ 32) << 2, v); }
+__device__ inline double other_half(double v) {
+  return __hiloint2double(other_half(__double2hiint(v)), other_half(__double2loint(v)));
+}
+__device__ inline unsigned long long other_half(unsigned long long v) {
+  return ((unsigned long long)(unsigned)other_half((int)(v >> 32)) << 32) | (unsigned)other_half((int)v);
+}
+
 // In-kernel phase stamps (diagnostic build -DSMPC_STAMPS only; the shipped kernel executes none of this).
 #ifdef SMPC_STAMPS
 #define SMPC_STAMP(ctx, phase) do { const unsigned long long _t = __builtin_amdgcn_s_memtime(); (ctx).acc[phase] += _t - (ctx).t_last; (ctx).t_last = _t; } while (0)
@@ -219,7 +229,22 @@ __device__ inline void load_scene(Ctx& c, int scene, bool stage = true) {
 struct NeedAll { __device__ inline bool operator()() const { return true; } };
 // Shape: where T, N, CH, bl and what follows from them come from — the launch values (RuntimeShape) or the literals of a
 // FixedShape (smpc_launch.hpp). The arithmetic on doubles and the order of every sum are the same in both.
-template <int NB, int W, bool kRows, bool kVT = false, bool kSP = false, class Shape = RuntimeShape, class NeedRest = NeedAll>
+// kLone (the solve kernels of lone_trip_kernel()): a trip the caller marks lone — one slot of the wave idle for good, the
+// other live with people and N >= 2; trip_mode() — walks the agents two at a time. Both halves evaluate pair_force() in
+// the same instructions, the owner lanes (the live slot) for agent 2i, their mirror lanes of the idle half (the helpers)
+// for agent 2i + 1 at the owner's pose; the owner lane then accumulates its own Force and, fetched across the halves,
+// the mirror lane's, with the statements of the paired loop in the order of the paired loop: agents 0, 1, ..., N - 1.
+// Every operand of every sum is the value the owner's own evaluation would have produced, so a scene's result does not
+// depend on whether, or from which sweep on, its trips were lone. The idle half's own sums are junk and go nowhere, as
+// ever.
+// The trip's mode travels in a word of the slot's LDS (the spare eighth integer of the horizon block, which only the
+// kernels with a horizon per scene fill, and those have no lone trips), written by the solve kernel before the sweep and
+// read where the sweep needs it: held in scalar registers from the trip's head to the agent loop it spilled four of them.
+enum TripMode { kTripPaired = 0, kTripOwner = 1, kTripHelper = 2 };
+__device__ inline int* trip_mode(const Ctx& c) { return reinterpret_cast<int*>(c.lds + c.L.hz) + 7; }
+
+template <int NB, int W, bool kRows, bool kVT = false, bool kSP = false, class Shape = RuntimeShape, bool kLone = false,
+          class NeedRest = NeedAll>
 __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double* out_J, NeedRest need_rest = NeedRest()) {
   constexpr int P = 2 * NB;
   const auto& k = *c.kp;
@@ -238,6 +263,20 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
   // latency (HBM in the stand-alone K1 kernel) passes behind the rollout
   const v4d* agr = reinterpret_cast<const v4d*>(c.ag) + tl;
   v4d rec0 = {0.0, 0.0, 0.0, 0.0}, rec1 = {0.0, 0.0, 0.0, 0.0};
+  bool lone = false, hlp = false;  // kLone: a lone trip (wave-uniform); this lane is a helper
+  if constexpr (kLone) {
+    const int mode = *trip_mode(c);
+    lone = __builtin_amdgcn_readfirstlane(mode) != kTripPaired;
+    hlp = mode == kTripHelper;
+  }
+  if (kLone && lone) {
+    // a lone trip: the helper lanes read the owner's records, agents 1, 3, ... where the owner takes 0, 2, ... (their own
+    // scene's pointer is not needed again: the proxemics fetch behind the loop is in bounds in either scene)
+    // (every exchange across the halves is executed by all lanes: a lane switched off hands nothing over)
+    const v4d* owner_agr = reinterpret_cast<const v4d*>(other_half(reinterpret_cast<unsigned long long>(agr)));
+    agr = hlp ? owner_agr : agr;
+    rec0 = agr[(hlp ? 1 : 0) * T]; rec1 = agr[min(hlp ? 3 : 2, N - 1) * T];
+  } else
   if (c.has_people) { rec0 = agr[0]; rec1 = agr[(N > 1 ? 1 : 0) * T]; }
 
   // ---- a1 rollout (update_state.hpp:37-63), block-structured. The recurrences are sums, so they are evaluated as
@@ -311,7 +350,12 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
   // valid agent of the proxemics critic: eight values across the divergent branch instead of the 23 running sums
   double sw_r = 0.0, sw_gx = 0.0, sw_gy = 0.0, sw_gt = 0.0, sw_gv = 0.0;
   double pbest = 1.7976931348623157e308, pdx = 0.0, pdy = 0.0;
-  if (c.has_people) {
+  if constexpr (kLone) {  // (read again rather than kept)
+    const int mode = *trip_mode(c);
+    lone = __builtin_amdgcn_readfirstlane(mode) != kTripPaired;
+    hlp = mode == kTripHelper;
+  }
+  if (c.has_people || (kLone && hlp)) {
     double soc[kSoc];
 #pragma unroll
     for (int i = 0; i < kSoc; ++i) soc[i] = 0.0;
@@ -320,8 +364,8 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
     const MathTabP mt = &k.mt;
     const double* atab = c.atab;
     const unsigned long long* vmask = reinterpret_cast<const unsigned long long*>(c.lds + c.L.valid);
-    const unsigned long long vm = vmask[tl];
-    const double rvx = vb * c1, rvy = vb * s1;  // meVel, social_work:170-171
+    unsigned long long vm = vmask[tl];
+    double rvx = vb * c1, rvy = vb * s1;  // meVel, social_work:170-171
     int pidx = 0;  // proxemics: index of the nearest valid agent (first minimum wins: std::min on duals)
     bool redo = false;  // some pair of this lane is not a regular one
     // One robot-agent pair: the robot of a step at (px, py) with velocity (pvx, pvy) against agent a of that step.
@@ -329,29 +373,35 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
     // is F(diff, u), diff = robot - agent, u = robotVel - agentVel; the force on the agent from the robot
     // (:137-143; every column, phantoms included) is F(-diff, -u) = -F with the same derivatives, so |.|^2 and its
     // gradient are those of F.
+    // (the nearest-agent test and the sums as text: a lone trip's loop runs the same statements, on a Force that may have
+    // been evaluated in the other half of the wave)
+#define SMPC_PAIR_NEAREST(d2, a, valid) \
+      const bool nearer = valid & (d2 < pbest); \
+      pbest = nearer ? d2 : pbest; \
+      pidx = nearer ? a : pidx;
+    // |diff| < 1e-6 -> diff := (1e-6, 0), :181-184, breaks the symmetry above: redo.
+    // Derivatives with respect to the robot's (theta, v) are one rotation of the u-derivatives that is the same for every
+    // agent of this step (u = v (cos theta, sin theta) - agentVel): sum the u-derivatives, rotate once after the loop.
+#define SMPC_PAIR_ADD(F, special, d2, valid) \
+      redo |= special | (d2 < 1e-12); \
+      const double m = valid ? 1.0 : 0.0; \
+      soc[0] = fma(m, F.fx, soc[0]); soc[1] = fma(m, F.fy, soc[1]); \
+      soc[2] = fma(m, F.dfx_dx, soc[2]); soc[3] = fma(m, F.dfy_dx, soc[3]); \
+      soc[4] = fma(m, F.dfx_dy, soc[4]); soc[5] = fma(m, F.dfy_dy, soc[5]); \
+      su[0] = fma(m, F.dfx_dux, su[0]); su[1] = fma(m, F.dfy_dux, su[1]); \
+      su[2] = fma(m, F.dfx_duy, su[2]); su[3] = fma(m, F.dfy_duy, su[3]); \
+      soc[10] = fma(F.fx, F.fx, fma(F.fy, F.fy, soc[10])); \
+      qh[0] = fma(F.fx, F.dfx_dx, fma(F.fy, F.dfy_dx, qh[0])); \
+      qh[1] = fma(F.fx, F.dfx_dy, fma(F.fy, F.dfy_dy, qh[1])); \
+      qh[2] = fma(F.fx, F.dfx_dux, fma(F.fy, F.dfy_dux, qh[2])); \
+      qh[3] = fma(F.fx, F.dfx_duy, fma(F.fy, F.dfy_duy, qh[3]));
     auto pair = [&](const v4d& rec, int a, bool valid, double px, double py, double pvx, double pvy) {
       const double apx = rec[0], apy = rec[1], awx = rec[2], awy = rec[3];
       const double dx = px - apx, dy = py - apy;
       const double d2 = fma(dx, dx, dy * dy);
-      const bool nearer = valid & (d2 < pbest);
-      pbest = nearer ? d2 : pbest;
-      pidx = nearer ? a : pidx;
+      SMPC_PAIR_NEAREST(d2, a, valid)
       const Force F = pair_force(mt, atab, dx, dy, pvx - awx, pvy - awy);
-      redo |= F.special | (d2 < 1e-12);  // |diff| < 1e-6 -> diff := (1e-6, 0), :181-184, breaks the symmetry above
-      const double m = valid ? 1.0 : 0.0;
-      soc[0] = fma(m, F.fx, soc[0]); soc[1] = fma(m, F.fy, soc[1]);
-      soc[2] = fma(m, F.dfx_dx, soc[2]); soc[3] = fma(m, F.dfy_dx, soc[3]);
-      soc[4] = fma(m, F.dfx_dy, soc[4]); soc[5] = fma(m, F.dfy_dy, soc[5]);
-      // derivatives with respect to the robot's (theta, v) are one rotation of the u-derivatives that is the same
-      // for every agent of this step (u = v (cos theta, sin theta) - agentVel): sum the u-derivatives, rotate once
-      // after the loop
-      su[0] = fma(m, F.dfx_dux, su[0]); su[1] = fma(m, F.dfy_dux, su[1]);
-      su[2] = fma(m, F.dfx_duy, su[2]); su[3] = fma(m, F.dfy_duy, su[3]);
-      soc[10] = fma(F.fx, F.fx, fma(F.fy, F.fy, soc[10]));
-      qh[0] = fma(F.fx, F.dfx_dx, fma(F.fy, F.dfy_dx, qh[0]));
-      qh[1] = fma(F.fx, F.dfx_dy, fma(F.fy, F.dfy_dy, qh[1]));
-      qh[2] = fma(F.fx, F.dfx_dux, fma(F.fy, F.dfy_dux, qh[2]));
-      qh[3] = fma(F.fx, F.dfx_duy, fma(F.fy, F.dfy_duy, qh[3]));
+      SMPC_PAIR_ADD(F, F.special, d2, valid)
     };
     const int A = (W == 64) ? Shape::hp_A(k) : N;  // agents the owner lane walks itself (helper_owner_agents(): N without helpers)
     if (W == 64 && A < N) {
@@ -419,6 +469,58 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
         // the helper's agents come after the owner's: a tie stays with the owner (std::min keeps the first minimum)
         if (pr[15] < pbest) { pbest = pr[15]; pidx = tag & 4095; }
         redo |= tag >= 4096;
+      }
+    } else if constexpr (kLone) {
+      // ---- the kernels with lone trips (see the head of sweep()): one loop for both kinds of trip — a second copy of
+      // pair_force() in the kernel costs registers the sweep does not have. A paired trip walks agent a per iteration, as
+      // the loop below does; a lone trip agents a (owner half) and a + 1 (helper half).
+      // A helper lane's own pose and velocity wait in LDS (behind the scans, in the part of the Gram reduction buffer that is
+      // idle until the critics are done): its critics below rely on them for addresses in bounds.
+      double* keep = c.lds + c.L.cs + 6 * (T + 1) + 4 * sl;
+      int mine = 0, step = 1;
+      if (lone) {
+        keep[0] = X; keep[1] = Y; keep[2] = rvx; keep[3] = rvy;
+        const unsigned long long ovm = other_half(vm);  // selects behind the exchanges: every lane hands over
+        const double oX = other_half(X), oY = other_half(Y), ovx = other_half(rvx), ovy = other_half(rvy);
+        vm = hlp ? ovm : vm; X = hlp ? oX : X; Y = hlp ? oY : Y; rvx = hlp ? ovx : rvx; rvy = hlp ? ovy : rvy;
+        mine = hlp ? 1 : 0;
+        step = 2;
+      }
+      for (int a = 0; a < N; a += step) {
+        const v4d rec = rec0;  // of agent a + mine (the helper's last unit of an odd N: some record, its Force is not used)
+        rec0 = rec1;
+        const int ahead = a + mine + 2 * step;
+        if (ahead < N) rec1 = agr[ahead * T];
+        const double apx = rec[0], apy = rec[1], awx = rec[2], awy = rec[3];
+        const double dx = X - apx, dy = Y - apy;
+        double d2 = fma(dx, dx, dy * dy);
+        Force F = pair_force(mt, atab, dx, dy, rvx - awx, rvy - awy);
+        int special = F.special ? 1 : 0;
+        {
+          const bool valid = (vm >> a) & 1ull;
+          SMPC_PAIR_NEAREST(d2, a, valid)
+          SMPC_PAIR_ADD(F, (special != 0), d2, valid)
+        }
+        if (step == 2 && a + 1 < N) {  // (wave-uniform) agent a + 1: the mirror lane's evaluation
+          // the Force crosses in the registers it has, behind the sums that read it (the scheduler would start the exchange
+          // early and hold both copies)
+          __builtin_amdgcn_sched_barrier(0);
+          F.fx = other_half(F.fx); F.fy = other_half(F.fy);
+          F.dfx_dx = other_half(F.dfx_dx); F.dfy_dx = other_half(F.dfy_dx);
+          F.dfx_dy = other_half(F.dfx_dy); F.dfy_dy = other_half(F.dfy_dy);
+          F.dfx_dux = other_half(F.dfx_dux); F.dfy_dux = other_half(F.dfy_dux);
+          F.dfx_duy = other_half(F.dfx_duy); F.dfy_duy = other_half(F.dfy_duy);
+          d2 = other_half(d2);
+          special = other_half(special);
+          __builtin_amdgcn_sched_barrier(0);
+          const bool valid = (vm >> (a + 1)) & 1ull;
+          SMPC_PAIR_NEAREST(d2, (a + 1), valid)
+          SMPC_PAIR_ADD(F, (special != 0), d2, valid)
+        }
+      }
+      if (step == 2) {  // (step and mine, not the flags they came from: two scalar registers fewer through the loop)
+        redo = redo & (mine == 0);  // the re-walk in the general form is the owner's alone
+        X = keep[0]; Y = keep[1]; rvx = keep[2]; rvy = keep[3];  // (an owner lane reads back what it wrote)
       }
     } else {
       for (int a = 0; a < N; ++a) {
@@ -859,6 +961,8 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
   SMPC_STAMP(c, 5);
   return view;
 #undef SPRM
+#undef SMPC_PAIR_NEAREST
+#undef SMPC_PAIR_ADD
 }
 
 // A sweep result is usable iff every residual and Jacobian entry was finite: a non-finite entry makes the

@@ -236,10 +236,20 @@ int launch(smpc_handle* h, Staging& st, const smpc::SweepPlan& plan, const smpc:
     k.queue = h->queue;
     k.full_gram = kn.full_gram ? 1 : 0;
     k.prio_step = kn.prio_step;
+    k.lone_help = kn.no_lone_help ? 0 : 1;
+    // the trip counters behind the scene counter are zeroed only for the launch that reports them: every other launch
+    // issues the one four-byte memset it always issued (the captured tick graphs of the sharded episodes hold this node)
+    if (kn.debug_grid) SMPC_HIP_CHECK(hipMemsetAsync(h->queue + 1, 0, (smpc::kQueueWords - 1) * sizeof(int), h->stream));
     SMPC_HIP_CHECK(hipMemsetAsync(h->queue, 0, sizeof(int), h->stream));
   }
   SMPC_TRY(stamps_attach(k, grid));
   SMPC_TRY(st.timed([&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(smpc::kWave), shmem, h->stream, k); return SMPC_OK; }));
+  if (kn.debug_grid && !eval) {  // what the kernel counted (zeros from a kernel without lone trips, lone_trip_kernel())
+    int words[smpc::kQueueWords];
+    SMPC_HIP_CHECK(hipStreamSynchronize(h->stream));
+    SMPC_HIP_CHECK(hipMemcpy(words, h->queue, sizeof(words), hipMemcpyDeviceToHost));
+    std::fprintf(stderr, "[smpc] solve kernel: %d trips, %d with one slot idle for good, %d helped\n", words[2], words[1], words[3]);
+  }
   return stamps_dump(h, k, grid, eval);
 }
 
