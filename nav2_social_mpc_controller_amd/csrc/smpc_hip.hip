@@ -15,7 +15,7 @@
 //   smpc_stage_kernel<W>     the staging pass of the people block (smpc_stage_kernel.hpp);
 //   the probe kernels (smpc_probes.hpp);
 //   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window,
-//   metrics, crowd, local costmap).
+//   metrics, crowd, local costmap, global plan).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -35,6 +35,7 @@
 #include "smpc_crowd.hpp"
 #include "smpc_local_costmap.hpp"
 #include "../../include/smpc_local_costmap.h"
+#include "smpc_global_plan.hpp"
 
 extern "C" {
 
@@ -102,6 +103,7 @@ void smpc_destroy(smpc_handle* h) {
   if (h->stage_rec) (void)hipFree(h->stage_rec);
   if (h->stage_aux) (void)hipFree(h->stage_aux);
   if (h->neutral_sp) (void)hipFree(h->neutral_sp);
+  if (h->gp_fail) (void)hipFree(h->gp_fail);
   if (h->stage) (void)hipFree(h->stage);
   if (h->pin) (void)hipHostFree(h->pin);
   delete h;
@@ -655,6 +657,95 @@ int smpc_local_costmap_batch(smpc_handle* h, const smpc_local_costmap_in* in, in
     const size_t grid = B < (size_t)h->num_cu * 8 ? B : (size_t)h->num_cu * 8;  // a fixed grid that strides over the robots
     SMPC_TRY(st.timed([&] {
       hipLaunchKernelGGL(smpc::smpc_local_costmap_kernel, dim3((unsigned)grid), dim3(smpc::kLcThreads), 0, h->stream, p);
+      return SMPC_OK;
+    }));
+  }
+  return st.finish();
+}
+
+// what smpc_goal_field_batch and smpc_extract_plan_batch check alike: the world, the resolution and the cost parameters
+static int check_plan_world(int32_t world_x, int32_t world_y, double resolution, const smpc_plan_cost_params& c, smpc::GpCost* cost) {
+  if (world_x < 1 || world_y < 1) { set_error("a non-positive world size"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(resolution) || !(resolution > 0.0)) { set_error("resolution must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (c.neutral_cost < 1 || c.cost_weight < 0) { set_error("neutral_cost must be >= 1 and cost_weight >= 0"); return SMPC_ERR_INVALID_ARG; }
+  const int64_t w_max = (int64_t)c.neutral_cost + 255 * (int64_t)c.cost_weight;
+  if (w_max > 65535) { set_error("neutral_cost + 255 * cost_weight must be <= 65535"); return SMPC_ERR_INVALID_ARG; }
+  const int64_t cells = (int64_t)world_x * world_y;
+  if (cells >= (int64_t)1 << 31) { set_error("a world of 2^31 cells or more is not supported"); return SMPC_ERR_UNSUPPORTED; }
+  if (cells * 7 * w_max >= ((int64_t)1 << 32) - 1) {  // < 2^31 * 2^19
+    set_error("world_x * world_y * 7 * (neutral_cost + 255 * cost_weight) must stay below 2^32 - 1: potentials are 32 bits"); return SMPC_ERR_UNSUPPORTED;
+  }
+  cost->neutral = c.neutral_cost; cost->weight = c.cost_weight;
+  cost->lethal_min = c.lethal_min_cost; cost->allow_unknown = c.allow_unknown ? 1u : 0u;
+  return SMPC_OK;
+}
+
+int smpc_goal_field_batch(smpc_handle* h, const smpc_goal_field_in* in, uint32_t* field, int32_t* status) {
+  if (!h || !in || !field) { set_error("null handle / input / field"); return SMPC_ERR_INVALID_ARG; }
+  if (!in->world || !in->world_origin || !in->goal) { set_error("null input array"); return SMPC_ERR_INVALID_ARG; }
+  if (in->G < 0) { set_error("bad G"); return SMPC_ERR_INVALID_ARG; }
+  smpc::GoalFieldParams p;
+  std::memset(&p, 0, sizeof(p));
+  SMPC_TRY(check_plan_world(in->world_x, in->world_y, in->resolution, in->cost, &p.cost));
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  p.G = in->G; p.world_x = in->world_x; p.world_y = in->world_y; p.world_shared = in->world_shared ? 1 : 0;
+  p.resolution = in->resolution;
+  p.tiles_x = (in->world_x + smpc::kGfTile - 1) / smpc::kGfTile;
+  p.n_tiles = p.tiles_x * ((in->world_y + smpc::kGfTile - 1) / smpc::kGfTile);  // < 2^31 cells: fits
+  p.tiles_per_flag = (p.n_tiles + smpc::kGfFlagCap - 1) / smpc::kGfFlagCap;
+  p.n_flags = (p.n_tiles + p.tiles_per_flag - 1) / p.tiles_per_flag;
+  const size_t G = in->G, cells = (size_t)in->world_x * in->world_y, nworld = in->world_shared ? 1 : G;
+  if (G > 0 && !h->gp_fail) SMPC_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->gp_fail), sizeof(uint32_t)));  // once per handle
+  p.fail = h->gp_fail;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.world, in->world, nworld * cells));
+  SMPC_TRY(st.in(p.world_origin, in->world_origin, nworld * 2));
+  SMPC_TRY(st.in(p.goal, in->goal, G * 2));
+  SMPC_TRY(st.out(p.field, field, G * cells));
+  SMPC_TRY(st.out(p.status, status, G));
+  uint32_t failed = 0;
+  if (G > 0) {
+    SMPC_HIP_CHECK(hipMemsetAsync(h->gp_fail, 0, sizeof(uint32_t), h->stream));
+    SMPC_TRY(st.timed([&] {
+      hipLaunchKernelGGL(smpc::smpc_goal_field_kernel, dim3((unsigned)G), dim3(smpc::kGfThreads), 0, h->stream, p);
+      return SMPC_OK;
+    }));
+    // the one word this call reads back, with device pointers too: did every field settle within its bound?
+    SMPC_HIP_CHECK(hipMemcpyAsync(&failed, h->gp_fail, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    SMPC_HIP_CHECK(hipStreamSynchronize(h->stream));
+  }
+  SMPC_TRY(st.finish());
+  if (failed) { set_error("a goal field did not settle within world_x * world_y sweeps"); return SMPC_ERR_DEVICE; }
+  return SMPC_OK;
+}
+
+int smpc_extract_plan_batch(smpc_handle* h, const smpc_extract_plan_in* in, double* plan, int32_t* plan_len, int32_t* error) {
+  if (!h || !in || !plan || !plan_len) { set_error("null handle / input / plan / plan_len"); return SMPC_ERR_INVALID_ARG; }
+  if (!in->world || !in->world_origin || !in->field || !in->goal || !in->robot_goal || !in->pose) { set_error("null input array"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B < 0 || in->G < 0 || in->L < 2 || in->stride < 1) { set_error("bad B / G, L < 2 or stride < 1"); return SMPC_ERR_INVALID_ARG; }
+  smpc::ExtractPlanParams p;
+  std::memset(&p, 0, sizeof(p));
+  SMPC_TRY(check_plan_world(in->world_x, in->world_y, in->resolution, in->cost, &p.cost));
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  p.B = in->B; p.G = in->G; p.L = in->L; p.stride = in->stride;
+  p.world_x = in->world_x; p.world_y = in->world_y; p.world_shared = in->world_shared ? 1 : 0;
+  p.resolution = in->resolution;
+  const size_t B = in->B, G = in->G, cells = (size_t)in->world_x * in->world_y, nworld = in->world_shared ? 1 : G;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.world, in->world, nworld * cells));
+  SMPC_TRY(st.in(p.world_origin, in->world_origin, nworld * 2));
+  SMPC_TRY(st.in(p.field, in->field, G * cells));
+  SMPC_TRY(st.in(p.goal, in->goal, G * 2));
+  SMPC_TRY(st.in(p.robot_goal, in->robot_goal, B));
+  SMPC_TRY(st.in(p.pose, in->pose, B * 3));
+  // read and written: the rows the kernel leaves alone keep the caller's bytes on the way through device memory too
+  SMPC_TRY(st.inout(p.plan, plan, B * (size_t)in->L * 2));
+  SMPC_TRY(st.out(p.plan_len, plan_len, B));
+  SMPC_TRY(st.out(p.error, error, B));
+  if (B > 0) {
+    const size_t per_block = smpc::kEpThreads / 8;
+    SMPC_TRY(st.timed([&] {
+      hipLaunchKernelGGL(smpc::smpc_extract_plan_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kEpThreads), 0, h->stream, p);
       return SMPC_OK;
     }));
   }

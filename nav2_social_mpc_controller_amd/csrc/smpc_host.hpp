@@ -31,6 +31,7 @@ struct smpc_handle {
   size_t neutral_sp_bytes = 0;   // (grow-only; prm never changes, so rows once written stay valid)
   char* pin = nullptr;    // page-locked host mirror of the arena's first pin_cap bytes: the small arrays of a host-pointer call
   size_t pin_cap = 0;     // travel in ONE copy each way instead of one pageable hipMemcpy per array (Staging, below)
+  uint32_t* gp_fail = nullptr;  // smpc_goal_field_batch: the word its kernel sets when a field did not settle (first call)
 };
 
 namespace {

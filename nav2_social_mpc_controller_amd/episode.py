@@ -6,6 +6,8 @@
     format_to_optimize + TrajectoryMemory   (src/optimizer.cpp:172-190, 484-551)  -> smpc_format_to_optimize_batch
     ObstacleDistance grid (optional, once)   (src/optimizer.cpp:593-605, 'TODO')   -> smpc_obstacle_distance_batch
     rolling local costmap (optional)         (Nav2's LayeredCostmap::updateMap)    -> smpc_local_costmap_batch
+    global plans (optional, at the start and   (Nav2's planner server; the library's -> smpc_goal_field_batch,
+    on replan(), never inside a tick)          own integer cost rule)                 smpc_extract_plan_batch
     project_people                           (src/optimizer.cpp:554-728)           -> smpc_project_people_batch
     problem assembly + ceres::Solve + unpack (src/optimizer.cpp:197-446)           -> smpc_solve_batch
     memory store                             (src/optimizer.cpp:448-449)           -> smpc_memory_store_batch
@@ -38,7 +40,8 @@ import numpy as np
 
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
-from .params import CrowdGroupParams, CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams, check_scene_param_rows
+from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, TrajectorizerParams,
+                     check_scene_param_rows)
 from .scenes import SceneBatch, World
 from .solver import BatchSolver, point, set_od_grid
 
@@ -93,7 +96,7 @@ class BatchEpisode:
     PER_GRID = ("od_indexes", "od_origin", "od_distances")
     # the same object for every shard
     FORWARDED = ("od_resolution", "device", "traj_params", "fov_angle", "order_hint", "plan_window", "obstacles_from_costmap",
-                 "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost")
+                 "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost", "planner")
 
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
@@ -103,7 +106,8 @@ class BatchEpisode:
                  metrics: MetricsParams = None, goal: np.ndarray = None, od_distances: np.ndarray = None,
                  crowd: CrowdParams = None, person_waypoints: np.ndarray = None, person_n_waypoints: np.ndarray = None,
                  person_speed: np.ndarray = None, person_groups: np.ndarray = None,
-                 crowd_groups: CrowdGroupParams = None, world: World = None, outside_cost: int = 255):
+                 crowd_groups: CrowdGroupParams = None, world: World = None, outside_cost: int = 255,
+                 planner: GlobalPlanParams = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -149,7 +153,14 @@ class BatchEpisode:
         outside_cost. The first tick, and the first replay of a captured graph, write every window (`force`). With
         obstacles_from_costmap the ObstacleDistance grid is computed from the world map, once, shared by all robots, with
         the world's origin (with distances when metrics ask for them); host-given od_* are taken as they are. None:
-        nothing is allocated and nothing is launched."""
+        nothing is allocated and nothing is launched.
+        planner: the global plans come from the world map (include/smpc_global_plan.h) instead of `plan`, which is refused:
+        needs `world`, `traj_params` and goal [B,2]. One goal field per distinct row of `goal` (found on the host;
+        self.robot_goal [B] maps the robots onto them) is computed here, once (smpc_goal_field_batch), and every robot's
+        plan is walked down its field from its start pose (smpc_extract_plan_batch) into self.plan [B,planner.max_poses,2],
+        self.plan_len and self.plan_error [B] (enum smpc_plan_error; a robot with an error other than TRUNCATED has
+        plan_len 0 and gets no command). From there on this is the episode that was handed these arrays as `plan`.
+        replan() walks again from the current poses. None: nothing is allocated and nothing is launched."""
         import torch
 
         self.torch = torch
@@ -159,7 +170,12 @@ class BatchEpisode:
         # library kernels and the few torch ops of the world model share one stream, so they are ordered
         self.solver.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
         self.B, self.T, self.N = scenes.B, scenes.T, scenes.N
-        if plan is not None:
+        if planner is not None:
+            if plan is not None or plan_len is not None:
+                raise ValueError("planner computes the global plans: plan / plan_len cannot be given as well")
+            if world is None or traj_params is None or goal is None:
+                raise ValueError("planner needs world, traj_params and goal [B,2]")
+        if plan is not None or planner is not None:
             # Plan mode: every robot is solved with the horizon its own trajectorized path gives it (smpc_format_batch.n_poses
             # -> T_scene). The arrays are sized for the longest one: a path of exactly max_poses = round(max_time / dt)
             # poses is not cut by format_to_optimize (src/optimizer.cpp:491-497) and so has one step more than the longer,
@@ -172,7 +188,7 @@ class BatchEpisode:
         self._init_grid(od_indexes, od_origin, od_resolution, od_distances, obstacles_from_costmap, obstacle_min_cost,
                         unknown_is_obstacle, distances=metrics is not None)
         self._init_memory()
-        self._init_plan(plan, plan_len, traj_params, plan_window)
+        self._init_plan(plan, plan_len, traj_params, plan_window, planner, goal)
         self._init_solve(order_hint, scene_params)
         self._init_metrics(metrics, goal, plan, plan_len)
         self._init_crowd(crowd, person_waypoints, person_n_waypoints, person_speed, person_groups, crowd_groups)
@@ -180,6 +196,8 @@ class BatchEpisode:
         self.graph = None
         self.gstream = None
         self.ticks = 0
+        if planner is not None:
+            self.replan()
 
     # -- construction, by concern: device buffers first, then (_bind) the structs that point into them -----------------
     def _upload(self, a, dtype):
@@ -274,15 +292,36 @@ class BatchEpisode:
         self.T_scene = self.torch.full((B,), T, dtype=i32, device=self.dev)         # horizon of every robot this tick
         self.max_poses = int(np.round(np.float32(self.params.max_time) / np.float32(self.params.time_step)))
 
-    def _init_plan(self, plan, plan_len, traj_params, plan_window):
+    def _init_planner(self, planner, goal):
+        """The goal fields of the robots' distinct goals, computed once, and the buffers every (re)plan is walked into."""
+        B, i32 = self.B, self.torch.int32
+        goal = np.ascontiguousarray(goal, np.float64)
+        assert goal.shape == (B, 2), "goal [B,2]"
+        goals, robot_goal = np.unique(goal, axis=0, return_inverse=True)
+        G = goals.shape[0]
+        self.plan_goals = self._upload(goals, np.float64)                              # [G,2]
+        self.robot_goal = self._upload(np.asarray(robot_goal).reshape(B), np.int32)    # [B]
+        self.goal_field = self.torch.empty((G, self.world.cells_y, self.world.cells_x), dtype=i32, device=self.dev)  # uint32 bits
+        self.goal_status = self._zeros(G, dtype=i32)
+        gf = point(BatchSolver.goal_field_c(planner, G, self.world.cells_x, self.world.cells_y, True, self.resolution, 1),
+                   {"world": self.world_map, "world_origin": self.world_origin, "goal": self.plan_goals})
+        self.solver.goal_field_device(gf, self.goal_field.data_ptr(), self.goal_status.data_ptr())
+        self.plan_error = self._zeros(B, dtype=i32)
+        return self._zeros(B, planner.max_poses, 2), self._zeros(B, dtype=i32)
+
+    def _init_plan(self, plan, plan_len, traj_params, plan_window, planner=None, goal=None):
         """The global plans with the trajectorizer's (and the plan window's) outputs, or the rows of the arc stand-in."""
         B, i32 = self.B, self.torch.int32
         self.traj = traj_params
+        self.planner = planner
         self.plan, self.plan_window, self.rows = None, None, self.T + 1
-        if plan is not None:
+        if plan is not None or planner is not None:
             assert traj_params is not None and traj_params.max_steps + 1 >= self.T + 1
-            self.plan = self._upload(plan, np.float64)
-            self.plan_len = self._upload(plan_len, np.int32)
+            if planner is not None:
+                self.plan, self.plan_len = self._init_planner(planner, goal)
+            else:
+                self.plan = self._upload(plan, np.float64)
+                self.plan_len = self._upload(plan_len, np.int32)
             self.rows = traj_params.max_steps + 1
             self.traj_n = self._zeros(B, dtype=i32)
             self.traj_err = self._zeros(B, dtype=i32)
@@ -365,6 +404,11 @@ class BatchEpisode:
                                                                self.resolution, 1, self.outside_cost, force),
                                    {"world": self.world_map, "world_origin": self.world_origin, "pose": self.pose})
                       for force in (False, True)}
+        if self.planner is not None:
+            c.extract = point(BatchSolver.extract_plan_c(self.planner, B, int(self.plan_goals.shape[0]), self.world.cells_x,
+                                                         self.world.cells_y, True, self.resolution, 1),
+                              {"world": self.world_map, "world_origin": self.world_origin, "field": self.goal_field,
+                               "goal": self.plan_goals, "robot_goal": self.robot_goal, "pose": self.pose})
         if planned:
             L = int(self.plan.shape[1])
             c.traj = point(BatchSolver.trajectorize_c(self.traj, B, L, 1),
@@ -442,6 +486,19 @@ class BatchEpisode:
         self.solver.local_costmap_device(self._c.roll[self._force_roll], self.costmap_cell.data_ptr(), self.costmap.data_ptr(),
                                          self.costmap_origin.data_ptr(), self.costmap_moved.data_ptr())
         self._force_roll = False
+
+    def replan(self):
+        """Every robot's plan again, from its current pose down its goal's field, into the same self.plan / self.plan_len /
+        self.plan_error; the plan window starts at the head of the new plans. Between ticks; never inside a captured one."""
+        if self.planner is None:
+            raise ValueError("this episode was built without planner")
+        torch = self.torch
+        if self.gstream is not None and torch.cuda.current_stream(self.dev) != self.gstream:
+            with torch.cuda.stream(self.gstream):  # after capture_graph the library's handle lives on the capture stream
+                return self.replan()
+        self.solver.extract_plan_device(self._c.extract, self.plan.data_ptr(), self.plan_len.data_ptr(), self.plan_error.data_ptr())
+        if self.plan_window is not None:
+            self.plan_start.zero_()
 
     def _host(self, *names, **renamed) -> dict:
         """Host copies of device buffers for a TickRecord: {name: self.<name>} and {key: self.<attribute>}."""

@@ -87,6 +87,33 @@ class CrowdGroupParams:
 
 
 @dataclass
+class GlobalPlanParams:
+    """Global plans on a world map (include/smpc_global_plan.h): what entering a cell costs, w = neutral_cost + cost_weight *
+    cost (integers: a goal field is exact), which cells are passable (cost < lethal_min_cost, and 255 with allow_unknown),
+    the rows of a plan (max_poses) and how many path cells lie between two poses (stride)."""
+    neutral_cost: int = 50
+    cost_weight: int = 1
+    lethal_min_cost: int = 253
+    allow_unknown: bool = False
+    max_poses: int = 400
+    stride: int = 1
+
+    def __post_init__(self):
+        if self.neutral_cost < 1 or self.cost_weight < 0 or self.neutral_cost + 255 * self.cost_weight > 65535:
+            raise ValueError("GlobalPlanParams: neutral_cost >= 1, cost_weight >= 0 and neutral_cost + 255 * cost_weight <= 65535")
+        if not 0 <= self.lethal_min_cost <= 255:
+            raise ValueError(f"GlobalPlanParams.lethal_min_cost must be 0..255, got {self.lethal_min_cost}")
+        if self.max_poses < 2 or self.stride < 1:
+            raise ValueError("GlobalPlanParams: max_poses >= 2 and stride >= 1")
+
+    def world_supported(self, cells_x: int, cells_y: int) -> bool:
+        """Does the library take a world of this size with these costs (include/smpc_global_plan.h's two
+        SMPC_ERR_UNSUPPORTED)? Potentials are 32 bits: no path may cost 2^32 - 1 (the marker of an unreachable cell) or more."""
+        cells = int(cells_x) * int(cells_y)
+        return cells < 2 ** 31 and cells * 7 * (self.neutral_cost + 255 * self.cost_weight) < 2 ** 32 - 1
+
+
+@dataclass
 class OptimizerParams:
     # optimizer.* (src/optimizer.cpp:26-55, 76-83)
     linear_solver_type: str = "SPARSE_NORMAL_CHOLESKY"

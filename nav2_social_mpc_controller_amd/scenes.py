@@ -509,3 +509,25 @@ def scenes_in_world(params: OptimizerParams, world: World, B: int, N: int, seed:
     sc.costmap_shared = False
     sc.validate(sc.init_params.shape[1])
     return sc
+
+
+def world_goals(world: World, start_xy: np.ndarray, seed: int = 0x5EED0005, margin: float = 1.0, min_dist: float = 3.0,
+                tries: int = 32) -> np.ndarray:
+    """goal [B,2]: where each robot of start_xy [B,2] is sent on `world` (BatchEpisode(planner=..., goal=...)): the first of
+    `tries` candidates, uniform over the floor at least `margin` from its border, that lies on a free cell (cost 0) at least
+    min_dist from the robot's start; without one, the centre of the free cell nearest the floor's centre. A pure function
+    of its arguments through `uniform` (fields 1 and 2, keyed by the robot's index)."""
+    start_xy = np.asarray(start_xy, np.float64).reshape(-1, 2)
+    ids = np.arange(start_xy.shape[0], dtype=np.int64)
+    res, Hx, Hy = world.resolution, world.cells_x, world.cells_y
+    x = world.origin[0] + margin + uniform(seed, ids, 1, tries) * (Hx * res - 2.0 * margin)    # [B,tries]
+    y = world.origin[1] + margin + uniform(seed, ids, 2, tries) * (Hy * res - 2.0 * margin)
+    ci = np.clip(np.floor((x - world.origin[0]) / res).astype(np.int64), 0, Hx - 1)
+    cj = np.clip(np.floor((y - world.origin[1]) / res).astype(np.int64), 0, Hy - 1)
+    ok = (world.map[cj, ci] == 0) & (np.hypot(x - start_xy[:, 0:1], y - start_xy[:, 1:2]) >= min_dist)
+    jj, ii = np.meshgrid(np.arange(Hy), np.arange(Hx), indexing="ij")
+    flat = int(np.argmin(np.where(world.map == 0, (ii + 0.5 - 0.5 * Hx) ** 2 + (jj + 0.5 - 0.5 * Hy) ** 2, np.inf)))
+    pick = np.argmax(ok, axis=1)[:, None]
+    gx = np.where(ok.any(axis=1), np.take_along_axis(x, pick, 1)[:, 0], world.origin[0] + ((flat % Hx) + 0.5) * res)
+    gy = np.where(ok.any(axis=1), np.take_along_axis(y, pick, 1)[:, 0], world.origin[1] + ((flat // Hx) + 0.5) * res)
+    return np.ascontiguousarray(np.stack([gx, gy], axis=1))

@@ -11,12 +11,13 @@ import os
 
 import numpy as np
 
-from . import _abi, _abi_local_costmap
+from . import _abi, _abi_global_plan, _abi_local_costmap
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
+from ._abi_global_plan import SmpcExtractPlanIn, SmpcGoalFieldIn
 from ._abi_local_costmap import SmpcLocalCostmapIn
-from .params import CrowdGroupParams, CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams
+from .params import CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, TrajectorizerParams
 from .scenes import SceneBatch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -53,7 +54,8 @@ def load_library():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_abi.FUNCTIONS, **_abi.FIXED_SHAPE_FUNCTIONS, **_abi_local_costmap.FUNCTIONS}.items():
+    for name, (restype, argtypes) in {**_abi.FUNCTIONS, **_abi.FIXED_SHAPE_FUNCTIONS, **_abi_local_costmap.FUNCTIONS,
+                                       **_abi_global_plan.FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -651,6 +653,82 @@ class BatchSolver:
         the handle's stream."""
         assert lc.on_device == 1
         self._call("smpc_local_costmap_batch", lc, cell_ptr, costmap_ptr, origin_ptr, moved_ptr or None)
+
+    # -- global plans on a world map (smpc_goal_field_batch / smpc_extract_plan_batch, include/smpc_global_plan.h) ------
+    @staticmethod
+    def _plan_world_c(st, gp: GlobalPlanParams, world_x: int, world_y: int, world_shared: bool, resolution: float, on_device: int):
+        """The members SmpcGoalFieldIn and SmpcExtractPlanIn share."""
+        st.on_device, st.world_x, st.world_y, st.world_shared = int(on_device), int(world_x), int(world_y), 1 if world_shared else 0
+        st.resolution = float(resolution)
+        st.cost.neutral_cost, st.cost.cost_weight = int(gp.neutral_cost), int(gp.cost_weight)
+        st.cost.lethal_min_cost, st.cost.allow_unknown = int(gp.lethal_min_cost), 1 if gp.allow_unknown else 0
+        return st
+
+    @staticmethod
+    def goal_field_c(gp: GlobalPlanParams, G: int, world_x: int, world_y: int, world_shared: bool, resolution: float,
+                     on_device: int) -> SmpcGoalFieldIn:
+        return BatchSolver._plan_world_c(SmpcGoalFieldIn(G=int(G)), gp, world_x, world_y, world_shared, resolution, on_device)
+
+    @staticmethod
+    def extract_plan_c(gp: GlobalPlanParams, B: int, G: int, world_x: int, world_y: int, world_shared: bool, resolution: float,
+                       on_device: int) -> SmpcExtractPlanIn:
+        st = SmpcExtractPlanIn(B=int(B), G=int(G), L=int(gp.max_poses), stride=int(gp.stride))
+        return BatchSolver._plan_world_c(st, gp, world_x, world_y, world_shared, resolution, on_device)
+
+    @staticmethod
+    def _plan_world_arrays(world, world_origin, G: int):
+        world = np.ascontiguousarray(world, np.uint8)
+        shared = world.ndim == 2
+        world_origin = np.ascontiguousarray(world_origin, np.float64).reshape(-1, 2)
+        assert shared or world.shape[0] == G
+        assert world_origin.shape == ((1, 2) if shared else (G, 2))
+        return world, world_origin, shared
+
+    def goal_field(self, gp: GlobalPlanParams, world: np.ndarray, world_origin: np.ndarray, resolution: float, goal: np.ndarray):
+        """The goal fields of G goal points (host arrays): world [Hy,Hx] uint8 with world_origin [2] (one map shared by all
+        goals) or [G,Hy,Hx] with [G,2], goal [G,2]. Returns (field [G,Hy,Hx] uint32: the exact cost-to-go of every cell,
+        0xFFFFFFFF where there is none; status [G] int32: 0 ok, 1 the goal has no cell, 2 its cell is impassable)."""
+        goal = np.ascontiguousarray(goal, np.float64).reshape(-1, 2)
+        G = goal.shape[0]
+        world, world_origin, shared = self._plan_world_arrays(world, world_origin, G)
+        gf = point(self.goal_field_c(gp, G, world.shape[-1], world.shape[-2], shared, resolution, 0),
+                   {"world": world, "world_origin": world_origin, "goal": goal})
+        field, status = np.zeros((G,) + world.shape[-2:], np.uint32), np.zeros(G, np.int32)
+        self._call("smpc_goal_field_batch", gf, _ptr(field), _ptr(status))
+        return field, status
+
+    def goal_field_device(self, gf: SmpcGoalFieldIn, field_ptr: int, status_ptr: int = 0):
+        """Device pointers in gf (on_device == 1) and for field and status (0: none). The kernel runs on the handle's
+        stream; the call waits for it (one word is read back): not for a captured tick."""
+        assert gf.on_device == 1
+        self._call("smpc_goal_field_batch", gf, field_ptr, status_ptr or None)
+
+    def extract_plan(self, gp: GlobalPlanParams, world: np.ndarray, world_origin: np.ndarray, resolution: float, field: np.ndarray,
+                     goal: np.ndarray, robot_goal: np.ndarray, pose: np.ndarray, plan: np.ndarray = None):
+        """The plans of B robots down their goals' fields (host arrays): field [G,Hy,Hx] uint32 (goal_field), goal [G,2],
+        robot_goal [B] int32, pose [B,3]; world as for goal_field. plan [B,gp.max_poses,2]: the rows before the call (default
+        NaN): the call writes the first plan_len rows of each robot and leaves the others. Returns (plan, plan_len [B]
+        int32, error [B] int32: enum smpc_plan_error, _abi_global_plan.PLAN_ERRORS)."""
+        goal = np.ascontiguousarray(goal, np.float64).reshape(-1, 2)
+        field = np.ascontiguousarray(field, np.uint32)
+        robot_goal = np.ascontiguousarray(robot_goal, np.int32)
+        pose = np.ascontiguousarray(pose, np.float64)
+        B, G = pose.shape[0], goal.shape[0]
+        world, world_origin, shared = self._plan_world_arrays(world, world_origin, G)
+        assert field.shape == (G,) + world.shape[-2:] and robot_goal.shape == (B,) and pose.shape == (B, 3)
+        plan = np.full((B, gp.max_poses, 2), np.nan) if plan is None else np.array(plan, dtype=np.float64, order="C")
+        assert plan.shape == (B, gp.max_poses, 2)
+        ep = point(self.extract_plan_c(gp, B, G, world.shape[-1], world.shape[-2], shared, resolution, 0),
+                   {"world": world, "world_origin": world_origin, "field": field, "goal": goal, "robot_goal": robot_goal, "pose": pose})
+        plan_len, error = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        self._call("smpc_extract_plan_batch", ep, _ptr(plan), _ptr(plan_len), _ptr(error))
+        return plan, plan_len, error
+
+    def extract_plan_device(self, ep: SmpcExtractPlanIn, plan_ptr: int, plan_len_ptr: int, error_ptr: int = 0):
+        """Device pointers in ep (on_device == 1) and for plan, plan_len and error (0: none); asynchronous on the handle's
+        stream."""
+        assert ep.on_device == 1
+        self._call("smpc_extract_plan_batch", ep, plan_ptr, plan_len_ptr, error_ptr or None)
 
     # -- warm start / input formatting (SURVEY §8 row f2): format_to_optimize + TrajectoryMemory for B scenes -----
     def format_to_optimize(self, path: np.ndarray, cmds: np.ndarray, speed: np.ndarray, memory: dict,

@@ -4,12 +4,15 @@ of a batch whose solve takes each robot's own critic weights and velocity bounds
 BatchEpisode(scene_params=...)); the device scores every robot as it drives (BatchEpisode(metrics=...)), and one line of
 summarize_metrics means is printed per set. Nothing but the final [B,24] metrics rows leaves the device.
 
-    python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]]
+    python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]] [--world-plans]
 
 --reactive: the persons are a reactive crowd (BatchEpisode(crowd=CrowdParams()), waypoints from scenes.crowd_waypoints)
 instead of walking straight on with constant velocity. --groups (with --reactive): half of the walking persons go in pairs
 and triples (scenes.crowd_groups -> BatchEpisode(person_groups=...)): companions share their waypoints and are held
 together by the Social Force Model's group force.
+--world-plans: the robots drive on one world map (scenes.make_world, 20 m x 20 m) with rolling local costmaps, each to a seeded
+goal of its own (scenes.world_goals) along a plan walked down the goal's field (BatchEpisode(world=, planner=, goal=): a pose
+every second path cell, pruned by the plan window as the robot advances) instead of along an arc from its start pose.
 """
 import argparse
 import os
@@ -40,6 +43,7 @@ def main():
     ap.add_argument("--plan-poses", type=int, default=120, help="plan length in poses of 0.05 m (120: a 6 m drive)")
     ap.add_argument("--reactive", action="store_true", help="persons react: Social Force Model crowd with seeded waypoints")
     ap.add_argument("--groups", action="store_true", help="with --reactive: half of the walking persons go in pairs and triples")
+    ap.add_argument("--world-plans", action="store_true", help="one world map, seeded goals, plans from the world's goal fields")
     a = ap.parse_args()
     if a.groups and not a.reactive:
         ap.error("--groups needs --reactive")
@@ -47,17 +51,28 @@ def main():
     import numpy as np
 
     from nav2_social_mpc_controller_amd.episode import BatchEpisode, arc_plans
-    from nav2_social_mpc_controller_amd.params import CrowdParams, MetricsParams, OptimizerParams, TrajectorizerParams, scene_param_rows
-    from nav2_social_mpc_controller_amd.scenes import crowd_groups, crowd_waypoints, make_scenes, uniform
+    from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, TrajectorizerParams,
+                                                       scene_param_rows)
+    from nav2_social_mpc_controller_amd.scenes import (crowd_groups, crowd_waypoints, make_scenes, make_world, scenes_in_world, uniform,
+                                                       world_goals)
     from nav2_social_mpc_controller_amd.solver import summarize_metrics
 
     prm = OptimizerParams.readme()
     sets = parameter_sets(prm)
     S, n = len(sets), a.scenes
-    one = make_scenes(prm, n, a.agents, map_cells=400)                      # 20 m maps: the drive stays inside
+    if a.world_plans:
+        world = make_world(400, 400, 0.05)                                  # one 20 m floor for everybody
+        one = scenes_in_world(prm, world, n, a.agents, margin=3.0)
+    else:
+        one = make_scenes(prm, n, a.agents, map_cells=400)                  # 20 m maps: the drive stays inside
     sc = one.select(np.tile(np.arange(n), S))                               # every set sees the same scenes
     w_ref = np.tile((uniform(0x5EED0001, np.arange(n), 6)[:, 0] * 2.0 - 1.0) * 0.6, S)
-    plan, plan_len = arc_plans(sc.pose0, 0.1 * w_ref, L=a.plan_poses)
+    if a.world_plans:                                                       # every set drives to the same goals
+        plans = dict(world=world, planner=GlobalPlanParams(stride=2), goal=np.tile(world_goals(world, one.pose0[:, :2]), (S, 1)),
+                     plan_window=(4.0, 10.0))
+    else:
+        plan, plan_len = arc_plans(sc.pose0, 0.1 * w_ref, L=a.plan_poses)
+        plans = dict(plan=plan, plan_len=plan_len)
     rows = scene_param_rows(list(sets.values()), np.repeat(np.arange(S), n))
     tp = TrajectorizerParams(desired_linear_vel=prm.desired_linear_vel, max_time=prm.max_time, time_step=prm.time_step)
     crowd = {}
@@ -67,8 +82,8 @@ def main():
             gid, wp, n_wp = crowd_groups(one)
             crowd["person_groups"] = np.tile(gid, (S, 1))
         crowd.update(crowd=CrowdParams(), person_waypoints=np.tile(wp, (S, 1, 1, 1)), person_n_waypoints=np.tile(n_wp, (S, 1)))
-    ep = BatchEpisode(prm, sc, w_ref, plan=plan, plan_len=plan_len, traj_params=tp, fov_angle=np.pi / 4,
-                      obstacles_from_costmap=True, scene_params=rows, metrics=MetricsParams(), **crowd)
+    ep = BatchEpisode(prm, sc, w_ref, traj_params=tp, fov_angle=np.pi / 4, obstacles_from_costmap=True, scene_params=rows,
+                      metrics=MetricsParams(), **plans, **crowd)
     ep.capture_graph()
     for _ in range(a.ticks):
         ep.replay()
