@@ -15,7 +15,7 @@
 //   smpc_stage_kernel<W>     the staging pass of the people block (smpc_stage_kernel.hpp);
 //   the probe kernels (smpc_probes.hpp);
 //   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window,
-//   metrics, crowd, local costmap, global plan).
+//   metrics, crowd, local costmap, global plan, visibility).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -36,6 +36,8 @@
 #include "smpc_local_costmap.hpp"
 #include "../../include/smpc_local_costmap.h"
 #include "smpc_global_plan.hpp"
+#include "smpc_visibility.hpp"
+#include "../../include/smpc_visibility.h"
 
 extern "C" {
 
@@ -746,6 +748,43 @@ int smpc_extract_plan_batch(smpc_handle* h, const smpc_extract_plan_in* in, doub
     const size_t per_block = smpc::kEpThreads / 8;
     SMPC_TRY(st.timed([&] {
       hipLaunchKernelGGL(smpc::smpc_extract_plan_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kEpThreads), 0, h->stream, p);
+      return SMPC_OK;
+    }));
+  }
+  return st.finish();
+}
+
+int smpc_visible_people_batch(smpc_handle* h, const smpc_visibility_in* in, double* visible, int32_t* visible_count, uint8_t* seen) {
+  if (!h || !in || !visible || !visible_count) { set_error("null handle / input / visible / visible_count"); return SMPC_ERR_INVALID_ARG; }
+  if (!in->world || !in->world_origin || !in->robot_pose || !in->people || !in->count) { set_error("null input array"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B < 0 || in->Np < 1 || in->world_x < 1 || in->world_y < 1) { set_error("bad B, Np < 1 or a non-positive world size"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) { set_error("resolution must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->max_range) || !(in->max_range > 0.0)) { set_error("max_range must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  // a ray of at most 32769 cells per axis: every product of the column rule fits 32 unsigned bits
+  if (!(in->max_range / in->resolution <= 32768.0)) { set_error("max_range / resolution must not exceed 32768 cells"); return SMPC_ERR_UNSUPPORTED; }
+  const int64_t cells = (int64_t)in->world_x * in->world_y;
+  if (cells >= (int64_t)1 << 31) { set_error("a world of 2^31 cells or more is not supported"); return SMPC_ERR_UNSUPPORTED; }
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::VisibilityParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.B = in->B; p.Np = in->Np; p.world_x = in->world_x; p.world_y = in->world_y; p.world_shared = in->world_shared ? 1 : 0;
+  p.occ.min_cost = in->occlusion_min_cost; p.occ.unknown = in->unknown_occludes ? 1u : 0u;
+  p.resolution = in->resolution; p.max_range = in->max_range;
+  const size_t B = in->B, Np = in->Np, nworld = in->world_shared ? 1 : B;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.world, in->world, nworld * (size_t)cells));
+  SMPC_TRY(st.in(p.world_origin, in->world_origin, nworld * 2));
+  SMPC_TRY(st.in(p.robot_pose, in->robot_pose, B * 3));
+  SMPC_TRY(st.in(p.people, in->people, B * Np * 5));
+  SMPC_TRY(st.in(p.count, in->count, B));
+  // read and written: the rows and flags the kernel leaves alone keep the caller's bytes on the way through device memory too
+  SMPC_TRY(st.inout(p.visible, visible, B * Np * 5));
+  SMPC_TRY(st.out(p.visible_count, visible_count, B));
+  SMPC_TRY(st.inout(p.seen, seen, B * Np));
+  if (B > 0) {
+    const size_t per_block = smpc::kVisThreads / 64;
+    SMPC_TRY(st.timed([&] {
+      hipLaunchKernelGGL(smpc::smpc_visible_people_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kVisThreads), 0, h->stream, p);
       return SMPC_OK;
     }));
   }

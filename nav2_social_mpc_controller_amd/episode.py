@@ -6,6 +6,7 @@
     format_to_optimize + TrajectoryMemory   (src/optimizer.cpp:172-190, 484-551)  -> smpc_format_to_optimize_batch
     ObstacleDistance grid (optional, once)   (src/optimizer.cpp:593-605, 'TODO')   -> smpc_obstacle_distance_batch
     rolling local costmap (optional)         (Nav2's LayeredCostmap::updateMap)    -> smpc_local_costmap_batch
+    line-of-sight filter (optional)          (none: the library's own rule)        -> smpc_visible_people_batch
     global plans (optional, at the start and   (Nav2's planner server; the library's -> smpc_goal_field_batch,
     on replan(), never inside a tick)          own integer cost rule)                 smpc_extract_plan_batch
     project_people                           (src/optimizer.cpp:554-728)           -> smpc_project_people_batch
@@ -41,7 +42,7 @@ import numpy as np
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
 from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, TrajectorizerParams,
-                     check_scene_param_rows)
+                     VisibilityParams, check_scene_param_rows)
 from .scenes import SceneBatch, World
 from .solver import BatchSolver, point, set_od_grid
 
@@ -85,6 +86,10 @@ class TickRecord:
     costmap_cell: np.ndarray = None    # [B,2] world cell of every window's cell (0,0)
     costmap_origin: np.ndarray = None  # [B,2]
     costmap_moved: np.ndarray = None   # [B] smpc_local_costmap_batch's moved
+    # the line-of-sight filter's outputs (BatchEpisode(visibility=...)): what the tick's people_to_status read
+    person_seen: np.ndarray = None     # [B,Np] uint8 enum smpc_seen_code (flags from person_count[b] on: not written)
+    seen_count: np.ndarray = None      # [B]
+    seen_persons: np.ndarray = None    # [B,Np,5] (rows from seen_count[b] on: not written)
 
 
 class BatchEpisode:
@@ -96,7 +101,8 @@ class BatchEpisode:
     PER_GRID = ("od_indexes", "od_origin", "od_distances")
     # the same object for every shard
     FORWARDED = ("od_resolution", "device", "traj_params", "fov_angle", "order_hint", "plan_window", "obstacles_from_costmap",
-                 "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost", "planner")
+                 "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost", "planner",
+                 "visibility")
 
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
@@ -107,7 +113,7 @@ class BatchEpisode:
                  crowd: CrowdParams = None, person_waypoints: np.ndarray = None, person_n_waypoints: np.ndarray = None,
                  person_speed: np.ndarray = None, person_groups: np.ndarray = None,
                  crowd_groups: CrowdGroupParams = None, world: World = None, outside_cost: int = 255,
-                 planner: GlobalPlanParams = None):
+                 planner: GlobalPlanParams = None, visibility: VisibilityParams = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -160,7 +166,14 @@ class BatchEpisode:
         plan is walked down its field from its start pose (smpc_extract_plan_batch) into self.plan [B,planner.max_poses,2],
         self.plan_len and self.plan_error [B] (enum smpc_plan_error; a robot with an error other than TRUNCATED has
         plan_len 0 and gets no command). From there on this is the episode that was handed these arrays as `plan`.
-        replan() walks again from the current poses. None: nothing is allocated and nothing is launched."""
+        replan() walks again from the current poses. None: nothing is allocated and nothing is launched.
+        visibility: the robots perceive only the persons they have in line of sight on the world map
+        (include/smpc_visibility.h): needs `world`. Every tick, after the roll and the plan stage and directly before
+        people_to_status, smpc_visible_people_batch compacts the persons within visibility.max_range whose sight line no
+        cell of the world occludes into self.seen_persons [B,Np,5] / self.seen_count [B] (with self.person_seen [B,Np]
+        uint8, enum smpc_seen_code), and people_to_status reads those in place of self.persons / self.person_count. The
+        crowd step, the metrics and the world's move keep the true persons. None: nothing is allocated and nothing is
+        launched."""
         import torch
 
         self.torch = torch
@@ -175,6 +188,8 @@ class BatchEpisode:
                 raise ValueError("planner computes the global plans: plan / plan_len cannot be given as well")
             if world is None or traj_params is None or goal is None:
                 raise ValueError("planner needs world, traj_params and goal [B,2]")
+        if visibility is not None and world is None:
+            raise ValueError("visibility needs world: the sight lines run over the world map")
         if plan is not None or planner is not None:
             # Plan mode: every robot is solved with the horizon its own trajectorized path gives it (smpc_format_batch.n_poses
             # -> T_scene). The arrays are sized for the longest one: a path of exactly max_poses = round(max_time / dt)
@@ -192,6 +207,7 @@ class BatchEpisode:
         self._init_solve(order_hint, scene_params)
         self._init_metrics(metrics, goal, plan, plan_len)
         self._init_crowd(crowd, person_waypoints, person_n_waypoints, person_speed, person_groups, crowd_groups)
+        self._init_visibility(visibility)
         self._bind()
         self.graph = None
         self.gstream = None
@@ -392,6 +408,18 @@ class BatchEpisode:
             self.person_groups = self._upload(person_groups, np.int32)
             self.crowd_group_params = crowd_groups if crowd_groups is not None else CrowdGroupParams()
 
+    def _init_visibility(self, visibility):
+        """What the line-of-sight filter writes every tick: fixed addresses, people_to_status reads the first two."""
+        self.visibility = visibility
+        if visibility is None:
+            return
+        if not visibility.supported(self.resolution):
+            raise ValueError("visibility.max_range / resolution exceeds 32768 cells")
+        B, Np = self.B, int(self.persons.shape[1])
+        self.seen_persons = self._zeros(B, Np, 5)
+        self.seen_count = self._zeros(B, dtype=self.torch.int32)
+        self.person_seen = self._zeros(B, Np, dtype=self.torch.uint8)
+
     def _bind(self):
         """Every struct a tick hands to the library, built once: every buffer the kernels read keeps its address from tick
         to tick (the state is updated in place), and the stream lives in the solver's handle, so nothing here changes
@@ -421,6 +449,12 @@ class BatchEpisode:
             c.traj_out = point(SmpcTrajectorizeOut(), {"path": self.plan_path, "cmds": self.plan_cmds, "cmds_vy": self.traj_vy,
                                                        "n_poses": self.traj_n, "error": self.traj_err})
         c.people = point(SmpcPeopleBatch(B=B, Np=Np, N=N, on_device=1), {"people": self.persons, "count": self.person_count})
+        if self.visibility is not None:  # the controller gets the persons in line of sight; the world keeps them all
+            c.visibility = point(BatchSolver.visibility_c(self.visibility, B, Np, self.world.cells_x, self.world.cells_y, True,
+                                                          self.resolution, 1),
+                                 {"world": self.world_map, "world_origin": self.world_origin, "robot_pose": self.pose,
+                                  "people": self.persons, "count": self.person_count})
+            point(c.people, {"people": self.seen_persons, "count": self.seen_count})
         if self.fov_angle is not None:
             point(c.people, {"robot_pose": self.pose, "costmap_origin": self.costmap_origin})
             c.people.fov_angle, c.people.costmap_shared = float(self.fov_angle), 1 if self.costmap_shared else 0
@@ -540,6 +574,11 @@ class BatchEpisode:
             rec.update(self._host("persons", "person_count"))
             if crowd:
                 rec.update(self._host(cursor_before="person_cursor"))
+        if self.visibility is not None:  # the persons in line of sight, directly in front of the filter that reads them
+            s.visible_people_device(c.visibility, self.seen_persons.data_ptr(), self.seen_count.data_ptr(), self.person_seen.data_ptr())
+            timed("visibility")
+            if record:
+                rec.update(self._host("person_seen", "seen_count", "seen_persons"))
         # 0. field-of-view filter + people_to_status
         s.people_to_status_device(c.people, self.people.data_ptr(), self.has_people.data_ptr())
         timed("people")

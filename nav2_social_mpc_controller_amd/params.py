@@ -114,6 +114,26 @@ class GlobalPlanParams:
 
 
 @dataclass
+class VisibilityParams:
+    """The line-of-sight filter of the people a robot perceives on a world map (include/smpc_visibility.h): the detector's
+    range in metres, which cells block sight (cost >= occlusion_min_cost, and 255 only with unknown_occludes)."""
+    max_range: float = 10.0
+    occlusion_min_cost: int = 254
+    unknown_occludes: bool = False
+
+    def __post_init__(self):
+        if not (np.isfinite(self.max_range) and self.max_range > 0.0):
+            raise ValueError(f"VisibilityParams.max_range must be finite and > 0, got {self.max_range}")
+        if not 0 <= self.occlusion_min_cost <= 255:
+            raise ValueError(f"VisibilityParams.occlusion_min_cost must be 0..255, got {self.occlusion_min_cost}")
+
+    def supported(self, resolution: float) -> bool:
+        """Does the library take this range on a map of this resolution (include/smpc_visibility.h's SMPC_ERR_UNSUPPORTED)?
+        A ray may span at most 32768 cells: max_range / resolution <= 32768, the quotient of the two doubles."""
+        return bool(np.float64(self.max_range) / np.float64(resolution) <= 32768.0)
+
+
+@dataclass
 class OptimizerParams:
     # optimizer.* (src/optimizer.cpp:26-55, 76-83)
     linear_solver_type: str = "SPARSE_NORMAL_CHOLESKY"

@@ -11,13 +11,15 @@ import os
 
 import numpy as np
 
-from . import _abi, _abi_global_plan, _abi_local_costmap
+from . import _abi, _abi_global_plan, _abi_local_costmap, _abi_visibility
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
 from ._abi_global_plan import SmpcExtractPlanIn, SmpcGoalFieldIn
 from ._abi_local_costmap import SmpcLocalCostmapIn
-from .params import CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, TrajectorizerParams
+from ._abi_visibility import SmpcVisibilityIn
+from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, TrajectorizerParams,
+                     VisibilityParams)
 from .scenes import SceneBatch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -55,7 +57,7 @@ def load_library():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_abi.FUNCTIONS, **_abi.FIXED_SHAPE_FUNCTIONS, **_abi_local_costmap.FUNCTIONS,
-                                       **_abi_global_plan.FUNCTIONS}.items():
+                                       **_abi_global_plan.FUNCTIONS, **_abi_visibility.FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -729,6 +731,44 @@ class BatchSolver:
         stream."""
         assert ep.on_device == 1
         self._call("smpc_extract_plan_batch", ep, plan_ptr, plan_len_ptr, error_ptr or None)
+
+    # -- line-of-sight filter of the people (smpc_visible_people_batch, include/smpc_visibility.h) -----------------------
+    @staticmethod
+    def visibility_c(vp: VisibilityParams, B: int, Np: int, world_x: int, world_y: int, world_shared: bool, resolution: float,
+                     on_device: int) -> SmpcVisibilityIn:
+        return SmpcVisibilityIn(B=int(B), Np=int(Np), on_device=int(on_device), world_x=int(world_x), world_y=int(world_y),
+                                world_shared=1 if world_shared else 0, occlusion_min_cost=int(vp.occlusion_min_cost),
+                                unknown_occludes=1 if vp.unknown_occludes else 0, resolution=float(resolution),
+                                max_range=float(vp.max_range))
+
+    def visible_people(self, vp: VisibilityParams, world: np.ndarray, world_origin: np.ndarray, resolution: float,
+                       robot_pose: np.ndarray, people: np.ndarray, count: np.ndarray, visible: np.ndarray = None,
+                       seen: np.ndarray = None):
+        """The persons each of B robots has in line of sight (host arrays): world [Hy,Hx] uint8 with world_origin [2] (one map
+        shared by all robots) or [B,Hy,Hx] with [B,2], robot_pose [B,3], people [B,Np,5], count [B] int32. visible [B,Np,5] /
+        seen [B,Np] uint8: the arrays before the call (default NaN / 0xEE): the call writes the first visible_count rows
+        and the first count flags of each robot and leaves the others. Returns (visible, visible_count [B] int32, seen:
+        _abi_visibility.SEEN_CODES)."""
+        robot_pose = np.ascontiguousarray(robot_pose, np.float64)
+        people = np.ascontiguousarray(people, np.float64)
+        count = np.ascontiguousarray(count, np.int32)
+        B, Np = people.shape[0], people.shape[1]
+        world, world_origin, shared = self._plan_world_arrays(world, world_origin, B)
+        assert people.shape == (B, Np, 5) and robot_pose.shape == (B, 3) and count.shape == (B,)
+        visible = np.full((B, Np, 5), np.nan) if visible is None else np.array(visible, dtype=np.float64, order="C")
+        seen = np.full((B, Np), 0xEE, np.uint8) if seen is None else np.array(seen, dtype=np.uint8, order="C")
+        assert visible.shape == (B, Np, 5) and seen.shape == (B, Np)
+        vi = point(self.visibility_c(vp, B, Np, world.shape[-1], world.shape[-2], shared, resolution, 0),
+                   {"world": world, "world_origin": world_origin, "robot_pose": robot_pose, "people": people, "count": count})
+        visible_count = np.zeros(B, np.int32)
+        self._call("smpc_visible_people_batch", vi, _ptr(visible), _ptr(visible_count), _ptr(seen))
+        return visible, visible_count, seen
+
+    def visible_people_device(self, vi: SmpcVisibilityIn, visible_ptr: int, visible_count_ptr: int, seen_ptr: int = 0):
+        """Device pointers in vi (on_device == 1) and for visible, visible_count and seen (0: none); asynchronous on the
+        handle's stream."""
+        assert vi.on_device == 1
+        self._call("smpc_visible_people_batch", vi, visible_ptr, visible_count_ptr, seen_ptr or None)
 
     # -- warm start / input formatting (SURVEY §8 row f2): format_to_optimize + TrajectoryMemory for B scenes -----
     def format_to_optimize(self, path: np.ndarray, cmds: np.ndarray, speed: np.ndarray, memory: dict,

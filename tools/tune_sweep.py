@@ -4,7 +4,8 @@ of a batch whose solve takes each robot's own critic weights and velocity bounds
 BatchEpisode(scene_params=...)); the device scores every robot as it drives (BatchEpisode(metrics=...)), and one line of
 summarize_metrics means is printed per set. Nothing but the final [B,24] metrics rows leaves the device.
 
-    python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]] [--world-plans]
+    python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]]
+                                [--world-plans [--occlusion [RANGE]]]
 
 --reactive: the persons are a reactive crowd (BatchEpisode(crowd=CrowdParams()), waypoints from scenes.crowd_waypoints)
 instead of walking straight on with constant velocity. --groups (with --reactive): half of the walking persons go in pairs
@@ -13,6 +14,9 @@ together by the Social Force Model's group force.
 --world-plans: the robots drive on one world map (scenes.make_world, 20 m x 20 m) with rolling local costmaps, each to a seeded
 goal of its own (scenes.world_goals) along a plan walked down the goal's field (BatchEpisode(world=, planner=, goal=): a pose
 every second path cell, pruned by the plan window as the robot advances) instead of along an arc from its start pose.
+--occlusion [RANGE] (with --world-plans): the robots perceive only the persons they have in line of sight on that map, within
+RANGE metres (default 10; BatchEpisode(visibility=VisibilityParams(max_range=RANGE))): a person behind a pillar or a wall is
+not planned around until it steps out. The metrics keep scoring the true persons.
 """
 import argparse
 import os
@@ -44,15 +48,19 @@ def main():
     ap.add_argument("--reactive", action="store_true", help="persons react: Social Force Model crowd with seeded waypoints")
     ap.add_argument("--groups", action="store_true", help="with --reactive: half of the walking persons go in pairs and triples")
     ap.add_argument("--world-plans", action="store_true", help="one world map, seeded goals, plans from the world's goal fields")
+    ap.add_argument("--occlusion", type=float, nargs="?", const=10.0, default=None, metavar="RANGE",
+                    help="with --world-plans: line-of-sight filter of the perceived persons, detector range in metres (default 10)")
     a = ap.parse_args()
     if a.groups and not a.reactive:
         ap.error("--groups needs --reactive")
+    if a.occlusion is not None and not a.world_plans:
+        ap.error("--occlusion needs --world-plans")
 
     import numpy as np
 
     from nav2_social_mpc_controller_amd.episode import BatchEpisode, arc_plans
     from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, TrajectorizerParams,
-                                                       scene_param_rows)
+                                                       VisibilityParams, scene_param_rows)
     from nav2_social_mpc_controller_amd.scenes import (crowd_groups, crowd_waypoints, make_scenes, make_world, scenes_in_world, uniform,
                                                        world_goals)
     from nav2_social_mpc_controller_amd.solver import summarize_metrics
@@ -70,6 +78,8 @@ def main():
     if a.world_plans:                                                       # every set drives to the same goals
         plans = dict(world=world, planner=GlobalPlanParams(stride=2), goal=np.tile(world_goals(world, one.pose0[:, :2]), (S, 1)),
                      plan_window=(4.0, 10.0))
+        if a.occlusion is not None:
+            plans["visibility"] = VisibilityParams(max_range=a.occlusion)
     else:
         plan, plan_len = arc_plans(sc.pose0, 0.1 * w_ref, L=a.plan_poses)
         plans = dict(plan=plan, plan_len=plan_len)
