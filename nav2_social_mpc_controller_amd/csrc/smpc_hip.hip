@@ -15,7 +15,7 @@
 //   smpc_stage_kernel<W>     the staging pass of the people block (smpc_stage_kernel.hpp);
 //   the probe kernels (smpc_probes.hpp);
 //   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window,
-//   metrics, crowd, local costmap, global plan, visibility).
+//   metrics, crowd, local costmap, global plan, visibility, nearest agents).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -38,6 +38,8 @@
 #include "smpc_global_plan.hpp"
 #include "smpc_visibility.hpp"
 #include "../../include/smpc_visibility.h"
+#include "smpc_nearest.hpp"
+#include "../../include/smpc_nearest.h"
 
 extern "C" {
 
@@ -788,6 +790,61 @@ int smpc_visible_people_batch(smpc_handle* h, const smpc_visibility_in* in, doub
       return SMPC_OK;
     }));
   }
+  return st.finish();
+}
+
+uint64_t smpc_nearest_workspace_bytes(int32_t A, int32_t grid_x, int32_t grid_y) {
+  if (A < 0 || A > SMPC_NEAREST_MAX_ROWS || grid_x < 1 || grid_y < 1 || (int64_t)grid_x * grid_y > SMPC_NEAREST_MAX_BINS) return 0;
+  const uint64_t words = 2ull * (uint64_t)grid_x * (uint64_t)grid_y + 1ull + (uint64_t)A;
+  return (words * 4ull + 255ull) & ~255ull;
+}
+
+int smpc_nearest_people_batch(smpc_handle* h, const smpc_nearest_in* in, double* people, int32_t* count, int32_t* source) {
+  if (!h || !in || !people || !count) { set_error("null handle / input / people / count"); return SMPC_ERR_INVALID_ARG; }
+  if (!in->robot_pose || (!in->agents && in->A > 0)) { set_error("null robot_pose, or null agents with A > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B < 0 || in->A < 0 || in->Np < 1 || in->grid_x < 1 || in->grid_y < 1) { set_error("bad B or A, Np < 1 or a grid side < 1"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->grid_origin[0]) || !std::isfinite(in->grid_origin[1])) { set_error("grid_origin must be finite"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->bin_size) || !(in->bin_size > 0.0)) { set_error("bin_size must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->max_range) || !(in->max_range > 0.0)) { set_error("max_range must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  {
+    const volatile double least = in->max_range * SMPC_NEAREST_BIN_MARGIN;  // the product of the two doubles, rounded once
+    if (!(in->bin_size >= least)) { set_error("bin_size must be at least max_range * SMPC_NEAREST_BIN_MARGIN"); return SMPC_ERR_INVALID_ARG; }
+  }
+  if (in->Np > SMPC_MAX_AGENTS) { set_error("Np > 64 persons is not supported"); return SMPC_ERR_UNSUPPORTED; }
+  if ((int64_t)in->grid_x * in->grid_y > SMPC_NEAREST_MAX_BINS) { set_error("more than 65536 bins are not supported"); return SMPC_ERR_UNSUPPORTED; }
+  if (in->A > SMPC_NEAREST_MAX_ROWS) { set_error("more than 2^24 agents are not supported"); return SMPC_ERR_UNSUPPORTED; }
+  const uint64_t ws_bytes = smpc_nearest_workspace_bytes(in->A, in->grid_x, in->grid_y);
+  if (in->on_device && (!in->workspace || in->workspace_bytes < ws_bytes)) { set_error("workspace is null or smaller than smpc_nearest_workspace_bytes()"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B == 0) return SMPC_OK;
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::NearestParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.B = in->B; p.Np = in->Np; p.A = in->A; p.grid_x = in->grid_x; p.grid_y = in->grid_y;
+  p.ox = in->grid_origin[0]; p.oy = in->grid_origin[1]; p.bin_size = in->bin_size; p.max_range = in->max_range;
+  const size_t B = in->B, Np = in->Np, A = in->A, G = (size_t)in->grid_x * (size_t)in->grid_y;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.agents, in->agents, A * 5));
+  SMPC_TRY(st.in(p.robot_pose, in->robot_pose, B * 3));
+  SMPC_TRY(st.in(p.self, in->self, B));
+  // read and written: the rows and sources the kernel leaves alone keep the caller's bytes on the way through device memory too
+  SMPC_TRY(st.inout(p.people, people, B * Np * 5));
+  SMPC_TRY(st.out(p.count, count, B));
+  SMPC_TRY(st.inout(p.source, source, B * Np));
+  void* ws = in->workspace;
+  SMPC_TRY(st.scratch(ws, (size_t)ws_bytes));
+  p.offsets = static_cast<int32_t*>(ws);
+  p.cursor = p.offsets + G + 1;
+  p.rows = p.cursor + G;
+  SMPC_TRY(st.timed([&] {
+    SMPC_HIP_CHECK(hipMemsetAsync(p.cursor, 0, G * sizeof(int32_t), h->stream));
+    const unsigned agent_blocks = (unsigned)((A + smpc::kNnThreads - 1) / smpc::kNnThreads);
+    if (A > 0) hipLaunchKernelGGL(smpc::smpc_nearest_count_kernel, dim3(agent_blocks), dim3(smpc::kNnThreads), 0, h->stream, p);
+    hipLaunchKernelGGL(smpc::smpc_nearest_scan_kernel, dim3(1), dim3(smpc::kNnScanThreads), 0, h->stream, p);
+    if (A > 0) hipLaunchKernelGGL(smpc::smpc_nearest_scatter_kernel, dim3(agent_blocks), dim3(smpc::kNnThreads), 0, h->stream, p);
+    const size_t per_block = smpc::kNnThreads / 64;
+    hipLaunchKernelGGL(smpc::smpc_nearest_query_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kNnThreads), 0, h->stream, p);
+    return SMPC_OK;
+  }));
   return st.finish();
 }
 

@@ -90,6 +90,9 @@ class Staging {
   template <typename T> int in(const T*& dev, const T* src, size_t n) { return bind(dev, src, src, nullptr, n * sizeof(T)); }
   template <typename T> int out(T*& dev, T* dst, size_t n) { return bind(dev, dst, nullptr, dst, n * sizeof(T)); }
   template <typename T> int inout(T*& dev, T* buf, size_t n) { return bind(dev, buf, buf, buf, n * sizeof(T)); }
+  // device room that only the call's kernels use (a workspace the caller of a host-pointer call need not bring): nothing
+  // is copied either way. Device-pointer calls bring their own: `dev` is left as it is.
+  int scratch(void*& dev, size_t bytes) { return host ? take(bytes, &dev) : SMPC_OK; }
   // the gathered inputs cross here (timed() does it before the kernels)
   int flush_up() {
     if (up_hi > up_lo) SMPC_HIP_CHECK(hipMemcpyAsync(h->stage + up_lo, h->pin + up_lo, up_hi - up_lo, hipMemcpyHostToDevice, h->stream));

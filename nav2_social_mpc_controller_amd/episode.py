@@ -6,6 +6,7 @@
     format_to_optimize + TrajectoryMemory   (src/optimizer.cpp:172-190, 484-551)  -> smpc_format_to_optimize_batch
     ObstacleDistance grid (optional, once)   (src/optimizer.cpp:593-605, 'TODO')   -> smpc_obstacle_distance_batch
     rolling local costmap (optional)         (Nav2's LayeredCostmap::updateMap)    -> smpc_local_costmap_batch
+    nearest-agent gather (optional)          (none: the library's own rule)        -> smpc_nearest_people_batch
     line-of-sight filter (optional)          (none: the library's own rule)        -> smpc_visible_people_batch
     global plans (optional, at the start and   (Nav2's planner server; the library's -> smpc_goal_field_batch,
     on replan(), never inside a tick)          own integer cost rule)                 smpc_extract_plan_batch
@@ -42,7 +43,7 @@ import numpy as np
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
 from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, TrajectorizerParams,
-                     VisibilityParams, check_scene_param_rows)
+                     SharedWorldParams, VisibilityParams, check_scene_param_rows)
 from .scenes import SceneBatch, World
 from .solver import BatchSolver, point, set_od_grid
 
@@ -90,6 +91,11 @@ class TickRecord:
     person_seen: np.ndarray = None     # [B,Np] uint8 enum smpc_seen_code (flags from person_count[b] on: not written)
     seen_count: np.ndarray = None      # [B]
     seen_persons: np.ndarray = None    # [B,Np,5] (rows from seen_count[b] on: not written)
+    # the shared world (BatchEpisode(shared=...)): the table the tick's gather read (`persons`, `person_count` and
+    # `person_source` are what it wrote), and with metrics the table the gather in front of the sample read
+    agents: np.ndarray = None          # [M+B,5] or [M,5]
+    person_source: np.ndarray = None   # [B,Np] rows of `agents` (from person_count[b] on: not written)
+    agents_after: np.ndarray = None    # as agents, after the move (persons_after is gathered from it)
 
 
 class BatchEpisode:
@@ -102,7 +108,7 @@ class BatchEpisode:
     # the same object for every shard
     FORWARDED = ("od_resolution", "device", "traj_params", "fov_angle", "order_hint", "plan_window", "obstacles_from_costmap",
                  "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost", "planner",
-                 "visibility")
+                 "visibility", "shared", "pool")
 
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
@@ -113,7 +119,8 @@ class BatchEpisode:
                  crowd: CrowdParams = None, person_waypoints: np.ndarray = None, person_n_waypoints: np.ndarray = None,
                  person_speed: np.ndarray = None, person_groups: np.ndarray = None,
                  crowd_groups: CrowdGroupParams = None, world: World = None, outside_cost: int = 255,
-                 planner: GlobalPlanParams = None, visibility: VisibilityParams = None):
+                 planner: GlobalPlanParams = None, visibility: VisibilityParams = None,
+                 shared: SharedWorldParams = None, pool: np.ndarray = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -173,7 +180,20 @@ class BatchEpisode:
         cell of the world occludes into self.seen_persons [B,Np,5] / self.seen_count [B] (with self.person_seen [B,Np]
         uint8, enum smpc_seen_code), and people_to_status reads those in place of self.persons / self.person_count. The
         crowd step, the metrics and the world's move keep the true persons. None: nothing is allocated and nothing is
-        launched."""
+        launched.
+        shared: one world for all robots (include/smpc_nearest.h): needs `world`; `crowd` and the person_* arguments are
+        refused (they move private rows). The scenes' own people are not uploaded. self.agents [M+B,5] is one table of
+        people_msgs::Person rows: the M rows of pool [M,5] (e.g. scenes.shared_pool; None: no pedestrians) followed, with
+        shared.robots_as_people, by one row per robot (x, y, v cos yaw, v sin yaw, w), which self.agent_self [B] = M + b
+        keeps a robot from perceiving as somebody else (without robots_as_people the table is the pool alone and
+        agent_self is -1). Every tick, after the roll and the plan stage and before the line-of-sight filter, the robots'
+        rows are refreshed from self.pose and self.speed and smpc_nearest_people_batch writes each robot's at most
+        Np = shared.max_people (default: the scenes' N) nearest agents within shared.max_range, nearest first, into
+        self.persons [B,Np,5] / self.person_count [B] (self.person_source [B,Np]: their rows of the table), the addresses
+        everything behind it reads. The pool moves with constant velocity, in place; the caller may rewrite
+        self.agents[:M] between ticks. With `metrics` the rows are refreshed and gathered a second time after the move, so
+        that the sample sees the world as the period leaves it, the other robots at their new poses included. None (then
+        pool must be None too): nothing is allocated and nothing is launched."""
         import torch
 
         self.torch = torch
@@ -190,6 +210,16 @@ class BatchEpisode:
                 raise ValueError("planner needs world, traj_params and goal [B,2]")
         if visibility is not None and world is None:
             raise ValueError("visibility needs world: the sight lines run over the world map")
+        if shared is None and pool is not None:
+            raise ValueError("pool needs shared=SharedWorldParams(...)")
+        if shared is not None:
+            if world is None:
+                raise ValueError("shared needs world: the robots and the pool share its floor")
+            private = dict(crowd=crowd, person_waypoints=person_waypoints, person_n_waypoints=person_n_waypoints,
+                           person_speed=person_speed, person_groups=person_groups)
+            given = sorted(k for k, v in private.items() if v is not None)
+            if given:
+                raise ValueError(f"shared refuses {', '.join(given)}: the reactive crowd step moves private rows")
         if plan is not None or planner is not None:
             # Plan mode: every robot is solved with the horizon its own trajectorized path gives it (smpc_format_batch.n_poses
             # -> T_scene). The arrays are sized for the longest one: a path of exactly max_poses = round(max_time / dt)
@@ -198,7 +228,7 @@ class BatchEpisode:
             assert self.T == params.rollout_steps
             self.T += 1
         self.P = params.dims(self.T, True)[3]
-        self._init_world(scenes, w_ref, fov_angle)
+        self._init_world(scenes, w_ref, fov_angle, shared)
         self._init_rolling(world, outside_cost)
         self._init_grid(od_indexes, od_origin, od_resolution, od_distances, obstacles_from_costmap, obstacle_min_cost,
                         unknown_is_obstacle, distances=metrics is not None)
@@ -208,6 +238,7 @@ class BatchEpisode:
         self._init_metrics(metrics, goal, plan, plan_len)
         self._init_crowd(crowd, person_waypoints, person_n_waypoints, person_speed, person_groups, crowd_groups)
         self._init_visibility(visibility)
+        self._init_shared(shared, pool)
         self._bind()
         self.graph = None
         self.gstream = None
@@ -222,7 +253,7 @@ class BatchEpisode:
     def _zeros(self, *shape, dtype=None):
         return self.torch.zeros(shape, dtype=dtype or self.torch.float64, device=self.dev)
 
-    def _init_world(self, scenes, w_ref, fov_angle):
+    def _init_world(self, scenes, w_ref, fov_angle, shared=None):
         """The robots, the persons and the costmaps."""
         i32 = self.torch.int32
         self.pose = self._upload(scenes.pose0.copy(), np.float64)                 # [B,3] current robot pose
@@ -236,8 +267,15 @@ class BatchEpisode:
         persons = np.stack([st0[:, :, 0], st0[:, :, 1], st0[:, :, 4] * np.cos(st0[:, :, 2]), st0[:, :, 4] * np.sin(st0[:, :, 2]),
                             st0[:, :, 5]], axis=-1)
         count = np.where(scenes.has_people != 0, (st0[:, :, 3] != -1.0).sum(axis=1), 0)
-        self.persons = self._upload(persons, np.float64)
-        self.person_count = self._upload(count, np.int32)
+        if shared is not None:  # the gather writes them every tick; the scenes' own people stay on the host
+            Np = int(shared.max_people) if shared.max_people is not None else self.N
+            if not 1 <= Np <= 64:
+                raise ValueError(f"shared needs 1 <= max_people <= 64 rows per robot, got {Np}")
+            self.persons = self._zeros(self.B, Np, 5)
+            self.person_count = self._zeros(self.B, dtype=i32)
+        else:
+            self.persons = self._upload(persons, np.float64)
+            self.person_count = self._upload(count, np.int32)
         self.fov_angle = fov_angle
         self.people = self._zeros(self.B, self.N, 6)                                    # people_to_status output
         self.has_people = self._zeros(self.B, dtype=self.torch.uint8)
@@ -420,6 +458,28 @@ class BatchEpisode:
         self.seen_count = self._zeros(B, dtype=self.torch.int32)
         self.person_seen = self._zeros(B, Np, dtype=self.torch.uint8)
 
+    def _init_shared(self, shared, pool):
+        """The table of a shared world, the gather's bins and workspace, and what it writes besides persons / person_count."""
+        self.shared = shared
+        if shared is None:
+            return
+        torch, B = self.torch, self.B
+        pool = np.zeros((0, 5)) if pool is None else np.ascontiguousarray(pool, np.float64)
+        assert pool.ndim == 2 and pool.shape[1] == 5, "pool [M,5]"
+        self.M = M = int(pool.shape[0])
+        rows = B if shared.robots_as_people else 0
+        self.agents = self._zeros(M + rows, 5)
+        if M > 0:
+            self.agents[:M].copy_(self._upload(pool, np.float64))
+        self.agent_self = (torch.arange(M, M + B, dtype=torch.int32, device=self.dev) if rows
+                           else torch.full((B,), -1, dtype=torch.int32, device=self.dev))
+        self.person_source = torch.full((B, int(self.persons.shape[1])), -1, dtype=torch.int32, device=self.dev)
+        self.shared_grid = shared.grid(self.world)
+        nbytes = self.solver.nearest_workspace_bytes(M + rows, self.shared_grid[0], self.shared_grid[1])
+        if nbytes == 0:
+            raise ValueError("the shared world's table or bins exceed the library's limits (include/smpc_nearest.h)")
+        self.nearest_workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.dev)
+
     def _bind(self):
         """Every struct a tick hands to the library, built once: every buffer the kernels read keeps its address from tick
         to tick (the state is updated in place), and the stream lives in the solver's handle, so nothing here changes
@@ -449,6 +509,12 @@ class BatchEpisode:
             c.traj_out = point(SmpcTrajectorizeOut(), {"path": self.plan_path, "cmds": self.plan_cmds, "cmds_vy": self.traj_vy,
                                                        "n_poses": self.traj_n, "error": self.traj_err})
         c.people = point(SmpcPeopleBatch(B=B, Np=Np, N=N, on_device=1), {"people": self.persons, "count": self.person_count})
+        if self.shared is not None:
+            gx, gy, origin, bin_size = self.shared_grid
+            c.nearest = point(BatchSolver.nearest_c(B, Np, int(self.agents.shape[0]), gx, gy, origin, bin_size, self.shared.max_range, 1),
+                              {"agents": self.agents if int(self.agents.shape[0]) > 0 else None, "robot_pose": self.pose,
+                               "self": self.agent_self, "workspace": self.nearest_workspace})
+            c.nearest.workspace_bytes = int(self.nearest_workspace.numel())
         if self.visibility is not None:  # the controller gets the persons in line of sight; the world keeps them all
             c.visibility = point(BatchSolver.visibility_c(self.visibility, B, Np, self.world.cells_x, self.world.cells_y, True,
                                                           self.resolution, 1),
@@ -521,6 +587,19 @@ class BatchEpisode:
                                          self.costmap_origin.data_ptr(), self.costmap_moved.data_ptr())
         self._force_roll = False
 
+    def _gather(self):
+        """The shared world as the robots perceive it now: the robots' rows of the table from pose and speed (x, y,
+        v cos yaw, v sin yaw, w), then every robot's nearest agents into persons / person_count / person_source."""
+        torch, M = self.torch, self.M
+        if self.shared.robots_as_people:
+            v, th = self.speed[:, 0], self.pose[:, 2]
+            self.agents[M:, 0:2] = self.pose[:, 0:2]
+            self.agents[M:, 2] = v * torch.cos(th)
+            self.agents[M:, 3] = v * torch.sin(th)
+            self.agents[M:, 4] = self.speed[:, 1]
+        self.solver.nearest_people_device(self._c.nearest, self.persons.data_ptr(), self.person_count.data_ptr(),
+                                          self.person_source.data_ptr())
+
     def replan(self):
         """Every robot's plan again, from its current pose down its goal's field, into the same self.plan / self.plan_len /
         self.plan_error; the plan window starts at the head of the new plans. Between ticks; never inside a captured one."""
@@ -566,6 +645,11 @@ class BatchEpisode:
         self._plan(timing)
         if planned:
             timed("trajectorize")
+        if self.shared is not None:  # one crowd for everybody, the other robots in it
+            self._gather()
+            timed("nearest")
+            if record:
+                rec.update(self._host("agents", "person_source"))
         if record:
             if planned:
                 rec.update(self._host(traj_n_poses="traj_n"))
@@ -622,10 +706,19 @@ class BatchEpisode:
         # state is updated in place: every buffer the kernels read keeps its address from tick to tick (_bind)
         self.pose.copy_(torch.where(optimised, self.res["path"][:, 0, :], moved))
         self.speed.copy_(self.cmd_vel)
-        if not crowd:
+        if self.shared is not None:  # the pool walks on; what a robot perceives of it is gathered, not moved
+            M = self.M
+            self.agents[:M, 0] += self.agents[:M, 2] * dt
+            self.agents[:M, 1] += self.agents[:M, 3] * dt
+        elif not crowd:
             self.persons[:, :, 0] += self.persons[:, :, 2] * dt
             self.persons[:, :, 1] += self.persons[:, :, 3] * dt
         if self.metrics_params is not None:  # 6. one metrics sample of the world as the period leaves it
+            if self.shared is not None:  # ... the other robots at their new poses included
+                self._gather()
+                timed("nearest_after")
+                if record:
+                    rec.update(self._host(agents_after="agents"))
             self._metrics_sample()
             timed("metrics")
         if record:
@@ -664,6 +757,8 @@ class BatchEpisode:
             state += ("metrics_acc",)  # the warm-up tick's sample does not count
         if self.crowd_params is not None:
             state += ("person_cursor",)
+        if self.shared is not None:
+            state += ("agents", "person_count", "person_source")
         with torch.cuda.stream(self.gstream):
             saved = {k: getattr(self, k).clone() for k in state}
             ticks = self.ticks
@@ -755,7 +850,8 @@ def concurrent_streams(n: int, device: str, candidates: int = 12):
 
 
 class ShardedEpisode:
-    """The robots of a batch are independent of each other (every scene has its own plan, people, memory), so a tick of
+    """The robots of a batch are independent of each other (every scene has its own plan, people, memory; a shared world,
+    BatchEpisode(shared=...), is therefore refused), so a tick of
     B robots can be issued as `shards` chains of B / shards robots on separate HIP streams: while one shard's solve
     launch drains its last long-running scenes, the other shards' kernels keep the CUs busy (the same overlap the
     serving bench gets from independent batches; a single chain pays the tail of every launch). Three things make it
@@ -774,6 +870,8 @@ class ShardedEpisode:
         of them (shard_kwargs)."""
         import torch
 
+        if episode_kw.get("shared") is not None or episode_kw.get("pool") is not None:
+            raise ValueError("ShardedEpisode refuses shared / pool: its shards are independent by construction")
         self.torch = torch
         B = scenes.B
         shards = max(1, min(shards, B))

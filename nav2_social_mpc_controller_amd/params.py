@@ -134,6 +134,34 @@ class VisibilityParams:
 
 
 @dataclass
+class SharedWorldParams:
+    """One world for all robots of an episode (include/smpc_nearest.h; BatchEpisode(shared=..., pool=...)): every tick each
+    robot is handed its at most max_people nearest agents within max_range (the detector's range in metres, VisibilityParams'
+    default) out of one table: the shared pedestrians, followed, with robots_as_people, by the robots themselves.
+    max_people None: the scenes' N."""
+    max_range: float = 10.0
+    max_people: int = None
+    robots_as_people: bool = True
+
+    def __post_init__(self):
+        if not (np.isfinite(self.max_range) and self.max_range > 0.0):
+            raise ValueError(f"SharedWorldParams.max_range must be finite and > 0, got {self.max_range}")
+        if self.max_people is not None and not 1 <= int(self.max_people) <= 64:
+            raise ValueError(f"SharedWorldParams.max_people must be 1..64 (SMPC_MAX_AGENTS), got {self.max_people}")
+
+    def grid(self, world):
+        """The bins of the gather on `world` (scenes.World): (grid_x, grid_y, origin [2], bin_size). The origin is the
+        world's; bin_size = max(max_range * (1 + 2^-20), larger side / 256), so that there are at most 256 x 256 = 65536
+        bins (the library's limit); grid_x x grid_y bins cover the floor (at least one each)."""
+        res = float(world.resolution)
+        width, height = world.cells_x * res, world.cells_y * res
+        bin_size = max(float(np.float64(self.max_range) * np.float64(1.0 + 2.0 ** -20)), max(width, height) / 256.0)
+        grid_x = min(256, max(1, int(np.ceil(width / bin_size))))
+        grid_y = min(256, max(1, int(np.ceil(height / bin_size))))
+        return grid_x, grid_y, np.asarray(world.origin, np.float64).reshape(2).copy(), bin_size
+
+
+@dataclass
 class OptimizerParams:
     # optimizer.* (src/optimizer.cpp:26-55, 76-83)
     linear_solver_type: str = "SPARSE_NORMAL_CHOLESKY"

@@ -531,3 +531,28 @@ def world_goals(world: World, start_xy: np.ndarray, seed: int = 0x5EED0005, marg
     gx = np.where(ok.any(axis=1), np.take_along_axis(x, pick, 1)[:, 0], world.origin[0] + ((flat % Hx) + 0.5) * res)
     gy = np.where(ok.any(axis=1), np.take_along_axis(y, pick, 1)[:, 0], world.origin[1] + ((flat // Hx) + 0.5) * res)
     return np.ascontiguousarray(np.stack([gx, gy], axis=1))
+
+
+def shared_pool(world: World, M: int, seed: int = 0x5EED0006, margin: float = 1.0, tries: int = 32,
+                standing_fraction: float = 0.2) -> np.ndarray:
+    """pool [M,5]: the pedestrians of a shared world (BatchEpisode(shared=..., pool=...)) as people_msgs::Person rows x, y,
+    vx, vy, vz. Each stands on a free cell of `world` (cost 0): the first of `tries` candidates, uniform over the floor at
+    least `margin` from its border, that lies on one; without one, the centre of the free cell nearest the floor's centre.
+    Speeds by make_scenes' law: standing_fraction of them stand, the others walk at 0.2 .. 1.2 m/s along a uniform heading;
+    vz = 0. A pure function of its arguments through `uniform` (fields 1 .. 5, keyed by the person's index)."""
+    ids = np.arange(int(M), dtype=np.int64)
+    res, Hx, Hy = world.resolution, world.cells_x, world.cells_y
+    x = world.origin[0] + margin + uniform(seed, ids, 1, tries) * (Hx * res - 2.0 * margin)    # [M,tries]
+    y = world.origin[1] + margin + uniform(seed, ids, 2, tries) * (Hy * res - 2.0 * margin)
+    ci = np.clip(np.floor((x - world.origin[0]) / res).astype(np.int64), 0, Hx - 1)
+    cj = np.clip(np.floor((y - world.origin[1]) / res).astype(np.int64), 0, Hy - 1)
+    ok = world.map[cj, ci] == 0
+    jj, ii = np.meshgrid(np.arange(Hy), np.arange(Hx), indexing="ij")
+    flat = int(np.argmin(np.where(world.map == 0, (ii + 0.5 - 0.5 * Hx) ** 2 + (jj + 0.5 - 0.5 * Hy) ** 2, np.inf)))
+    pick = np.argmax(ok, axis=1)[:, None]
+    px = np.where(ok.any(axis=1), np.take_along_axis(x, pick, 1)[:, 0], world.origin[0] + ((flat % Hx) + 0.5) * res)
+    py = np.where(ok.any(axis=1), np.take_along_axis(y, pick, 1)[:, 0], world.origin[1] + ((flat // Hx) + 0.5) * res)
+    heading = (uniform(seed, ids, 3)[:, 0] * 2.0 - 1.0) * np.pi
+    standing = uniform(seed, ids, 4)[:, 0] < standing_fraction
+    lv = np.where(standing, 0.0, 0.2 + uniform(seed, ids, 5)[:, 0])
+    return np.ascontiguousarray(np.stack([px, py, lv * np.cos(heading), lv * np.sin(heading), np.zeros(int(M))], axis=1))

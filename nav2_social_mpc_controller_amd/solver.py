@@ -11,12 +11,13 @@ import os
 
 import numpy as np
 
-from . import _abi, _abi_global_plan, _abi_local_costmap, _abi_visibility
+from . import _abi, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_visibility
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
 from ._abi_global_plan import SmpcExtractPlanIn, SmpcGoalFieldIn
 from ._abi_local_costmap import SmpcLocalCostmapIn
+from ._abi_nearest import SmpcNearestIn
 from ._abi_visibility import SmpcVisibilityIn
 from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, TrajectorizerParams,
                      VisibilityParams)
@@ -57,7 +58,7 @@ def load_library():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_abi.FUNCTIONS, **_abi.FIXED_SHAPE_FUNCTIONS, **_abi_local_costmap.FUNCTIONS,
-                                       **_abi_global_plan.FUNCTIONS, **_abi_visibility.FUNCTIONS}.items():
+                                       **_abi_global_plan.FUNCTIONS, **_abi_visibility.FUNCTIONS, **_abi_nearest.FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -769,6 +770,51 @@ class BatchSolver:
         handle's stream."""
         assert vi.on_device == 1
         self._call("smpc_visible_people_batch", vi, visible_ptr, visible_count_ptr, seen_ptr or None)
+
+    # -- nearest-agent gather of a shared world (smpc_nearest_people_batch, include/smpc_nearest.h) -----------------------
+    @staticmethod
+    def nearest_c(B: int, Np: int, A: int, grid_x: int, grid_y: int, grid_origin, bin_size: float, max_range: float,
+                  on_device: int) -> SmpcNearestIn:
+        ni = SmpcNearestIn(B=int(B), Np=int(Np), A=int(A), on_device=int(on_device), grid_x=int(grid_x), grid_y=int(grid_y),
+                           bin_size=float(bin_size), max_range=float(max_range))
+        ni.grid_origin[0], ni.grid_origin[1] = float(grid_origin[0]), float(grid_origin[1])
+        return ni
+
+    def nearest_workspace_bytes(self, A: int, grid_x: int, grid_y: int) -> int:
+        """Bytes of device memory smpc_nearest_people_batch needs as `workspace` for A agents on grid_x x grid_y bins (0 for a
+        shape the call refuses)."""
+        return int(self.lib.smpc_nearest_workspace_bytes(int(A), int(grid_x), int(grid_y)))
+
+    def nearest_people(self, agents: np.ndarray, robot_pose: np.ndarray, Np: int, grid_x: int, grid_y: int, grid_origin,
+                       bin_size: float, max_range: float, self_row: np.ndarray = None, people: np.ndarray = None,
+                       source: np.ndarray = None):
+        """Each of B robots' at most Np nearest agents within max_range out of one table (host arrays): agents [A,5],
+        robot_pose [B,3], self_row [B] int32 (the row of `agents` that is the robot itself, < 0: none) or None; the bins
+        (grid_x x grid_y of bin_size from grid_origin [2], e.g. params.SharedWorldParams.grid) do not show in the result.
+        people [B,Np,5] / source [B,Np] int32: the arrays before the call (default NaN / -1): the call writes the first
+        count rows of each robot, nearest first, and leaves the others. Returns (people, count [B] int32, source: the rows
+        of `agents`)."""
+        agents = np.ascontiguousarray(agents, np.float64).reshape(-1, 5)
+        robot_pose = np.ascontiguousarray(robot_pose, np.float64)
+        B, A, Np = robot_pose.shape[0], agents.shape[0], int(Np)
+        assert robot_pose.shape == (B, 3)
+        if self_row is not None:
+            self_row = np.ascontiguousarray(self_row, np.int32)
+            assert self_row.shape == (B,)
+        people = np.full((B, Np, 5), np.nan) if people is None else np.array(people, dtype=np.float64, order="C")
+        source = np.full((B, Np), -1, np.int32) if source is None else np.array(source, dtype=np.int32, order="C")
+        assert people.shape == (B, Np, 5) and source.shape == (B, Np)
+        ni = point(self.nearest_c(B, Np, A, grid_x, grid_y, grid_origin, bin_size, max_range, 0),
+                   {"agents": agents if A > 0 else None, "robot_pose": robot_pose, "self": self_row})
+        count = np.zeros(B, np.int32)
+        self._call("smpc_nearest_people_batch", ni, _ptr(people), _ptr(count), _ptr(source))
+        return people, count, source
+
+    def nearest_people_device(self, ni: SmpcNearestIn, people_ptr: int, count_ptr: int, source_ptr: int = 0):
+        """Device pointers in ni (on_device == 1, workspace included) and for people, count and source (0: none);
+        asynchronous on the handle's stream."""
+        assert ni.on_device == 1
+        self._call("smpc_nearest_people_batch", ni, people_ptr, count_ptr, source_ptr or None)
 
     # -- warm start / input formatting (SURVEY §8 row f2): format_to_optimize + TrajectoryMemory for B scenes -----
     def format_to_optimize(self, path: np.ndarray, cmds: np.ndarray, speed: np.ndarray, memory: dict,

@@ -5,7 +5,7 @@ BatchEpisode(scene_params=...)); the device scores every robot as it drives (Bat
 summarize_metrics means is printed per set. Nothing but the final [B,24] metrics rows leaves the device.
 
     python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]]
-                                [--world-plans [--occlusion [RANGE]]]
+                                [--world-plans [--occlusion [RANGE]] [--shared-crowd M]]
 
 --reactive: the persons are a reactive crowd (BatchEpisode(crowd=CrowdParams()), waypoints from scenes.crowd_waypoints)
 instead of walking straight on with constant velocity. --groups (with --reactive): half of the walking persons go in pairs
@@ -17,6 +17,11 @@ every second path cell, pruned by the plan window as the robot advances) instead
 --occlusion [RANGE] (with --world-plans): the robots perceive only the persons they have in line of sight on that map, within
 RANGE metres (default 10; BatchEpisode(visibility=VisibilityParams(max_range=RANGE))): a person behind a pillar or a wall is
 not planned around until it steps out. The metrics keep scoring the true persons.
+--shared-crowd M (with --world-plans): instead of a private list of persons per robot, one pool of M pedestrians
+(scenes.shared_pool) walks that floor and every robot perceives its nearest --agents of them within 10 m, or within RANGE with
+--occlusion (BatchEpisode(shared=SharedWorldParams(robots_as_people=False), pool=...)). The pool does not react, so every
+parameter set meets the same crowd; the sets do not perceive each other's robots, which start from the same poses. The
+metrics score what a robot perceives.
 """
 import argparse
 import os
@@ -50,7 +55,11 @@ def main():
     ap.add_argument("--world-plans", action="store_true", help="one world map, seeded goals, plans from the world's goal fields")
     ap.add_argument("--occlusion", type=float, nargs="?", const=10.0, default=None, metavar="RANGE",
                     help="with --world-plans: line-of-sight filter of the perceived persons, detector range in metres (default 10)")
+    ap.add_argument("--shared-crowd", type=int, default=None, metavar="M",
+                    help="with --world-plans: one pool of M pedestrians for all robots instead of a private list each")
     a = ap.parse_args()
+    if a.shared_crowd is not None and (not a.world_plans or a.reactive):
+        ap.error("--shared-crowd needs --world-plans and excludes --reactive")
     if a.groups and not a.reactive:
         ap.error("--groups needs --reactive")
     if a.occlusion is not None and not a.world_plans:
@@ -59,10 +68,10 @@ def main():
     import numpy as np
 
     from nav2_social_mpc_controller_amd.episode import BatchEpisode, arc_plans
-    from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, TrajectorizerParams,
-                                                       VisibilityParams, scene_param_rows)
-    from nav2_social_mpc_controller_amd.scenes import (crowd_groups, crowd_waypoints, make_scenes, make_world, scenes_in_world, uniform,
-                                                       world_goals)
+    from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, SharedWorldParams,
+                                                       TrajectorizerParams, VisibilityParams, scene_param_rows)
+    from nav2_social_mpc_controller_amd.scenes import (crowd_groups, crowd_waypoints, make_scenes, make_world, scenes_in_world, shared_pool,
+                                                       uniform, world_goals)
     from nav2_social_mpc_controller_amd.solver import summarize_metrics
 
     prm = OptimizerParams.readme()
@@ -80,6 +89,9 @@ def main():
                      plan_window=(4.0, 10.0))
         if a.occlusion is not None:
             plans["visibility"] = VisibilityParams(max_range=a.occlusion)
+        if a.shared_crowd is not None:                                      # one crowd for every set, the same for each
+            plans.update(shared=SharedWorldParams(max_range=a.occlusion if a.occlusion is not None else 10.0, robots_as_people=False),
+                         pool=shared_pool(world, a.shared_crowd))
     else:
         plan, plan_len = arc_plans(sc.pose0, 0.1 * w_ref, L=a.plan_poses)
         plans = dict(plan=plan, plan_len=plan_len)
