@@ -51,8 +51,8 @@ struct KParams {
   double* o_final_cost;
   int* queue;  // [kQueueWords]: [0] the scene work queue, zeroed before every solve launch; behind it what the kernels with
                // lone trips count (lone_trip_kernel()): [1] trips with exactly one slot idle for good, [2] all trips,
-               // [3] the trips of [1] that took the helped agent loop — running sums, zeroed by a launch under
-               // SMPC_DEBUG_GRID, which reports them
+               // [3] the trips of [1] that took the helped agent loop — counted (kLoneCount) and zeroed only by a
+               // launch under SMPC_DEBUG_GRID, which reports them
   // staged people block (smpc_stage_people_batch / the library's own staging pass): what the sweep reads
   const double* people_rec;  // [B][N][T][4]  px, py, vx, vy of people_proj[t + 1][a]
   const double* people_aux;  // [B][T][2]     bit mask of valid agents (u64 bits), agent-angle target (kNoTarget: none)
@@ -62,8 +62,10 @@ struct KParams {
   int full_gram;             // != 0: every sweep of a solve forms the whole Gram (SMPC_FULL_GRAM: the check that stopping at
                              // its last column changes nothing)
   int prio_step;             // > 0: a wave whose oldest scene has made n sweeps runs at wave priority min(n / prio_step, 3)
-  int lone_help;             // != 0: a trip with one slot idle for good is a lone trip, its idle half evaluates every other
-                             // agent (sweep()); 0 (SMPC_NO_LONE_HELP): every trip is paired. Results are the same bit for bit
+  int lone_trips;            // LoneTripBits. kLoneHelp: a trip with one slot idle for good is a lone trip, its idle half
+                             // evaluates every other agent (sweep()); without it (SMPC_NO_LONE_HELP) every trip is paired.
+                             // Results are the same bit for bit. kLoneCount (SMPC_DEBUG_GRID): the launch counts its trips
+                             // into queue[1..3]; without it no trip pays for the counting and those words are left alone
   double* stage_rec;         // staging kernel outputs (same layouts)
   double* stage_aux;
   unsigned long long* stamps;  // diagnostic builds only (SMPC_STAMPS): per-wave cycle sums per phase, [grid][8]
@@ -89,6 +91,7 @@ struct KParams {
 };
 constexpr int kTraceCols = SMPC_TRACE_COLS;
 constexpr int kQueueWords = 4;  // KParams::queue
+enum LoneTripBits { kLoneHelp = 1, kLoneCount = 2 };  // KParams::lone_trips
 
 // The solve kernels that know lone trips (sweep(), kLone): two scenes per wave, launch-constant horizon and weights, no
 // trace. Every other kernel is compiled without a line of it.

@@ -450,9 +450,24 @@ enum Phase { PH_FETCH = 0, PH_INIT = 1, PH_LS = 2, PH_REEVAL = 3, PH_DONE = 4, P
 enum Scal { S_COST = 0, S_XNORM, S_GMAX, S_RADIUS, S_DECF, S_MCC, S_GD0, S_DIRMAX, S_PREV_X, S_PREV_V, S_PREV_G,
             S_CUR_X, S_CUR_V, S_CUR_G, S_INITIAL_COST, S_FIRST_V, S_COUNT };
 
+// The state machine's flags, bits of LmRegs::flags: one word that is parked and fetched as it is (seven bools were packed
+// and unpacked with shifts around every sweep).
+enum LmFlag { LF_STEP_SUCCESSFUL = 1, LF_AT_LEAST_ONE = 2, LF_PREV_VV = 4, LF_PREV_GV = 8, LF_CUR_VV = 16, LF_CUR_GV = 32,
+              LF_FIRST_VV = 64 };
+
 struct LmRegs {  // slot-uniform integers / flags kept in registers
   int phase, iter, evals, num_invalid, ls_iters, n_samples, status, reason;
-  bool step_successful, at_least_one, prev_vv, prev_gv, cur_vv, cur_gv, first_vv;
+  int flags;  // LmFlag bits
+  __device__ bool has(int f) const { return (flags & f) != 0; }
+  __device__ void set(int f, bool v) { flags = v ? (flags | f) : (flags & ~f); }
+  // flag `to` takes the value of flag `from`
+  __device__ void copy(int to, int from) { set(to, has(from)); }
 };
+
+// 2^-e for a power of two d = 2^e within [2^-1021, 2^1022]: exact, so that x * pow2_reciprocal(d) is the correctly rounded
+// x / d wherever that quotient is a normal number (the trust-region radius: within [1e-32, 1e16], divided by 2, 4, 8, ...)
+__device__ inline double pow2_reciprocal(double d) {
+  return __longlong_as_double(0x7fe0000000000000ll - __double_as_longlong(d));
+}
 
 }  // namespace smpc

@@ -24,7 +24,7 @@ struct Knobs {
   bool full_gram = false;     // SMPC_FULL_GRAM: KParams::full_gram
   bool debug_grid = false;    // SMPC_DEBUG_GRID: a solve launch reports its LDS bytes and waves per CU on stderr and, once it has
                               // finished, its trips: all, those with one slot idle for good, those that took the helped loop
-  bool no_lone_help = false;  // SMPC_NO_LONE_HELP: KParams::lone_help = 0, every trip of a solve is paired
+  bool no_lone_help = false;  // SMPC_NO_LONE_HELP: KParams::lone_trips without kLoneHelp, every trip of a solve is paired
 };
 
 inline Knobs read_knobs() {

@@ -59,14 +59,38 @@
     return (__ballot(pred) & slot_bits) != 0ull;
   };
   // sums / maximum over the parameters: every active lane leaves its terms in the site's words, then every lane adds
-  // them up in index order
-  auto reduce3 = [&](double a, double b, double m, double& sa, double& sb, double& sm) {
+  // them up in index order. One form per need — a sum (row 0), two sums (rows 0 and 1), a sum and a maximum (rows 0 and
+  // 2) — so that a site pays for the channels it uses; each channel is the same in every form.
+  auto reduce_sum = [&](double a, double& sa) {
     double* w3 = rs;
-    if (act) { w3[q] = a; w3[P + q] = b; w3[2 * P + q] = m; }
+    if (act) w3[q] = a;
     wave_lds_fence();
-    sa = 0.0; sb = 0.0; sm = 0.0;
+    sa = 0.0;
 #pragma unroll
-    for (int i = 0; i < P; ++i) { sa += w3[i]; sb += w3[P + i]; sm = fmax(sm, w3[2 * P + i]); }
+    for (int i = 0; i < P; ++i) sa += w3[i];
+  };
+  auto reduce_sum2 = [&](double a, double b, double& sa, double& sb) {
+    double* w3 = rs;
+    if (act) { w3[q] = a; w3[P + q] = b; }
+    wave_lds_fence();
+    sa = 0.0; sb = 0.0;
+#pragma unroll
+    for (int i = 0; i < P; ++i) { sa += w3[i]; sb += w3[P + i]; }
+  };
+  // The maximum as one v_max_f64 per term: fmax() canonicalises both operands first (13 instructions for six maxima).
+  // The terms are fabs() of arithmetic results, never a signalling NaN, and a quiet NaN is dropped by the instruction as
+  // fmax() drops it: the maximum of the other terms comes out, as ever.
+  auto reduce_sum_max = [&](double a, double m, double& sa, double& sm) {
+    double* w3 = rs;
+    if (act) { w3[q] = a; w3[2 * P + q] = m; }
+    wave_lds_fence();
+    sa = 0.0; sm = 0.0;
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      sa += w3[i];
+      const double mi = w3[2 * P + i];
+      asm("v_max_f64 %0, %1, %2" : "=v"(sm) : "v"(sm), "v"(mi));
+    }
   };
 
   // kTrace: row `row` of the slot's scene, columns in the order of smpc_trace_out (iter is the row index itself)
@@ -87,23 +111,20 @@
   R.phase = PH_FETCH;
   R.iter = R.evals = R.num_invalid = R.ls_iters = R.n_samples = 0;
   R.status = SMPC_NO_CONVERGENCE; R.reason = SMPC_REASON_MAX_ITERATIONS;
-  R.step_successful = R.at_least_one = R.prev_vv = R.prev_gv = R.cur_vv = R.cur_gv = R.first_vv = false;
+  R.flags = 0;
   auto park = [&]() {
     rw[0] = R.iter; rw[1] = R.evals; rw[2] = R.num_invalid; rw[3] = R.ls_iters; rw[4] = R.n_samples; rw[5] = R.status;
-    rw[6] = R.reason;
-    rw[7] = (R.step_successful ? 1 : 0) | (R.at_least_one ? 2 : 0) | (R.prev_vv ? 4 : 0) | (R.prev_gv ? 8 : 0) |
-            (R.cur_vv ? 16 : 0) | (R.cur_gv ? 32 : 0) | (R.first_vv ? 64 : 0);
+    rw[6] = R.reason; rw[7] = R.flags;
   };
   auto unpark = [&]() {
     R.iter = rw[0]; R.evals = rw[1]; R.num_invalid = rw[2]; R.ls_iters = rw[3]; R.n_samples = rw[4]; R.status = rw[5];
-    R.reason = rw[6];
-    const int f = rw[7];
-    R.step_successful = f & 1; R.at_least_one = f & 2; R.prev_vv = f & 4; R.prev_gv = f & 8;
-    R.cur_vv = f & 16; R.cur_gv = f & 32; R.first_vv = f & 64;
+    R.reason = rw[6]; R.flags = rw[7];
   };
   bool ever_loaded = false;
   // kLone: this wave's trips, those with one slot idle for good and those helped, 21 bits each in one word of LDS behind
   // the state machine's parked integers (each slot keeps the wave's count; a wave makes far fewer than 2^21 trips)
+  // Counted only in a launch that reports the counts (kLoneCount of KParams::lone_trips): a trip of any other launch pays
+  // one scalar test for it.
   if constexpr (kLone) *reinterpret_cast<unsigned long long*>(rw + 8) = 0ull;
 #ifdef SMPC_STAMPS
   for (int i = 0; i < 8; ++i) c.acc[i] = 0;
@@ -159,13 +180,13 @@
           v = clampd(k.init_params[(size_t)scene * P + q] + 0.0, lo0, hi0);  // Plus(x, 0): project the start point (A.4)
         }
         if (act) { xc[q] = v; xt[q] = v; }
-        double xn, u0, u1;
-        reduce3(v * v, 0.0, 0.0, xn, u0, u1);
+        double xn;
+        reduce_sum(v * v, xn);
         sv[S_XNORM] = fast_sqrt(xn);
         R.phase = PH_INIT;
         R.iter = 0; R.evals = 0; R.num_invalid = 0;
         R.status = SMPC_NO_CONVERGENCE; R.reason = SMPC_REASON_MAX_ITERATIONS;
-        R.step_successful = true; R.at_least_one = false;
+        R.set(LF_STEP_SUCCESSFUL, true); R.set(LF_AT_LEAST_ONE, false);
       } else {
         if (!ever_loaded) {  // keep the sweep's memory accesses in bounds for a slot that never got a scene
           load_scene<W, kVT, kSP, Shape, Shape::kStageAtFetch>(c, 0, false);  // (a kernel that stages at the fetch: not here)
@@ -184,9 +205,9 @@
       const bool idle = R.phase == PH_IDLE;
       const unsigned long long ib = __ballot(idle);
       const bool half = ((ib ^ (ib >> 32)) & 1ull) != 0ull;  // (the phase is uniform over a slot)
-      const bool lone = half && k.lone_help != 0 && Shape::N(k) >= 2 && __ballot(!idle && c.has_people) != 0ull;
+      const bool lone = half && (k.lone_trips & kLoneHelp) != 0 && Shape::N(k) >= 2 && __ballot(!idle && c.has_people) != 0ull;
       *trip_mode(c) = !lone ? kTripPaired : idle ? kTripHelper : kTripOwner;
-      *reinterpret_cast<unsigned long long*>(rw + 8) += 1ull + (half ? 1ull << 21 : 0ull) + (lone ? 1ull << 42 : 0ull);
+      if (k.lone_trips & kLoneCount) *reinterpret_cast<unsigned long long*>(rw + 8) += 1ull + (half ? 1ull << 21 : 0ull) + (lone ? 1ull << 42 : 0ull);
     }
     if (k.prio_step > 0) {
       // Attained-service priority: the launch ends when its longest scene does, and a scene's sweeps are a dependent
@@ -255,19 +276,19 @@
         gu[q] = g; gs[q] = g * scq;
         gm = fabs(xa - clampd(xa - g, lo_q, hi_q));
       }
-      double xn, u0, gmax;
-      reduce3(xa * xa, 0.0, gm, xn, u0, gmax);
+      double xn, gmax;
+      reduce_sum_max(xa * xa, gm, xn, gmax);
       sv[S_XNORM] = fast_sqrt(xn);
       sv[S_GMAX] = gmax;
     };
     auto candidate = [&]() {  // A.9 tests on the candidate = current trial point; A.10 strategy update
       const double cost = sv[S_COST];
-      const double cand_cost = R.cur_vv ? sv[S_CUR_V] : 1.7976931348623157e308;
+      const double cand_cost = R.has(LF_CUR_VV) ? sv[S_CUR_V] : 1.7976931348623157e308;
       const double d = act ? xc[q] - xt[q] : 0.0;
-      double sn2, u0, u1;
-      reduce3(d * d, 0.0, 0.0, sn2, u0, u1);
+      double sn2;
+      reduce_sum(d * d, sn2);
       const double step_norm = fast_sqrt(sn2);
-      const bool tol_allowed = !prm.fixed_iterations && (!prm.tol_needs_successful_step || R.at_least_one);
+      const bool tol_allowed = !prm.fixed_iterations && (!prm.tol_needs_successful_step || R.has(LF_AT_LEAST_ONE));
       if (tol_allowed && step_norm <= prm.param_tol * (sv[S_XNORM] + prm.param_tol)) {
         if constexpr (kTrace) trace_row(R.iter, cost, cost - cand_cost, sv[S_GMAX], step_norm, 0.0, sv[S_RADIUS], R.n_samples, false);
         R.status = SMPC_CONVERGENCE; R.reason = SMPC_REASON_PARAMETER_TOL; R.phase = PH_DONE; return;
@@ -287,16 +308,16 @@
       if (rho > 1e-3) {
         adopt_trial_point();
         sv[S_COST] = cand_cost;
-        R.step_successful = true; R.at_least_one = true;
+        R.flags |= LF_STEP_SUCCESSFUL | LF_AT_LEAST_ONE;
         const double t = 2.0 * rho - 1.0;
         sv[S_RADIUS] = fmin(1e16, div_fast(sv[S_RADIUS], fmax(1.0 / 3.0, 1.0 - t * t * t)));
         sv[S_DECF] = 2.0;
       } else {
-        sv[S_RADIUS] = sv[S_RADIUS] / sv[S_DECF];
+        sv[S_RADIUS] = sv[S_RADIUS] * pow2_reciprocal(sv[S_DECF]);  // S_DECF is 2, 4, 8, ...: the quotient, exactly
         sv[S_DECF] *= 2.0;
       }
       if constexpr (kTrace) {  // cost, gmax and radius behind the update: of the adopted point where the step was accepted
-        trace_row(R.iter, sv[S_COST], cost_change, sv[S_GMAX], step_norm, rho, sv[S_RADIUS], R.n_samples, R.step_successful);
+        trace_row(R.iter, sv[S_COST], cost_change, sv[S_GMAX], step_norm, rho, sv[S_RADIUS], R.n_samples, R.has(LF_STEP_SUCCESSFUL));
       }
       new_iteration = true;
     };
@@ -321,14 +342,14 @@
       ++R.evals;
       // record the sample just evaluated (LineSearchFunction::Evaluate, A.8)
       const double dq = act ? dl[q] : 0.0;
-      double gd, u0, u1;
-      reduce3(act ? dq * GH.base[q * GH.ld + P] : 0.0, 0.0, 0.0, gd, u0, u1);
-      R.cur_vv = finite && isfinite(val);
-      R.cur_gv = R.cur_vv && isfinite(gd);
+      double gd;
+      reduce_sum(act ? dq * GH.base[q * GH.ld + P] : 0.0, gd);
+      const bool cur_vv = finite && isfinite(val), cur_gv = cur_vv && isfinite(gd);
+      R.set(LF_CUR_VV, cur_vv); R.set(LF_CUR_GV, cur_gv);
       sv[S_CUR_V] = val; sv[S_CUR_G] = gd;
       const double alpha = sv[S_CUR_X];
-      if (R.n_samples == 1) { sv[S_FIRST_V] = val; R.first_vv = R.cur_vv; }  // the full step: candidate if the search fails
-      if (R.cur_vv && armijo_holds(val, sv[S_COST], sv[S_GD0], alpha)) {
+      if (R.n_samples == 1) { sv[S_FIRST_V] = val; R.set(LF_FIRST_VV, cur_vv); }  // the full step: candidate if the search fails
+      if (cur_vv && armijo_holds(val, sv[S_COST], sv[S_GD0], alpha)) {
         // Armijo satisfied: delta *= alpha; the candidate is this very point
         if (act) dl[q] = dq * alpha;
         candidate();
@@ -338,8 +359,8 @@
         double step_size = 0.0;
         if (!failed) {
           Sample lower{0.0, sv[S_COST], sv[S_GD0], true, true};
-          Sample previous{sv[S_PREV_X], sv[S_PREV_V], sv[S_PREV_G], R.prev_vv, R.prev_gv};
-          Sample current{alpha, val, gd, R.cur_vv, R.cur_gv};
+          Sample previous{sv[S_PREV_X], sv[S_PREV_V], sv[S_PREV_G], R.has(LF_PREV_VV), R.has(LF_PREV_GV)};
+          Sample current{alpha, val, gd, cur_vv, cur_gv};
           SMPC_STAMP(c, 6);
           if (!interpolate_step_fast(lower, previous, current, 1e-3 * alpha, 0.6 * alpha, step_size))
           { SMPC_LS_COUNT(7, 1); step_size = interpolate_step(lower, previous, current, 1e-3 * alpha, 0.6 * alpha, scratch); }
@@ -347,7 +368,7 @@
           failed = step_size * sv[S_DIRMAX] < 1e-9;
         }
         if (!failed) {
-          sv[S_PREV_X] = alpha; sv[S_PREV_V] = val; sv[S_PREV_G] = gd; R.prev_vv = R.cur_vv; R.prev_gv = R.cur_gv;
+          sv[S_PREV_X] = alpha; sv[S_PREV_V] = val; sv[S_PREV_G] = gd; R.set(LF_PREV_VV, cur_vv); R.set(LF_PREV_GV, cur_gv);
           sv[S_CUR_X] = step_size;
           if (act) xt[q] = clampd(xc[q] + step_size * dq, lo_q, hi_q);
           ++R.n_samples;
@@ -357,12 +378,12 @@
           // alpha = 1 cannot be (cost - value_1 < -1e-4 g.delta < 1e-3 model_cost_change). Only in that never-seen case
           // the point is swept again (PH_REEVAL) so that the accepted state is built from its own Gram.
           if (act) xt[q] = clampd(xc[q] + dq, lo_q, hi_q);
-          const double v1 = R.first_vv ? sv[S_FIRST_V] : 1.7976931348623157e308;
-          const bool would_accept = R.first_vv && ((sv[S_COST] - v1) / sv[S_MCC] > 1e-3);
+          const double v1 = R.has(LF_FIRST_VV) ? sv[S_FIRST_V] : 1.7976931348623157e308;
+          const bool would_accept = R.has(LF_FIRST_VV) && ((sv[S_COST] - v1) / sv[S_MCC] > 1e-3);
           if (would_accept) {
             R.phase = PH_REEVAL;
           } else {
-            R.cur_vv = R.first_vv;
+            R.copy(LF_CUR_VV, LF_FIRST_VV);
             sv[S_CUR_V] = v1;
             wave_lds_fence();
             candidate();
@@ -373,7 +394,7 @@
       }
     } else if (R.phase == PH_REEVAL) {
       ++R.evals;
-      R.cur_vv = finite && isfinite(val);
+      R.set(LF_CUR_VV, finite && isfinite(val));
       sv[S_CUR_V] = val;
       candidate();
     }
@@ -382,10 +403,10 @@
     if (new_iteration) {
       for (;;) {
         if (R.iter >= prm.max_iterations) { R.status = SMPC_NO_CONVERGENCE; R.reason = SMPC_REASON_MAX_ITERATIONS; R.phase = PH_DONE; break; }
-        if (R.step_successful && sv[S_GMAX] <= prm.gradient_tol && !prm.fixed_iterations) { R.status = SMPC_CONVERGENCE; R.reason = SMPC_REASON_GRADIENT_TOL; R.phase = PH_DONE; break; }
+        if (R.has(LF_STEP_SUCCESSFUL) && sv[S_GMAX] <= prm.gradient_tol && !prm.fixed_iterations) { R.status = SMPC_CONVERGENCE; R.reason = SMPC_REASON_GRADIENT_TOL; R.phase = PH_DONE; break; }
         if (sv[S_RADIUS] <= 1e-32) { R.status = SMPC_CONVERGENCE; R.reason = SMPC_REASON_MIN_RADIUS; R.phase = PH_DONE; break; }
         ++R.iter;
-        R.step_successful = false;
+        R.set(LF_STEP_SUCCESSFUL, false);
         // (the column masks "q == j" / "q > j" of this block stay inside it: hoisted out of this retry loop they were two
         // scalar registers each, 4 NB of them, spilled)
         int ql = q;
@@ -443,14 +464,14 @@
           double rowv = 0.0;
 #pragma unroll
           for (int b = 0; b < P; ++b) rowv = fma(arow[b], bc[3 * P + b], rowv);
-          double sg, sHs, u1;
-          reduce3(stepq * gsq, act ? stepq * rowv : 0.0, 0.0, sg, sHs, u1);
+          double sg, sHs;
+          reduce_sum2(stepq * gsq, act ? stepq * rowv : 0.0, sg, sHs);
           mcc = -sg - 0.5 * sHs;
           valid = mcc > 0.0;
         }
         if (!valid) {
           if (++R.num_invalid >= 5) { R.status = SMPC_FAILURE; R.reason = SMPC_REASON_INVALID_STEPS; R.phase = PH_DONE; break; }
-          sv[S_RADIUS] = radius / sv[S_DECF]; sv[S_DECF] *= 2.0;
+          sv[S_RADIUS] = radius * pow2_reciprocal(sv[S_DECF]); sv[S_DECF] *= 2.0;
           wave_lds_fence();
           if constexpr (kTrace) trace_row(R.iter, sv[S_COST], 0.0, sv[S_GMAX], 0.0, 0.0, sv[S_RADIUS], 0, false);
           continue;
@@ -464,11 +485,11 @@
           gq = gu[q] * dq;
           xt[q] = clampd(xc[q] + 1.0 * dq, lo_q, hi_q);
         }
-        double gd0, u0, dirmax;
-        reduce3(gq, 0.0, fabs(dq), gd0, u0, dirmax);
+        double gd0, dirmax;
+        reduce_sum_max(gq, fabs(dq), gd0, dirmax);
         sv[S_GD0] = gd0; sv[S_DIRMAX] = dirmax;
         sv[S_CUR_X] = 1.0;
-        R.prev_vv = R.prev_gv = false;
+        R.flags &= ~(LF_PREV_VV | LF_PREV_GV);
         R.ls_iters = 0; R.n_samples = 1;
         R.phase = PH_LS;
         break;
@@ -548,7 +569,7 @@
     // LDS pointers, live to here, were four scalar registers spilled in the line search)
     const auto& ke = *c.kp;
     const LdsLayout Lx = make_layout(Shape::T(ke), Shape::N(ke), P, kLayoutSolve, W, kSP);
-    if (threadIdx.x == 0) {
+    if ((ke.lone_trips & kLoneCount) != 0 && threadIdx.x == 0) {
       const unsigned long long n = *reinterpret_cast<const unsigned long long*>(lds_all + Lx.lm + P * P + 6 * P + S_COUNT + 4);
       atomicAdd(ke.queue + 1, (int)((n >> 21) & 0x1fffffull));
       atomicAdd(ke.queue + 2, (int)(n & 0x1fffffull));

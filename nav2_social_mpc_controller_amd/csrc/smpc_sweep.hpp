@@ -275,9 +275,12 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
     // (every exchange across the halves is executed by all lanes: a lane switched off hands nothing over)
     const v4d* owner_agr = reinterpret_cast<const v4d*>(other_half(reinterpret_cast<unsigned long long>(agr)));
     agr = hlp ? owner_agr : agr;
-    rec0 = agr[(hlp ? 1 : 0) * T]; rec1 = agr[min(hlp ? 3 : 2, N - 1) * T];
+    rec0 = agr[(hlp ? 1 : 0) * T];  // (the lone-trip kernels' agent loop fetches one unit ahead: no second record)
   } else
-  if (c.has_people) { rec0 = agr[0]; rec1 = agr[(N > 1 ? 1 : 0) * T]; }
+  if (c.has_people) {
+    rec0 = agr[0];
+    if constexpr (!kLone) rec1 = agr[(N > 1 ? 1 : 0) * T];
+  }
 
   // ---- a1 rollout (update_state.hpp:37-63), block-structured. The recurrences are sums, so they are evaluated as
   // sums: theta_t = yaw0 + sum_b (w_b dt) * (steps of block b before t), and the positions through inclusive prefix
@@ -487,14 +490,17 @@ __device__ inline GramView sweep(Ctx& c, const double* xp, double* out_r, double
         step = 2;
       }
       for (int a = 0; a < N; a += step) {
-        const v4d rec = rec0;  // of agent a + mine (the helper's last unit of an odd N: some record, its Force is not used)
-        rec0 = rec1;
-        const int ahead = a + mine + 2 * step;
-        if (ahead < N) rec1 = agr[ahead * T];
-        const double apx = rec[0], apy = rec[1], awx = rec[2], awy = rec[3];
-        const double dx = X - apx, dy = Y - apy;
+        // rec0: of agent a + mine (the helper's last unit of an odd N: some record, its Force is not used). A record is dead
+        // four subtractions into the body, and the next unit's is fetched over it: one record in flight, nothing to rotate
+        // at the back edge (two in flight were eight 64-bit moves per pair). A body is some 800 cycles of VALU, enough for
+        // the L2 hit a solve's records are; K1 and the helper-lane loop, whose first touch comes from HBM, keep two.
+        double dx = X - rec0[0], dy = Y - rec0[1], ux = rvx - rec0[2], uy = rvy - rec0[3];
+        // (the differences are formed before the fetch is issued — left to itself the compiler fetches first, into other
+        // registers, and copies at the back edge; the index stays inside the list, as in the fetch ahead of the rollout)
+        asm volatile("" : "+v"(dx), "+v"(dy), "+v"(ux), "+v"(uy));
+        rec0 = agr[min(a + mine + step, N - 1) * T];
         double d2 = fma(dx, dx, dy * dy);
-        Force F = pair_force(mt, atab, dx, dy, rvx - awx, rvy - awy);
+        Force F = pair_force(mt, atab, dx, dy, ux, uy);
         int special = F.special ? 1 : 0;
         {
           const bool valid = (vm >> a) & 1ull;

@@ -236,7 +236,7 @@ int launch(smpc_handle* h, Staging& st, const smpc::SweepPlan& plan, const smpc:
     k.queue = h->queue;
     k.full_gram = kn.full_gram ? 1 : 0;
     k.prio_step = kn.prio_step;
-    k.lone_help = kn.no_lone_help ? 0 : 1;
+    k.lone_trips = (kn.no_lone_help ? 0 : smpc::kLoneHelp) | (kn.debug_grid ? smpc::kLoneCount : 0);
     // the trip counters behind the scene counter are zeroed only for the launch that reports them: every other launch
     // issues the one four-byte memset it always issued (the captured tick graphs of the sharded episodes hold this node)
     if (kn.debug_grid) SMPC_HIP_CHECK(hipMemsetAsync(h->queue + 1, 0, (smpc::kQueueWords - 1) * sizeof(int), h->stream));
