@@ -15,7 +15,7 @@
 //   smpc_stage_kernel<W>     the staging pass of the people block (smpc_stage_kernel.hpp);
 //   the probe kernels (smpc_probes.hpp);
 //   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window,
-//   metrics, crowd, local costmap, global plan, visibility, nearest agents).
+//   metrics, crowd, local costmap, global plan, visibility, nearest agents, pool crowd).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -40,6 +40,8 @@
 #include "../../include/smpc_visibility.h"
 #include "smpc_nearest.hpp"
 #include "../../include/smpc_nearest.h"
+#include "smpc_crowd_pool.hpp"
+#include "../../include/smpc_crowd_pool.h"
 
 extern "C" {
 
@@ -843,6 +845,86 @@ int smpc_nearest_people_batch(smpc_handle* h, const smpc_nearest_in* in, double*
     if (A > 0) hipLaunchKernelGGL(smpc::smpc_nearest_scatter_kernel, dim3(agent_blocks), dim3(smpc::kNnThreads), 0, h->stream, p);
     const size_t per_block = smpc::kNnThreads / 64;
     hipLaunchKernelGGL(smpc::smpc_nearest_query_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kNnThreads), 0, h->stream, p);
+    return SMPC_OK;
+  }));
+  return st.finish();
+}
+
+int smpc_crowd_pool_step_batch(smpc_handle* h, const smpc_crowd_pool_in* in, double* next, int32_t* cursor) {
+  if (!h || !in) { set_error("null handle / input"); return SMPC_ERR_INVALID_ARG; }
+  if (in->A < 0 || in->M < 0 || in->M > in->A || in->K < 1 || in->grid_x < 1 || in->grid_y < 1) {
+    set_error("bad A, M outside 0..A, K < 1 or a grid side < 1"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (!in->agents && in->A > 0) { set_error("null agents with A > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (in->M > 0 && (!next || !cursor || !in->waypoints || !in->n_waypoints)) { set_error("null next / cursor / waypoints / n_waypoints with M > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->grid_origin[0]) || !std::isfinite(in->grid_origin[1])) { set_error("grid_origin must be finite"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->bin_size) || !(in->bin_size > 0.0)) { set_error("bin_size must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->interaction_range) || !(in->interaction_range > 0.0)) { set_error("interaction_range must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  {
+    const volatile double least = in->interaction_range * SMPC_NEAREST_BIN_MARGIN;  // the product of the two doubles, rounded once
+    if (!(in->bin_size >= least)) { set_error("bin_size must be at least interaction_range * SMPC_NEAREST_BIN_MARGIN"); return SMPC_ERR_INVALID_ARG; }
+  }
+  if (!std::isfinite(in->dt) || !(in->dt > 0.0)) { set_error("dt must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (!(in->goal_radius >= 0.0) || !(in->person_radius >= 0.0) || !(in->desired_speed > 0.0)) {
+    set_error("negative radius or non-positive desired_speed"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (in->od_indexes && (!in->od_origin || in->od_width < 1 || in->od_height < 1 || !(in->od_resolution > 0.0f))) {
+    set_error("obstacle grid without origin or with a non-positive size or resolution"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (in->K > SMPC_MAX_WAYPOINTS) { set_error("K > 8 waypoints is not supported"); return SMPC_ERR_UNSUPPORTED; }
+  if ((int64_t)in->grid_x * in->grid_y > SMPC_NEAREST_MAX_BINS) { set_error("more than 65536 bins are not supported"); return SMPC_ERR_UNSUPPORTED; }
+  if (in->A > SMPC_NEAREST_MAX_ROWS) { set_error("more than 2^24 agents are not supported"); return SMPC_ERR_UNSUPPORTED; }
+  if (in->M > 0) {  // rule 6: the step is synchronous, `next` is no part of the table
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(in->agents), a1 = a0 + (uintptr_t)in->A * 5 * sizeof(double);
+    const uintptr_t n0 = reinterpret_cast<uintptr_t>(next), n1 = n0 + (uintptr_t)in->M * 5 * sizeof(double);
+    if (n0 < a1 && a0 < n1) { set_error("next overlaps agents"); return SMPC_ERR_INVALID_ARG; }
+  }
+  const uint64_t ws_bytes = smpc_nearest_workspace_bytes(in->A, in->grid_x, in->grid_y);
+  if (in->on_device && (!in->workspace || in->workspace_bytes < ws_bytes)) { set_error("workspace is null or smaller than smpc_nearest_workspace_bytes()"); return SMPC_ERR_INVALID_ARG; }
+  if (in->M == 0) return SMPC_OK;
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::CrowdPoolParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.M = in->M; p.A = in->A; p.K = in->K; p.cyclic = in->cyclic ? 1 : 0; p.grid_x = in->grid_x; p.grid_y = in->grid_y;
+  p.range = in->interaction_range; p.dt = in->dt;
+  p.goal_radius = in->goal_radius; p.person_radius = in->person_radius; p.desired_speed = in->desired_speed;
+  p.od_width = in->od_width; p.od_height = in->od_height; p.od_resolution = in->od_resolution;
+  smpc::fill_math_table(&p.mt);
+  smpc::NearestParams b;  // the gather's binning kernels, on the same table and workspace
+  std::memset(&b, 0, sizeof(b));
+  b.A = in->A; b.grid_x = in->grid_x; b.grid_y = in->grid_y;
+  b.ox = in->grid_origin[0]; b.oy = in->grid_origin[1]; b.bin_size = in->bin_size;
+  const size_t M = in->M, A = in->A, K = in->K, G = (size_t)in->grid_x * (size_t)in->grid_y;
+  const bool grid = in->od_indexes != nullptr;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.agents, in->agents, A * 5));
+  SMPC_TRY(st.in(p.waypoints, in->waypoints, M * K * 2));
+  SMPC_TRY(st.in(p.n_waypoints, in->n_waypoints, M));
+  SMPC_TRY(st.in(p.desired_speeds, in->desired_speeds, M));
+  SMPC_TRY(st.in(p.od_indexes, in->od_indexes, grid ? (size_t)in->od_width * in->od_height : 0));
+  SMPC_TRY(st.in(p.od_origin, grid ? in->od_origin : nullptr, 2));
+  SMPC_TRY(st.out(p.next, next, M * 5));
+  // read and written: the cursor of an inert mover keeps the caller's value on the way through device memory too
+  SMPC_TRY(st.inout(p.cursor, cursor, M));
+  void* ws = in->workspace;
+  SMPC_TRY(st.scratch(ws, (size_t)ws_bytes));
+  b.agents = p.agents;
+  b.offsets = static_cast<int32_t*>(ws);
+  b.cursor = b.offsets + G + 1;
+  b.rows = b.cursor + G;
+  p.offsets = b.offsets; p.rows = b.rows;
+  const bool bins_ready = in->on_device && in->bins_ready;
+  SMPC_TRY(st.timed([&] {
+    if (!bins_ready) {
+      SMPC_HIP_CHECK(hipMemsetAsync(b.cursor, 0, G * sizeof(int32_t), h->stream));
+      const unsigned agent_blocks = (unsigned)((A + smpc::kNnThreads - 1) / smpc::kNnThreads);
+      hipLaunchKernelGGL(smpc::smpc_nearest_count_kernel, dim3(agent_blocks), dim3(smpc::kNnThreads), 0, h->stream, b);
+      hipLaunchKernelGGL(smpc::smpc_nearest_scan_kernel, dim3(1), dim3(smpc::kNnScanThreads), 0, h->stream, b);
+      hipLaunchKernelGGL(smpc::smpc_nearest_scatter_kernel, dim3(agent_blocks), dim3(smpc::kNnThreads), 0, h->stream, b);
+    }
+    // one block column per bin, then the blocks that copy the movers that are in no bin
+    const unsigned columns = (unsigned)(G + (M + smpc::kCpThreads - 1) / smpc::kCpThreads);
+    hipLaunchKernelGGL(smpc::smpc_crowd_pool_step_kernel, dim3(columns, smpc::kCpSplit), dim3(smpc::kCpThreads), 0, h->stream, p);
     return SMPC_OK;
   }));
   return st.finish();

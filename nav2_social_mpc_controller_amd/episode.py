@@ -42,7 +42,7 @@ import numpy as np
 
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
-from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, TrajectorizerParams,
+from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, PoolCrowdParams, TrajectorizerParams,
                      SharedWorldParams, VisibilityParams, check_scene_param_rows)
 from .scenes import SceneBatch, World
 from .solver import BatchSolver, point, set_od_grid
@@ -96,6 +96,11 @@ class TickRecord:
     agents: np.ndarray = None          # [M+B,5] or [M,5]
     person_source: np.ndarray = None   # [B,Np] rows of `agents` (from person_count[b] on: not written)
     agents_after: np.ndarray = None    # as agents, after the move (persons_after is gathered from it)
+    # the reactive pool (BatchEpisode(pool_crowd=...)): what the tick's pool step wrote from `agents`, and the pedestrians'
+    # waypoint cursors around it
+    pool_next: np.ndarray = None           # [M,5]
+    pool_cursor_before: np.ndarray = None  # [M]
+    pool_cursor_after: np.ndarray = None   # [M]
 
 
 class BatchEpisode:
@@ -108,7 +113,7 @@ class BatchEpisode:
     # the same object for every shard
     FORWARDED = ("od_resolution", "device", "traj_params", "fov_angle", "order_hint", "plan_window", "obstacles_from_costmap",
                  "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost", "planner",
-                 "visibility", "shared", "pool")
+                 "visibility", "shared", "pool", "pool_crowd", "pool_waypoints", "pool_n_waypoints", "pool_speed")
 
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
@@ -120,7 +125,8 @@ class BatchEpisode:
                  person_speed: np.ndarray = None, person_groups: np.ndarray = None,
                  crowd_groups: CrowdGroupParams = None, world: World = None, outside_cost: int = 255,
                  planner: GlobalPlanParams = None, visibility: VisibilityParams = None,
-                 shared: SharedWorldParams = None, pool: np.ndarray = None):
+                 shared: SharedWorldParams = None, pool: np.ndarray = None, pool_crowd: PoolCrowdParams = None,
+                 pool_waypoints: np.ndarray = None, pool_n_waypoints: np.ndarray = None, pool_speed: np.ndarray = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -193,7 +199,14 @@ class BatchEpisode:
         everything behind it reads. The pool moves with constant velocity, in place; the caller may rewrite
         self.agents[:M] between ticks. With `metrics` the rows are refreshed and gathered a second time after the move, so
         that the sample sees the world as the period leaves it, the other robots at their new poses included. None (then
-        pool must be None too): nothing is allocated and nothing is launched."""
+        pool must be None too): nothing is allocated and nothing is launched.
+        pool_crowd: the pool moves as a reactive crowd (include/smpc_crowd_pool.h; needs shared and pool): every period one
+        smpc_crowd_pool_step_batch on the bins the tick's gather built (which are then sized for the larger of
+        shared.max_range and pool_crowd.interaction_range) takes the constant-velocity move's place: every pedestrian heads
+        for its current waypoint of pool_waypoints [M,K,2] / pool_n_waypoints [M] (e.g. scenes.pool_waypoints) and gives way
+        to the other pedestrians and, with shared.robots_as_people, to the robots, which it sees at the pose and speed the
+        period started from. pool_speed [M]: desired speeds (default pool_crowd.desired_speed for everybody). None (the
+        other three must be None too): nothing is allocated, nothing is launched and the pool walks straight on."""
         import torch
 
         self.torch = torch
@@ -212,6 +225,15 @@ class BatchEpisode:
             raise ValueError("visibility needs world: the sight lines run over the world map")
         if shared is None and pool is not None:
             raise ValueError("pool needs shared=SharedWorldParams(...)")
+        if pool_crowd is None:
+            given = sorted(k for k, v in dict(pool_waypoints=pool_waypoints, pool_n_waypoints=pool_n_waypoints,
+                                              pool_speed=pool_speed).items() if v is not None)
+            if given:
+                raise ValueError(f"{', '.join(given)} need pool_crowd=PoolCrowdParams(...)")
+        elif shared is None or pool is None:
+            raise ValueError("pool_crowd needs shared=SharedWorldParams(...) and pool [M,5]")
+        elif pool_waypoints is None or pool_n_waypoints is None:
+            raise ValueError("pool_crowd needs pool_waypoints [M,K,2] and pool_n_waypoints [M]")
         if shared is not None:
             if world is None:
                 raise ValueError("shared needs world: the robots and the pool share its floor")
@@ -238,7 +260,7 @@ class BatchEpisode:
         self._init_metrics(metrics, goal, plan, plan_len)
         self._init_crowd(crowd, person_waypoints, person_n_waypoints, person_speed, person_groups, crowd_groups)
         self._init_visibility(visibility)
-        self._init_shared(shared, pool)
+        self._init_shared(shared, pool, pool_crowd, pool_waypoints, pool_n_waypoints, pool_speed)
         self._bind()
         self.graph = None
         self.gstream = None
@@ -458,9 +480,11 @@ class BatchEpisode:
         self.seen_count = self._zeros(B, dtype=self.torch.int32)
         self.person_seen = self._zeros(B, Np, dtype=self.torch.uint8)
 
-    def _init_shared(self, shared, pool):
-        """The table of a shared world, the gather's bins and workspace, and what it writes besides persons / person_count."""
+    def _init_shared(self, shared, pool, pool_crowd=None, pool_waypoints=None, pool_n_waypoints=None, pool_speed=None):
+        """The table of a shared world, the gather's bins and workspace, and what it writes besides persons / person_count;
+        with pool_crowd what the pool's crowd step reads and writes."""
         self.shared = shared
+        self.pool_crowd = pool_crowd
         if shared is None:
             return
         torch, B = self.torch, self.B
@@ -474,11 +498,26 @@ class BatchEpisode:
         self.agent_self = (torch.arange(M, M + B, dtype=torch.int32, device=self.dev) if rows
                            else torch.full((B,), -1, dtype=torch.int32, device=self.dev))
         self.person_source = torch.full((B, int(self.persons.shape[1])), -1, dtype=torch.int32, device=self.dev)
-        self.shared_grid = shared.grid(self.world)
+        self.shared_grid = shared.grid(self.world) if pool_crowd is None else shared.grid(self.world, pool_crowd.interaction_range)
         nbytes = self.solver.nearest_workspace_bytes(M + rows, self.shared_grid[0], self.shared_grid[1])
         if nbytes == 0:
             raise ValueError("the shared world's table or bins exceed the library's limits (include/smpc_nearest.h)")
         self.nearest_workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.dev)
+        if pool_crowd is None:
+            return
+        if not self.od_shared:
+            raise ValueError("pool_crowd needs ONE ObstacleDistance grid for the floor (od_indexes [h,w], or obstacles_from_costmap)")
+        wp = np.ascontiguousarray(pool_waypoints, np.float64)
+        assert wp.ndim == 3 and wp.shape[0] == M and wp.shape[1] >= 1 and wp.shape[2] == 2, "pool_waypoints [M,K,2]"
+        assert np.shape(pool_n_waypoints) == (M,), "pool_n_waypoints [M]"
+        self.pool_wp = self._upload(wp, np.float64)
+        self.pool_nwp = self._upload(pool_n_waypoints, np.int32)
+        self.pool_next = self._zeros(M, 5)
+        self.pool_cursor = self._zeros(M, dtype=torch.int32)
+        self.pool_speed = None
+        if pool_speed is not None:
+            assert np.shape(pool_speed) == (M,), "pool_speed [M]"
+            self.pool_speed = self._upload(pool_speed, np.float64)
 
     def _bind(self):
         """Every struct a tick hands to the library, built once: every buffer the kernels read keeps its address from tick
@@ -515,6 +554,15 @@ class BatchEpisode:
                               {"agents": self.agents if int(self.agents.shape[0]) > 0 else None, "robot_pose": self.pose,
                                "self": self.agent_self, "workspace": self.nearest_workspace})
             c.nearest.workspace_bytes = int(self.nearest_workspace.numel())
+            if self.pool_crowd is not None and self.M > 0:  # the step reads the bins the tick's gather built: bins_ready
+                c.pool = point(BatchSolver.crowd_pool_c(self.pool_crowd, self.M, int(self.agents.shape[0]), int(self.pool_wp.shape[1]),
+                                                        prm.dt, gx, gy, origin, bin_size, 1, bins_ready=1),
+                               {"agents": self.agents, "waypoints": self.pool_wp, "n_waypoints": self.pool_nwp,
+                                "desired_speeds": self.pool_speed, "workspace": self.nearest_workspace})
+                c.pool.workspace_bytes = int(self.nearest_workspace.numel())
+                if self.od_indexes is not None and self.od_shared and self.od_h * self.od_w > 0:  # the world's one grid
+                    point(c.pool, {"od_indexes": self.od_indexes, "od_origin": self.od_origin})
+                    c.pool.od_height, c.pool.od_width, c.pool.od_resolution = int(self.od_h), int(self.od_w), float(self.od_resolution)
         if self.visibility is not None:  # the controller gets the persons in line of sight; the world keeps them all
             c.visibility = point(BatchSolver.visibility_c(self.visibility, B, Np, self.world.cells_x, self.world.cells_y, True,
                                                           self.resolution, 1),
@@ -629,6 +677,7 @@ class BatchEpisode:
                 return self.tick(record, timing)
         s, c, B, T = self.solver, self._c, self.B, self.T
         planned, windowed, crowd = self.plan is not None, self.plan_window is not None, self.crowd_params is not None
+        pool_crowd = self.shared is not None and self.pool_crowd is not None and self.M > 0
 
         def timed(stage):
             if timing is not None:
@@ -700,6 +749,13 @@ class BatchEpisode:
         if crowd:  # the persons' period: they see the pose it starts from and the command executed
             self._crowd_step()
             timed("crowd")
+        if pool_crowd:  # the pedestrians' period, from the table the tick's gather read: the robots where the period started
+            if record:
+                rec.update(self._host(pool_cursor_before="pool_cursor"))
+            s.crowd_pool_step_device(c.pool, self.pool_next.data_ptr(), self.pool_cursor.data_ptr())
+            timed("pool_crowd")
+            if record:
+                rec.update(self._host("pool_next", pool_cursor_after="pool_cursor"))
         v, w, th = self.cmd_vel[:, 0], self.cmd_vel[:, 1], self.pose[:, 2]
         moved = torch.stack([self.pose[:, 0] + v * torch.cos(th) * dt, self.pose[:, 1] + v * torch.sin(th) * dt, th + w * dt], dim=1)
         optimised = (self.cmd_source == 0)[:, None]
@@ -708,8 +764,11 @@ class BatchEpisode:
         self.speed.copy_(self.cmd_vel)
         if self.shared is not None:  # the pool walks on; what a robot perceives of it is gathered, not moved
             M = self.M
-            self.agents[:M, 0] += self.agents[:M, 2] * dt
-            self.agents[:M, 1] += self.agents[:M, 3] * dt
+            if pool_crowd:
+                self.agents[:M].copy_(self.pool_next)
+            else:
+                self.agents[:M, 0] += self.agents[:M, 2] * dt
+                self.agents[:M, 1] += self.agents[:M, 3] * dt
         elif not crowd:
             self.persons[:, :, 0] += self.persons[:, :, 2] * dt
             self.persons[:, :, 1] += self.persons[:, :, 3] * dt
@@ -759,6 +818,8 @@ class BatchEpisode:
             state += ("person_cursor",)
         if self.shared is not None:
             state += ("agents", "person_count", "person_source")
+            if self.pool_crowd is not None:
+                state += ("pool_cursor",)
         with torch.cuda.stream(self.gstream):
             saved = {k: getattr(self, k).clone() for k in state}
             ticks = self.ticks

@@ -72,6 +72,26 @@ class CrowdParams:
 
 
 @dataclass
+class PoolCrowdParams:
+    """The reactive crowd of a shared world (smpc_crowd_pool_in, include/smpc_crowd_pool.h; BatchEpisode(pool_crowd=...)):
+    the Social Force Model step that moves the shared pedestrians each control period. interaction_range: a pedestrian gives
+    way to every agent of the table (pedestrians and robots) within it, in metres; the other fields as CrowdParams."""
+    interaction_range: float = 5.0
+    goal_radius: float = 0.25
+    person_radius: float = 0.35
+    desired_speed: float = 0.6
+    cyclic: bool = True
+
+    def __post_init__(self):
+        if not (np.isfinite(self.interaction_range) and self.interaction_range > 0.0):
+            raise ValueError(f"PoolCrowdParams.interaction_range must be finite and > 0, got {self.interaction_range}")
+        if not self.goal_radius >= 0.0 or not self.person_radius >= 0.0:
+            raise ValueError(f"PoolCrowdParams radii must be >= 0, got {self.goal_radius}, {self.person_radius}")
+        if not self.desired_speed > 0.0:
+            raise ValueError(f"PoolCrowdParams.desired_speed must be > 0, got {self.desired_speed}")
+
+
+@dataclass
 class CrowdGroupParams:
     """The group force of the reactive crowd (smpc_crowd_groups, include/smpc.h; sfm.hpp forceFactorGroupGaze /
     GroupCoherence / GroupRepulsion): companions look towards each other, stay together and do not overlap."""
@@ -149,13 +169,16 @@ class SharedWorldParams:
         if self.max_people is not None and not 1 <= int(self.max_people) <= 64:
             raise ValueError(f"SharedWorldParams.max_people must be 1..64 (SMPC_MAX_AGENTS), got {self.max_people}")
 
-    def grid(self, world):
+    def grid(self, world, reach: float = None):
         """The bins of the gather on `world` (scenes.World): (grid_x, grid_y, origin [2], bin_size). The origin is the
         world's; bin_size = max(max_range * (1 + 2^-20), larger side / 256), so that there are at most 256 x 256 = 65536
-        bins (the library's limit); grid_x x grid_y bins cover the floor (at least one each)."""
+        bins (the library's limit); grid_x x grid_y bins cover the floor (at least one each). reach: a second range the
+        same bins must serve (PoolCrowdParams.interaction_range: the pool's crowd step reads the gather's bins):
+        max(max_range, reach) takes max_range's place."""
         res = float(world.resolution)
         width, height = world.cells_x * res, world.cells_y * res
-        bin_size = max(float(np.float64(self.max_range) * np.float64(1.0 + 2.0 ** -20)), max(width, height) / 256.0)
+        longest = self.max_range if reach is None else max(float(self.max_range), float(reach))
+        bin_size = max(float(np.float64(longest) * np.float64(1.0 + 2.0 ** -20)), max(width, height) / 256.0)
         grid_x = min(256, max(1, int(np.ceil(width / bin_size))))
         grid_y = min(256, max(1, int(np.ceil(height / bin_size))))
         return grid_x, grid_y, np.asarray(world.origin, np.float64).reshape(2).copy(), bin_size

@@ -556,3 +556,52 @@ def shared_pool(world: World, M: int, seed: int = 0x5EED0006, margin: float = 1.
     standing = uniform(seed, ids, 4)[:, 0] < standing_fraction
     lv = np.where(standing, 0.0, 0.2 + uniform(seed, ids, 5)[:, 0])
     return np.ascontiguousarray(np.stack([px, py, lv * np.cos(heading), lv * np.sin(heading), np.zeros(int(M))], axis=1))
+
+
+def pool_waypoints(world: World, pool: np.ndarray, K: int = 2, seed: int = 0x5EED0007, margin: float = 1.0, tries: int = 16):
+    """Waypoint lists for the pedestrians of a shared world (BatchEpisode(pool_crowd=..., pool_waypoints=...,
+    pool_n_waypoints=...)): (waypoints [M,K,2], n_waypoints [M]), a pure function of its arguments through `uniform` (keyed
+    by the person's index), by crowd_waypoints' law on the world map. Every waypoint lies on the floor, at least `margin`
+    from its border, on a free cell (cost 0). The first one lies straight ahead of the person's velocity, 0.5 .. 6 m away,
+    so an episode starts the way the constant-velocity pool does; the others are anywhere on the floor. Each is the first
+    of `tries` seeded candidates that qualifies (the first one falls back to the candidates of the others, all of them to
+    the free cell nearest the floor's centre). A person that stands, or a row that is not finite, gets no waypoints: it
+    stays where it is and only gives way."""
+    pool = np.asarray(pool, np.float64).reshape(-1, 5)
+    M, K = pool.shape[0], int(K)
+    ids = np.arange(M, dtype=np.int64)
+    res, Hx, Hy = float(world.resolution), world.cells_x, world.cells_y
+    ox, oy = float(world.origin[0]), float(world.origin[1])
+
+    def qualifies(x, y):                                                  # [M,tries] world points
+        with np.errstate(invalid="ignore"):
+            inside = (x >= ox + margin) & (x <= ox + Hx * res - margin) & (y >= oy + margin) & (y <= oy + Hy * res - margin)
+            ci = np.clip(np.floor((np.where(inside, x, ox) - ox) / res).astype(np.int64), 0, Hx - 1)
+            cj = np.clip(np.floor((np.where(inside, y, oy) - oy) / res).astype(np.int64), 0, Hy - 1)
+        return inside & (world.map[cj, ci] == 0)
+
+    def first_of(x, y, ok, fx, fy):                                       # the first qualifying candidate, else (fx, fy)
+        pick = np.argmax(ok, axis=1)[:, None]
+        any_ok = ok.any(axis=1)
+        return (np.where(any_ok, np.take_along_axis(x, pick, 1)[:, 0], fx), np.where(any_ok, np.take_along_axis(y, pick, 1)[:, 0], fy))
+
+    jj, ii = np.meshgrid(np.arange(Hy), np.arange(Hx), indexing="ij")
+    flat = int(np.argmin(np.where(world.map == 0, (ii + 0.5 - 0.5 * Hx) ** 2 + (jj + 0.5 - 0.5 * Hy) ** 2, np.inf)))
+    last_x, last_y = ox + ((flat % Hx) + 0.5) * res, oy + ((flat // Hx) + 0.5) * res
+    wp = np.zeros((M, K, 2))
+    anywhere = []
+    for k in range(K):
+        x = ox + margin + uniform(seed, ids, 200 + 2 * k, tries) * (Hx * res - 2.0 * margin)
+        y = oy + margin + uniform(seed, ids, 201 + 2 * k, tries) * (Hy * res - 2.0 * margin)
+        anywhere.append(first_of(x, y, qualifies(x, y), last_x, last_y))
+    speed = np.hypot(pool[:, 2], pool[:, 3])
+    walking = np.isfinite(pool[:, 0:4]).all(axis=1) & (speed > 0.0)
+    yaw = np.arctan2(np.where(walking, pool[:, 3], 0.0), np.where(walking, pool[:, 2], 1.0))
+    dist = 0.5 + 5.5 * uniform(seed, ids, 199, tries)
+    x = np.where(walking, pool[:, 0], ox)[:, None] + dist * np.cos(yaw)[:, None]
+    y = np.where(walking, pool[:, 1], oy)[:, None] + dist * np.sin(yaw)[:, None]
+    if K > 0:
+        wp[:, 0, 0], wp[:, 0, 1] = first_of(x, y, qualifies(x, y), *anywhere[0])
+    for k in range(1, K):
+        wp[:, k, 0], wp[:, k, 1] = anywhere[k]
+    return np.ascontiguousarray(wp), np.ascontiguousarray(np.where(walking, K, 0).astype(np.int32))

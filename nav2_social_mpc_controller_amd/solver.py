@@ -11,16 +11,17 @@ import os
 
 import numpy as np
 
-from . import _abi, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_visibility
+from . import _abi, _abi_crowd_pool, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_visibility
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
+from ._abi_crowd_pool import SmpcCrowdPoolIn
 from ._abi_global_plan import SmpcExtractPlanIn, SmpcGoalFieldIn
 from ._abi_local_costmap import SmpcLocalCostmapIn
 from ._abi_nearest import SmpcNearestIn
 from ._abi_visibility import SmpcVisibilityIn
-from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, TrajectorizerParams,
-                     VisibilityParams)
+from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, PoolCrowdParams,
+                     TrajectorizerParams, VisibilityParams)
 from .scenes import SceneBatch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -58,7 +59,8 @@ def load_library():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_abi.FUNCTIONS, **_abi.FIXED_SHAPE_FUNCTIONS, **_abi_local_costmap.FUNCTIONS,
-                                       **_abi_global_plan.FUNCTIONS, **_abi_visibility.FUNCTIONS, **_abi_nearest.FUNCTIONS}.items():
+                                       **_abi_global_plan.FUNCTIONS, **_abi_visibility.FUNCTIONS, **_abi_nearest.FUNCTIONS,
+                                       **_abi_crowd_pool.FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -815,6 +817,58 @@ class BatchSolver:
         asynchronous on the handle's stream."""
         assert ni.on_device == 1
         self._call("smpc_nearest_people_batch", ni, people_ptr, count_ptr, source_ptr or None)
+
+    # -- the reactive crowd of a shared world (smpc_crowd_pool_step_batch, include/smpc_crowd_pool.h) ----------------------
+    @staticmethod
+    def crowd_pool_c(cp: PoolCrowdParams, M: int, A: int, K: int, dt: float, grid_x: int, grid_y: int, grid_origin,
+                     bin_size: float, on_device: int, bins_ready: int = 0) -> SmpcCrowdPoolIn:
+        ci = SmpcCrowdPoolIn(M=int(M), A=int(A), K=int(K), on_device=int(on_device), cyclic=1 if cp.cyclic else 0,
+                             bins_ready=int(bins_ready), grid_x=int(grid_x), grid_y=int(grid_y), bin_size=float(bin_size),
+                             interaction_range=float(cp.interaction_range), dt=float(dt), goal_radius=cp.goal_radius,
+                             person_radius=cp.person_radius, desired_speed=cp.desired_speed)
+        ci.grid_origin[0], ci.grid_origin[1] = float(grid_origin[0]), float(grid_origin[1])
+        return ci
+
+    def crowd_pool_step(self, cp: PoolCrowdParams, dt: float, agents: np.ndarray, M: int, cursor: np.ndarray,
+                        waypoints: np.ndarray, n_waypoints: np.ndarray, grid_x: int, grid_y: int, grid_origin, bin_size: float,
+                        desired_speeds: np.ndarray = None, od_indexes: np.ndarray = None, od_origin: np.ndarray = None,
+                        od_resolution: float = None, next: np.ndarray = None):
+        """One control period of a shared world's pedestrians (host arrays): agents [A,5], of which rows 0 .. M-1 move and
+        the others are partners that stand in for themselves (the robots); cursor [M], waypoints [M,K,2], n_waypoints [M];
+        the bins (grid_x x grid_y of bin_size from grid_origin [2], e.g. params.SharedWorldParams.grid(world, reach)) do
+        not show in the result; optional desired_speeds [M] and one ObstacleDistance grid od_indexes [h,w] uint32 with
+        od_origin [2] and od_resolution. next [M,5]: the array before the call (default NaN). `agents` is left alone.
+        Returns (next [M,5], the updated copy of cursor)."""
+        agents = np.ascontiguousarray(agents, np.float64).reshape(-1, 5)
+        A, M = agents.shape[0], int(M)
+        rows = max(M, 0)
+        cursor = np.array(cursor, dtype=np.int32, order="C")
+        waypoints = np.ascontiguousarray(waypoints, np.float64)
+        n_waypoints = np.ascontiguousarray(n_waypoints, np.int32)
+        K = int(waypoints.shape[1])
+        assert cursor.shape == (rows,) and waypoints.shape == (rows, K, 2) and n_waypoints.shape == (rows,)
+        if desired_speeds is not None:
+            desired_speeds = np.ascontiguousarray(desired_speeds, np.float64)
+            assert desired_speeds.shape == (rows,)
+        next = np.full((rows, 5), np.nan) if next is None else np.array(next, dtype=np.float64, order="C")
+        assert next.shape == (rows, 5)
+        ci = point(self.crowd_pool_c(cp, M, A, K, dt, grid_x, grid_y, grid_origin, bin_size, 0),
+                   {"agents": agents if A > 0 else None, "waypoints": waypoints if rows > 0 else None,
+                    "n_waypoints": n_waypoints if rows > 0 else None, "desired_speeds": desired_speeds})
+        if od_indexes is not None:
+            grid = np.ascontiguousarray(od_indexes, np.uint32)
+            origin = np.ascontiguousarray(od_origin, np.float64).reshape(2)
+            assert grid.ndim == 2
+            point(ci, {"od_indexes": grid if grid.size else None, "od_origin": origin})
+            ci.od_height, ci.od_width, ci.od_resolution = int(grid.shape[0]), int(grid.shape[1]), float(od_resolution)
+        self._call("smpc_crowd_pool_step_batch", ci, _ptr(next) if rows > 0 else None, _ptr(cursor) if rows > 0 else None)
+        return next, cursor
+
+    def crowd_pool_step_device(self, ci: SmpcCrowdPoolIn, next_ptr: int, cursor_ptr: int):
+        """Device pointers in ci (on_device == 1, workspace included; bins_ready as the caller vouches) and for next and
+        cursor; asynchronous on the handle's stream."""
+        assert ci.on_device == 1
+        self._call("smpc_crowd_pool_step_batch", ci, next_ptr or None, cursor_ptr or None)
 
     # -- warm start / input formatting (SURVEY §8 row f2): format_to_optimize + TrajectoryMemory for B scenes -----
     def format_to_optimize(self, path: np.ndarray, cmds: np.ndarray, speed: np.ndarray, memory: dict,

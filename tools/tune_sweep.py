@@ -19,9 +19,11 @@ RANGE metres (default 10; BatchEpisode(visibility=VisibilityParams(max_range=RAN
 not planned around until it steps out. The metrics keep scoring the true persons.
 --shared-crowd M (with --world-plans): instead of a private list of persons per robot, one pool of M pedestrians
 (scenes.shared_pool) walks that floor and every robot perceives its nearest --agents of them within 10 m, or within RANGE with
---occlusion (BatchEpisode(shared=SharedWorldParams(robots_as_people=False), pool=...)). The pool does not react, so every
-parameter set meets the same crowd; the sets do not perceive each other's robots, which start from the same poses. The
-metrics score what a robot perceives.
+--occlusion (BatchEpisode(shared=SharedWorldParams(robots_as_people=False), pool=...)). The sets do not perceive each other's
+robots, which start from the same poses, and the pool does not see them either, so every parameter set meets the same
+crowd. The metrics score what a robot perceives. With --reactive the pool is a reactive crowd (BatchEpisode(pool_crowd=
+PoolCrowdParams()), waypoints from scenes.pool_waypoints): the pedestrians head for their waypoints and give way to each
+other within 5 m. --groups with it is refused: the pool's step has no group forces.
 """
 import argparse
 import os
@@ -58,8 +60,10 @@ def main():
     ap.add_argument("--shared-crowd", type=int, default=None, metavar="M",
                     help="with --world-plans: one pool of M pedestrians for all robots instead of a private list each")
     a = ap.parse_args()
-    if a.shared_crowd is not None and (not a.world_plans or a.reactive):
-        ap.error("--shared-crowd needs --world-plans and excludes --reactive")
+    if a.shared_crowd is not None and not a.world_plans:
+        ap.error("--shared-crowd needs --world-plans")
+    if a.shared_crowd is not None and a.groups:
+        ap.error("--shared-crowd excludes --groups: the pool's crowd step has no group forces")
     if a.groups and not a.reactive:
         ap.error("--groups needs --reactive")
     if a.occlusion is not None and not a.world_plans:
@@ -68,10 +72,10 @@ def main():
     import numpy as np
 
     from nav2_social_mpc_controller_amd.episode import BatchEpisode, arc_plans
-    from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, SharedWorldParams,
-                                                       TrajectorizerParams, VisibilityParams, scene_param_rows)
-    from nav2_social_mpc_controller_amd.scenes import (crowd_groups, crowd_waypoints, make_scenes, make_world, scenes_in_world, shared_pool,
-                                                       uniform, world_goals)
+    from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, PoolCrowdParams,
+                                                       SharedWorldParams, TrajectorizerParams, VisibilityParams, scene_param_rows)
+    from nav2_social_mpc_controller_amd.scenes import (crowd_groups, crowd_waypoints, make_scenes, make_world, pool_waypoints, scenes_in_world,
+                                                       shared_pool, uniform, world_goals)
     from nav2_social_mpc_controller_amd.solver import summarize_metrics
 
     prm = OptimizerParams.readme()
@@ -92,13 +96,16 @@ def main():
         if a.shared_crowd is not None:                                      # one crowd for every set, the same for each
             plans.update(shared=SharedWorldParams(max_range=a.occlusion if a.occlusion is not None else 10.0, robots_as_people=False),
                          pool=shared_pool(world, a.shared_crowd))
+            if a.reactive:                                                  # the pool reacts: one launch per tick on the gather's bins
+                wp, n_wp = pool_waypoints(world, plans["pool"])
+                plans.update(pool_crowd=PoolCrowdParams(), pool_waypoints=wp, pool_n_waypoints=n_wp)
     else:
         plan, plan_len = arc_plans(sc.pose0, 0.1 * w_ref, L=a.plan_poses)
         plans = dict(plan=plan, plan_len=plan_len)
     rows = scene_param_rows(list(sets.values()), np.repeat(np.arange(S), n))
     tp = TrajectorizerParams(desired_linear_vel=prm.desired_linear_vel, max_time=prm.max_time, time_step=prm.time_step)
     crowd = {}
-    if a.reactive:
+    if a.reactive and a.shared_crowd is None:
         wp, n_wp = crowd_waypoints(one)                                     # every set meets the same crowd
         if a.groups:
             gid, wp, n_wp = crowd_groups(one)
