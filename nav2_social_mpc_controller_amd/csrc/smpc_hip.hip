@@ -15,7 +15,7 @@
 //   smpc_stage_kernel<W>     the staging pass of the people block (smpc_stage_kernel.hpp);
 //   the probe kernels (smpc_probes.hpp);
 //   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window,
-//   metrics, crowd, local costmap, global plan, visibility, nearest agents, pool crowd).
+//   metrics, crowd, local costmap, global plan, visibility, nearest agents, pool crowd, sensed costmap).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -42,6 +42,8 @@
 #include "../../include/smpc_nearest.h"
 #include "smpc_crowd_pool.hpp"
 #include "../../include/smpc_crowd_pool.h"
+#include "smpc_sensed_costmap.hpp"
+#include "../../include/smpc_sensed_costmap.h"
 
 extern "C" {
 
@@ -792,6 +794,69 @@ int smpc_visible_people_batch(smpc_handle* h, const smpc_visibility_in* in, doub
       return SMPC_OK;
     }));
   }
+  return st.finish();
+}
+
+static_assert(smpc::kSensedReach == SMPC_SENSED_MAX_REACH && smpc::kScSide == SMPC_SENSED_MAX_SIZE && smpc::kScMaxD2 == SMPC_SENSED_MAX_D2,
+              "smpc_sensed_costmap.h and the kernel disagree on a limit");
+
+// floor(sqrt(v)) for 0 <= v < 2^31
+static int32_t isqrt_i32(int32_t v) {
+  int64_t r = (int64_t)std::sqrt((double)v);
+  while (r * r > v) --r;
+  while ((r + 1) * (r + 1) <= v) ++r;
+  return (int32_t)r;
+}
+
+int smpc_sensed_costmap_batch(smpc_handle* h, const smpc_sensed_costmap_in* in, uint8_t* costmap, uint8_t* beam_kind, int32_t* beam_cell) {
+  if (!h || !in || !costmap) { set_error("null handle / input / costmap"); return SMPC_ERR_INVALID_ARG; }
+  if (!in->world || !in->world_origin || !in->robot_pose || !in->people || !in->count || !in->cell || !in->beam_cells || !in->inflation_cost) {
+    set_error("null input array"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (in->B < 0 || in->Np < 1 || in->size_x < 1 || in->size_y < 1 || in->world_x < 1 || in->world_y < 1) {
+    set_error("bad B, Np < 1 or a non-positive window / world size"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) { set_error("resolution must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (in->n_beams < 1 || in->agent_d2 < 0 || in->d2_max < 0 || in->base > 1) {
+    set_error("n_beams < 1, a negative agent_d2 or d2_max, or base > 1"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (in->size_x > SMPC_SENSED_MAX_SIZE || in->size_y > SMPC_SENSED_MAX_SIZE) { set_error("a window side of more than 256 cells is not supported"); return SMPC_ERR_UNSUPPORTED; }
+  if (in->d2_max > SMPC_SENSED_MAX_D2) { set_error("d2_max > 1024 is not supported"); return SMPC_ERR_UNSUPPORTED; }
+  if (in->n_beams > SMPC_SENSED_MAX_BEAMS) { set_error("more than 4096 beams are not supported"); return SMPC_ERR_UNSUPPORTED; }
+  const int64_t world_cells = (int64_t)in->world_x * in->world_y;
+  if (world_cells >= (int64_t)1 << 31) { set_error("a world of 2^31 cells or more is not supported"); return SMPC_ERR_UNSUPPORTED; }
+  if (in->B == 0) return SMPC_OK;
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::SensedCostmapParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.B = in->B; p.Np = in->Np; p.size_x = in->size_x; p.size_y = in->size_y; p.world_x = in->world_x; p.world_y = in->world_y;
+  p.world_shared = in->world_shared ? 1 : 0; p.n_beams = in->n_beams;
+  p.agent_d2 = in->agent_d2; p.agent_r = isqrt_i32(in->agent_d2); p.d2_max = in->d2_max; p.r = isqrt_i32(in->d2_max);
+  p.base = in->base; p.outside = 0x01010101u * in->outside_cost;
+  p.occ.min_cost = in->occlusion_min_cost; p.occ.unknown = in->unknown_occludes ? 1u : 0u;
+  p.resolution = in->resolution;
+  const size_t B = in->B, Np = in->Np, nworld = in->world_shared ? 1 : B, cells = (size_t)in->size_x * (size_t)in->size_y, K = in->n_beams;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.world, in->world, nworld * (size_t)world_cells));
+  SMPC_TRY(st.in(p.world_origin, in->world_origin, nworld * 2));
+  SMPC_TRY(st.in(p.robot_pose, in->robot_pose, B * 3));
+  SMPC_TRY(st.in(p.people, in->people, B * Np * 5));
+  SMPC_TRY(st.in(p.count, in->count, B));
+  SMPC_TRY(st.in(p.cell, in->cell, B * 2));
+  SMPC_TRY(st.in(p.beam_cells, in->beam_cells, K * 2));
+  SMPC_TRY(st.in(p.inflation_cost, in->inflation_cost, (size_t)in->d2_max + 1));
+  SMPC_TRY(st.out(p.costmap, costmap, B * cells));
+  SMPC_TRY(st.out(p.beam_kind, beam_kind, B * K));
+  SMPC_TRY(st.out(p.beam_cell, beam_cell, B * K * 2));
+  // 16-byte stores need every window to start on a 16-byte boundary and every 8-byte half to lie in one window row
+  p.wide = (in->size_x % 8 == 0 && cells % 16 == 0 && reinterpret_cast<uintptr_t>(p.costmap) % 16 == 0) ? 1 : 0;
+  // one workgroup per robot (a loop over the robots inside the kernel kept every argument alive and spilled SGPRs); the
+  // grid is folded so that no dimension exceeds 2^15 x 2^16 workgroups
+  const size_t gx = B < 32768 ? B : 32768, gy = (B + gx - 1) / gx;
+  SMPC_TRY(st.timed([&] {
+    hipLaunchKernelGGL(smpc::smpc_sensed_costmap_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(smpc::kScThreads), 0, h->stream, p);
+    return SMPC_OK;
+  }));
   return st.finish();
 }
 

@@ -7,6 +7,8 @@
     ObstacleDistance grid (optional, once)   (src/optimizer.cpp:593-605, 'TODO')   -> smpc_obstacle_distance_batch
     rolling local costmap (optional)         (Nav2's LayeredCostmap::updateMap)    -> smpc_local_costmap_batch
     nearest-agent gather (optional)          (none: the library's own rule)        -> smpc_nearest_people_batch
+    sensed local costmap (optional)          (Nav2's ObstacleLayer + InflationLayer;
+                                              the library's own memoryless scan)   -> smpc_sensed_costmap_batch
     line-of-sight filter (optional)          (none: the library's own rule)        -> smpc_visible_people_batch
     global plans (optional, at the start and   (Nav2's planner server; the library's -> smpc_goal_field_batch,
     on replan(), never inside a tick)          own integer cost rule)                 smpc_extract_plan_batch
@@ -33,7 +35,9 @@ stood in for by the simplest thing that has the same shape:
     world map as the reference controller does on Nav2's rolling local costmap: every tick starts with
     smpc_local_costmap_batch, which moves each robot's window to its pose by whole cells and cuts the windows that moved
     out of the world map into the buffers the solve reads; the ObstacleDistance grid of the projection, the crowd and
-    the metrics is the world's, computed once.
+    the metrics is the world's, computed once. With BatchEpisode(sensor=SensorParams(...)) the windows hold what a
+    laser scan from the robot hits, walls, persons and other robots alike, inflated (smpc_sensed_costmap_batch), as the
+    reference's shipped local costmap does, in place of the cut of the pre-inflated world map.
 """
 from dataclasses import dataclass
 from types import SimpleNamespace
@@ -42,8 +46,8 @@ import numpy as np
 
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
-from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, PoolCrowdParams, TrajectorizerParams,
-                     SharedWorldParams, VisibilityParams, check_scene_param_rows)
+from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, PoolCrowdParams, SensorParams,
+                     TrajectorizerParams, SharedWorldParams, VisibilityParams, check_scene_param_rows)
 from .scenes import SceneBatch, World
 from .solver import BatchSolver, point, set_od_grid
 
@@ -101,6 +105,11 @@ class TickRecord:
     pool_next: np.ndarray = None           # [M,5]
     pool_cursor_before: np.ndarray = None  # [M]
     pool_cursor_after: np.ndarray = None   # [M]
+    # the sensed local costmaps (BatchEpisode(sensor=...)): what the tick's scan wrote from robot_pose, persons, person_count
+    # and costmap_cell, and what the tick's solve read
+    sensed_costmap: np.ndarray = None      # [B,size_y,size_x] uint8
+    beam_kind: np.ndarray = None           # [B,n_beams] uint8 enum smpc_beam_kind
+    beam_cell: np.ndarray = None           # [B,n_beams,2] int32
 
 
 class BatchEpisode:
@@ -113,7 +122,7 @@ class BatchEpisode:
     # the same object for every shard
     FORWARDED = ("od_resolution", "device", "traj_params", "fov_angle", "order_hint", "plan_window", "obstacles_from_costmap",
                  "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost", "planner",
-                 "visibility", "shared", "pool", "pool_crowd", "pool_waypoints", "pool_n_waypoints", "pool_speed")
+                 "visibility", "shared", "pool", "pool_crowd", "pool_waypoints", "pool_n_waypoints", "pool_speed", "sensor")
 
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
@@ -126,7 +135,8 @@ class BatchEpisode:
                  crowd_groups: CrowdGroupParams = None, world: World = None, outside_cost: int = 255,
                  planner: GlobalPlanParams = None, visibility: VisibilityParams = None,
                  shared: SharedWorldParams = None, pool: np.ndarray = None, pool_crowd: PoolCrowdParams = None,
-                 pool_waypoints: np.ndarray = None, pool_n_waypoints: np.ndarray = None, pool_speed: np.ndarray = None):
+                 pool_waypoints: np.ndarray = None, pool_n_waypoints: np.ndarray = None, pool_speed: np.ndarray = None,
+                 sensor: SensorParams = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -206,7 +216,14 @@ class BatchEpisode:
         for its current waypoint of pool_waypoints [M,K,2] / pool_n_waypoints [M] (e.g. scenes.pool_waypoints) and gives way
         to the other pedestrians and, with shared.robots_as_people, to the robots, which it sees at the pose and speed the
         period started from. pool_speed [M]: desired speeds (default pool_crowd.desired_speed for everybody). None (the
-        other three must be None too): nothing is allocated, nothing is launched and the pool walks straight on."""
+        other three must be None too): nothing is allocated, nothing is launched and the pool walks straight on.
+        sensor: the robots' windows are sensed (include/smpc_sensed_costmap.h): needs `world`. Every tick, after the roll, the
+        plan stage and the shared world's gather and before the line-of-sight filter, one smpc_sensed_costmap_batch casts
+        sensor.n_beams beams from self.pose over the world map and the true self.persons / self.person_count (with `shared`
+        the other robots among them), marks the cells they stop at in the windows at self.costmap_cell, inflates the marks
+        and rewrites self.costmap, which the solve reads; self.beam_kind [B,n_beams] (enum smpc_beam_kind) and
+        self.beam_cell [B,n_beams,2] hold each beam's outcome. sensor.base "world" keeps the world cut underneath. The
+        ObstacleDistance grid stays the world's. None: nothing is allocated and nothing is launched."""
         import torch
 
         self.torch = torch
@@ -223,6 +240,8 @@ class BatchEpisode:
                 raise ValueError("planner needs world, traj_params and goal [B,2]")
         if visibility is not None and world is None:
             raise ValueError("visibility needs world: the sight lines run over the world map")
+        if sensor is not None and world is None:
+            raise ValueError("sensor needs world: the scan runs over the world map")
         if shared is None and pool is not None:
             raise ValueError("pool needs shared=SharedWorldParams(...)")
         if pool_crowd is None:
@@ -261,6 +280,7 @@ class BatchEpisode:
         self._init_crowd(crowd, person_waypoints, person_n_waypoints, person_speed, person_groups, crowd_groups)
         self._init_visibility(visibility)
         self._init_shared(shared, pool, pool_crowd, pool_waypoints, pool_n_waypoints, pool_speed)
+        self._init_sensor(sensor)
         self._bind()
         self.graph = None
         self.gstream = None
@@ -519,6 +539,21 @@ class BatchEpisode:
             assert np.shape(pool_speed) == (M,), "pool_speed [M]"
             self.pool_speed = self._upload(pool_speed, np.float64)
 
+    def _init_sensor(self, sensor):
+        """The scan's tables (fixed for the episode) and what it writes besides the windows."""
+        self.sensor = sensor
+        if sensor is None:
+            return
+        if not sensor.supported(self.resolution):
+            raise ValueError("sensor: max_range beyond 127 cells or inflation_radius beyond 32 cells at the world's resolution")
+        if self.size_x > 256 or self.size_y > 256:
+            raise ValueError("sensor needs windows of at most 256 x 256 cells")
+        table, _ = sensor.inflation_table(self.resolution)
+        self.sensor_beams = self._upload(sensor.beam_cells(self.resolution), np.int32)     # [n_beams,2]
+        self.sensor_table = self._upload(table, np.uint8)                                  # [d2_max + 1]
+        self.beam_kind = self._zeros(self.B, int(sensor.n_beams), dtype=self.torch.uint8)
+        self.beam_cell = self._zeros(self.B, int(sensor.n_beams), 2, dtype=self.torch.int32)
+
     def _bind(self):
         """Every struct a tick hands to the library, built once: every buffer the kernels read keeps its address from tick
         to tick (the state is updated in place), and the stream lives in the solver's handle, so nothing here changes
@@ -569,6 +604,15 @@ class BatchEpisode:
                                  {"world": self.world_map, "world_origin": self.world_origin, "robot_pose": self.pose,
                                   "people": self.persons, "count": self.person_count})
             point(c.people, {"people": self.seen_persons, "count": self.seen_count})
+        if self.sensor is not None:  # the scan sees the true persons, whatever the controller is told of them
+            sp = self.sensor
+            c.sensor = point(BatchSolver.sensed_costmap_c(B, Np, self.size_x, self.size_y, self.world.cells_x, self.world.cells_y, True,
+                                                          self.resolution, 1, int(sp.n_beams), sp.agent_d2(self.resolution),
+                                                          int(self.sensor_table.numel()) - 1, sp.BASES.index(sp.base), self.outside_cost,
+                                                          sp.occlusion_min_cost, sp.unknown_occludes),
+                             {"world": self.world_map, "world_origin": self.world_origin, "robot_pose": self.pose,
+                              "people": self.persons, "count": self.person_count, "cell": self.costmap_cell,
+                              "beam_cells": self.sensor_beams, "inflation_cost": self.sensor_table})
         if self.fov_angle is not None:
             point(c.people, {"robot_pose": self.pose, "costmap_origin": self.costmap_origin})
             c.people.fov_angle, c.people.costmap_shared = float(self.fov_angle), 1 if self.costmap_shared else 0
@@ -707,6 +751,11 @@ class BatchEpisode:
             rec.update(self._host("persons", "person_count"))
             if crowd:
                 rec.update(self._host(cursor_before="person_cursor"))
+        if self.sensor is not None:  # what the scan hits, inflated, into the windows the solve reads
+            s.sensed_costmap_device(c.sensor, self.costmap.data_ptr(), self.beam_kind.data_ptr(), self.beam_cell.data_ptr())
+            timed("sensed_costmap")
+            if record:
+                rec.update(self._host("beam_kind", "beam_cell", sensed_costmap="costmap"))
         if self.visibility is not None:  # the persons in line of sight, directly in front of the filter that reads them
             s.visible_people_device(c.visibility, self.seen_persons.data_ptr(), self.seen_count.data_ptr(), self.person_seen.data_ptr())
             timed("visibility")

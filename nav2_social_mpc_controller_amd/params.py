@@ -154,6 +154,75 @@ class VisibilityParams:
 
 
 @dataclass
+class SensorParams:
+    """Sensed local costmaps (include/smpc_sensed_costmap.h; BatchEpisode(sensor=...)): every tick one 360-degree scan of
+    n_beams beams out to max_range metres marks the cells it stops at (world cells with cost >= occlusion_min_cost, 255 only
+    with unknown_occludes, and the discs of agent_radius metres around the agents), and the marks are inflated as Nav2's
+    InflationLayer does (inflation_radius, cost_scaling_factor, inscribed_radius). The defaults are the local costmap of the
+    reference's shipped parameter files: marking out to 2.5 m, inflation radius 0.7 m, scaling 3.0. base: "free" (the
+    reference's: no static layer) or "world" (the larger of the sensed cost and the world cut)."""
+    n_beams: int = 360
+    max_range: float = 2.5
+    agent_radius: float = 0.3
+    inflation_radius: float = 0.7
+    cost_scaling_factor: float = 3.0
+    inscribed_radius: float = 0.0
+    occlusion_min_cost: int = 254
+    unknown_occludes: bool = False
+    base: str = "free"
+
+    BASES = ("free", "world")
+
+    def __post_init__(self):
+        if not 1 <= int(self.n_beams) <= 4096:
+            raise ValueError(f"SensorParams.n_beams must be 1..4096, got {self.n_beams}")
+        for name in ("max_range", "cost_scaling_factor"):
+            v = getattr(self, name)
+            if not (np.isfinite(v) and v > 0.0):
+                raise ValueError(f"SensorParams.{name} must be finite and > 0, got {v}")
+        for name in ("agent_radius", "inflation_radius", "inscribed_radius"):
+            v = getattr(self, name)
+            if not (np.isfinite(v) and v >= 0.0):
+                raise ValueError(f"SensorParams.{name} must be finite and >= 0, got {v}")
+        if not 0 <= self.occlusion_min_cost <= 255:
+            raise ValueError(f"SensorParams.occlusion_min_cost must be 0..255, got {self.occlusion_min_cost}")
+        if self.base not in self.BASES:
+            raise ValueError(f"SensorParams.base must be one of {self.BASES}, got {self.base!r}")
+
+    def beam_cells(self, resolution: float) -> np.ndarray:
+        """[n_beams,2] int32: the end-cell offset of beam k is (rint(R cos t), rint(R sin t)) with t = 2 pi k / n_beams and
+        R = max_range / resolution, the range in cells."""
+        R = np.float64(self.max_range) / np.float64(resolution)
+        t = 2.0 * np.pi * np.arange(int(self.n_beams), dtype=np.float64) / np.float64(self.n_beams)
+        return np.stack([np.rint(R * np.cos(t)), np.rint(R * np.sin(t))], axis=1).astype(np.int32)
+
+    def agent_d2(self, resolution: float) -> int:
+        """An agent occupies the cells within agent_radius of its own: the squared radius in cells, rounded down."""
+        ra = np.float64(self.agent_radius) / np.float64(resolution)
+        return int(np.floor(ra * ra + 1e-9))
+
+    def inflation_table(self, resolution: float):
+        """(inflation_cost [d2_max + 1] uint8, d2_max): Nav2's InflationLayer::computeCost by squared cell distance: 254 at
+        distance 0, 253 within inscribed_radius, else uint8(252 * exp(-cost_scaling_factor * (d - inscribed_radius))) with d
+        in metres; out to r = floor(inflation_radius / resolution + 1e-9) cells, d2_max = r * r."""
+        r = int(np.floor(np.float64(self.inflation_radius) / np.float64(resolution) + 1e-9))
+        d2 = np.arange(r * r + 1, dtype=np.float64)
+        d = np.sqrt(d2) * np.float64(resolution)
+        cost = np.floor(252.0 * np.exp(-np.float64(self.cost_scaling_factor) * (d - np.float64(self.inscribed_radius))))
+        cost = np.where(d <= self.inscribed_radius, 253.0, np.minimum(cost, 252.0))
+        cost[0] = 254.0
+        return cost.astype(np.uint8), r * r
+
+    def supported(self, resolution: float) -> bool:
+        """Does the library take these on a map of this resolution (include/smpc_sensed_costmap.h's limits)? Every beam
+        within 127 cells per axis (the kernel gives longer ones the kind INVALID), an inflation radius of at most 32 cells
+        and an agent_d2 below 2^31."""
+        r = np.floor(np.float64(self.inflation_radius) / np.float64(resolution) + 1e-9)
+        ra = np.float64(self.agent_radius) / np.float64(resolution)
+        return bool(np.float64(self.max_range) / np.float64(resolution) <= 127.0 and r <= 32 and ra * ra + 1e-9 < 2.0 ** 31)
+
+
+@dataclass
 class SharedWorldParams:
     """One world for all robots of an episode (include/smpc_nearest.h; BatchEpisode(shared=..., pool=...)): every tick each
     robot is handed its at most max_people nearest agents within max_range (the detector's range in metres, VisibilityParams'

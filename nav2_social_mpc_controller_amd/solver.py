@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from . import _abi, _abi_crowd_pool, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_visibility
+from . import _abi, _abi_crowd_pool, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_sensed_costmap, _abi_visibility
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
@@ -19,6 +19,7 @@ from ._abi_crowd_pool import SmpcCrowdPoolIn
 from ._abi_global_plan import SmpcExtractPlanIn, SmpcGoalFieldIn
 from ._abi_local_costmap import SmpcLocalCostmapIn
 from ._abi_nearest import SmpcNearestIn
+from ._abi_sensed_costmap import SmpcSensedCostmapIn
 from ._abi_visibility import SmpcVisibilityIn
 from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, PoolCrowdParams,
                      TrajectorizerParams, VisibilityParams)
@@ -60,7 +61,7 @@ def load_library():
     lib = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_abi.FUNCTIONS, **_abi.FIXED_SHAPE_FUNCTIONS, **_abi_local_costmap.FUNCTIONS,
                                        **_abi_global_plan.FUNCTIONS, **_abi_visibility.FUNCTIONS, **_abi_nearest.FUNCTIONS,
-                                       **_abi_crowd_pool.FUNCTIONS}.items():
+                                       **_abi_crowd_pool.FUNCTIONS, **_abi_sensed_costmap.FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -772,6 +773,55 @@ class BatchSolver:
         handle's stream."""
         assert vi.on_device == 1
         self._call("smpc_visible_people_batch", vi, visible_ptr, visible_count_ptr, seen_ptr or None)
+
+    # -- sensed local costmaps (smpc_sensed_costmap_batch, include/smpc_sensed_costmap.h) ----------------------------------
+    @staticmethod
+    def sensed_costmap_c(B: int, Np: int, size_x: int, size_y: int, world_x: int, world_y: int, world_shared: bool, resolution: float,
+                         on_device: int, n_beams: int, agent_d2: int, d2_max: int, base: int = 0, outside_cost: int = 255,
+                         occlusion_min_cost: int = 254, unknown_occludes: bool = False) -> SmpcSensedCostmapIn:
+        if not 0 <= int(outside_cost) <= 255:
+            raise SmpcError(f"outside_cost must be 0..255, got {outside_cost}")
+        return SmpcSensedCostmapIn(B=int(B), Np=int(Np), on_device=int(on_device), size_x=int(size_x), size_y=int(size_y),
+                                   world_x=int(world_x), world_y=int(world_y), world_shared=1 if world_shared else 0,
+                                   n_beams=int(n_beams), agent_d2=int(agent_d2), d2_max=int(d2_max),
+                                   occlusion_min_cost=int(occlusion_min_cost), unknown_occludes=1 if unknown_occludes else 0,
+                                   base=int(base), outside_cost=int(outside_cost), resolution=float(resolution))
+
+    def sensed_costmap(self, world: np.ndarray, world_origin: np.ndarray, resolution: float, robot_pose: np.ndarray,
+                       people: np.ndarray, count: np.ndarray, cell: np.ndarray, size_x: int, size_y: int, beam_cells: np.ndarray,
+                       agent_d2: int, inflation_cost: np.ndarray, base: int = 0, outside_cost: int = 255,
+                       occlusion_min_cost: int = 254, unknown_occludes: bool = False, beams: bool = True):
+        """The sensed windows of B robots (host arrays): world [Hy,Hx] uint8 with world_origin [2] (one map shared by all
+        robots) or [B,Hy,Hx] with [B,2], robot_pose [B,3], people [B,Np,5], count [B] int32, cell [B,2] int32 (the world cell of
+        every window's cell (0,0)), beam_cells [n_beams,2] int32 (e.g. SensorParams.beam_cells), inflation_cost [d2_max + 1]
+        uint8 (e.g. SensorParams.inflation_table). Returns (costmap [B,size_y,size_x] uint8, beam_kind [B,n_beams] uint8:
+        _abi_sensed_costmap.BEAM_KINDS, beam_cell [B,n_beams,2] int32); the last two None with beams=False, which passes NULL
+        arrays."""
+        robot_pose = np.ascontiguousarray(robot_pose, np.float64)
+        people = np.ascontiguousarray(people, np.float64)
+        count = np.ascontiguousarray(count, np.int32)
+        cell = np.ascontiguousarray(cell, np.int32)
+        beam_cells = np.ascontiguousarray(beam_cells, np.int32)
+        inflation_cost = np.ascontiguousarray(inflation_cost, np.uint8)
+        B, Np, K = people.shape[0], people.shape[1], beam_cells.shape[0]
+        world, world_origin, shared = self._plan_world_arrays(world, world_origin, B)
+        assert people.shape == (B, Np, 5) and robot_pose.shape == (B, 3) and count.shape == (B,) and cell.shape == (B, 2)
+        assert beam_cells.shape == (K, 2) and inflation_cost.ndim == 1 and inflation_cost.size >= 1
+        si = point(self.sensed_costmap_c(B, Np, size_x, size_y, world.shape[-1], world.shape[-2], shared, resolution, 0, K, agent_d2,
+                                         inflation_cost.size - 1, base, outside_cost, occlusion_min_cost, unknown_occludes),
+                   {"world": world, "world_origin": world_origin, "robot_pose": robot_pose, "people": people, "count": count,
+                    "cell": cell, "beam_cells": beam_cells, "inflation_cost": inflation_cost})
+        costmap = np.zeros((B, int(size_y), int(size_x)), np.uint8)
+        kind = np.zeros((B, K), np.uint8) if beams else None
+        hit = np.zeros((B, K, 2), np.int32) if beams else None
+        self._call("smpc_sensed_costmap_batch", si, _ptr(costmap), _ptr(kind), _ptr(hit))
+        return costmap, kind, hit
+
+    def sensed_costmap_device(self, si: SmpcSensedCostmapIn, costmap_ptr: int, beam_kind_ptr: int = 0, beam_cell_ptr: int = 0):
+        """Device pointers in si (on_device == 1) and for costmap, beam_kind and beam_cell (0: none); asynchronous on the
+        handle's stream."""
+        assert si.on_device == 1
+        self._call("smpc_sensed_costmap_batch", si, costmap_ptr, beam_kind_ptr or None, beam_cell_ptr or None)
 
     # -- nearest-agent gather of a shared world (smpc_nearest_people_batch, include/smpc_nearest.h) -----------------------
     @staticmethod

@@ -5,7 +5,7 @@ BatchEpisode(scene_params=...)); the device scores every robot as it drives (Bat
 summarize_metrics means is printed per set. Nothing but the final [B,24] metrics rows leaves the device.
 
     python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]]
-                                [--world-plans [--occlusion [RANGE]] [--shared-crowd M]]
+                                [--world-plans [--occlusion [RANGE]] [--shared-crowd M] [--sensed-costmap]]
 
 --reactive: the persons are a reactive crowd (BatchEpisode(crowd=CrowdParams()), waypoints from scenes.crowd_waypoints)
 instead of walking straight on with constant velocity. --groups (with --reactive): half of the walking persons go in pairs
@@ -24,6 +24,10 @@ robots, which start from the same poses, and the pool does not see them either, 
 crowd. The metrics score what a robot perceives. With --reactive the pool is a reactive crowd (BatchEpisode(pool_crowd=
 PoolCrowdParams()), waypoints from scenes.pool_waypoints): the pedestrians head for their waypoints and give way to each
 other within 5 m. --groups with it is refused: the pool's step has no group forces.
+--sensed-costmap (with --world-plans): the windows the solve's ObstacleCost critic reads hold what a laser scan from the robot
+hits, walls and persons alike, inflated (BatchEpisode(sensor=SensorParams()): 360 beams out to 2.5 m, inflation 0.7 m with
+scaling 3.0 and no static layer, the local costmap of the reference's shipped parameter files), in place of the cut of the
+pre-inflated world map: the map obstacle_weight has to be tuned against.
 """
 import argparse
 import os
@@ -59,7 +63,11 @@ def main():
                     help="with --world-plans: line-of-sight filter of the perceived persons, detector range in metres (default 10)")
     ap.add_argument("--shared-crowd", type=int, default=None, metavar="M",
                     help="with --world-plans: one pool of M pedestrians for all robots instead of a private list each")
+    ap.add_argument("--sensed-costmap", action="store_true",
+                    help="with --world-plans: the local costmaps are sensed (a scan marks walls and persons, then inflation)")
     a = ap.parse_args()
+    if a.sensed_costmap and not a.world_plans:
+        ap.error("--sensed-costmap needs --world-plans")
     if a.shared_crowd is not None and not a.world_plans:
         ap.error("--shared-crowd needs --world-plans")
     if a.shared_crowd is not None and a.groups:
@@ -73,7 +81,7 @@ def main():
 
     from nav2_social_mpc_controller_amd.episode import BatchEpisode, arc_plans
     from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, PoolCrowdParams,
-                                                       SharedWorldParams, TrajectorizerParams, VisibilityParams, scene_param_rows)
+                                                       SensorParams, SharedWorldParams, TrajectorizerParams, VisibilityParams, scene_param_rows)
     from nav2_social_mpc_controller_amd.scenes import (crowd_groups, crowd_waypoints, make_scenes, make_world, pool_waypoints, scenes_in_world,
                                                        shared_pool, uniform, world_goals)
     from nav2_social_mpc_controller_amd.solver import summarize_metrics
@@ -93,6 +101,8 @@ def main():
                      plan_window=(4.0, 10.0))
         if a.occlusion is not None:
             plans["visibility"] = VisibilityParams(max_range=a.occlusion)
+        if a.sensed_costmap:
+            plans["sensor"] = SensorParams()
         if a.shared_crowd is not None:                                      # one crowd for every set, the same for each
             plans.update(shared=SharedWorldParams(max_range=a.occlusion if a.occlusion is not None else 10.0, robots_as_people=False),
                          pool=shared_pool(world, a.shared_crowd))
