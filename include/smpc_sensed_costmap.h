@@ -4,7 +4,8 @@
  * The reference controller is deployed on a rolling local costmap of two layers, an ObstacleLayer fed by one laser scan and
  * an InflationLayer, with no static layer: its costmap holds what the scanner hits, walls and legs alike, inflated. This
  * call is the library's own rule for that: a MEMORYLESS scan, rebuilt every tick from the world map and the agents it is
- * handed. Nav2's persistent marking and its ray-trace clearing over several scans are out of scope. It runs behind
+ * handed. Nav2's persistent marking and its ray-trace clearing over several scans are smpc_obstacle_memory_batch
+ * (include/smpc_obstacle_memory.h), which adds a state to this rule. It runs behind
  * smpc_local_costmap_batch, whose `cell` it reads, and writes the windows smpc_scene_batch reads. */
 #ifndef SMPC_SENSED_COSTMAP_H
 #define SMPC_SENSED_COSTMAP_H

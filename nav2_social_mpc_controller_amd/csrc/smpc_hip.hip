@@ -15,7 +15,7 @@
 //   smpc_stage_kernel<W>     the staging pass of the people block (smpc_stage_kernel.hpp);
 //   the probe kernels (smpc_probes.hpp);
 //   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window,
-//   metrics, crowd, local costmap, global plan, visibility, nearest agents, pool crowd, sensed costmap).
+//   metrics, crowd, local costmap, global plan, visibility, nearest agents, pool crowd, sensed costmap, obstacle memory).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -44,6 +44,8 @@
 #include "../../include/smpc_crowd_pool.h"
 #include "smpc_sensed_costmap.hpp"
 #include "../../include/smpc_sensed_costmap.h"
+#include "smpc_obstacle_memory.hpp"
+#include "../../include/smpc_obstacle_memory.h"
 
 extern "C" {
 
@@ -808,8 +810,8 @@ static int32_t isqrt_i32(int32_t v) {
   return (int32_t)r;
 }
 
-int smpc_sensed_costmap_batch(smpc_handle* h, const smpc_sensed_costmap_in* in, uint8_t* costmap, uint8_t* beam_kind, int32_t* beam_cell) {
-  if (!h || !in || !costmap) { set_error("null handle / input / costmap"); return SMPC_ERR_INVALID_ARG; }
+// the refusals of smpc_sensed_costmap_batch on its input struct (smpc_obstacle_memory_batch has the same on `scan`)
+static int sensed_check(const smpc_sensed_costmap_in* in) {
   if (!in->world || !in->world_origin || !in->robot_pose || !in->people || !in->count || !in->cell || !in->beam_cells || !in->inflation_cost) {
     set_error("null input array"); return SMPC_ERR_INVALID_ARG;
   }
@@ -823,11 +825,13 @@ int smpc_sensed_costmap_batch(smpc_handle* h, const smpc_sensed_costmap_in* in, 
   if (in->size_x > SMPC_SENSED_MAX_SIZE || in->size_y > SMPC_SENSED_MAX_SIZE) { set_error("a window side of more than 256 cells is not supported"); return SMPC_ERR_UNSUPPORTED; }
   if (in->d2_max > SMPC_SENSED_MAX_D2) { set_error("d2_max > 1024 is not supported"); return SMPC_ERR_UNSUPPORTED; }
   if (in->n_beams > SMPC_SENSED_MAX_BEAMS) { set_error("more than 4096 beams are not supported"); return SMPC_ERR_UNSUPPORTED; }
-  const int64_t world_cells = (int64_t)in->world_x * in->world_y;
-  if (world_cells >= (int64_t)1 << 31) { set_error("a world of 2^31 cells or more is not supported"); return SMPC_ERR_UNSUPPORTED; }
-  if (in->B == 0) return SMPC_OK;
-  SMPC_HIP_CHECK(hipSetDevice(h->device));
-  smpc::SensedCostmapParams p;
+  if ((int64_t)in->world_x * in->world_y >= (int64_t)1 << 31) { set_error("a world of 2^31 cells or more is not supported"); return SMPC_ERR_UNSUPPORTED; }
+  return SMPC_OK;
+}
+
+// the kernel's view of a checked input struct with B > 0: scalars, staged arrays and the store path
+static int sensed_params(Staging& st, const smpc_sensed_costmap_in* in, uint8_t* costmap, uint8_t* beam_kind, int32_t* beam_cell,
+                         smpc::SensedCostmapParams& p) {
   std::memset(&p, 0, sizeof(p));
   p.B = in->B; p.Np = in->Np; p.size_x = in->size_x; p.size_y = in->size_y; p.world_x = in->world_x; p.world_y = in->world_y;
   p.world_shared = in->world_shared ? 1 : 0; p.n_beams = in->n_beams;
@@ -836,8 +840,8 @@ int smpc_sensed_costmap_batch(smpc_handle* h, const smpc_sensed_costmap_in* in, 
   p.occ.min_cost = in->occlusion_min_cost; p.occ.unknown = in->unknown_occludes ? 1u : 0u;
   p.resolution = in->resolution;
   const size_t B = in->B, Np = in->Np, nworld = in->world_shared ? 1 : B, cells = (size_t)in->size_x * (size_t)in->size_y, K = in->n_beams;
-  Staging st(h, in->on_device);
-  SMPC_TRY(st.in(p.world, in->world, nworld * (size_t)world_cells));
+  const size_t world_cells = (size_t)in->world_x * (size_t)in->world_y;
+  SMPC_TRY(st.in(p.world, in->world, nworld * world_cells));
   SMPC_TRY(st.in(p.world_origin, in->world_origin, nworld * 2));
   SMPC_TRY(st.in(p.robot_pose, in->robot_pose, B * 3));
   SMPC_TRY(st.in(p.people, in->people, B * Np * 5));
@@ -850,11 +854,47 @@ int smpc_sensed_costmap_batch(smpc_handle* h, const smpc_sensed_costmap_in* in, 
   SMPC_TRY(st.out(p.beam_cell, beam_cell, B * K * 2));
   // 16-byte stores need every window to start on a 16-byte boundary and every 8-byte half to lie in one window row
   p.wide = (in->size_x % 8 == 0 && cells % 16 == 0 && reinterpret_cast<uintptr_t>(p.costmap) % 16 == 0) ? 1 : 0;
+  return SMPC_OK;
+}
+
+int smpc_sensed_costmap_batch(smpc_handle* h, const smpc_sensed_costmap_in* in, uint8_t* costmap, uint8_t* beam_kind, int32_t* beam_cell) {
+  if (!h || !in || !costmap) { set_error("null handle / input / costmap"); return SMPC_ERR_INVALID_ARG; }
+  SMPC_TRY(sensed_check(in));
+  if (in->B == 0) return SMPC_OK;
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::SensedCostmapParams p;
+  Staging st(h, in->on_device);
+  SMPC_TRY(sensed_params(st, in, costmap, beam_kind, beam_cell, p));
   // one workgroup per robot (a loop over the robots inside the kernel kept every argument alive and spilled SGPRs); the
   // grid is folded so that no dimension exceeds 2^15 x 2^16 workgroups
-  const size_t gx = B < 32768 ? B : 32768, gy = (B + gx - 1) / gx;
+  const size_t B = in->B, gx = B < 32768 ? B : 32768, gy = (B + gx - 1) / gx;
   SMPC_TRY(st.timed([&] {
     hipLaunchKernelGGL(smpc::smpc_sensed_costmap_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(smpc::kScThreads), 0, h->stream, p);
+    return SMPC_OK;
+  }));
+  return st.finish();
+}
+
+int smpc_obstacle_memory_batch(smpc_handle* h, const smpc_obstacle_memory_in* in, uint32_t* memory, int32_t* memory_cell, uint8_t* costmap,
+                               uint8_t* beam_kind, int32_t* beam_cell) {
+  if (!h || !in || !costmap) { set_error("null handle / input / costmap"); return SMPC_ERR_INVALID_ARG; }
+  if (!memory || !memory_cell) { set_error("null memory / memory_cell"); return SMPC_ERR_INVALID_ARG; }
+  SMPC_TRY(sensed_check(&in->scan));
+  if (in->mark_d2 < 0 || in->footprint_d2 < -1) { set_error("mark_d2 < 0 or footprint_d2 < -1"); return SMPC_ERR_INVALID_ARG; }
+  if (in->scan.B == 0) return SMPC_OK;
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::ObstacleMemoryParams p;
+  std::memset(&p, 0, sizeof(p));
+  Staging st(h, in->scan.on_device);
+  SMPC_TRY(sensed_params(st, &in->scan, costmap, beam_kind, beam_cell, p.sc));
+  p.mark_d2 = in->mark_d2; p.footprint_d2 = in->footprint_d2;
+  p.footprint_r = in->footprint_d2 >= 0 ? isqrt_i32(in->footprint_d2) : -1;
+  const size_t B = in->scan.B, words = ((size_t)in->scan.size_x + 31) / 32;
+  SMPC_TRY(st.inout(p.memory, memory, B * (size_t)in->scan.size_y * words));
+  SMPC_TRY(st.inout(p.memory_cell, memory_cell, B * 2));
+  const size_t gx = B < 32768 ? B : 32768, gy = (B + gx - 1) / gx;  // one workgroup per robot, folded as above
+  SMPC_TRY(st.timed([&] {
+    hipLaunchKernelGGL(smpc::smpc_obstacle_memory_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(smpc::kScThreads), 0, h->stream, p);
     return SMPC_OK;
   }));
   return st.finish();

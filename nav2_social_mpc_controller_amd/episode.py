@@ -9,6 +9,8 @@
     nearest-agent gather (optional)          (none: the library's own rule)        -> smpc_nearest_people_batch
     sensed local costmap (optional)          (Nav2's ObstacleLayer + InflationLayer;
                                               the library's own memoryless scan)   -> smpc_sensed_costmap_batch
+      ... with memory (optional)             (its persistent marking and ray-trace
+                                              clearing; the library's own rule)     -> smpc_obstacle_memory_batch
     line-of-sight filter (optional)          (none: the library's own rule)        -> smpc_visible_people_batch
     global plans (optional, at the start and   (Nav2's planner server; the library's -> smpc_goal_field_batch,
     on replan(), never inside a tick)          own integer cost rule)                 smpc_extract_plan_batch
@@ -46,8 +48,8 @@ import numpy as np
 
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
-from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, PoolCrowdParams, SensorParams,
-                     TrajectorizerParams, SharedWorldParams, VisibilityParams, check_scene_param_rows)
+from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, ObstacleMemoryParams, OptimizerParams, PoolCrowdParams,
+                     SensorParams, TrajectorizerParams, SharedWorldParams, VisibilityParams, check_scene_param_rows)
 from .scenes import SceneBatch, World
 from .solver import BatchSolver, point, set_od_grid
 
@@ -110,6 +112,11 @@ class TickRecord:
     sensed_costmap: np.ndarray = None      # [B,size_y,size_x] uint8
     beam_kind: np.ndarray = None           # [B,n_beams] uint8 enum smpc_beam_kind
     beam_cell: np.ndarray = None           # [B,n_beams,2] int32
+    # the scan's memory (BatchEpisode(sensor=..., sensor_memory=...)): the mark bitmaps and their window cells the tick's
+    # smpc_obstacle_memory_batch read, and the bitmaps it wrote (their window cells are costmap_cell)
+    obstacle_memory_before: np.ndarray = None       # [B,size_y,(size_x + 31) // 32] int32 (the bits of the call's uint32 words)
+    obstacle_memory_cell_before: np.ndarray = None  # [B,2] int32
+    obstacle_memory_after: np.ndarray = None        # as obstacle_memory_before
 
 
 class BatchEpisode:
@@ -122,7 +129,8 @@ class BatchEpisode:
     # the same object for every shard
     FORWARDED = ("od_resolution", "device", "traj_params", "fov_angle", "order_hint", "plan_window", "obstacles_from_costmap",
                  "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost", "planner",
-                 "visibility", "shared", "pool", "pool_crowd", "pool_waypoints", "pool_n_waypoints", "pool_speed", "sensor")
+                 "visibility", "shared", "pool", "pool_crowd", "pool_waypoints", "pool_n_waypoints", "pool_speed", "sensor",
+                 "sensor_memory")
 
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
@@ -136,7 +144,7 @@ class BatchEpisode:
                  planner: GlobalPlanParams = None, visibility: VisibilityParams = None,
                  shared: SharedWorldParams = None, pool: np.ndarray = None, pool_crowd: PoolCrowdParams = None,
                  pool_waypoints: np.ndarray = None, pool_n_waypoints: np.ndarray = None, pool_speed: np.ndarray = None,
-                 sensor: SensorParams = None):
+                 sensor: SensorParams = None, sensor_memory: ObstacleMemoryParams = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -223,7 +231,13 @@ class BatchEpisode:
         the other robots among them), marks the cells they stop at in the windows at self.costmap_cell, inflates the marks
         and rewrites self.costmap, which the solve reads; self.beam_kind [B,n_beams] (enum smpc_beam_kind) and
         self.beam_cell [B,n_beams,2] hold each beam's outcome. sensor.base "world" keeps the world cut underneath. The
-        ObstacleDistance grid stays the world's. None: nothing is allocated and nothing is launched."""
+        ObstacleDistance grid stays the world's. None: nothing is allocated and nothing is launched.
+        sensor_memory: the scan has a memory (include/smpc_obstacle_memory.h): needs `sensor`. One
+        smpc_obstacle_memory_batch takes the place of the tick's smpc_sensed_costmap_batch: the beams reach out to
+        sensor_memory.raytrace_range and clear the cells they pass, hits are marked within sensor.max_range, the cells
+        under the robot are cleared, and a mark stays until a beam passes it. The state is self.obstacle_memory
+        [B,size_y,(size_x + 31) // 32] int32 (one bit per window cell, zero at the start) and self.obstacle_memory_cell
+        [B,2]. None: nothing is allocated, nothing new is launched and the episode is the sensed one bit for bit."""
         import torch
 
         self.torch = torch
@@ -242,6 +256,8 @@ class BatchEpisode:
             raise ValueError("visibility needs world: the sight lines run over the world map")
         if sensor is not None and world is None:
             raise ValueError("sensor needs world: the scan runs over the world map")
+        if sensor_memory is not None and sensor is None:
+            raise ValueError("sensor_memory needs sensor=SensorParams(...): it is the scan's memory")
         if shared is None and pool is not None:
             raise ValueError("pool needs shared=SharedWorldParams(...)")
         if pool_crowd is None:
@@ -280,7 +296,7 @@ class BatchEpisode:
         self._init_crowd(crowd, person_waypoints, person_n_waypoints, person_speed, person_groups, crowd_groups)
         self._init_visibility(visibility)
         self._init_shared(shared, pool, pool_crowd, pool_waypoints, pool_n_waypoints, pool_speed)
-        self._init_sensor(sensor)
+        self._init_sensor(sensor, sensor_memory)
         self._bind()
         self.graph = None
         self.gstream = None
@@ -539,9 +555,10 @@ class BatchEpisode:
             assert np.shape(pool_speed) == (M,), "pool_speed [M]"
             self.pool_speed = self._upload(pool_speed, np.float64)
 
-    def _init_sensor(self, sensor):
-        """The scan's tables (fixed for the episode) and what it writes besides the windows."""
+    def _init_sensor(self, sensor, sensor_memory=None):
+        """The scan's tables (fixed for the episode), what it writes besides the windows, and its memory."""
         self.sensor = sensor
+        self.sensor_memory = sensor_memory
         if sensor is None:
             return
         if not sensor.supported(self.resolution):
@@ -549,7 +566,14 @@ class BatchEpisode:
         if self.size_x > 256 or self.size_y > 256:
             raise ValueError("sensor needs windows of at most 256 x 256 cells")
         table, _ = sensor.inflation_table(self.resolution)
-        self.sensor_beams = self._upload(sensor.beam_cells(self.resolution), np.int32)     # [n_beams,2]
+        beams = sensor.beam_cells(self.resolution)
+        if sensor_memory is not None:
+            if not sensor_memory.supported(sensor, self.resolution):
+                raise ValueError("sensor_memory: raytrace_range beyond 127 cells at the world's resolution")
+            beams = sensor_memory.beam_cells(sensor, self.resolution)                      # the same directions, out to the clearing range
+            self.obstacle_memory = self._zeros(self.B, self.size_y, (self.size_x + 31) // 32, dtype=self.torch.int32)
+            self.obstacle_memory_cell = self._zeros(self.B, 2, dtype=self.torch.int32)
+        self.sensor_beams = self._upload(beams, np.int32)                                  # [n_beams,2]
         self.sensor_table = self._upload(table, np.uint8)                                  # [d2_max + 1]
         self.beam_kind = self._zeros(self.B, int(sensor.n_beams), dtype=self.torch.uint8)
         self.beam_cell = self._zeros(self.B, int(sensor.n_beams), 2, dtype=self.torch.int32)
@@ -613,6 +637,9 @@ class BatchEpisode:
                              {"world": self.world_map, "world_origin": self.world_origin, "robot_pose": self.pose,
                               "people": self.persons, "count": self.person_count, "cell": self.costmap_cell,
                               "beam_cells": self.sensor_beams, "inflation_cost": self.sensor_table})
+            if self.sensor_memory is not None:
+                c.sensor_memory = BatchSolver.obstacle_memory_c(c.sensor, self.sensor_memory.mark_d2(sp, self.resolution),
+                                                                self.sensor_memory.footprint_d2(self.resolution))
         if self.fov_angle is not None:
             point(c.people, {"robot_pose": self.pose, "costmap_origin": self.costmap_origin})
             c.people.fov_angle, c.people.costmap_shared = float(self.fov_angle), 1 if self.costmap_shared else 0
@@ -751,7 +778,15 @@ class BatchEpisode:
             rec.update(self._host("persons", "person_count"))
             if crowd:
                 rec.update(self._host(cursor_before="person_cursor"))
-        if self.sensor is not None:  # what the scan hits, inflated, into the windows the solve reads
+        if self.sensor_memory is not None:  # the scan with its memory: marks stay until a beam passes them
+            if record:
+                rec.update(self._host(obstacle_memory_before="obstacle_memory", obstacle_memory_cell_before="obstacle_memory_cell"))
+            s.obstacle_memory_device(c.sensor_memory, self.obstacle_memory.data_ptr(), self.obstacle_memory_cell.data_ptr(),
+                                     self.costmap.data_ptr(), self.beam_kind.data_ptr(), self.beam_cell.data_ptr())
+            timed("obstacle_memory")
+            if record:
+                rec.update(self._host("beam_kind", "beam_cell", sensed_costmap="costmap", obstacle_memory_after="obstacle_memory"))
+        elif self.sensor is not None:  # what the scan hits, inflated, into the windows the solve reads
             s.sensed_costmap_device(c.sensor, self.costmap.data_ptr(), self.beam_kind.data_ptr(), self.beam_cell.data_ptr())
             timed("sensed_costmap")
             if record:
@@ -869,6 +904,8 @@ class BatchEpisode:
             state += ("agents", "person_count", "person_source")
             if self.pool_crowd is not None:
                 state += ("pool_cursor",)
+        if self.sensor_memory is not None:
+            state += ("obstacle_memory", "obstacle_memory_cell")
         with torch.cuda.stream(self.gstream):
             saved = {k: getattr(self, k).clone() for k in state}
             ticks = self.ticks

@@ -223,6 +223,59 @@ class SensorParams:
 
 
 @dataclass
+class ObstacleMemoryParams:
+    """Sensed local costmaps with memory (include/smpc_obstacle_memory.h; BatchEpisode(sensor=..., sensor_memory=...)): a
+    mark stays in the window until a later beam passes through its cell, as in Nav2's ObstacleLayer. The beams reach out to
+    raytrace_range metres and clear what they pass; a hit is marked only within the sensor's max_range (Nav2's
+    obstacle_max_range); the cells within footprint_radius of the robot's are cleared after marking (None: none). The
+    defaults are the reference's shipped local costmap: raytrace_max_range 3.0 m and the inscribed radius of its 0.48 m
+    square footprint."""
+    raytrace_range: float = 3.0
+    footprint_radius: float = 0.24
+
+    def __post_init__(self):
+        if not (np.isfinite(self.raytrace_range) and self.raytrace_range > 0.0):
+            raise ValueError(f"ObstacleMemoryParams.raytrace_range must be finite and > 0, got {self.raytrace_range}")
+        if self.footprint_radius is not None and not (np.isfinite(self.footprint_radius) and self.footprint_radius >= 0.0):
+            raise ValueError(f"ObstacleMemoryParams.footprint_radius must be None or finite and >= 0, got {self.footprint_radius}")
+
+    def check(self, sensor: "SensorParams"):
+        """raytrace_range >= sensor.max_range > 0: a ray clears at least as far as it marks."""
+        if not (np.isfinite(sensor.max_range) and sensor.max_range > 0.0 and self.raytrace_range >= sensor.max_range):
+            raise ValueError(f"ObstacleMemoryParams.raytrace_range ({self.raytrace_range}) must be >= SensorParams.max_range "
+                             f"({sensor.max_range}) > 0")
+
+    def beam_cells(self, sensor: "SensorParams", resolution: float) -> np.ndarray:
+        """[n_beams,2] int32: the sensor's beam directions (SensorParams.beam_cells) at raytrace_range."""
+        self.check(sensor)
+        R = np.float64(self.raytrace_range) / np.float64(resolution)
+        t = 2.0 * np.pi * np.arange(int(sensor.n_beams), dtype=np.float64) / np.float64(sensor.n_beams)
+        return np.stack([np.rint(R * np.cos(t)), np.rint(R * np.sin(t))], axis=1).astype(np.int32)
+
+    @staticmethod
+    def _d2(radius: float, resolution: float) -> int:
+        r = np.float64(radius) / np.float64(resolution)   # SensorParams.agent_d2's rounding
+        return int(np.floor(r * r + 1e-9))
+
+    def mark_d2(self, sensor: "SensorParams", resolution: float) -> int:
+        """A hit is marked within the sensor's max_range: the squared range in cells, rounded down."""
+        self.check(sensor)
+        return self._d2(sensor.max_range, resolution)
+
+    def footprint_d2(self, resolution: float) -> int:
+        """The squared footprint radius in cells, rounded down; -1 without a footprint."""
+        return -1 if self.footprint_radius is None else self._d2(self.footprint_radius, resolution)
+
+    def supported(self, sensor: "SensorParams", resolution: float) -> bool:
+        """Does the library cast these beams (include/smpc_sensed_costmap.h's reach of 127 cells per axis), with squared
+        radii that fit the struct's int32 fields?"""
+        fr = 0.0 if self.footprint_radius is None else np.float64(self.footprint_radius) / np.float64(resolution)
+        mr = np.float64(sensor.max_range) / np.float64(resolution)
+        return bool(np.float64(self.raytrace_range) / np.float64(resolution) <= 127.0 and fr * fr + 1e-9 < 2.0 ** 31
+                    and mr * mr + 1e-9 < 2.0 ** 31)
+
+
+@dataclass
 class SharedWorldParams:
     """One world for all robots of an episode (include/smpc_nearest.h; BatchEpisode(shared=..., pool=...)): every tick each
     robot is handed its at most max_people nearest agents within max_range (the detector's range in metres, VisibilityParams'

@@ -11,7 +11,8 @@ import os
 
 import numpy as np
 
-from . import _abi, _abi_crowd_pool, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_sensed_costmap, _abi_visibility
+from . import (_abi, _abi_crowd_pool, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_obstacle_memory, _abi_sensed_costmap,
+               _abi_visibility)
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
@@ -19,6 +20,7 @@ from ._abi_crowd_pool import SmpcCrowdPoolIn
 from ._abi_global_plan import SmpcExtractPlanIn, SmpcGoalFieldIn
 from ._abi_local_costmap import SmpcLocalCostmapIn
 from ._abi_nearest import SmpcNearestIn
+from ._abi_obstacle_memory import SmpcObstacleMemoryIn
 from ._abi_sensed_costmap import SmpcSensedCostmapIn
 from ._abi_visibility import SmpcVisibilityIn
 from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, PoolCrowdParams,
@@ -61,7 +63,8 @@ def load_library():
     lib = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_abi.FUNCTIONS, **_abi.FIXED_SHAPE_FUNCTIONS, **_abi_local_costmap.FUNCTIONS,
                                        **_abi_global_plan.FUNCTIONS, **_abi_visibility.FUNCTIONS, **_abi_nearest.FUNCTIONS,
-                                       **_abi_crowd_pool.FUNCTIONS, **_abi_sensed_costmap.FUNCTIONS}.items():
+                                       **_abi_crowd_pool.FUNCTIONS, **_abi_sensed_costmap.FUNCTIONS,
+                                       **_abi_obstacle_memory.FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -822,6 +825,55 @@ class BatchSolver:
         handle's stream."""
         assert si.on_device == 1
         self._call("smpc_sensed_costmap_batch", si, costmap_ptr, beam_kind_ptr or None, beam_cell_ptr or None)
+
+    # -- sensed local costmaps with memory (smpc_obstacle_memory_batch, include/smpc_obstacle_memory.h) ---------------------
+    @staticmethod
+    def obstacle_memory_c(scan: SmpcSensedCostmapIn, mark_d2: int, footprint_d2: int = -1) -> SmpcObstacleMemoryIn:
+        """The input struct around a copy of `scan` (sensed_costmap_c's, pointers and all)."""
+        mi = SmpcObstacleMemoryIn(mark_d2=int(mark_d2), footprint_d2=int(footprint_d2))
+        C.memmove(C.byref(mi.scan), C.byref(scan), C.sizeof(SmpcSensedCostmapIn))
+        return mi
+
+    def obstacle_memory(self, memory: np.ndarray, memory_cell: np.ndarray, world: np.ndarray, world_origin: np.ndarray, resolution: float,
+                        robot_pose: np.ndarray, people: np.ndarray, count: np.ndarray, cell: np.ndarray, size_x: int, size_y: int,
+                        beam_cells: np.ndarray, agent_d2: int, inflation_cost: np.ndarray, mark_d2: int, footprint_d2: int = -1,
+                        base: int = 0, outside_cost: int = 255, occlusion_min_cost: int = 254, unknown_occludes: bool = False,
+                        beams: bool = True):
+        """One call of the sensed windows with memory on host arrays: memory [B,size_y,(size_x + 31) // 32] uint32 and
+        memory_cell [B,2] int32 are the state the last call returned (zeros to start with; they are not modified), every
+        other argument as sensed_costmap's, with beam_cells out to the clearing range. Returns (costmap, beam_kind,
+        beam_cell, new memory, new memory_cell); the two beam arrays None with beams=False."""
+        robot_pose = np.ascontiguousarray(robot_pose, np.float64)
+        people = np.ascontiguousarray(people, np.float64)
+        count = np.ascontiguousarray(count, np.int32)
+        cell = np.ascontiguousarray(cell, np.int32)
+        beam_cells = np.ascontiguousarray(beam_cells, np.int32)
+        inflation_cost = np.ascontiguousarray(inflation_cost, np.uint8)
+        B, Np, K = people.shape[0], people.shape[1], beam_cells.shape[0]
+        memory = np.array(memory, np.uint32, order="C")
+        memory_cell = np.array(memory_cell, np.int32, order="C")
+        world, world_origin, shared = self._plan_world_arrays(world, world_origin, B)
+        assert people.shape == (B, Np, 5) and robot_pose.shape == (B, 3) and count.shape == (B,) and cell.shape == (B, 2)
+        assert beam_cells.shape == (K, 2) and inflation_cost.ndim == 1 and inflation_cost.size >= 1
+        assert memory.shape == (B, int(size_y), (int(size_x) + 31) // 32) and memory_cell.shape == (B, 2)
+        arrays = {"world": world, "world_origin": world_origin, "robot_pose": robot_pose, "people": people, "count": count,
+                  "cell": cell, "beam_cells": beam_cells, "inflation_cost": inflation_cost}
+        si = point(self.sensed_costmap_c(B, Np, size_x, size_y, world.shape[-1], world.shape[-2], shared, resolution, 0, K, agent_d2,
+                                         inflation_cost.size - 1, base, outside_cost, occlusion_min_cost, unknown_occludes), arrays)
+        mi = self.obstacle_memory_c(si, mark_d2, footprint_d2)
+        costmap = np.zeros((B, int(size_y), int(size_x)), np.uint8)
+        kind = np.zeros((B, K), np.uint8) if beams else None
+        hit = np.zeros((B, K, 2), np.int32) if beams else None
+        self._call("smpc_obstacle_memory_batch", mi, _ptr(memory), _ptr(memory_cell), _ptr(costmap), _ptr(kind), _ptr(hit))
+        del arrays
+        return costmap, kind, hit, memory, memory_cell
+
+    def obstacle_memory_device(self, mi: SmpcObstacleMemoryIn, memory_ptr: int, memory_cell_ptr: int, costmap_ptr: int,
+                               beam_kind_ptr: int = 0, beam_cell_ptr: int = 0):
+        """Device pointers in mi.scan (on_device == 1) and for memory, memory_cell (both read and written), costmap,
+        beam_kind and beam_cell (0: none); asynchronous on the handle's stream."""
+        assert mi.scan.on_device == 1
+        self._call("smpc_obstacle_memory_batch", mi, memory_ptr, memory_cell_ptr, costmap_ptr, beam_kind_ptr or None, beam_cell_ptr or None)
 
     # -- nearest-agent gather of a shared world (smpc_nearest_people_batch, include/smpc_nearest.h) -----------------------
     @staticmethod

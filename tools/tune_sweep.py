@@ -5,7 +5,7 @@ BatchEpisode(scene_params=...)); the device scores every robot as it drives (Bat
 summarize_metrics means is printed per set. Nothing but the final [B,24] metrics rows leaves the device.
 
     python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]]
-                                [--world-plans [--occlusion [RANGE]] [--shared-crowd M] [--sensed-costmap]]
+                                [--world-plans [--occlusion [RANGE]] [--shared-crowd M] [--sensed-costmap [--obstacle-memory]]]
 
 --reactive: the persons are a reactive crowd (BatchEpisode(crowd=CrowdParams()), waypoints from scenes.crowd_waypoints)
 instead of walking straight on with constant velocity. --groups (with --reactive): half of the walking persons go in pairs
@@ -28,6 +28,9 @@ other within 5 m. --groups with it is refused: the pool's step has no group forc
 hits, walls and persons alike, inflated (BatchEpisode(sensor=SensorParams()): 360 beams out to 2.5 m, inflation 0.7 m with
 scaling 3.0 and no static layer, the local costmap of the reference's shipped parameter files), in place of the cut of the
 pre-inflated world map: the map obstacle_weight has to be tuned against.
+--obstacle-memory (with --sensed-costmap): the scan has Nav2's memory (BatchEpisode(sensor_memory=ObstacleMemoryParams()):
+a mark stays until a later beam passes its cell, the beams clear out to 3.0 m and mark out to 2.5 m, the cells under the
+robot are always free), so a person who steps out of sight leaves lethal cells where last seen, as on the reference's costmap.
 """
 import argparse
 import os
@@ -65,7 +68,11 @@ def main():
                     help="with --world-plans: one pool of M pedestrians for all robots instead of a private list each")
     ap.add_argument("--sensed-costmap", action="store_true",
                     help="with --world-plans: the local costmaps are sensed (a scan marks walls and persons, then inflation)")
+    ap.add_argument("--obstacle-memory", action="store_true",
+                    help="with --sensed-costmap: marks persist until a beam clears them (Nav2's ObstacleLayer)")
     a = ap.parse_args()
+    if a.obstacle_memory and not a.sensed_costmap:
+        ap.error("--obstacle-memory needs --sensed-costmap")
     if a.sensed_costmap and not a.world_plans:
         ap.error("--sensed-costmap needs --world-plans")
     if a.shared_crowd is not None and not a.world_plans:
@@ -80,8 +87,8 @@ def main():
     import numpy as np
 
     from nav2_social_mpc_controller_amd.episode import BatchEpisode, arc_plans
-    from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, PoolCrowdParams,
-                                                       SensorParams, SharedWorldParams, TrajectorizerParams, VisibilityParams, scene_param_rows)
+    from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, ObstacleMemoryParams, OptimizerParams,
+                                                       PoolCrowdParams, SensorParams, SharedWorldParams, TrajectorizerParams, VisibilityParams, scene_param_rows)
     from nav2_social_mpc_controller_amd.scenes import (crowd_groups, crowd_waypoints, make_scenes, make_world, pool_waypoints, scenes_in_world,
                                                        shared_pool, uniform, world_goals)
     from nav2_social_mpc_controller_amd.solver import summarize_metrics
@@ -103,6 +110,8 @@ def main():
             plans["visibility"] = VisibilityParams(max_range=a.occlusion)
         if a.sensed_costmap:
             plans["sensor"] = SensorParams()
+            if a.obstacle_memory:
+                plans["sensor_memory"] = ObstacleMemoryParams()
         if a.shared_crowd is not None:                                      # one crowd for every set, the same for each
             plans.update(shared=SharedWorldParams(max_range=a.occlusion if a.occlusion is not None else 10.0, robots_as_people=False),
                          pool=shared_pool(world, a.shared_crowd))
