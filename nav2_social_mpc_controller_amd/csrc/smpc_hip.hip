@@ -15,7 +15,8 @@
 //   smpc_stage_kernel<W>     the staging pass of the people block (smpc_stage_kernel.hpp);
 //   the probe kernels (smpc_probes.hpp);
 //   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window,
-//   metrics, crowd, local costmap, global plan, visibility, nearest agents, pool crowd, sensed costmap, obstacle memory).
+//   metrics, crowd, local costmap, global plan, visibility, nearest agents, pool crowd, sensed costmap, obstacle memory,
+//   people tracks).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -46,6 +47,8 @@
 #include "../../include/smpc_sensed_costmap.h"
 #include "smpc_obstacle_memory.hpp"
 #include "../../include/smpc_obstacle_memory.h"
+#include "smpc_tracker.hpp"
+#include "../../include/smpc_tracker.h"
 
 extern "C" {
 
@@ -895,6 +898,49 @@ int smpc_obstacle_memory_batch(smpc_handle* h, const smpc_obstacle_memory_in* in
   const size_t gx = B < 32768 ? B : 32768, gy = (B + gx - 1) / gx;  // one workgroup per robot, folded as above
   SMPC_TRY(st.timed([&] {
     hipLaunchKernelGGL(smpc::smpc_obstacle_memory_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(smpc::kScThreads), 0, h->stream, p);
+    return SMPC_OK;
+  }));
+  return st.finish();
+}
+
+int smpc_track_people_batch(smpc_handle* h, const smpc_tracker_in* in, double* tracks, int32_t* track_meta, int32_t* next_id, double* people,
+                            int32_t* count, int32_t* out_track) {
+  if (!h || !in || !tracks || !track_meta || !next_id || !people || !count) {
+    set_error("null handle / input / tracks / track_meta / next_id / people / count"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (!in->detections || !in->det_count || !in->robot_pose) { set_error("null input array"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B < 0 || in->Nd < 1 || in->Nt < 1 || in->Np < 1) { set_error("bad B, or Nd, Nt or Np < 1"); return SMPC_ERR_INVALID_ARG; }
+  if (in->confirm_hits < 1 || in->max_missed < 0) { set_error("confirm_hits < 1 or max_missed < 0"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->dt) || !(in->dt > 0.0)) { set_error("dt must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->gate) || !(in->gate > 0.0)) { set_error("gate must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->alpha) || !(in->alpha >= 0.0) || !std::isfinite(in->gain) || !(in->gain >= 0.0)) {
+    set_error("alpha and gain must be finite and >= 0"); return SMPC_ERR_INVALID_ARG;
+  }
+  // the kernel's bounds: lane i owns slot i, detection i and output rank i of one wavefront
+  if (in->Nd > SMPC_MAX_AGENTS || in->Nt > SMPC_MAX_AGENTS || in->Np > SMPC_MAX_AGENTS) {
+    set_error("Nd, Nt or Np > 64 is not supported"); return SMPC_ERR_UNSUPPORTED;
+  }
+  if (in->B == 0) return SMPC_OK;
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::TrackerParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.B = in->B; p.Nd = in->Nd; p.Nt = in->Nt; p.Np = in->Np; p.confirm_hits = in->confirm_hits; p.max_missed = in->max_missed;
+  p.dt = in->dt; p.alpha = in->alpha; p.gain = in->gain; p.gate = in->gate;
+  const size_t B = in->B, Nd = in->Nd, Nt = in->Nt, Np = in->Np;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.detections, in->detections, B * Nd * 5));
+  SMPC_TRY(st.in(p.det_count, in->det_count, B));
+  SMPC_TRY(st.in(p.robot_pose, in->robot_pose, B * 3));
+  SMPC_TRY(st.inout(p.tracks, tracks, B * Nt * 4));
+  SMPC_TRY(st.inout(p.meta, track_meta, B * Nt * 4));
+  SMPC_TRY(st.inout(p.next_id, next_id, B));
+  // read and written: the rows the kernel leaves alone keep the caller's bytes on the way through device memory too
+  SMPC_TRY(st.inout(p.people, people, B * Np * 5));
+  SMPC_TRY(st.out(p.count, count, B));
+  SMPC_TRY(st.inout(p.out_track, out_track, B * Np * 2));
+  const size_t per_block = smpc::kTkThreads / 64;
+  SMPC_TRY(st.timed([&] {
+    hipLaunchKernelGGL(smpc::smpc_track_people_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kTkThreads), 0, h->stream, p);
     return SMPC_OK;
   }));
   return st.finish();

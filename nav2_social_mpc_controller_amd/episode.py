@@ -12,6 +12,8 @@
       ... with memory (optional)             (its persistent marking and ray-trace
                                               clearing; the library's own rule)     -> smpc_obstacle_memory_batch
     line-of-sight filter (optional)          (none: the library's own rule)        -> smpc_visible_people_batch
+    people tracks (optional)                 (the deployment's own tracker behind
+                                              people_msgs::People; the library's rule) -> smpc_track_people_batch
     global plans (optional, at the start and   (Nav2's planner server; the library's -> smpc_goal_field_batch,
     on replan(), never inside a tick)          own integer cost rule)                 smpc_extract_plan_batch
     project_people                           (src/optimizer.cpp:554-728)           -> smpc_project_people_batch
@@ -49,7 +51,7 @@ import numpy as np
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
 from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, ObstacleMemoryParams, OptimizerParams, PoolCrowdParams,
-                     SensorParams, TrajectorizerParams, SharedWorldParams, VisibilityParams, check_scene_param_rows)
+                     SensorParams, TrackerParams, TrajectorizerParams, SharedWorldParams, VisibilityParams, check_scene_param_rows)
 from .scenes import SceneBatch, World
 from .solver import BatchSolver, point, set_od_grid
 
@@ -117,6 +119,18 @@ class TickRecord:
     obstacle_memory_before: np.ndarray = None       # [B,size_y,(size_x + 31) // 32] int32 (the bits of the call's uint32 words)
     obstacle_memory_cell_before: np.ndarray = None  # [B,2] int32
     obstacle_memory_after: np.ndarray = None        # as obstacle_memory_before
+    # the people tracks (BatchEpisode(tracker=...)): the state the tick's smpc_track_people_batch read (its detections are
+    # seen_persons / seen_count with visibility, else persons / person_count) and wrote, and what the tick's
+    # people_to_status read
+    tracks_before: np.ndarray = None          # [B,slots,4] x, y, vx, vy
+    track_meta_before: np.ndarray = None      # [B,slots,4] int32 state, hits, missed, id
+    track_next_id_before: np.ndarray = None   # [B] int32
+    tracks_after: np.ndarray = None
+    track_meta_after: np.ndarray = None
+    track_next_id_after: np.ndarray = None
+    tracked_persons: np.ndarray = None        # [B,Np,5] (rows from tracked_count[b] on: not written)
+    tracked_count: np.ndarray = None          # [B]
+    tracked_source: np.ndarray = None         # [B,Np,2] int32 slot, id (rows from tracked_count[b] on: not written)
 
 
 class BatchEpisode:
@@ -130,7 +144,7 @@ class BatchEpisode:
     FORWARDED = ("od_resolution", "device", "traj_params", "fov_angle", "order_hint", "plan_window", "obstacles_from_costmap",
                  "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost", "planner",
                  "visibility", "shared", "pool", "pool_crowd", "pool_waypoints", "pool_n_waypoints", "pool_speed", "sensor",
-                 "sensor_memory")
+                 "sensor_memory", "tracker")
 
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
@@ -144,7 +158,7 @@ class BatchEpisode:
                  planner: GlobalPlanParams = None, visibility: VisibilityParams = None,
                  shared: SharedWorldParams = None, pool: np.ndarray = None, pool_crowd: PoolCrowdParams = None,
                  pool_waypoints: np.ndarray = None, pool_n_waypoints: np.ndarray = None, pool_speed: np.ndarray = None,
-                 sensor: SensorParams = None, sensor_memory: ObstacleMemoryParams = None):
+                 sensor: SensorParams = None, sensor_memory: ObstacleMemoryParams = None, tracker: TrackerParams = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -237,7 +251,17 @@ class BatchEpisode:
         sensor_memory.raytrace_range and clear the cells they pass, hits are marked within sensor.max_range, the cells
         under the robot are cleared, and a mark stays until a beam passes it. The state is self.obstacle_memory
         [B,size_y,(size_x + 31) // 32] int32 (one bit per window cell, zero at the start) and self.obstacle_memory_cell
-        [B,2]. None: nothing is allocated, nothing new is launched and the episode is the sensed one bit for bit."""
+        [B,2]. None: nothing is allocated, nothing new is launched and the episode is the sensed one bit for bit.
+        tracker: the controller is handed tracks instead of the simulator's rows (include/smpc_tracker.h). Every tick,
+        directly in front of people_to_status, one smpc_track_people_batch associates the tick's detections (with
+        `visibility` self.seen_persons / self.seen_count, else self.persons / self.person_count; only x and y are read) with
+        the robot's tracks, estimates their velocity from positions alone with dt = params.dt, coasts a track whose person
+        is not detected for at most tracker.max_missed ticks, and writes the confirmed tracks nearest first into
+        self.tracked_persons [B,Np,5] / self.tracked_count [B] (self.tracked_source [B,Np,2]: slot and id), which
+        people_to_status reads. The state is self.tracks [B,slots,4], self.track_meta [B,slots,4] int32 and
+        self.track_next_id [B] int32, zero at the start. The world model, the crowd steps, the scan and the metrics keep
+        reading the true self.persons. None: nothing is allocated, nothing is launched and the episode is the one without
+        bit for bit."""
         import torch
 
         self.torch = torch
@@ -297,6 +321,7 @@ class BatchEpisode:
         self._init_visibility(visibility)
         self._init_shared(shared, pool, pool_crowd, pool_waypoints, pool_n_waypoints, pool_speed)
         self._init_sensor(sensor, sensor_memory)
+        self._init_tracker(tracker)
         self._bind()
         self.graph = None
         self.gstream = None
@@ -516,6 +541,24 @@ class BatchEpisode:
         self.seen_count = self._zeros(B, dtype=self.torch.int32)
         self.person_seen = self._zeros(B, Np, dtype=self.torch.uint8)
 
+    def _init_tracker(self, tracker):
+        """The tracks of every robot (zero: no tracks) and what the tracker writes every tick: fixed addresses,
+        people_to_status reads the first two."""
+        self.tracker = tracker
+        if tracker is None:
+            return
+        if not isinstance(tracker, TrackerParams):
+            raise ValueError("tracker must be a TrackerParams")
+        if not tracker.supported(self.params.dt):
+            raise ValueError("tracker: more than 64 slots, or no finite beta / dt with params.dt")
+        B, Np, Nt = self.B, int(self.persons.shape[1]), int(tracker.slots)
+        self.tracks = self._zeros(B, Nt, 4)
+        self.track_meta = self._zeros(B, Nt, 4, dtype=self.torch.int32)
+        self.track_next_id = self._zeros(B, dtype=self.torch.int32)
+        self.tracked_persons = self._zeros(B, Np, 5)
+        self.tracked_count = self._zeros(B, dtype=self.torch.int32)
+        self.tracked_source = self._zeros(B, Np, 2, dtype=self.torch.int32)
+
     def _init_shared(self, shared, pool, pool_crowd=None, pool_waypoints=None, pool_n_waypoints=None, pool_speed=None):
         """The table of a shared world, the gather's bins and workspace, and what it writes besides persons / person_count;
         with pool_crowd what the pool's crowd step reads and writes."""
@@ -628,6 +671,10 @@ class BatchEpisode:
                                  {"world": self.world_map, "world_origin": self.world_origin, "robot_pose": self.pose,
                                   "people": self.persons, "count": self.person_count})
             point(c.people, {"people": self.seen_persons, "count": self.seen_count})
+        if self.tracker is not None:  # the controller gets tracks of what is detected: the last stage in front of the filter
+            c.tracker = point(BatchSolver.tracker_c(self.tracker, B, Np, Np, prm.dt, 1),
+                              {"detections": c.people.people, "det_count": c.people.count, "robot_pose": self.pose})
+            point(c.people, {"people": self.tracked_persons, "count": self.tracked_count})
         if self.sensor is not None:  # the scan sees the true persons, whatever the controller is told of them
             sp = self.sensor
             c.sensor = point(BatchSolver.sensed_costmap_c(B, Np, self.size_x, self.size_y, self.world.cells_x, self.world.cells_y, True,
@@ -796,6 +843,15 @@ class BatchEpisode:
             timed("visibility")
             if record:
                 rec.update(self._host("person_seen", "seen_count", "seen_persons"))
+        if self.tracker is not None:  # tracks of the detections: velocities from positions, and a memory of who stepped out of sight
+            if record:
+                rec.update(self._host(tracks_before="tracks", track_meta_before="track_meta", track_next_id_before="track_next_id"))
+            s.track_people_device(c.tracker, self.tracks.data_ptr(), self.track_meta.data_ptr(), self.track_next_id.data_ptr(),
+                                  self.tracked_persons.data_ptr(), self.tracked_count.data_ptr(), self.tracked_source.data_ptr())
+            timed("tracker")
+            if record:
+                rec.update(self._host("tracked_persons", "tracked_count", "tracked_source", tracks_after="tracks",
+                                      track_meta_after="track_meta", track_next_id_after="track_next_id"))
         # 0. field-of-view filter + people_to_status
         s.people_to_status_device(c.people, self.people.data_ptr(), self.has_people.data_ptr())
         timed("people")
@@ -906,6 +962,8 @@ class BatchEpisode:
                 state += ("pool_cursor",)
         if self.sensor_memory is not None:
             state += ("obstacle_memory", "obstacle_memory_cell")
+        if self.tracker is not None:
+            state += ("tracks", "track_meta", "track_next_id")
         with torch.cuda.stream(self.gstream):
             saved = {k: getattr(self, k).clone() for k in state}
             ticks = self.ticks

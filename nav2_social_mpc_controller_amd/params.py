@@ -276,6 +276,49 @@ class ObstacleMemoryParams:
 
 
 @dataclass
+class TrackerParams:
+    """People tracks (include/smpc_tracker.h; BatchEpisode(tracker=...)): every tick the detections are associated with
+    the robot's tracks by position alone (greedy by distance inside `gate` metres of the predicted position), a matched
+    track takes an alpha-beta update (position xp + alpha * r, velocity v + beta / dt * r), an unmatched one coasts with its
+    velocity for at most max_missed ticks, and a new track is handed on once it has confirm_hits detections. slots: tracks
+    per robot (at most 64). The defaults follow a detection every 0.1 s of a pedestrian at walking speed: a gate of 0.6 m is
+    five times the step of 1.2 m/s, and 20 coasted ticks are 2 s behind a pillar."""
+    alpha: float = 0.5
+    beta: float = 0.2
+    gate: float = 0.6
+    confirm_hits: int = 3
+    max_missed: int = 20
+    slots: int = 16
+
+    def __post_init__(self):
+        for name in ("alpha", "beta"):
+            v = getattr(self, name)
+            if not (np.isfinite(v) and v >= 0.0):
+                raise ValueError(f"TrackerParams.{name} must be finite and >= 0, got {v}")
+        if not (np.isfinite(self.gate) and self.gate > 0.0):
+            raise ValueError(f"TrackerParams.gate must be finite and > 0, got {self.gate}")
+        if int(self.confirm_hits) != self.confirm_hits or self.confirm_hits < 1:
+            raise ValueError(f"TrackerParams.confirm_hits must be an integer >= 1, got {self.confirm_hits}")
+        if int(self.max_missed) != self.max_missed or self.max_missed < 0:
+            raise ValueError(f"TrackerParams.max_missed must be an integer >= 0, got {self.max_missed}")
+        if int(self.slots) != self.slots or self.slots < 1:
+            raise ValueError(f"TrackerParams.slots must be an integer >= 1, got {self.slots}")
+
+    def gain(self, dt: float) -> float:
+        """beta / dt: the velocity gain the call takes (one division, here and not in the kernel)."""
+        if not (np.isfinite(dt) and dt > 0.0):
+            raise ValueError(f"TrackerParams.gain: dt must be finite and > 0, got {dt}")
+        return float(np.float64(self.beta) / np.float64(dt))
+
+    def supported(self, dt: float = None) -> bool:
+        """Does the library run these tracks: at most 64 slots, counters that fit the struct's int32 fields and, with `dt`, a
+        finite gain?"""
+        ok = self.slots <= 64 and self.confirm_hits < 2 ** 31 and self.max_missed < 2 ** 31
+        with np.errstate(over="ignore"):
+            return bool(ok and (dt is None or (np.isfinite(dt) and dt > 0.0 and np.isfinite(np.float64(self.beta) / np.float64(dt)))))
+
+
+@dataclass
 class SharedWorldParams:
     """One world for all robots of an episode (include/smpc_nearest.h; BatchEpisode(shared=..., pool=...)): every tick each
     robot is handed its at most max_people nearest agents within max_range (the detector's range in metres, VisibilityParams'

@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from . import (_abi, _abi_crowd_pool, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_obstacle_memory, _abi_sensed_costmap,
-               _abi_visibility)
+               _abi_tracker, _abi_visibility)
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
@@ -22,9 +22,10 @@ from ._abi_local_costmap import SmpcLocalCostmapIn
 from ._abi_nearest import SmpcNearestIn
 from ._abi_obstacle_memory import SmpcObstacleMemoryIn
 from ._abi_sensed_costmap import SmpcSensedCostmapIn
+from ._abi_tracker import SmpcTrackerIn
 from ._abi_visibility import SmpcVisibilityIn
 from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, PoolCrowdParams,
-                     TrajectorizerParams, VisibilityParams)
+                     TrackerParams, TrajectorizerParams, VisibilityParams)
 from .scenes import SceneBatch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -64,7 +65,7 @@ def load_library():
     for name, (restype, argtypes) in {**_abi.FUNCTIONS, **_abi.FIXED_SHAPE_FUNCTIONS, **_abi_local_costmap.FUNCTIONS,
                                        **_abi_global_plan.FUNCTIONS, **_abi_visibility.FUNCTIONS, **_abi_nearest.FUNCTIONS,
                                        **_abi_crowd_pool.FUNCTIONS, **_abi_sensed_costmap.FUNCTIONS,
-                                       **_abi_obstacle_memory.FUNCTIONS}.items():
+                                       **_abi_obstacle_memory.FUNCTIONS, **_abi_tracker.FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -776,6 +777,51 @@ class BatchSolver:
         handle's stream."""
         assert vi.on_device == 1
         self._call("smpc_visible_people_batch", vi, visible_ptr, visible_count_ptr, seen_ptr or None)
+
+    # -- people tracks (smpc_track_people_batch, include/smpc_tracker.h) ----------------------------------------------------
+    @staticmethod
+    def tracker_c(tp: TrackerParams, B: int, Nd: int, Np: int, dt: float, on_device: int) -> SmpcTrackerIn:
+        return SmpcTrackerIn(B=int(B), Nd=int(Nd), Nt=int(tp.slots), Np=int(Np), on_device=int(on_device),
+                             confirm_hits=int(tp.confirm_hits), max_missed=int(tp.max_missed), dt=float(dt), alpha=float(tp.alpha),
+                             gain=tp.gain(dt), gate=float(tp.gate))
+
+    def track_people(self, tp: TrackerParams, dt: float, tracks: np.ndarray, track_meta: np.ndarray, next_id: np.ndarray,
+                     detections: np.ndarray, det_count: np.ndarray, robot_pose: np.ndarray, Np: int = None, people: np.ndarray = None,
+                     out_track: np.ndarray = None, with_out_track: bool = True):
+        """One tick of the people tracker on host arrays: tracks [B,Nt,4] float64, track_meta [B,Nt,4] int32 and next_id [B]
+        int32 are the state the last call returned (zeros to start with; they are not modified), Nt = tp.slots; detections
+        [B,Nd,5] (only x and y are read), det_count [B] int32, robot_pose [B,3]. people [B,Np,5] / out_track [B,Np,2] int32:
+        the arrays before the call (default NaN / -1): the call writes the first count rows of each robot and leaves the
+        others. Returns (people, count [B] int32, out_track or None with with_out_track=False, new tracks, new track_meta,
+        new next_id)."""
+        detections = np.ascontiguousarray(detections, np.float64)
+        det_count = np.ascontiguousarray(det_count, np.int32)
+        robot_pose = np.ascontiguousarray(robot_pose, np.float64)
+        B, Nd, Nt = detections.shape[0], detections.shape[1], int(tp.slots)
+        Np = Nt if Np is None else int(Np)
+        tracks = np.array(tracks, np.float64, order="C")
+        track_meta = np.array(track_meta, np.int32, order="C")
+        next_id = np.array(next_id, np.int32, order="C")
+        assert detections.shape == (B, Nd, 5) and det_count.shape == (B,) and robot_pose.shape == (B, 3)
+        assert tracks.shape == (B, Nt, 4) and track_meta.shape == (B, Nt, 4) and next_id.shape == (B,)
+        people = np.full((B, Np, 5), np.nan) if people is None else np.array(people, dtype=np.float64, order="C")
+        if with_out_track:
+            out_track = np.full((B, Np, 2), -1, np.int32) if out_track is None else np.array(out_track, dtype=np.int32, order="C")
+            assert out_track.shape == (B, Np, 2)
+        else:
+            out_track = None
+        assert people.shape == (B, Np, 5)
+        ti = point(self.tracker_c(tp, B, Nd, Np, dt, 0), {"detections": detections, "det_count": det_count, "robot_pose": robot_pose})
+        count = np.zeros(B, np.int32)
+        self._call("smpc_track_people_batch", ti, _ptr(tracks), _ptr(track_meta), _ptr(next_id), _ptr(people), _ptr(count), _ptr(out_track))
+        return people, count, out_track, tracks, track_meta, next_id
+
+    def track_people_device(self, ti: SmpcTrackerIn, tracks_ptr: int, track_meta_ptr: int, next_id_ptr: int, people_ptr: int,
+                            count_ptr: int, out_track_ptr: int = 0):
+        """Device pointers in ti (on_device == 1) and for the state (tracks, track_meta, next_id: read and written), people,
+        count and out_track (0: none); asynchronous on the handle's stream."""
+        assert ti.on_device == 1
+        self._call("smpc_track_people_batch", ti, tracks_ptr, track_meta_ptr, next_id_ptr, people_ptr, count_ptr, out_track_ptr or None)
 
     # -- sensed local costmaps (smpc_sensed_costmap_batch, include/smpc_sensed_costmap.h) ----------------------------------
     @staticmethod

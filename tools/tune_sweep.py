@@ -4,7 +4,7 @@ of a batch whose solve takes each robot's own critic weights and velocity bounds
 BatchEpisode(scene_params=...)); the device scores every robot as it drives (BatchEpisode(metrics=...)), and one line of
 summarize_metrics means is printed per set. Nothing but the final [B,24] metrics rows leaves the device.
 
-    python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]]
+    python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]] [--tracker]
                                 [--world-plans [--occlusion [RANGE]] [--shared-crowd M] [--sensed-costmap [--obstacle-memory]]]
 
 --reactive: the persons are a reactive crowd (BatchEpisode(crowd=CrowdParams()), waypoints from scenes.crowd_waypoints)
@@ -31,6 +31,10 @@ pre-inflated world map: the map obstacle_weight has to be tuned against.
 --obstacle-memory (with --sensed-costmap): the scan has Nav2's memory (BatchEpisode(sensor_memory=ObstacleMemoryParams()):
 a mark stays until a later beam passes its cell, the beams clear out to 3.0 m and mark out to 2.5 m, the cells under the
 robot are always free), so a person who steps out of sight leaves lethal cells where last seen, as on the reference's costmap.
+--tracker (with or without --world-plans --occlusion): the controller is handed tracks of what it detects instead of the
+simulator's own rows (BatchEpisode(tracker=TrackerParams())): velocities estimated from positions alone by an alpha-beta
+filter, a new person handed on at the third detection, and a person who steps out of sight coasted on for up to 20 ticks.
+The tuning then meets the velocities a deployed tracker would deliver. The metrics keep scoring the true persons.
 """
 import argparse
 import os
@@ -70,6 +74,8 @@ def main():
                     help="with --world-plans: the local costmaps are sensed (a scan marks walls and persons, then inflation)")
     ap.add_argument("--obstacle-memory", action="store_true",
                     help="with --sensed-costmap: marks persist until a beam clears them (Nav2's ObstacleLayer)")
+    ap.add_argument("--tracker", action="store_true",
+                    help="the controller is handed tracks of the detected persons (velocity from positions, coasting when hidden)")
     a = ap.parse_args()
     if a.obstacle_memory and not a.sensed_costmap:
         ap.error("--obstacle-memory needs --sensed-costmap")
@@ -88,7 +94,8 @@ def main():
 
     from nav2_social_mpc_controller_amd.episode import BatchEpisode, arc_plans
     from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, ObstacleMemoryParams, OptimizerParams,
-                                                       PoolCrowdParams, SensorParams, SharedWorldParams, TrajectorizerParams, VisibilityParams, scene_param_rows)
+                                                       PoolCrowdParams, SensorParams, SharedWorldParams, TrackerParams, TrajectorizerParams, VisibilityParams,
+                                                       scene_param_rows)
     from nav2_social_mpc_controller_amd.scenes import (crowd_groups, crowd_waypoints, make_scenes, make_world, pool_waypoints, scenes_in_world,
                                                        shared_pool, uniform, world_goals)
     from nav2_social_mpc_controller_amd.solver import summarize_metrics
@@ -130,6 +137,8 @@ def main():
             gid, wp, n_wp = crowd_groups(one)
             crowd["person_groups"] = np.tile(gid, (S, 1))
         crowd.update(crowd=CrowdParams(), person_waypoints=np.tile(wp, (S, 1, 1, 1)), person_n_waypoints=np.tile(n_wp, (S, 1)))
+    if a.tracker:
+        plans["tracker"] = TrackerParams(slots=max(16, min(64, 2 * a.agents)))
     ep = BatchEpisode(prm, sc, w_ref, traj_params=tp, fov_angle=np.pi / 4, obstacles_from_costmap=True, scene_params=rows,
                       metrics=MetricsParams(), **plans, **crowd)
     ep.capture_graph()
