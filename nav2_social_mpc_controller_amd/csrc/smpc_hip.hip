@@ -16,7 +16,7 @@
 //   the probe kernels (smpc_probes.hpp);
 //   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window,
 //   metrics, crowd, local costmap, global plan, visibility, nearest agents, pool crowd, sensed costmap, obstacle memory,
-//   people tracks).
+//   people tracks, people detections).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -49,6 +49,8 @@
 #include "../../include/smpc_obstacle_memory.h"
 #include "smpc_tracker.hpp"
 #include "../../include/smpc_tracker.h"
+#include "smpc_detector.hpp"
+#include "../../include/smpc_detector.h"
 
 extern "C" {
 
@@ -941,6 +943,47 @@ int smpc_track_people_batch(smpc_handle* h, const smpc_tracker_in* in, double* t
   const size_t per_block = smpc::kTkThreads / 64;
   SMPC_TRY(st.timed([&] {
     hipLaunchKernelGGL(smpc::smpc_track_people_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kTkThreads), 0, h->stream, p);
+    return SMPC_OK;
+  }));
+  return st.finish();
+}
+
+int smpc_detect_people_batch(smpc_handle* h, const smpc_detector_in* in, uint32_t* draw_state, double* detections, int32_t* det_count,
+                             int32_t* det_source, uint8_t* outcome) {
+  if (!h || !in || !draw_state || !detections || !det_count) {
+    set_error("null handle / input / draw_state / detections / det_count"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (!in->people || !in->count || !in->robot_pose) { set_error("null input array"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B < 0 || in->Np < 1 || in->Nd < 1 || in->Kc < 0) { set_error("bad B, Np or Nd < 1, or Kc < 0"); return SMPC_ERR_INVALID_ARG; }
+  for (const double v : {in->body_radius, in->noise_scale, in->noise_growth, in->clutter_scale})
+    if (!std::isfinite(v) || !(v >= 0.0)) {
+      set_error("body_radius, noise_scale, noise_growth and clutter_scale must be finite and >= 0"); return SMPC_ERR_INVALID_ARG;
+    }
+  // the kernel's bounds: lane j owns person j, clutter candidate j and at most one output rank of one wavefront
+  if (in->Np > SMPC_MAX_AGENTS || in->Nd > SMPC_MAX_AGENTS || in->Kc > SMPC_MAX_AGENTS) {
+    set_error("Np, Nd or Kc > 64 is not supported"); return SMPC_ERR_UNSUPPORTED;
+  }
+  if (in->B == 0) return SMPC_OK;
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::DetectorParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.B = in->B; p.Np = in->Np; p.Nd = in->Nd; p.Kc = in->Kc;
+  p.seed_lo = in->seed_lo; p.seed_hi = in->seed_hi; p.miss_threshold = in->miss_threshold; p.clutter_threshold = in->clutter_threshold;
+  p.body_radius = in->body_radius; p.noise_scale = in->noise_scale; p.noise_growth = in->noise_growth; p.clutter_scale = in->clutter_scale;
+  const size_t B = in->B, Np = in->Np, Nd = in->Nd;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.people, in->people, B * Np * 5));
+  SMPC_TRY(st.in(p.count, in->count, B));
+  SMPC_TRY(st.in(p.robot_pose, in->robot_pose, B * 3));
+  SMPC_TRY(st.inout(p.draw_state, draw_state, B * 2));
+  // read and written: the rows the kernel leaves alone keep the caller's bytes on the way through device memory too
+  SMPC_TRY(st.inout(p.detections, detections, B * Nd * 5));
+  SMPC_TRY(st.out(p.det_count, det_count, B));
+  SMPC_TRY(st.inout(p.det_source, det_source, B * Nd));
+  SMPC_TRY(st.inout(p.outcome, outcome, B * Np));
+  const size_t per_block = smpc::kDtThreads / 64;
+  SMPC_TRY(st.timed([&] {
+    hipLaunchKernelGGL(smpc::smpc_detect_people_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kDtThreads), 0, h->stream, p);
     return SMPC_OK;
   }));
   return st.finish();

@@ -12,6 +12,8 @@
       ... with memory (optional)             (its persistent marking and ray-trace
                                               clearing; the library's own rule)     -> smpc_obstacle_memory_batch
     line-of-sight filter (optional)          (none: the library's own rule)        -> smpc_visible_people_batch
+    people detections (optional)             (the deployment's own detector; the
+                                              library's own rule)                   -> smpc_detect_people_batch
     people tracks (optional)                 (the deployment's own tracker behind
                                               people_msgs::People; the library's rule) -> smpc_track_people_batch
     global plans (optional, at the start and   (Nav2's planner server; the library's -> smpc_goal_field_batch,
@@ -50,7 +52,7 @@ import numpy as np
 
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
-from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, ObstacleMemoryParams, OptimizerParams, PoolCrowdParams,
+from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, ObstacleMemoryParams, OptimizerParams, PoolCrowdParams,
                      SensorParams, TrackerParams, TrajectorizerParams, SharedWorldParams, VisibilityParams, check_scene_param_rows)
 from .scenes import SceneBatch, World
 from .solver import BatchSolver, point, set_od_grid
@@ -131,6 +133,15 @@ class TickRecord:
     tracked_persons: np.ndarray = None        # [B,Np,5] (rows from tracked_count[b] on: not written)
     tracked_count: np.ndarray = None          # [B]
     tracked_source: np.ndarray = None         # [B,Np,2] int32 slot, id (rows from tracked_count[b] on: not written)
+    # the people detections (BatchEpisode(detector=...)): the state the tick's smpc_detect_people_batch read (its persons are
+    # seen_persons / seen_count with visibility, else persons / person_count) and wrote, and what the tracker (or, without
+    # one, people_to_status) read
+    draw_state_before: np.ndarray = None      # [B,2] uint32 stream id, tick counter
+    draw_state_after: np.ndarray = None
+    detected_persons: np.ndarray = None       # [B,Nd,5] (rows from detected_count[b] on: not written)
+    detected_count: np.ndarray = None         # [B]
+    detected_source: np.ndarray = None        # [B,Nd] int32 person j, or -1 - c of clutter candidate c (rows from detected_count[b] on: not written)
+    person_outcome: np.ndarray = None         # [B,Np] uint8 smpc_detect_outcome (persons from the count on: not written)
 
 
 class BatchEpisode:
@@ -144,7 +155,7 @@ class BatchEpisode:
     FORWARDED = ("od_resolution", "device", "traj_params", "fov_angle", "order_hint", "plan_window", "obstacles_from_costmap",
                  "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost", "planner",
                  "visibility", "shared", "pool", "pool_crowd", "pool_waypoints", "pool_n_waypoints", "pool_speed", "sensor",
-                 "sensor_memory", "tracker")
+                 "sensor_memory", "tracker", "detector")
 
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
@@ -158,7 +169,8 @@ class BatchEpisode:
                  planner: GlobalPlanParams = None, visibility: VisibilityParams = None,
                  shared: SharedWorldParams = None, pool: np.ndarray = None, pool_crowd: PoolCrowdParams = None,
                  pool_waypoints: np.ndarray = None, pool_n_waypoints: np.ndarray = None, pool_speed: np.ndarray = None,
-                 sensor: SensorParams = None, sensor_memory: ObstacleMemoryParams = None, tracker: TrackerParams = None):
+                 sensor: SensorParams = None, sensor_memory: ObstacleMemoryParams = None, tracker: TrackerParams = None,
+                 detector: DetectorParams = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -261,7 +273,18 @@ class BatchEpisode:
         people_to_status reads. The state is self.tracks [B,slots,4], self.track_meta [B,slots,4] int32 and
         self.track_next_id [B] int32, zero at the start. The world model, the crowd steps, the scan and the metrics keep
         reading the true self.persons. None: nothing is allocated, nothing is launched and the episode is the one without
-        bit for bit."""
+        bit for bit.
+        detector: the controller is handed what a detector would report (include/smpc_detector.h). Every tick, behind the
+        line-of-sight filter and in front of the tracker, one smpc_detect_people_batch reads self.seen_persons /
+        self.seen_count with `visibility`, else self.persons / self.person_count: persons behind another person's body
+        and missed persons leave, the others are reported with range-dependent position noise, clutter is appended, into
+        self.detected_persons [B,Nd,5] / self.detected_count [B] (self.detected_source [B,Nd], self.person_outcome [B,Np]
+        uint8), Nd = min(64, Np + detector.clutter_candidates), which the tracker (or, without one, people_to_status)
+        reads. The state is self.draw_state [B,2] int32 (the bits of the call's uint32 words): the robot's stream id
+        (its index; set_detector_streams() gives a part of a larger batch the ids of its robots there, as ShardedEpisode
+        does) and its tick counter, zero at the start, which lives on the device so that a replayed graph draws fresh
+        numbers every tick. The world model, the crowd steps, the scan and the metrics keep reading the true self.persons.
+        None: nothing is allocated, nothing is launched and the episode is the one without bit for bit."""
         import torch
 
         self.torch = torch
@@ -322,6 +345,7 @@ class BatchEpisode:
         self._init_shared(shared, pool, pool_crowd, pool_waypoints, pool_n_waypoints, pool_speed)
         self._init_sensor(sensor, sensor_memory)
         self._init_tracker(tracker)
+        self._init_detector(detector)
         self._bind()
         self.graph = None
         self.gstream = None
@@ -559,6 +583,35 @@ class BatchEpisode:
         self.tracked_count = self._zeros(B, dtype=self.torch.int32)
         self.tracked_source = self._zeros(B, Np, 2, dtype=self.torch.int32)
 
+    def _init_detector(self, detector):
+        """The draw state of every robot (stream id = its index, counter 0) and what the detector writes every tick: fixed
+        addresses, the tracker or people_to_status reads the first two."""
+        self.detector = detector
+        if detector is None:
+            return
+        if not isinstance(detector, DetectorParams):
+            raise ValueError("detector must be a DetectorParams")
+        if not detector.supported():
+            raise ValueError("detector: more than 64 clutter candidates")
+        B, Np = self.B, int(self.persons.shape[1])
+        Nd = min(64, Np + int(detector.clutter_candidates))
+        self.draw_state = self._zeros(B, 2, dtype=self.torch.int32)
+        self.draw_state[:, 0] = self.torch.arange(B, dtype=self.torch.int32, device=self.draw_state.device)
+        self.detected_persons = self._zeros(B, Nd, 5)
+        self.detected_count = self._zeros(B, dtype=self.torch.int32)
+        self.detected_source = self._zeros(B, Nd, dtype=self.torch.int32)
+        self.person_outcome = self._zeros(B, Np, dtype=self.torch.uint8)
+
+    def set_detector_streams(self, streams):
+        """streams [B] (0 .. 2^32 - 1): the stream ids of this episode's robots in place of their indices, so that a part of a
+        larger batch draws what the same robots draw there. In place: a captured graph reads the new ids."""
+        if self.detector is None:
+            raise ValueError("this episode was built without detector")
+        ids = np.asarray(streams)
+        if ids.shape != (self.B,) or (ids != ids.astype(np.uint32)).any():
+            raise ValueError("set_detector_streams: one id in 0 .. 2^32 - 1 per robot")
+        self.draw_state[:, 0].copy_(self.torch.from_numpy(ids.astype(np.uint32).view(np.int32).copy()))
+
     def _init_shared(self, shared, pool, pool_crowd=None, pool_waypoints=None, pool_n_waypoints=None, pool_speed=None):
         """The table of a shared world, the gather's bins and workspace, and what it writes besides persons / person_count;
         with pool_crowd what the pool's crowd step reads and writes."""
@@ -671,10 +724,18 @@ class BatchEpisode:
                                  {"world": self.world_map, "world_origin": self.world_origin, "robot_pose": self.pose,
                                   "people": self.persons, "count": self.person_count})
             point(c.people, {"people": self.seen_persons, "count": self.seen_count})
+        Nd = Np
+        if self.detector is not None:  # what a detector would report of them: behind line of sight, in front of the tracker
+            Nd = int(self.detected_persons.shape[1])
+            c.detector = point(BatchSolver.detector_c(self.detector, B, Np, Nd, 1),
+                               {"people": c.people.people, "count": c.people.count, "robot_pose": self.pose})
+            point(c.people, {"people": self.detected_persons, "count": self.detected_count})
+            c.people.Np = Nd
         if self.tracker is not None:  # the controller gets tracks of what is detected: the last stage in front of the filter
-            c.tracker = point(BatchSolver.tracker_c(self.tracker, B, Np, Np, prm.dt, 1),
+            c.tracker = point(BatchSolver.tracker_c(self.tracker, B, Nd, Np, prm.dt, 1),
                               {"detections": c.people.people, "det_count": c.people.count, "robot_pose": self.pose})
             point(c.people, {"people": self.tracked_persons, "count": self.tracked_count})
+            c.people.Np = Np
         if self.sensor is not None:  # the scan sees the true persons, whatever the controller is told of them
             sp = self.sensor
             c.sensor = point(BatchSolver.sensed_costmap_c(B, Np, self.size_x, self.size_y, self.world.cells_x, self.world.cells_y, True,
@@ -843,6 +904,15 @@ class BatchEpisode:
             timed("visibility")
             if record:
                 rec.update(self._host("person_seen", "seen_count", "seen_persons"))
+        if self.detector is not None:  # what a detector would report: body occlusion, misses, noise, clutter
+            if record:
+                rec["draw_state_before"] = self.draw_state.cpu().numpy().view(np.uint32).copy()
+            s.detect_people_device(c.detector, self.draw_state.data_ptr(), self.detected_persons.data_ptr(), self.detected_count.data_ptr(),
+                                   self.detected_source.data_ptr(), self.person_outcome.data_ptr())
+            timed("detector")
+            if record:
+                rec.update(self._host("detected_persons", "detected_count", "detected_source", "person_outcome"))
+                rec["draw_state_after"] = self.draw_state.cpu().numpy().view(np.uint32).copy()
         if self.tracker is not None:  # tracks of the detections: velocities from positions, and a memory of who stepped out of sight
             if record:
                 rec.update(self._host(tracks_before="tracks", track_meta_before="track_meta", track_next_id_before="track_next_id"))
@@ -964,6 +1034,8 @@ class BatchEpisode:
             state += ("obstacle_memory", "obstacle_memory_cell")
         if self.tracker is not None:
             state += ("tracks", "track_meta", "track_next_id")
+        if self.detector is not None:
+            state += ("draw_state",)
         with torch.cuda.stream(self.gstream):
             saved = {k: getattr(self, k).clone() for k in state}
             ticks = self.ticks
@@ -1072,13 +1144,17 @@ class ShardedEpisode:
                  od_origin: np.ndarray, od_resolution: float, device: int = 0, shards: int = 3, graphs: bool = True,
                  solve_share: int = None, **episode_kw):
         """episode_kw: the other keyword arguments of BatchEpisode, for all B robots; every shard gets its robots' part
-        of them (shard_kwargs)."""
+        of them (shard_kwargs). detector_streams [B] (with detector=; default arange(B)): the robots' stream ids; every
+        shard gets its robots' (BatchEpisode.set_detector_streams), so a shard draws what the same robots draw unsharded."""
         import torch
 
         if episode_kw.get("shared") is not None or episode_kw.get("pool") is not None:
             raise ValueError("ShardedEpisode refuses shared / pool: its shards are independent by construction")
         self.torch = torch
         B = scenes.B
+        detector_streams = episode_kw.pop("detector_streams", None)
+        if detector_streams is not None and episode_kw.get("detector") is None:
+            raise ValueError("detector_streams needs detector")
         shards = max(1, min(shards, B))
         edges = [B * k // shards for k in range(shards + 1)]
         self.slices = [slice(edges[k], edges[k + 1]) for k in range(shards) if edges[k + 1] > edges[k]]
@@ -1089,6 +1165,8 @@ class ShardedEpisode:
             idx = np.arange(sl.start, sl.stop)
             with torch.cuda.stream(st):  # the shard's solver handle binds to the stream current at construction
                 self.parts.append(BatchEpisode(params, scenes.select(idx), np.asarray(w_ref)[idx], **shard_kwargs(kw, idx, B)))
+                if self.parts[-1].detector is not None:
+                    self.parts[-1].set_detector_streams(idx if detector_streams is None else np.asarray(detector_streams)[idx])
         self.B = B
         self.graphs = graphs
         for part in self.parts:  # every shard's persistent solve grid takes its share of the resident wavefronts

@@ -319,6 +319,64 @@ class TrackerParams:
 
 
 @dataclass
+class DetectorParams:
+    """People detections (include/smpc_detector.h; BatchEpisode(detector=...)): every tick the persons a robot is handed
+    become what a detector would report of them. A person whose sight line passes within body_radius metres of another
+    person's centre is hidden (0: no body occlusion); a visible person is missed with probability p_miss; a detected one is
+    reported with a position noise of standard deviation sigma + sigma_growth * range^2 metres per axis (the sum of four
+    uniform words, so bounded by 2 sqrt(3) standard deviations); each of clutter_candidates (at most 64) false detections
+    exists with probability p_clutter, uniform in a square of half-side clutter_range metres around the robot. seed: the
+    64-bit key of the counter-based generator; a robot's draws depend on (seed, its stream id, its tick counter, the row)
+    alone. The defaults follow a leg or torso detector on a planar scan: 3 cm at the sensor, 23 cm at 10 m."""
+    body_radius: float = 0.25
+    p_miss: float = 0.1
+    sigma: float = 0.03
+    sigma_growth: float = 0.002
+    clutter_candidates: int = 2
+    p_clutter: float = 0.05
+    clutter_range: float = 5.0
+    seed: int = 0
+
+    def __post_init__(self):
+        for name in ("body_radius", "sigma", "sigma_growth", "clutter_range"):
+            v = getattr(self, name)
+            if not (np.isfinite(v) and v >= 0.0):
+                raise ValueError(f"DetectorParams.{name} must be finite and >= 0, got {v}")
+        for name in ("p_miss", "p_clutter"):
+            v = getattr(self, name)
+            if not (np.isfinite(v) and 0.0 <= v <= 1.0):
+                raise ValueError(f"DetectorParams.{name} must lie in [0, 1], got {v}")
+        if int(self.clutter_candidates) != self.clutter_candidates or self.clutter_candidates < 0:
+            raise ValueError(f"DetectorParams.clutter_candidates must be an integer >= 0, got {self.clutter_candidates}")
+        if int(self.seed) != self.seed or not 0 <= self.seed < 2 ** 64:
+            raise ValueError(f"DetectorParams.seed must be an integer in 0 .. 2^64 - 1, got {self.seed}")
+
+    @staticmethod
+    def _threshold(p: float) -> int:
+        return min(int(np.floor(np.float64(p) * np.float64(2.0 ** 32) + np.float64(0.5))), 2 ** 32 - 1)
+
+    def thresholds(self):
+        """(miss_threshold, clutter_threshold): p * 2^32 rounded to nearest (a half upwards), clamped to 2^32 - 1; a draw
+        below the threshold fires, so p = 1 misses all but one draw in 2^32."""
+        return self._threshold(self.p_miss), self._threshold(self.p_clutter)
+
+    def scales(self):
+        """(noise_scale, noise_growth, clutter_scale) as the call takes them: sigma * sqrt(3) / 2^32 (the noise sum has the
+        standard deviation 2^32 / sqrt(3) to within 2^-65), sigma_growth * sqrt(3) / 2^32, clutter_range / 2^31."""
+        root3, two32 = np.sqrt(np.float64(3.0)), np.float64(2.0 ** 32)
+        return (float(np.float64(self.sigma) * root3 / two32), float(np.float64(self.sigma_growth) * root3 / two32),
+                float(np.float64(self.clutter_range) / np.float64(2.0 ** 31)))
+
+    def key(self):
+        """(seed_lo, seed_hi)"""
+        return int(self.seed) & 0xFFFFFFFF, int(self.seed) >> 32
+
+    def supported(self) -> bool:
+        """Does the library run this detector: at most 64 clutter candidates?"""
+        return self.clutter_candidates <= 64
+
+
+@dataclass
 class SharedWorldParams:
     """One world for all robots of an episode (include/smpc_nearest.h; BatchEpisode(shared=..., pool=...)): every tick each
     robot is handed its at most max_people nearest agents within max_range (the detector's range in metres, VisibilityParams'

@@ -11,11 +11,12 @@ import os
 
 import numpy as np
 
-from . import (_abi, _abi_crowd_pool, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_obstacle_memory, _abi_sensed_costmap,
+from . import (_abi, _abi_crowd_pool, _abi_detector, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_obstacle_memory, _abi_sensed_costmap,
                _abi_tracker, _abi_visibility)
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
+from ._abi_detector import SmpcDetectorIn
 from ._abi_crowd_pool import SmpcCrowdPoolIn
 from ._abi_global_plan import SmpcExtractPlanIn, SmpcGoalFieldIn
 from ._abi_local_costmap import SmpcLocalCostmapIn
@@ -24,7 +25,7 @@ from ._abi_obstacle_memory import SmpcObstacleMemoryIn
 from ._abi_sensed_costmap import SmpcSensedCostmapIn
 from ._abi_tracker import SmpcTrackerIn
 from ._abi_visibility import SmpcVisibilityIn
-from .params import (CrowdGroupParams, CrowdParams, GlobalPlanParams, MetricsParams, OptimizerParams, PoolCrowdParams,
+from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, OptimizerParams, PoolCrowdParams,
                      TrackerParams, TrajectorizerParams, VisibilityParams)
 from .scenes import SceneBatch
 
@@ -65,7 +66,8 @@ def load_library():
     for name, (restype, argtypes) in {**_abi.FUNCTIONS, **_abi.FIXED_SHAPE_FUNCTIONS, **_abi_local_costmap.FUNCTIONS,
                                        **_abi_global_plan.FUNCTIONS, **_abi_visibility.FUNCTIONS, **_abi_nearest.FUNCTIONS,
                                        **_abi_crowd_pool.FUNCTIONS, **_abi_sensed_costmap.FUNCTIONS,
-                                       **_abi_obstacle_memory.FUNCTIONS, **_abi_tracker.FUNCTIONS}.items():
+                                       **_abi_obstacle_memory.FUNCTIONS, **_abi_tracker.FUNCTIONS,
+                                       **_abi_detector.FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -822,6 +824,56 @@ class BatchSolver:
         count and out_track (0: none); asynchronous on the handle's stream."""
         assert ti.on_device == 1
         self._call("smpc_track_people_batch", ti, tracks_ptr, track_meta_ptr, next_id_ptr, people_ptr, count_ptr, out_track_ptr or None)
+
+    # -- people detections (smpc_detect_people_batch, include/smpc_detector.h) ----------------------------------------------
+    @staticmethod
+    def detector_c(dp: DetectorParams, B: int, Np: int, Nd: int, on_device: int) -> SmpcDetectorIn:
+        miss, clutter = dp.thresholds()
+        noise_scale, noise_growth, clutter_scale = dp.scales()
+        seed_lo, seed_hi = dp.key()
+        return SmpcDetectorIn(B=int(B), Np=int(Np), Nd=int(Nd), Kc=int(dp.clutter_candidates), on_device=int(on_device), seed_lo=seed_lo,
+                              seed_hi=seed_hi, miss_threshold=miss, clutter_threshold=clutter, body_radius=float(dp.body_radius),
+                              noise_scale=noise_scale, noise_growth=noise_growth, clutter_scale=clutter_scale)
+
+    def detect_people(self, dp: DetectorParams, draw_state: np.ndarray, people: np.ndarray, count: np.ndarray, robot_pose: np.ndarray,
+                      Nd: int = None, detections: np.ndarray = None, det_source: np.ndarray = None, outcome: np.ndarray = None,
+                      with_source: bool = True, with_outcome: bool = True):
+        """One tick of the detector model on host arrays: draw_state [B,2] uint32 (stream id, tick counter) is the state the
+        last call returned (it is not modified); people [B,Np,5], count [B] int32, robot_pose [B,3]. detections [B,Nd,5] /
+        det_source [B,Nd] int32 / outcome [B,Np] uint8: the arrays before the call (default NaN / -99 / 255): the call writes
+        the first det_count rows of each robot, and the outcome of the first clamp(count, 0, Np) persons, and leaves the others.
+        Returns (detections, det_count [B] int32, det_source or None with with_source=False, outcome or None with
+        with_outcome=False, new draw_state)."""
+        people = np.ascontiguousarray(people, np.float64)
+        count = np.ascontiguousarray(count, np.int32)
+        robot_pose = np.ascontiguousarray(robot_pose, np.float64)
+        draw_state = np.array(draw_state, np.uint32, order="C")
+        B, Np = people.shape[0], people.shape[1]
+        Nd = Np if Nd is None else int(Nd)
+        assert people.shape == (B, Np, 5) and count.shape == (B,) and robot_pose.shape == (B, 3) and draw_state.shape == (B, 2)
+        detections = np.full((B, Nd, 5), np.nan) if detections is None else np.array(detections, dtype=np.float64, order="C")
+        assert detections.shape == (B, Nd, 5)
+        if with_source:
+            det_source = np.full((B, Nd), -99, np.int32) if det_source is None else np.array(det_source, dtype=np.int32, order="C")
+            assert det_source.shape == (B, Nd)
+        else:
+            det_source = None
+        if with_outcome:
+            outcome = np.full((B, Np), 255, np.uint8) if outcome is None else np.array(outcome, dtype=np.uint8, order="C")
+            assert outcome.shape == (B, Np)
+        else:
+            outcome = None
+        di = point(self.detector_c(dp, B, Np, Nd, 0), {"people": people, "count": count, "robot_pose": robot_pose})
+        det_count = np.zeros(B, np.int32)
+        self._call("smpc_detect_people_batch", di, _ptr(draw_state), _ptr(detections), _ptr(det_count), _ptr(det_source), _ptr(outcome))
+        return detections, det_count, det_source, outcome, draw_state
+
+    def detect_people_device(self, di: SmpcDetectorIn, draw_state_ptr: int, detections_ptr: int, det_count_ptr: int, det_source_ptr: int = 0,
+                             outcome_ptr: int = 0):
+        """Device pointers in di (on_device == 1) and for the state (draw_state: read and written), detections, det_count,
+        det_source and outcome (0: none); asynchronous on the handle's stream."""
+        assert di.on_device == 1
+        self._call("smpc_detect_people_batch", di, draw_state_ptr, detections_ptr, det_count_ptr, det_source_ptr or None, outcome_ptr or None)
 
     # -- sensed local costmaps (smpc_sensed_costmap_batch, include/smpc_sensed_costmap.h) ----------------------------------
     @staticmethod
