@@ -320,7 +320,7 @@ def test_edge_cases(Solver, oracle):
         return np.max(cmd_err(s.solve(scenes)["cmds"][firm], ref["cmds"][firm])) <= CMD_TOL
     short = make_scenes(prm, 8, 3, T=2, map_cells=80, seed=402, standing_fraction=0.0)
     assert agree(short)
-    # robot driving off the costmap: clamp-to-edge interpolation
+    # robot driving off the costmap: clamp-to-edge interpolation (aimed at cell by cell in tests/test_gpu_obstacle_edges.py)
     edge = make_scenes(prm, 8, 3, map_cells=20, seed=403, standing_fraction=0.0)
     assert agree(edge)
     # shared costmap
