@@ -16,7 +16,7 @@
 //   the probe kernels (smpc_probes.hpp);
 //   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window,
 //   metrics, crowd, local costmap, global plan, visibility, nearest agents, pool crowd, sensed costmap, obstacle memory,
-//   people tracks, people detections).
+//   people tracks, people detections, robot plant).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -51,6 +51,8 @@
 #include "../../include/smpc_tracker.h"
 #include "smpc_detector.hpp"
 #include "../../include/smpc_detector.h"
+#include "smpc_plant.hpp"
+#include "../../include/smpc_plant.h"
 
 extern "C" {
 
@@ -984,6 +986,64 @@ int smpc_detect_people_batch(smpc_handle* h, const smpc_detector_in* in, uint32_
   const size_t per_block = smpc::kDtThreads / 64;
   SMPC_TRY(st.timed([&] {
     hipLaunchKernelGGL(smpc::smpc_detect_people_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kDtThreads), 0, h->stream, p);
+    return SMPC_OK;
+  }));
+  return st.finish();
+}
+
+int smpc_robot_plant_batch(smpc_handle* h, const smpc_plant_in* in, double* pose, double* twist, double* cmd_queue, uint32_t* plant_tick,
+                           int32_t* contact, double* heading_cs) {
+  if (!h || !in || !pose || !twist || !plant_tick || !contact) {
+    set_error("null handle / input / pose / twist / plant_tick / contact"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (!in->cmd || !in->agents || !in->count) { set_error("null input array"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B < 0 || in->Np < 1 || in->S < 1 || in->L < 0 || in->footprint_d2 < -1) {
+    set_error("bad B, Np or S < 1, L < 0 or footprint_d2 < -1"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (in->L > 0 && !cmd_queue) { set_error("null cmd_queue with L > 0"); return SMPC_ERR_INVALID_ARG; }
+  for (const double v : {in->dt, in->w_max, in->contact_dist})
+    if (!std::isfinite(v) || !(v >= 0.0)) { set_error("dt, w_max and contact_dist must be finite and >= 0"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->v_min) || !std::isfinite(in->v_max) || !(in->v_min <= in->v_max)) {
+    set_error("v_min and v_max must be finite with v_min <= v_max"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) { set_error("resolution must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  for (const double v : {in->dv_up, in->dv_down, in->dw})
+    if (!(v >= 0.0)) { set_error("dv_up, dv_down and dw must be >= 0 (+inf allowed)"); return SMPC_ERR_INVALID_ARG; }
+  if (in->world && (in->Hx < 1 || in->Hy < 1)) { set_error("world given with Hx or Hy < 1"); return SMPC_ERR_INVALID_ARG; }
+  // the kernel's bounds: lane j owns agent j, the queue has 8 slots, the footprint's square at most 31 x 31 offsets
+  if (in->Np > SMPC_MAX_AGENTS || in->S > SMPC_PLANT_MAX_SUBSTEPS || in->L > SMPC_PLANT_MAX_LATENCY ||
+      in->footprint_d2 > SMPC_PLANT_MAX_FOOTPRINT_D2) {
+    set_error("Np > 64, S > 16, L > 8 or footprint_d2 > 225 is not supported"); return SMPC_ERR_UNSUPPORTED;
+  }
+  if (in->B == 0) return SMPC_OK;
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::PlantParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.B = in->B; p.Np = in->Np; p.S = in->S; p.L = in->L;
+  p.dt = in->dt; p.v_min = in->v_min; p.v_max = in->v_max; p.w_max = in->w_max;
+  p.dv_up = in->dv_up; p.dv_down = in->dv_down; p.dw = in->dw; p.contact2 = smpc::pl_contact2(in->contact_dist);
+  p.res = in->resolution; p.ox = in->world_origin[0]; p.oy = in->world_origin[1];
+  const bool walls = in->world != nullptr && in->footprint_d2 >= 0;
+  p.walls.Hx = in->Hx; p.walls.Hy = in->Hy; p.walls.footprint_d2 = walls ? in->footprint_d2 : -1;
+  p.walls.r = walls ? smpc::pl_isqrt(in->footprint_d2) : 0;
+  p.walls.min_cost = in->wall_min_cost; p.walls.unknown = in->unknown_is_wall ? 1 : 0; p.walls.outside = in->outside_is_wall ? 1 : 0;
+  smpc::fill_math_table(&p.mt);
+  const size_t B = in->B, Np = in->Np;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.walls.world, walls ? in->world : nullptr, (size_t)in->Hx * (size_t)in->Hy));
+  SMPC_TRY(st.in(p.cmd, in->cmd, B * 2));
+  SMPC_TRY(st.in(p.agents, in->agents, B * Np * 5));
+  SMPC_TRY(st.in(p.count, in->count, B));
+  SMPC_TRY(st.inout(p.pose, pose, B * 3));
+  SMPC_TRY(st.inout(p.twist, twist, B * 2));
+  SMPC_TRY(st.inout(p.queue, in->L > 0 ? cmd_queue : nullptr, B * SMPC_PLANT_MAX_LATENCY * 2));
+  SMPC_TRY(st.inout(p.tick, plant_tick, B));
+  SMPC_TRY(st.out(p.contact, contact, B * 2));
+  // read and written: the row of a robot whose state is not finite keeps the caller's bytes on the way through device memory too
+  SMPC_TRY(st.inout(p.heading, heading_cs, B * 2));
+  const size_t per_block = smpc::kPlThreads / 64;
+  SMPC_TRY(st.timed([&] {
+    hipLaunchKernelGGL(smpc::smpc_robot_plant_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kPlThreads), 0, h->stream, p);
     return SMPC_OK;
   }));
   return st.finish();

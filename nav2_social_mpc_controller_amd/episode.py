@@ -21,6 +21,8 @@
     project_people                           (src/optimizer.cpp:554-728)           -> smpc_project_people_batch
     problem assembly + ceres::Solve + unpack (src/optimizer.cpp:197-446)           -> smpc_solve_batch
     memory store                             (src/optimizer.cpp:448-449)           -> smpc_memory_store_batch
+    robot plant (optional)                   (the deployment's base behind cmd_vel;
+                                              the library's own rule)               -> smpc_robot_plant_batch
 
 preceded, when global plans are given, by PathTrajectorizer::trajectorize (src/path_trajectorizer.cpp:120-288 ->
 smpc_trajectorize_path_batch) as in SocialMPCController::computeVelocityCommands (src/social_mpc_controller.cpp:176-189),
@@ -30,6 +32,8 @@ stood in for by the simplest thing that has the same shape:
   * the world: the robot executes the command computeVelocityCommands returns for one period — the first optimised
     command (it lands on the first pose of the optimised path), the trajectorizer's first command when the solve was
     not usable (src/social_mpc_controller.cpp:241-245), 0.1 m/s straight ahead when there is no trajectory (:180-189);
+    with BatchEpisode(plant=PlantParams(...)) that command is executed by a model of the base instead
+    (smpc_robot_plant_batch): delayed, clamped, limited in its rate of change, and stopped by walls and agents;
     people move with constant velocity, walking through the robot, the walls and off the map, or, with
     BatchEpisode(crowd=CrowdParams(...)), as a reactive crowd: every period smpc_crowd_step_batch moves every robot's
     persons one step of the Social Force Model the controller itself predicts them with (sfm.hpp computeForces /
@@ -53,7 +57,7 @@ import numpy as np
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
 from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, ObstacleMemoryParams, OptimizerParams, PoolCrowdParams,
-                     SensorParams, TrackerParams, TrajectorizerParams, SharedWorldParams, VisibilityParams, check_scene_param_rows)
+                     PlantParams, SensorParams, TrackerParams, TrajectorizerParams, SharedWorldParams, VisibilityParams, check_scene_param_rows)
 from .scenes import SceneBatch, World
 from .solver import BatchSolver, point, set_od_grid
 
@@ -142,6 +146,17 @@ class TickRecord:
     detected_count: np.ndarray = None         # [B]
     detected_source: np.ndarray = None        # [B,Nd] int32 person j, or -1 - c of clutter candidate c (rows from detected_count[b] on: not written)
     person_outcome: np.ndarray = None         # [B,Np] uint8 smpc_detect_outcome (persons from the count on: not written)
+    # the robot plant (BatchEpisode(plant=...)): what the tick's smpc_robot_plant_batch read besides robot_pose, speed (the twist
+    # the tick started with) and cmd_vel, and what it wrote besides pose_after
+    plant_agents: np.ndarray = None           # [B,Np,5] the true persons as the call saw them (after the tick's crowd step)
+    plant_agent_count: np.ndarray = None      # [B]
+    plant_queue_before: np.ndarray = None     # [B,8,2] the commands under way
+    plant_tick_before: np.ndarray = None      # [B] uint32
+    plant_queue_after: np.ndarray = None
+    plant_tick_after: np.ndarray = None
+    plant_contact: np.ndarray = None          # [B,2] int32 enum smpc_plant_flag bits, substeps advanced
+    heading_cs: np.ndarray = None             # [B,2] cosine and sine of the heading the period started with
+    speed_after: np.ndarray = None            # [B,2] the executed twist: the next tick's `speed`
 
 
 class BatchEpisode:
@@ -155,7 +170,7 @@ class BatchEpisode:
     FORWARDED = ("od_resolution", "device", "traj_params", "fov_angle", "order_hint", "plan_window", "obstacles_from_costmap",
                  "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost", "planner",
                  "visibility", "shared", "pool", "pool_crowd", "pool_waypoints", "pool_n_waypoints", "pool_speed", "sensor",
-                 "sensor_memory", "tracker", "detector")
+                 "sensor_memory", "tracker", "detector", "plant")
 
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
@@ -170,7 +185,7 @@ class BatchEpisode:
                  shared: SharedWorldParams = None, pool: np.ndarray = None, pool_crowd: PoolCrowdParams = None,
                  pool_waypoints: np.ndarray = None, pool_n_waypoints: np.ndarray = None, pool_speed: np.ndarray = None,
                  sensor: SensorParams = None, sensor_memory: ObstacleMemoryParams = None, tracker: TrackerParams = None,
-                 detector: DetectorParams = None):
+                 detector: DetectorParams = None, plant: PlantParams = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -284,6 +299,17 @@ class BatchEpisode:
         (its index; set_detector_streams() gives a part of a larger batch the ids of its robots there, as ShardedEpisode
         does) and its tick counter, zero at the start, which lives on the device so that a replayed graph draws fresh
         numbers every tick. The world model, the crowd steps, the scan and the metrics keep reading the true self.persons.
+        None: nothing is allocated, nothing is launched and the episode is the one without bit for bit.
+        plant: the command is executed by a model of the base (include/smpc_plant.h) instead of being taken for the motion.
+        Every tick, after the command selection and the crowd steps, one smpc_robot_plant_batch takes the place of the torch
+        move of pose and speed: the command selected plant.latency_ticks periods ago is clamped to params' velocity bounds,
+        limited by plant.max_accel / max_decel / max_ang_accel, and integrated with the motion model (x, y with the old
+        heading, then the heading) in plant.substeps steps that end in front of a wall cell of the world map (with `world`;
+        else there are no walls) or an agent of the true self.persons / self.person_count (with `shared` the other robots
+        among them). Every robot is moved by the motion model, whether its solve was usable or not. self.speed becomes the
+        executed twist, which the next warm start and the metrics read. The state is self.plant_queue [B,8,2],
+        self.plant_tick [B] int32 (the bits of the call's uint32 words), zero at the start; self.plant_contact [B,2] int32
+        holds each robot's flags (enum smpc_plant_flag) and substeps, self.heading_cs [B,2] the heading's cosine and sine.
         None: nothing is allocated, nothing is launched and the episode is the one without bit for bit."""
         import torch
 
@@ -346,6 +372,7 @@ class BatchEpisode:
         self._init_sensor(sensor, sensor_memory)
         self._init_tracker(tracker)
         self._init_detector(detector)
+        self._init_plant(plant)
         self._bind()
         self.graph = None
         self.gstream = None
@@ -602,6 +629,27 @@ class BatchEpisode:
         self.detected_source = self._zeros(B, Nd, dtype=self.torch.int32)
         self.person_outcome = self._zeros(B, Np, dtype=self.torch.uint8)
 
+    @staticmethod
+    def check_plant(plant, resolution: float = None):
+        """What BatchEpisode(plant=...) refuses (resolution: the world's, None without one)."""
+        if not isinstance(plant, PlantParams):
+            raise ValueError("plant must be a PlantParams")
+        if not plant.supported(resolution):
+            raise ValueError("plant: robot_radius beyond 15 cells at the world's resolution")
+
+    def _init_plant(self, plant):
+        """The commands under way and the tick counter of every robot (zero: at rest, nothing under way), and what the plant
+        writes every tick besides pose and speed: fixed addresses."""
+        self.plant = plant
+        if plant is None:
+            return
+        self.check_plant(plant, self.resolution if self.world is not None else None)
+        B = self.B
+        self.plant_queue = self._zeros(B, 8, 2)
+        self.plant_tick = self._zeros(B, dtype=self.torch.int32)
+        self.plant_contact = self._zeros(B, 2, dtype=self.torch.int32)
+        self.heading_cs = self._zeros(B, 2)
+
     def set_detector_streams(self, streams):
         """streams [B] (0 .. 2^32 - 1): the stream ids of this episode's robots in place of their indices, so that a part of a
         larger batch draws what the same robots draw there. In place: a captured graph reads the new ids."""
@@ -780,10 +828,17 @@ class BatchEpisode:
             c.groups = None
             if self.person_groups is not None:
                 c.groups = BatchSolver.crowd_groups_c(self.crowd_group_params, self.person_groups.data_ptr())
+        if self.plant is not None:  # the plant sees the true persons and the world's walls, whatever the controller is told
+            if self.world is not None:
+                c.plant = point(BatchSolver.plant_c(self.plant, prm, B, Np, 1, self.world.cells_x, self.world.cells_y, self.resolution,
+                                                    np.asarray(self.world.origin, np.float64).reshape(2)), {"world": self.world_map})
+            else:
+                c.plant = BatchSolver.plant_c(self.plant, prm, B, Np, 1)
+            point(c.plant, {"cmd": self.cmd_vel, "agents": self.persons, "count": self.person_count})
         if self.metrics_params is not None:
             c.metrics = point(BatchSolver.metrics_c(self.metrics_params, B, Np, prm.dt, 1),
-                              {"robot_pose": self.pose, "robot_twist": self.cmd_vel, "people": self.persons,
-                               "count": self.person_count, "goal": self.goal, "status": self.res["status"],
+                              {"robot_pose": self.pose, "robot_twist": self.cmd_vel if self.plant is None else self.speed,  # the twist executed
+                               "people": self.persons, "count": self.person_count, "goal": self.goal, "status": self.res["status"],
                                "source": self.cmd_source})
             if hasattr(self, "od_distances"):  # the clearance columns
                 set_od_grid(c.metrics, "od_distances", self.od_distances, self.od_origin, self.od_resolution, od)
@@ -966,12 +1021,23 @@ class BatchEpisode:
             timed("pool_crowd")
             if record:
                 rec.update(self._host("pool_next", pool_cursor_after="pool_cursor"))
-        v, w, th = self.cmd_vel[:, 0], self.cmd_vel[:, 1], self.pose[:, 2]
-        moved = torch.stack([self.pose[:, 0] + v * torch.cos(th) * dt, self.pose[:, 1] + v * torch.sin(th) * dt, th + w * dt], dim=1)
-        optimised = (self.cmd_source == 0)[:, None]
-        # state is updated in place: every buffer the kernels read keeps its address from tick to tick (_bind)
-        self.pose.copy_(torch.where(optimised, self.res["path"][:, 0, :], moved))
-        self.speed.copy_(self.cmd_vel)
+        if self.plant is not None:  # the base executes the command: limits, latency, and contacts with walls and agents
+            if record:
+                rec.update(self._host(plant_agents="persons", plant_agent_count="person_count", plant_queue_before="plant_queue"))
+                rec["plant_tick_before"] = self.plant_tick.cpu().numpy().view(np.uint32).copy()
+            s.robot_plant_device(c.plant, self.pose.data_ptr(), self.speed.data_ptr(), self.plant_queue.data_ptr(),
+                                 self.plant_tick.data_ptr(), self.plant_contact.data_ptr(), self.heading_cs.data_ptr())
+            timed("plant")
+            if record:
+                rec.update(self._host("plant_contact", "heading_cs", plant_queue_after="plant_queue", speed_after="speed"))
+                rec["plant_tick_after"] = self.plant_tick.cpu().numpy().view(np.uint32).copy()
+        else:
+            v, w, th = self.cmd_vel[:, 0], self.cmd_vel[:, 1], self.pose[:, 2]
+            moved = torch.stack([self.pose[:, 0] + v * torch.cos(th) * dt, self.pose[:, 1] + v * torch.sin(th) * dt, th + w * dt], dim=1)
+            optimised = (self.cmd_source == 0)[:, None]
+            # state is updated in place: every buffer the kernels read keeps its address from tick to tick (_bind)
+            self.pose.copy_(torch.where(optimised, self.res["path"][:, 0, :], moved))
+            self.speed.copy_(self.cmd_vel)
         if self.shared is not None:  # the pool walks on; what a robot perceives of it is gathered, not moved
             M = self.M
             if pool_crowd:
@@ -1036,6 +1102,8 @@ class BatchEpisode:
             state += ("tracks", "track_meta", "track_next_id")
         if self.detector is not None:
             state += ("draw_state",)
+        if self.plant is not None:
+            state += ("plant_queue", "plant_tick")
         with torch.cuda.stream(self.gstream):
             saved = {k: getattr(self, k).clone() for k in state}
             ticks = self.ticks

@@ -377,6 +377,79 @@ class DetectorParams:
 
 
 @dataclass
+class PlantParams:
+    """The robot plant (include/smpc_plant.h; BatchEpisode(plant=...)): every tick the selected command is executed by a
+    model of the base instead of being taken for the motion. The command that was selected latency_ticks periods ago is
+    clamped to the velocity bounds (OptimizerParams' v_min, v_max, w_max), the speed may grow by at most max_accel * dt and
+    shrink by at most max_decel * dt in one period, the turn rate may change by max_ang_accel * dt, and the period's straight
+    segment is walked in `substeps` steps that end in front of the first one that brings the disc of robot_radius closer to
+    a wall cell (world cost >= wall_min_cost, 255 only with unknown_is_wall, beyond the map with outside_is_wall) or to an
+    agent whose centre is within robot_radius + agent_radius. robot_radius None: no walls; agent_radius None: no agents.
+    The defaults are a differential-drive base of the reference's size class: 2.5 m/s^2, 3.2 rad/s^2 (Nav2's shipped
+    velocity smoother), a disc of 0.24 m (the inscribed radius of the reference's 0.48 m footprint) and persons of 0.3 m."""
+    max_accel: float = 2.5
+    max_decel: float = 2.5
+    max_ang_accel: float = 3.2
+    latency_ticks: int = 0
+    substeps: int = 8
+    robot_radius: float = 0.24
+    agent_radius: float = 0.3
+    wall_min_cost: int = 254
+    unknown_is_wall: bool = False
+    outside_is_wall: bool = True
+
+    def __post_init__(self):
+        for name in ("max_accel", "max_decel", "max_ang_accel"):
+            v = getattr(self, name)
+            if not v >= 0.0:   # +inf: no limit
+                raise ValueError(f"PlantParams.{name} must be >= 0 (inf: no limit), got {v}")
+        for name in ("robot_radius", "agent_radius"):
+            v = getattr(self, name)
+            if v is not None and not (np.isfinite(v) and v >= 0.0):
+                raise ValueError(f"PlantParams.{name} must be None or finite and >= 0, got {v}")
+        if int(self.latency_ticks) != self.latency_ticks or not 0 <= self.latency_ticks <= 8:
+            raise ValueError(f"PlantParams.latency_ticks must be an integer in 0..8, got {self.latency_ticks}")
+        if int(self.substeps) != self.substeps or not 1 <= self.substeps <= 16:
+            raise ValueError(f"PlantParams.substeps must be an integer in 1..16, got {self.substeps}")
+        if int(self.wall_min_cost) != self.wall_min_cost or not 0 <= self.wall_min_cost <= 255:
+            raise ValueError(f"PlantParams.wall_min_cost must be 0..255, got {self.wall_min_cost}")
+
+    @classmethod
+    def ideal(cls) -> "PlantParams":
+        """The plant that follows every command within the velocity bounds at once and touches nothing: infinite limits, no
+        latency, no contacts, one substep."""
+        inf = float("inf")
+        return cls(max_accel=inf, max_decel=inf, max_ang_accel=inf, latency_ticks=0, substeps=1, robot_radius=None, agent_radius=None)
+
+    def footprint_d2(self, resolution: float) -> int:
+        """The squared footprint radius in cells, rounded down as SensorParams.agent_d2 rounds; -1 without robot_radius."""
+        if self.robot_radius is None:
+            return -1
+        r = np.float64(self.robot_radius) / np.float64(resolution)
+        return int(np.floor(r * r + 1e-9))
+
+    def contact_dist(self) -> float:
+        """robot_radius + agent_radius (a missing robot_radius counts 0); 0.0, which no distance is below, without agent_radius."""
+        if self.agent_radius is None:
+            return 0.0
+        return float(np.float64(self.robot_radius or 0.0) + np.float64(self.agent_radius))
+
+    def deltas(self, dt: float):
+        """(dv_up, dv_down, dw) as the call takes them: acceleration * dt, one product each (inf stays inf, also with dt 0)."""
+        if not (np.isfinite(dt) and dt >= 0.0):
+            raise ValueError(f"PlantParams.deltas: dt must be finite and >= 0, got {dt}")
+        mul = lambda a: float("inf") if np.isinf(a) else float(np.float64(a) * np.float64(dt))
+        return mul(self.max_accel), mul(self.max_decel), mul(self.max_ang_accel)
+
+    def supported(self, resolution: float = None) -> bool:
+        """Does the library run this plant: with `resolution`, a footprint of at most 15 cells (footprint_d2 <= 225)?"""
+        if resolution is None or self.robot_radius is None:
+            return True
+        r = np.float64(self.robot_radius) / np.float64(resolution)
+        return bool(r * r + 1e-9 < 226.0)
+
+
+@dataclass
 class SharedWorldParams:
     """One world for all robots of an episode (include/smpc_nearest.h; BatchEpisode(shared=..., pool=...)): every tick each
     robot is handed its at most max_people nearest agents within max_range (the detector's range in metres, VisibilityParams'

@@ -11,8 +11,8 @@ import os
 
 import numpy as np
 
-from . import (_abi, _abi_crowd_pool, _abi_detector, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_obstacle_memory, _abi_sensed_costmap,
-               _abi_tracker, _abi_visibility)
+from . import (_abi, _abi_crowd_pool, _abi_detector, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_obstacle_memory, _abi_plant,
+               _abi_sensed_costmap, _abi_tracker, _abi_visibility)
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
@@ -22,10 +22,11 @@ from ._abi_global_plan import SmpcExtractPlanIn, SmpcGoalFieldIn
 from ._abi_local_costmap import SmpcLocalCostmapIn
 from ._abi_nearest import SmpcNearestIn
 from ._abi_obstacle_memory import SmpcObstacleMemoryIn
+from ._abi_plant import SmpcPlantIn
 from ._abi_sensed_costmap import SmpcSensedCostmapIn
 from ._abi_tracker import SmpcTrackerIn
 from ._abi_visibility import SmpcVisibilityIn
-from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, OptimizerParams, PoolCrowdParams,
+from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, OptimizerParams, PlantParams, PoolCrowdParams,
                      TrackerParams, TrajectorizerParams, VisibilityParams)
 from .scenes import SceneBatch
 
@@ -67,7 +68,7 @@ def load_library():
                                        **_abi_global_plan.FUNCTIONS, **_abi_visibility.FUNCTIONS, **_abi_nearest.FUNCTIONS,
                                        **_abi_crowd_pool.FUNCTIONS, **_abi_sensed_costmap.FUNCTIONS,
                                        **_abi_obstacle_memory.FUNCTIONS, **_abi_tracker.FUNCTIONS,
-                                       **_abi_detector.FUNCTIONS}.items():
+                                       **_abi_detector.FUNCTIONS, **_abi_plant.FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -874,6 +875,61 @@ class BatchSolver:
         det_source and outcome (0: none); asynchronous on the handle's stream."""
         assert di.on_device == 1
         self._call("smpc_detect_people_batch", di, draw_state_ptr, detections_ptr, det_count_ptr, det_source_ptr or None, outcome_ptr or None)
+
+    # -- robot plant (smpc_robot_plant_batch, include/smpc_plant.h) ----------------------------------------------------------
+    @staticmethod
+    def plant_c(pp: PlantParams, prm: OptimizerParams, B: int, Np: int, on_device: int, world_x: int = 0, world_y: int = 0,
+                resolution: float = 1.0, world_origin=(0.0, 0.0)) -> SmpcPlantIn:
+        """The call's struct without its pointers: the velocity bounds are prm's (v_min, v_max, w_max), the period prm.dt; the
+        walls are world_x x world_y cells of `resolution` at world_origin (point `world` at the map, or leave it NULL)."""
+        dv_up, dv_down, dw = pp.deltas(prm.dt)
+        pi = SmpcPlantIn(B=int(B), Np=int(Np), S=int(pp.substeps), L=int(pp.latency_ticks), on_device=int(on_device), Hx=int(world_x),
+                         Hy=int(world_y), footprint_d2=pp.footprint_d2(resolution), wall_min_cost=int(pp.wall_min_cost),
+                         unknown_is_wall=int(bool(pp.unknown_is_wall)), outside_is_wall=int(bool(pp.outside_is_wall)),
+                         dt=float(prm.dt), v_min=float(prm.v_min), v_max=float(prm.v_max), w_max=float(prm.w_max), dv_up=dv_up,
+                         dv_down=dv_down, dw=dw, contact_dist=pp.contact_dist(), resolution=float(resolution))
+        pi.world_origin[0], pi.world_origin[1] = float(world_origin[0]), float(world_origin[1])
+        return pi
+
+    def robot_plant(self, pi: SmpcPlantIn, pose: np.ndarray, twist: np.ndarray, cmd_queue: np.ndarray, plant_tick: np.ndarray,
+                    cmd: np.ndarray, agents: np.ndarray, count: np.ndarray, world: np.ndarray = None, contact: np.ndarray = None,
+                    heading_cs: np.ndarray = None, with_heading: bool = True):
+        """One period of the plant on host arrays. pi: plant_c(..., on_device=0) (its pointers are set here; world [Hy,Hx] uint8
+        or None). pose [B,3], twist [B,2], cmd_queue [B,8,2] (None with L == 0) and plant_tick [B] uint32 are the state the
+        last call returned (zeros to start with; they are not modified); cmd [B,2], agents [B,Np,5], count [B] int32.
+        contact [B,2] int32 / heading_cs [B,2]: the arrays before the call (default -1 / NaN). Returns (new pose, new twist,
+        new cmd_queue or None, new plant_tick, contact, heading_cs or None with with_heading=False)."""
+        cmd = np.ascontiguousarray(cmd, np.float64)
+        agents = np.ascontiguousarray(agents, np.float64)
+        count = np.ascontiguousarray(count, np.int32)
+        B, Np = agents.shape[0], agents.shape[1]
+        pose = np.array(pose, np.float64, order="C")
+        twist = np.array(twist, np.float64, order="C")
+        plant_tick = np.array(plant_tick, np.uint32, order="C")
+        cmd_queue = None if cmd_queue is None else np.array(cmd_queue, np.float64, order="C")
+        assert pi.on_device == 0 and pi.B == B and pi.Np == Np
+        assert cmd.shape == (B, 2) and agents.shape == (B, Np, 5) and count.shape == (B,)
+        assert pose.shape == (B, 3) and twist.shape == (B, 2) and plant_tick.shape == (B,)
+        assert cmd_queue is None or cmd_queue.shape == (B, 8, 2)
+        contact = np.full((B, 2), -1, np.int32) if contact is None else np.array(contact, dtype=np.int32, order="C")
+        if with_heading:
+            heading_cs = np.full((B, 2), np.nan) if heading_cs is None else np.array(heading_cs, dtype=np.float64, order="C")
+            assert heading_cs.shape == (B, 2)
+        else:
+            heading_cs = None
+        if world is not None:
+            world = np.ascontiguousarray(world, np.uint8)
+            assert world.shape == (pi.Hy, pi.Hx)
+        point(pi, {"world": world, "cmd": cmd, "agents": agents, "count": count})
+        self._call("smpc_robot_plant_batch", pi, _ptr(pose), _ptr(twist), _ptr(cmd_queue), _ptr(plant_tick), _ptr(contact), _ptr(heading_cs))
+        return pose, twist, cmd_queue, plant_tick, contact, heading_cs
+
+    def robot_plant_device(self, pi: SmpcPlantIn, pose_ptr: int, twist_ptr: int, cmd_queue_ptr: int, plant_tick_ptr: int, contact_ptr: int,
+                           heading_cs_ptr: int = 0):
+        """Device pointers in pi (on_device == 1) and for the state (pose, twist, cmd_queue, plant_tick: read and written),
+        contact and heading_cs (0: none); asynchronous on the handle's stream."""
+        assert pi.on_device == 1
+        self._call("smpc_robot_plant_batch", pi, pose_ptr, twist_ptr, cmd_queue_ptr or None, plant_tick_ptr, contact_ptr, heading_cs_ptr or None)
 
     # -- sensed local costmaps (smpc_sensed_costmap_batch, include/smpc_sensed_costmap.h) ----------------------------------
     @staticmethod

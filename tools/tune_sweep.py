@@ -4,7 +4,7 @@ of a batch whose solve takes each robot's own critic weights and velocity bounds
 BatchEpisode(scene_params=...)); the device scores every robot as it drives (BatchEpisode(metrics=...)), and one line of
 summarize_metrics means is printed per set. Nothing but the final [B,24] metrics rows leaves the device.
 
-    python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]] [--tracker] [--detector]
+    python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]] [--tracker] [--detector] [--plant]
                                 [--world-plans [--occlusion [RANGE]] [--shared-crowd M] [--sensed-costmap [--obstacle-memory]]]
 
 --reactive: the persons are a reactive crowd (BatchEpisode(crowd=CrowdParams()), waypoints from scenes.crowd_waypoints)
@@ -39,6 +39,11 @@ The tuning then meets the velocities a deployed tracker would deliver. The metri
 handed are what a detector would report (BatchEpisode(detector=DetectorParams())): a person behind another person's body is
 not reported, one in ten is missed, positions carry 3 cm of noise at the sensor and 23 cm at 10 m, and false detections
 appear around the robot. With --tracker the tuning meets a perception a robot has. The metrics keep scoring the true persons.
+--plant (with anything above): the command is executed by a model of the base (BatchEpisode(plant=PlantParams())): accelerations
+of 2.5 m/s^2 and 3.2 rad/s^2, and a disc of 0.24 m that stops where it would come closer to a wall cell of the world map (with
+--world-plans) or to a person it touches, instead of passing through. The velocity bounds are the base set's for every robot.
+The collision and time-to-goal columns then describe a robot that exists; a last column counts the robot-ticks of the final
+tick that a contact stopped.
 """
 import argparse
 import os
@@ -82,6 +87,8 @@ def main():
                     help="the controller is handed tracks of the detected persons (velocity from positions, coasting when hidden)")
     ap.add_argument("--detector", action="store_true",
                     help="the detections are a detector's: body occlusion, misses, range-dependent noise and clutter")
+    ap.add_argument("--plant", action="store_true",
+                    help="the command is executed under acceleration limits and stopped by contact with walls and persons")
     a = ap.parse_args()
     if a.obstacle_memory and not a.sensed_costmap:
         ap.error("--obstacle-memory needs --sensed-costmap")
@@ -100,7 +107,7 @@ def main():
 
     from nav2_social_mpc_controller_amd.episode import BatchEpisode, arc_plans
     from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, ObstacleMemoryParams, OptimizerParams,
-                                                       DetectorParams, PoolCrowdParams, SensorParams, SharedWorldParams, TrackerParams, TrajectorizerParams, VisibilityParams,
+                                                       DetectorParams, PlantParams, PoolCrowdParams, SensorParams, SharedWorldParams, TrackerParams, TrajectorizerParams, VisibilityParams,
                                                        scene_param_rows)
     from nav2_social_mpc_controller_amd.scenes import (crowd_groups, crowd_waypoints, make_scenes, make_world, pool_waypoints, scenes_in_world,
                                                        shared_pool, uniform, world_goals)
@@ -147,6 +154,8 @@ def main():
         plans["tracker"] = TrackerParams(slots=max(16, min(64, 2 * a.agents)))
     if a.detector:
         plans["detector"] = DetectorParams(clutter_candidates=min(2, 64 - a.agents))
+    if a.plant:
+        plans["plant"] = PlantParams()
     ep = BatchEpisode(prm, sc, w_ref, traj_params=tp, fov_angle=np.pi / 4, obstacles_from_costmap=True, scene_params=rows,
                       metrics=MetricsParams(), **plans, **crowd)
     ep.capture_graph()
@@ -154,6 +163,7 @@ def main():
         ep.replay()
     m = summarize_metrics(ep.metrics(), prm.dt)
     print(f"{S} parameter sets x {n} scenes, {a.agents} agents, {a.ticks} ticks of {prm.dt} s")
+    stopped = (ep.plant_contact[:, 0].cpu().numpy() & 3) != 0 if a.plant else np.zeros(S * n, bool)
     for k, name in enumerate(sets):
         sl = slice(k * n, (k + 1) * n)
         mean = lambda key: float(np.nanmean(m[key][sl])) if np.isfinite(m[key][sl]).any() else float("nan")
@@ -161,7 +171,8 @@ def main():
               f"mean_speed {mean('mean_speed'):.3f}  mean_min_person_dist {mean('mean_min_person_dist'):.3f}  "
               f"intimate {mean('intimate_share'):.3f}  personal {mean('personal_share'):.3f}  "
               f"social_work/m {mean('social_work_per_metre'):8.3f}  person_coll {m['person_collision'][sl].mean():.3f}  "
-              f"obstacle_coll {m['obstacle_collision'][sl].mean():.3f}  fallback {mean('fallback_share'):.3f}")
+              f"obstacle_coll {m['obstacle_collision'][sl].mean():.3f}  fallback {mean('fallback_share'):.3f}"
+              + (f"  stopped_by_contact {stopped[sl].mean():.3f}" if a.plant else ""))
 
 
 if __name__ == "__main__":
