@@ -16,7 +16,7 @@
 //   the probe kernels (smpc_probes.hpp);
 //   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window,
 //   metrics, crowd, local costmap, global plan, visibility, nearest agents, pool crowd, sensed costmap, obstacle memory,
-//   people tracks, people detections, robot plant).
+//   people tracks, people detections, robot plant, collision monitor).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -53,6 +53,8 @@
 #include "../../include/smpc_detector.h"
 #include "smpc_plant.hpp"
 #include "../../include/smpc_plant.h"
+#include "smpc_collision_monitor.hpp"
+#include "../../include/smpc_collision_monitor.h"
 
 extern "C" {
 
@@ -1044,6 +1046,73 @@ int smpc_robot_plant_batch(smpc_handle* h, const smpc_plant_in* in, double* pose
   const size_t per_block = smpc::kPlThreads / 64;
   SMPC_TRY(st.timed([&] {
     hipLaunchKernelGGL(smpc::smpc_robot_plant_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kPlThreads), 0, h->stream, p);
+    return SMPC_OK;
+  }));
+  return st.finish();
+}
+
+int smpc_collision_monitor_batch(smpc_handle* h, const smpc_collision_monitor_in* in, double* cmd_out, int32_t* action, int32_t* zone_points,
+                                 double* ratio, double* heading_cs, double* step_cs) {
+  if (!h || !in || !cmd_out || !action) { set_error("null handle / input / cmd_out / action"); return SMPC_ERR_INVALID_ARG; }
+  if (!in->zones || !in->robot_pose || !in->cmd || !in->beam_kind || !in->beam_cell) { set_error("null input array"); return SMPC_ERR_INVALID_ARG; }
+  if (cmd_out == in->cmd) { set_error("cmd_out must not be the buffer of cmd"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B < 0 || in->Z < 1 || in->n_beams < 1 || in->M < 0) { set_error("bad B, Z or n_beams < 1, or M < 0"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) { set_error("resolution must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (in->M > 0 && (!std::isfinite(in->sim_dt) || !(in->sim_dt > 0.0))) { set_error("sim_dt must be finite and > 0 with M > 0"); return SMPC_ERR_INVALID_ARG; }
+  // the kernel's bounds: the zones travel in the kernel arguments, a lane holds 8 points of a chunk, a zone 16 vertices
+  if (in->Z > SMPC_MONITOR_MAX_ZONES || in->M > SMPC_MONITOR_MAX_STEPS || in->n_beams > SMPC_SENSED_MAX_BEAMS) {
+    set_error("Z > 8, M > 32 or n_beams > 4096 is not supported"); return SMPC_ERR_UNSUPPORTED;
+  }
+  smpc::MonitorParams p;
+  std::memset(&p, 0, sizeof(p));
+  for (int zi = 0; zi < in->Z; ++zi) {
+    const smpc_monitor_zone& z = in->zones[zi];
+    smpc::MonitorZone& k = p.zones[zi];
+    if ((z.shape != SMPC_MONITOR_CIRCLE && z.shape != SMPC_MONITOR_POLYGON) || z.action < SMPC_MONITOR_STOP || z.action > SMPC_MONITOR_APPROACH) {
+      set_error("zone: unknown shape or action"); return SMPC_ERR_INVALID_ARG;
+    }
+    if (z.shape == SMPC_MONITOR_POLYGON && (z.n_vertices < 3 || z.n_vertices > SMPC_MONITOR_MAX_VERTICES)) {
+      set_error("zone: a polygon has 3..16 vertices"); return SMPC_ERR_INVALID_ARG;
+    }
+    if (z.min_points < 1) { set_error("zone: min_points < 1"); return SMPC_ERR_INVALID_ARG; }
+    if (!std::isfinite(z.radius) || !(z.radius >= 0.0) || !(z.linear_limit >= 0.0) || !(z.angular_limit >= 0.0)) {
+      set_error("zone: radius must be finite and >= 0, the limits >= 0"); return SMPC_ERR_INVALID_ARG;
+    }
+    if (!(z.slowdown_ratio >= 0.0 && z.slowdown_ratio <= 1.0)) { set_error("zone: slowdown_ratio outside [0, 1]"); return SMPC_ERR_INVALID_ARG; }
+    if (z.action == SMPC_MONITOR_APPROACH && in->M == 0) { set_error("an APPROACH zone needs M >= 1"); return SMPC_ERR_INVALID_ARG; }
+    k.shape = z.shape; k.action = z.action; k.min_points = z.min_points;
+    k.n = z.shape == SMPC_MONITOR_POLYGON ? z.n_vertices : 0;
+    for (int i = 0; i < k.n; ++i) {
+      if (!std::isfinite(z.vertices[i][0]) || !std::isfinite(z.vertices[i][1])) { set_error("zone: vertex not finite"); return SMPC_ERR_INVALID_ARG; }
+      k.vx[i] = z.vertices[i][0]; k.vy[i] = z.vertices[i][1];
+    }
+    k.radius2 = smpc::cm_radius2(z.radius); k.slowdown_ratio = z.slowdown_ratio;
+    k.linear_limit = z.linear_limit; k.angular_limit = z.angular_limit;
+    k.bound = smpc::cm_bound(k.shape, z.radius, k.n, k.vx, k.vy);
+  }
+  if (in->B == 0) return SMPC_OK;
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  p.B = in->B; p.n_beams = in->n_beams; p.Z = in->Z; p.M = in->M;
+  p.sim_dt = in->M > 0 ? in->sim_dt : 0.0; p.res = in->resolution; p.ox = in->world_origin[0]; p.oy = in->world_origin[1];
+  smpc::fill_math_table(&p.mt);
+  const size_t B = in->B, n = in->n_beams;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.pose, in->robot_pose, B * 3));
+  SMPC_TRY(st.in(p.cmd, in->cmd, B * 2));
+  SMPC_TRY(st.in(p.kind, in->beam_kind, B * n));
+  SMPC_TRY(st.in(p.cell, in->beam_cell, B * n * 2));
+  SMPC_TRY(st.out(p.cmd_out, cmd_out, B * 2));
+  SMPC_TRY(st.out(p.action, action, B * 4));
+  SMPC_TRY(st.out(p.zone_points, zone_points, B * (size_t)in->Z));
+  SMPC_TRY(st.out(p.ratio, ratio, B));
+  // read and written: the rows the rule does not write keep the caller's bytes on the way through device memory too
+  SMPC_TRY(st.inout(p.heading, heading_cs, B * 2));
+  SMPC_TRY(st.inout(p.step, step_cs, B * 2));
+  const size_t per_block = smpc::kCmThreads / 64;
+  const dim3 grid((unsigned)((B + per_block - 1) / per_block)), block(smpc::kCmThreads);
+  SMPC_TRY(st.timed([&] {
+    if (in->n_beams <= 64 * smpc::kCmSlots) hipLaunchKernelGGL(smpc::smpc_collision_monitor_kernel<true>, grid, block, 0, h->stream, p);
+    else hipLaunchKernelGGL(smpc::smpc_collision_monitor_kernel<false>, grid, block, 0, h->stream, p);
     return SMPC_OK;
   }));
   return st.finish();

@@ -21,6 +21,8 @@
     project_people                           (src/optimizer.cpp:554-728)           -> smpc_project_people_batch
     problem assembly + ceres::Solve + unpack (src/optimizer.cpp:197-446)           -> smpc_solve_batch
     memory store                             (src/optimizer.cpp:448-449)           -> smpc_memory_store_batch
+    collision monitor (optional)             (Nav2's collision_monitor behind the
+                                              controller; the library's own rule)   -> smpc_collision_monitor_batch
     robot plant (optional)                   (the deployment's base behind cmd_vel;
                                               the library's own rule)               -> smpc_robot_plant_batch
 
@@ -56,7 +58,7 @@ import numpy as np
 
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
-from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, ObstacleMemoryParams, OptimizerParams, PoolCrowdParams,
+from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, MonitorParams, ObstacleMemoryParams, OptimizerParams, PoolCrowdParams,
                      PlantParams, SensorParams, TrackerParams, TrajectorizerParams, SharedWorldParams, VisibilityParams, check_scene_param_rows)
 from .scenes import SceneBatch, World
 from .solver import BatchSolver, point, set_od_grid
@@ -157,6 +159,14 @@ class TickRecord:
     plant_contact: np.ndarray = None          # [B,2] int32 enum smpc_plant_flag bits, substeps advanced
     heading_cs: np.ndarray = None             # [B,2] cosine and sine of the heading the period started with
     speed_after: np.ndarray = None            # [B,2] the executed twist: the next tick's `speed`
+    # the collision monitor (BatchEpisode(monitor=...)): what the tick's smpc_collision_monitor_batch wrote, having read robot_pose,
+    # cmd_vel, beam_kind and beam_cell; cmd_safe is the command the crowd, the plant or the motion model were handed
+    cmd_safe: np.ndarray = None               # [B,2]
+    monitor_action: np.ndarray = None         # [B,4] int32 enum smpc_monitor_flag bits, the deciding zone, its collision step, the points
+    monitor_points: np.ndarray = None         # [B,Z] int32 points inside each zone at step 0
+    monitor_ratio: np.ndarray = None          # [B]
+    monitor_heading_cs: np.ndarray = None     # [B,2] cosine and sine of the heading the monitor obtained (rows of robots not finite: not written)
+    monitor_step_cs: np.ndarray = None        # [B,2] ... of one simulation step's angle
 
 
 class BatchEpisode:
@@ -170,7 +180,7 @@ class BatchEpisode:
     FORWARDED = ("od_resolution", "device", "traj_params", "fov_angle", "order_hint", "plan_window", "obstacles_from_costmap",
                  "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost", "planner",
                  "visibility", "shared", "pool", "pool_crowd", "pool_waypoints", "pool_n_waypoints", "pool_speed", "sensor",
-                 "sensor_memory", "tracker", "detector", "plant")
+                 "sensor_memory", "tracker", "detector", "plant", "monitor")
 
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
@@ -185,7 +195,7 @@ class BatchEpisode:
                  shared: SharedWorldParams = None, pool: np.ndarray = None, pool_crowd: PoolCrowdParams = None,
                  pool_waypoints: np.ndarray = None, pool_n_waypoints: np.ndarray = None, pool_speed: np.ndarray = None,
                  sensor: SensorParams = None, sensor_memory: ObstacleMemoryParams = None, tracker: TrackerParams = None,
-                 detector: DetectorParams = None, plant: PlantParams = None):
+                 detector: DetectorParams = None, plant: PlantParams = None, monitor: MonitorParams = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -310,6 +320,17 @@ class BatchEpisode:
         executed twist, which the next warm start and the metrics read. The state is self.plant_queue [B,8,2],
         self.plant_tick [B] int32 (the bits of the call's uint32 words), zero at the start; self.plant_contact [B,2] int32
         holds each robot's flags (enum smpc_plant_flag) and substeps, self.heading_cs [B,2] the heading's cosine and sine.
+        None: nothing is allocated, nothing is launched and the episode is the one without bit for bit.
+        monitor: the selected command passes a collision monitor (include/smpc_collision_monitor.h) before anything executes
+        it; needs `sensor`, with or without `sensor_memory`: the monitor reads the tick's scan. Directly behind the command
+        selection one smpc_collision_monitor_batch judges self.cmd_vel at self.pose against the cells the tick's beams
+        stopped at (self.beam_kind / self.beam_cell) and writes self.cmd_safe [B,2], self.monitor_action [B,4] int32
+        (enum smpc_monitor_flag bits, the deciding zone or -1, its collision step or -1, the robot's points),
+        self.monitor_points [B,Z] int32 and self.monitor_ratio [B]. Everything behind it that took self.cmd_vel for the
+        command being executed takes self.cmd_safe: the crowd steps, the plant, and without a plant the motion model, the next
+        warm start's speed and the metrics' twist; self.cmd_vel stays the controller's command. Without a plant a robot whose
+        command the monitor changed (ratio < 1) is moved by the motion model with the safe command instead of being placed
+        on the first optimised pose.
         None: nothing is allocated, nothing is launched and the episode is the one without bit for bit."""
         import torch
 
@@ -373,6 +394,7 @@ class BatchEpisode:
         self._init_tracker(tracker)
         self._init_detector(detector)
         self._init_plant(plant)
+        self._init_monitor(monitor)
         self._bind()
         self.graph = None
         self.gstream = None
@@ -650,6 +672,30 @@ class BatchEpisode:
         self.plant_contact = self._zeros(B, 2, dtype=self.torch.int32)
         self.heading_cs = self._zeros(B, 2)
 
+    @staticmethod
+    def check_monitor(monitor, sensor):
+        """What BatchEpisode(monitor=...) refuses (sensor: the episode's)."""
+        if not isinstance(monitor, MonitorParams):
+            raise ValueError("monitor must be a MonitorParams")
+        if sensor is None:
+            raise ValueError("monitor needs sensor=SensorParams(...): it reads the scan")
+        if not monitor.supported():
+            raise ValueError("monitor: more than 8 zones or more than 32 simulation steps")
+
+    def _init_monitor(self, monitor):
+        """What the monitor writes every tick: fixed addresses. It has no state."""
+        self.monitor = monitor
+        if monitor is None:
+            return
+        self.check_monitor(monitor, self.sensor)
+        B = self.B
+        self.cmd_safe = self._zeros(B, 2)
+        self.monitor_action = self._zeros(B, 4, dtype=self.torch.int32)
+        self.monitor_points = self._zeros(B, len(monitor.zones), dtype=self.torch.int32)
+        self.monitor_ratio = self._zeros(B)
+        self.monitor_heading_cs = self._zeros(B, 2)
+        self.monitor_step_cs = self._zeros(B, 2)
+
     def set_detector_streams(self, streams):
         """streams [B] (0 .. 2^32 - 1): the stream ids of this episode's robots in place of their indices, so that a part of a
         larger batch draws what the same robots draw there. In place: a captured graph reads the new ids."""
@@ -820,9 +866,15 @@ class BatchEpisode:
                           "costmap_origin": self.costmap_origin,
                           "order": self.order if self.order_hint else None,  # longest scenes of the previous period first
                           "T_scene": self.T_scene if planned else None, "scene_params": self.scene_params})
+        executed = self.cmd_vel  # the command that is executed: the monitor's when there is one
+        if self.monitor is not None:
+            c.monitor = point(BatchSolver.collision_monitor_c(self.monitor, B, int(self.sensor.n_beams), 1, self.resolution,
+                                                              np.asarray(self.world.origin, np.float64).reshape(2)),
+                              {"robot_pose": self.pose, "cmd": self.cmd_vel, "beam_kind": self.beam_kind, "beam_cell": self.beam_cell})
+            executed = self.cmd_safe
         if self.crowd_params is not None:
             c.crowd = point(BatchSolver.crowd_c(self.crowd_params, B, Np, int(self.person_wp.shape[2]), prm.dt, 1),
-                            {"robot_pose": self.pose, "robot_twist": self.cmd_vel, "count": self.person_count,
+                            {"robot_pose": self.pose, "robot_twist": executed, "count": self.person_count,
                              "waypoints": self.person_wp, "n_waypoints": self.person_nwp, "desired_speeds": self.person_speed})
             set_od_grid(c.crowd, "od_indexes", self.od_indexes, self.od_origin, self.od_resolution, od)
             c.groups = None
@@ -834,10 +886,10 @@ class BatchEpisode:
                                                     np.asarray(self.world.origin, np.float64).reshape(2)), {"world": self.world_map})
             else:
                 c.plant = BatchSolver.plant_c(self.plant, prm, B, Np, 1)
-            point(c.plant, {"cmd": self.cmd_vel, "agents": self.persons, "count": self.person_count})
+            point(c.plant, {"cmd": executed, "agents": self.persons, "count": self.person_count})
         if self.metrics_params is not None:
             c.metrics = point(BatchSolver.metrics_c(self.metrics_params, B, Np, prm.dt, 1),
-                              {"robot_pose": self.pose, "robot_twist": self.cmd_vel if self.plant is None else self.speed,  # the twist executed
+                              {"robot_pose": self.pose, "robot_twist": executed if self.plant is None else self.speed,  # the twist executed
                                "people": self.persons, "count": self.person_count, "goal": self.goal, "status": self.res["status"],
                                "source": self.cmd_source})
             if hasattr(self, "od_distances"):  # the clearance columns
@@ -1010,6 +1062,14 @@ class BatchEpisode:
         s.select_command_device(B, T, self.rows, self.traj_n.data_ptr() if planned else 0,
                                 self.plan_cmds.data_ptr(), self.res["status"].data_ptr(), self.res["cmds"].data_ptr(),
                                 self.cmd_vel.data_ptr(), self.cmd_source.data_ptr(), self.window_err.data_ptr() if windowed else 0)
+        executed = self.cmd_vel
+        if self.monitor is not None:  # the safety layer between the controller and the base: the tick's scan against its zones
+            s.collision_monitor_device(c.monitor, self.cmd_safe.data_ptr(), self.monitor_action.data_ptr(), self.monitor_points.data_ptr(),
+                                       self.monitor_ratio.data_ptr(), self.monitor_heading_cs.data_ptr(), self.monitor_step_cs.data_ptr())
+            timed("monitor")
+            executed = self.cmd_safe
+            if record:
+                rec.update(self._host("cmd_safe", "monitor_action", "monitor_points", "monitor_ratio", "monitor_heading_cs", "monitor_step_cs"))
         dt = self.params.dt
         if crowd:  # the persons' period: they see the pose it starts from and the command executed
             self._crowd_step()
@@ -1032,12 +1092,14 @@ class BatchEpisode:
                 rec.update(self._host("plant_contact", "heading_cs", plant_queue_after="plant_queue", speed_after="speed"))
                 rec["plant_tick_after"] = self.plant_tick.cpu().numpy().view(np.uint32).copy()
         else:
-            v, w, th = self.cmd_vel[:, 0], self.cmd_vel[:, 1], self.pose[:, 2]
+            v, w, th = executed[:, 0], executed[:, 1], self.pose[:, 2]
             moved = torch.stack([self.pose[:, 0] + v * torch.cos(th) * dt, self.pose[:, 1] + v * torch.sin(th) * dt, th + w * dt], dim=1)
             optimised = (self.cmd_source == 0)[:, None]
+            if self.monitor is not None:  # a command the monitor changed is not the one the optimised path was planned with
+                optimised = optimised & (self.monitor_ratio == 1.0)[:, None]
             # state is updated in place: every buffer the kernels read keeps its address from tick to tick (_bind)
             self.pose.copy_(torch.where(optimised, self.res["path"][:, 0, :], moved))
-            self.speed.copy_(self.cmd_vel)
+            self.speed.copy_(executed)
         if self.shared is not None:  # the pool walks on; what a robot perceives of it is gathered, not moved
             M = self.M
             if pool_crowd:

@@ -449,6 +449,99 @@ class PlantParams:
         return bool(r * r + 1e-9 < 226.0)
 
 
+MONITOR_SHAPES = {"circle": 0, "polygon": 1}
+MONITOR_ACTIONS = {"stop": 0, "slowdown": 1, "limit": 2, "approach": 3}
+
+
+@dataclass
+class MonitorZone:
+    """One zone of the collision monitor (smpc_monitor_zone of include/smpc_collision_monitor.h), in the robot's frame with x
+    forward: a circle of `radius` around the robot or a polygon of 3..16 `vertices` [(x, y), ..] in either orientation, which
+    triggers when at least min_points of the scan's points lie inside. action "stop": the command becomes (0, 0);
+    "slowdown": it is scaled by slowdown_ratio; "limit": it is scaled so that |v| <= linear_limit and |w| <= angular_limit;
+    "approach": the command is simulated over MonitorParams' horizon and scaled by the share of the horizon that passes
+    before the zone, carried along, triggers."""
+    action: str = "stop"
+    radius: float = None
+    vertices: tuple = None
+    min_points: int = 4
+    slowdown_ratio: float = 0.5
+    linear_limit: float = 0.5
+    angular_limit: float = 0.5
+
+    def __post_init__(self):
+        if self.action not in MONITOR_ACTIONS:
+            raise ValueError(f"MonitorZone.action must be one of {sorted(MONITOR_ACTIONS)}, got {self.action!r}")
+        if (self.radius is None) == (self.vertices is None):
+            raise ValueError("MonitorZone takes a radius (a circle) or vertices (a polygon), not both and not neither")
+        if self.radius is not None and not (np.isfinite(self.radius) and self.radius >= 0.0):
+            raise ValueError(f"MonitorZone.radius must be finite and >= 0, got {self.radius}")
+        if self.vertices is not None:
+            v = np.asarray(self.vertices, np.float64)
+            if v.ndim != 2 or v.shape[1] != 2 or not 3 <= v.shape[0] <= 16 or not np.isfinite(v).all():
+                raise ValueError("MonitorZone.vertices must be 3..16 finite (x, y) pairs")
+            self.vertices = tuple((float(x), float(y)) for x, y in v)
+        if int(self.min_points) != self.min_points or self.min_points < 1:
+            raise ValueError(f"MonitorZone.min_points must be an integer >= 1, got {self.min_points}")
+        if not 0.0 <= self.slowdown_ratio <= 1.0:
+            raise ValueError(f"MonitorZone.slowdown_ratio must lie in [0, 1], got {self.slowdown_ratio}")
+        for name in ("linear_limit", "angular_limit"):
+            if not getattr(self, name) >= 0.0:   # +inf: no limit
+                raise ValueError(f"MonitorZone.{name} must be >= 0 (inf: no limit), got {getattr(self, name)}")
+
+    @property
+    def shape(self) -> str:
+        return "circle" if self.vertices is None else "polygon"
+
+
+@dataclass
+class MonitorParams:
+    """The collision monitor (include/smpc_collision_monitor.h; BatchEpisode(monitor=..., sensor=...)): every tick the selected
+    command passes the zones, which look at the cells the tick's scan stopped at, before it reaches the base. zones: 1..8
+    MonitorZone, shared by all robots. The "approach" zones simulate the command for time_before_collision seconds in steps
+    of simulation_time_step: M = round(time_before_collision / simulation_time_step) steps, at most 32 (Nav2's
+    collision_monitor parameters of the same names)."""
+    zones: tuple = ()
+    time_before_collision: float = 1.2
+    simulation_time_step: float = 0.1
+
+    def __post_init__(self):
+        self.zones = tuple(self.zones)
+        if not self.zones or not all(isinstance(z, MonitorZone) for z in self.zones):
+            raise ValueError("MonitorParams.zones must be a non-empty sequence of MonitorZone")
+        if not (np.isfinite(self.time_before_collision) and self.time_before_collision >= 0.0):
+            raise ValueError(f"MonitorParams.time_before_collision must be finite and >= 0, got {self.time_before_collision}")
+        if not (np.isfinite(self.simulation_time_step) and self.simulation_time_step > 0.0):
+            raise ValueError(f"MonitorParams.simulation_time_step must be finite and > 0, got {self.simulation_time_step}")
+        if self.steps() < 1 and any(z.action == "approach" for z in self.zones):
+            raise ValueError("MonitorParams: an approach zone needs at least one simulation step (time_before_collision >= simulation_time_step / 2)")
+
+    def steps(self) -> int:
+        """M, the simulation steps of the approach zones."""
+        return int(round(float(self.time_before_collision) / float(self.simulation_time_step)))
+
+    def supported(self) -> bool:
+        """Does the library run this monitor: at most 8 zones and 32 simulation steps?"""
+        return len(self.zones) <= 8 and self.steps() <= 32
+
+    @classmethod
+    def nav2_like(cls, robot_radius: float = 0.24) -> "MonitorParams":
+        """Three zones in the manner of Nav2's shipped collision_monitor parameters around a robot of robot_radius: a STOP
+        circle a little beyond the body (1.25 radii), a SLOWDOWN polygon ahead of it (from the stop circle's rear to 5 radii
+        ahead, 2 radii to either side, ratio 0.5) and an APPROACH polygon of the footprint (the octagon that circumscribes
+        the disc), simulated 1.2 s ahead in steps of 0.1 s. Every zone triggers with 4 points."""
+        r = float(robot_radius)
+        if not (np.isfinite(r) and r > 0.0):
+            raise ValueError(f"MonitorParams.nav2_like: robot_radius must be finite and > 0, got {robot_radius}")
+        k = r / np.cos(np.pi / 8.0)
+        footprint = tuple((float(k * np.cos(np.pi / 8.0 + i * np.pi / 4.0)), float(k * np.sin(np.pi / 8.0 + i * np.pi / 4.0))) for i in range(8))
+        ahead = ((-1.25 * r, -2.0 * r), (5.0 * r, -2.0 * r), (5.0 * r, 2.0 * r), (-1.25 * r, 2.0 * r))
+        return cls(zones=(MonitorZone(action="stop", radius=1.25 * r, min_points=4),
+                          MonitorZone(action="slowdown", vertices=ahead, min_points=4, slowdown_ratio=0.5),
+                          MonitorZone(action="approach", vertices=footprint, min_points=4)),
+                   time_before_collision=1.2, simulation_time_step=0.1)
+
+
 @dataclass
 class SharedWorldParams:
     """One world for all robots of an episode (include/smpc_nearest.h; BatchEpisode(shared=..., pool=...)): every tick each

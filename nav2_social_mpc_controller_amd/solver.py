@@ -11,12 +11,13 @@ import os
 
 import numpy as np
 
-from . import (_abi, _abi_crowd_pool, _abi_detector, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_obstacle_memory, _abi_plant,
+from . import (_abi, _abi_collision_monitor, _abi_crowd_pool, _abi_detector, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_obstacle_memory, _abi_plant,
                _abi_sensed_costmap, _abi_tracker, _abi_visibility)
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
 from ._abi_detector import SmpcDetectorIn
+from ._abi_collision_monitor import SmpcCollisionMonitorIn, SmpcMonitorZone
 from ._abi_crowd_pool import SmpcCrowdPoolIn
 from ._abi_global_plan import SmpcExtractPlanIn, SmpcGoalFieldIn
 from ._abi_local_costmap import SmpcLocalCostmapIn
@@ -26,7 +27,7 @@ from ._abi_plant import SmpcPlantIn
 from ._abi_sensed_costmap import SmpcSensedCostmapIn
 from ._abi_tracker import SmpcTrackerIn
 from ._abi_visibility import SmpcVisibilityIn
-from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, OptimizerParams, PlantParams, PoolCrowdParams,
+from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, MonitorParams, OptimizerParams, PlantParams, PoolCrowdParams,
                      TrackerParams, TrajectorizerParams, VisibilityParams)
 from .scenes import SceneBatch
 
@@ -68,7 +69,8 @@ def load_library():
                                        **_abi_global_plan.FUNCTIONS, **_abi_visibility.FUNCTIONS, **_abi_nearest.FUNCTIONS,
                                        **_abi_crowd_pool.FUNCTIONS, **_abi_sensed_costmap.FUNCTIONS,
                                        **_abi_obstacle_memory.FUNCTIONS, **_abi_tracker.FUNCTIONS,
-                                       **_abi_detector.FUNCTIONS, **_abi_plant.FUNCTIONS}.items():
+                                       **_abi_detector.FUNCTIONS, **_abi_plant.FUNCTIONS,
+                                       **_abi_collision_monitor.FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -930,6 +932,68 @@ class BatchSolver:
         contact and heading_cs (0: none); asynchronous on the handle's stream."""
         assert pi.on_device == 1
         self._call("smpc_robot_plant_batch", pi, pose_ptr, twist_ptr, cmd_queue_ptr or None, plant_tick_ptr, contact_ptr, heading_cs_ptr or None)
+
+    # -- collision monitor (smpc_collision_monitor_batch, include/smpc_collision_monitor.h) ------------------------------------
+    @staticmethod
+    def collision_monitor_c(mp: MonitorParams, B: int, n_beams: int, on_device: int, resolution: float,
+                            world_origin=(0.0, 0.0)) -> SmpcCollisionMonitorIn:
+        """The call's struct without its array pointers: the zones (a host array the struct keeps alive as `_zones`: the
+        library reads it during every call, whatever on_device), M and sim_dt from mp, the cells of `resolution` at
+        world_origin that the beams' offsets count in."""
+        from .params import MONITOR_ACTIONS, MONITOR_SHAPES
+        zones = (SmpcMonitorZone * len(mp.zones))()
+        for zc, z in zip(zones, mp.zones):
+            zc.shape, zc.action, zc.min_points = MONITOR_SHAPES[z.shape], MONITOR_ACTIONS[z.action], int(z.min_points)
+            zc.radius = float(z.radius) if z.radius is not None else 0.0
+            zc.slowdown_ratio, zc.linear_limit, zc.angular_limit = float(z.slowdown_ratio), float(z.linear_limit), float(z.angular_limit)
+            zc.n_vertices = 0 if z.vertices is None else len(z.vertices)
+            for i, (vx, vy) in enumerate(z.vertices or ()):
+                zc.vertices[i][0], zc.vertices[i][1] = vx, vy
+        mi = SmpcCollisionMonitorIn(B=int(B), n_beams=int(n_beams), Z=len(mp.zones), M=mp.steps(), on_device=int(on_device),
+                                    sim_dt=float(mp.simulation_time_step), resolution=float(resolution))
+        mi.world_origin[0], mi.world_origin[1] = float(world_origin[0]), float(world_origin[1])
+        mi._zones = zones
+        mi.zones = C.addressof(zones)
+        return mi
+
+    def collision_monitor(self, mi: SmpcCollisionMonitorIn, robot_pose: np.ndarray, cmd: np.ndarray, beam_kind: np.ndarray,
+                          beam_cell: np.ndarray, with_zone_points: bool = True, with_ratio: bool = True, with_heading: bool = True,
+                          with_step: bool = True, fill: dict = None) -> dict:
+        """One call of the monitor on host arrays. mi: collision_monitor_c(..., on_device=0) (its array pointers are set here).
+        robot_pose [B,3], cmd [B,2], beam_kind [B,n_beams] uint8, beam_cell [B,n_beams,2] int32. Returns {"cmd_out" [B,2],
+        "action" [B,4] int32, "zone_points" [B,Z] int32, "ratio" [B], "heading_cs" [B,2], "step_cs" [B,2]}; an output
+        switched off by its with_* flag is passed as NULL and comes back None. What the call does not write keeps the
+        arrays' fill: NaN and -1, or the arrays `fill` gives by name."""
+        robot_pose = np.ascontiguousarray(robot_pose, np.float64)
+        cmd = np.ascontiguousarray(cmd, np.float64)
+        beam_kind = np.ascontiguousarray(beam_kind, np.uint8)
+        beam_cell = np.ascontiguousarray(beam_cell, np.int32)
+        B, n, Z = robot_pose.shape[0], mi.n_beams, mi.Z
+        assert mi.on_device == 0 and mi.B == B
+        assert robot_pose.shape == (B, 3) and cmd.shape == (B, 2) and beam_kind.shape == (B, n) and beam_cell.shape == (B, n, 2)
+        spec = {"cmd_out": ((B, 2), np.float64, np.nan, True), "action": ((B, 4), np.int32, -1, True),
+                "zone_points": ((B, Z), np.int32, -1, with_zone_points), "ratio": ((B,), np.float64, np.nan, with_ratio),
+                "heading_cs": ((B, 2), np.float64, np.nan, with_heading), "step_cs": ((B, 2), np.float64, np.nan, with_step)}
+        out = {}
+        for k, (shape, dtype, value, on) in spec.items():
+            if not on:
+                out[k] = None
+            elif fill is not None and k in fill:
+                out[k] = np.array(fill[k], dtype=dtype, order="C")
+                assert out[k].shape == shape
+            else:
+                out[k] = np.full(shape, value, dtype)
+        point(mi, {"robot_pose": robot_pose, "cmd": cmd, "beam_kind": beam_kind, "beam_cell": beam_cell})
+        self._call("smpc_collision_monitor_batch", mi, *(_ptr(out[k]) for k in spec))
+        return out
+
+    def collision_monitor_device(self, mi: SmpcCollisionMonitorIn, cmd_out_ptr: int, action_ptr: int, zone_points_ptr: int = 0,
+                                 ratio_ptr: int = 0, heading_cs_ptr: int = 0, step_cs_ptr: int = 0):
+        """Device pointers in mi (on_device == 1; its zones stay the host array collision_monitor_c made) and for the outputs
+        (0: none); asynchronous on the handle's stream."""
+        assert mi.on_device == 1
+        self._call("smpc_collision_monitor_batch", mi, cmd_out_ptr, action_ptr, zone_points_ptr or None, ratio_ptr or None,
+                   heading_cs_ptr or None, step_cs_ptr or None)
 
     # -- sensed local costmaps (smpc_sensed_costmap_batch, include/smpc_sensed_costmap.h) ----------------------------------
     @staticmethod

@@ -5,7 +5,7 @@ BatchEpisode(scene_params=...)); the device scores every robot as it drives (Bat
 summarize_metrics means is printed per set. Nothing but the final [B,24] metrics rows leaves the device.
 
     python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]] [--tracker] [--detector] [--plant]
-                                [--world-plans [--occlusion [RANGE]] [--shared-crowd M] [--sensed-costmap [--obstacle-memory]]]
+                                [--world-plans [--occlusion [RANGE]] [--shared-crowd M] [--sensed-costmap [--obstacle-memory] [--collision-monitor]]]
 
 --reactive: the persons are a reactive crowd (BatchEpisode(crowd=CrowdParams()), waypoints from scenes.crowd_waypoints)
 instead of walking straight on with constant velocity. --groups (with --reactive): half of the walking persons go in pairs
@@ -44,6 +44,10 @@ of 2.5 m/s^2 and 3.2 rad/s^2, and a disc of 0.24 m that stops where it would com
 --world-plans) or to a person it touches, instead of passing through. The velocity bounds are the base set's for every robot.
 The collision and time-to-goal columns then describe a robot that exists; a last column counts the robot-ticks of the final
 tick that a contact stopped.
+--collision-monitor (with --world-plans --sensed-costmap): the selected command passes a collision monitor before it is executed
+(BatchEpisode(monitor=MonitorParams.nav2_like(0.24))): a STOP circle just beyond the body, a SLOWDOWN polygon ahead and the
+footprint as APPROACH zone over 1.2 s, judged against the cells the tick's scan stopped at. The tuning then meets the safety layer
+a deployed controller runs under; a last column is the share of ticks in which the monitor changed the command (ratio < 1).
 """
 import argparse
 import os
@@ -87,9 +91,13 @@ def main():
                     help="the controller is handed tracks of the detected persons (velocity from positions, coasting when hidden)")
     ap.add_argument("--detector", action="store_true",
                     help="the detections are a detector's: body occlusion, misses, range-dependent noise and clutter")
+    ap.add_argument("--collision-monitor", action="store_true",
+                    help="the command passes scan-based stop, slowdown and approach zones (needs --world-plans --sensed-costmap)")
     ap.add_argument("--plant", action="store_true",
                     help="the command is executed under acceleration limits and stopped by contact with walls and persons")
     a = ap.parse_args()
+    if a.collision_monitor and not (a.world_plans and a.sensed_costmap):
+        ap.error("--collision-monitor needs --world-plans --sensed-costmap")
     if a.obstacle_memory and not a.sensed_costmap:
         ap.error("--obstacle-memory needs --sensed-costmap")
     if a.sensed_costmap and not a.world_plans:
@@ -107,7 +115,7 @@ def main():
 
     from nav2_social_mpc_controller_amd.episode import BatchEpisode, arc_plans
     from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, ObstacleMemoryParams, OptimizerParams,
-                                                       DetectorParams, PlantParams, PoolCrowdParams, SensorParams, SharedWorldParams, TrackerParams, TrajectorizerParams, VisibilityParams,
+                                                       DetectorParams, MonitorParams, PlantParams, PoolCrowdParams, SensorParams, SharedWorldParams, TrackerParams, TrajectorizerParams, VisibilityParams,
                                                        scene_param_rows)
     from nav2_social_mpc_controller_amd.scenes import (crowd_groups, crowd_waypoints, make_scenes, make_world, pool_waypoints, scenes_in_world,
                                                        shared_pool, uniform, world_goals)
@@ -156,12 +164,19 @@ def main():
         plans["detector"] = DetectorParams(clutter_candidates=min(2, 64 - a.agents))
     if a.plant:
         plans["plant"] = PlantParams()
+    if a.collision_monitor:
+        plans["monitor"] = MonitorParams.nav2_like(0.24)
     ep = BatchEpisode(prm, sc, w_ref, traj_params=tp, fov_angle=np.pi / 4, obstacles_from_costmap=True, scene_params=rows,
                       metrics=MetricsParams(), **plans, **crowd)
     ep.capture_graph()
+    changed = ep.torch.zeros(S * n, dtype=ep.torch.int64, device=ep.dev)   # ticks in which the monitor changed the robot's command
     for _ in range(a.ticks):
         ep.replay()
+        if a.collision_monitor:
+            with ep.torch.cuda.stream(ep.gstream):   # behind the tick, on its stream: nothing leaves the device
+                changed += ep.monitor_ratio < 1.0
     m = summarize_metrics(ep.metrics(), prm.dt)
+    changed = changed.cpu().numpy()
     print(f"{S} parameter sets x {n} scenes, {a.agents} agents, {a.ticks} ticks of {prm.dt} s")
     stopped = (ep.plant_contact[:, 0].cpu().numpy() & 3) != 0 if a.plant else np.zeros(S * n, bool)
     for k, name in enumerate(sets):
@@ -172,7 +187,8 @@ def main():
               f"intimate {mean('intimate_share'):.3f}  personal {mean('personal_share'):.3f}  "
               f"social_work/m {mean('social_work_per_metre'):8.3f}  person_coll {m['person_collision'][sl].mean():.3f}  "
               f"obstacle_coll {m['obstacle_collision'][sl].mean():.3f}  fallback {mean('fallback_share'):.3f}"
-              + (f"  stopped_by_contact {stopped[sl].mean():.3f}" if a.plant else ""))
+              + (f"  stopped_by_contact {stopped[sl].mean():.3f}" if a.plant else "")
+              + (f"  monitor_share {changed[sl].mean() / max(a.ticks, 1):.3f}" if a.collision_monitor else ""))
 
 
 if __name__ == "__main__":
