@@ -16,7 +16,7 @@
 //   the probe kernels (smpc_probes.hpp);
 //   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window,
 //   metrics, crowd, local costmap, global plan, visibility, nearest agents, pool crowd, sensed costmap, obstacle memory,
-//   people tracks, people detections, robot plant, collision monitor).
+//   people tracks, people detections, robot plant, collision monitor, people detections from the scan).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -55,6 +55,8 @@
 #include "../../include/smpc_plant.h"
 #include "smpc_collision_monitor.hpp"
 #include "../../include/smpc_collision_monitor.h"
+#include "smpc_scan_people.hpp"
+#include "../../include/smpc_scan_people.h"
 
 extern "C" {
 
@@ -1113,6 +1115,45 @@ int smpc_collision_monitor_batch(smpc_handle* h, const smpc_collision_monitor_in
   SMPC_TRY(st.timed([&] {
     if (in->n_beams <= 64 * smpc::kCmSlots) hipLaunchKernelGGL(smpc::smpc_collision_monitor_kernel<true>, grid, block, 0, h->stream, p);
     else hipLaunchKernelGGL(smpc::smpc_collision_monitor_kernel<false>, grid, block, 0, h->stream, p);
+    return SMPC_OK;
+  }));
+  return st.finish();
+}
+
+int smpc_scan_people_batch(smpc_handle* h, const smpc_scan_people_in* in, double* detections, int32_t* det_count, int32_t* det_segment,
+                           int32_t* seg_stats) {
+  if (!h || !in || !detections || !det_count) { set_error("null handle / input / detections / det_count"); return SMPC_ERR_INVALID_ARG; }
+  if (!in->robot_pose || !in->beam_kind || !in->beam_cell) { set_error("null input array"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B < 0 || in->n_beams < 1 || in->Nd < 1 || in->min_points < 1) { set_error("bad B, or n_beams, Nd or min_points < 1"); return SMPC_ERR_INVALID_ARG; }
+  if (in->link_d2 < 0 || in->width_d2_min < 0 || in->width_d2_max < 0 || in->range_d2 < 0 || in->width_d2_min > in->width_d2_max) {
+    set_error("link_d2, width_d2_min, width_d2_max and range_d2 must be >= 0, width_d2_min <= width_d2_max"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (in->subtract_map < 0 || in->subtract_map > 1) { set_error("subtract_map must be 0 or 1"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) { set_error("resolution must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->world_origin[0]) || !std::isfinite(in->world_origin[1])) { set_error("world_origin must be finite"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->body_offset) || !(in->body_offset >= 0.0)) { set_error("body_offset must be finite and >= 0"); return SMPC_ERR_INVALID_ARG; }
+  // the kernel's bounds: an output rank is below 64, the running sums of 4096 offsets fit 32 bits
+  if (in->n_beams > SMPC_SENSED_MAX_BEAMS || in->Nd > SMPC_MAX_AGENTS) { set_error("n_beams > 4096 or Nd > 64 is not supported"); return SMPC_ERR_UNSUPPORTED; }
+  if (in->B == 0) return SMPC_OK;
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::ScanPeopleParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.B = in->B; p.n_beams = in->n_beams; p.Nd = in->Nd; p.subtract_map = in->subtract_map; p.min_points = in->min_points;
+  p.link_d2 = in->link_d2; p.width_d2_min = in->width_d2_min; p.width_d2_max = in->width_d2_max; p.range_d2 = in->range_d2;
+  p.res = in->resolution; p.ox = in->world_origin[0]; p.oy = in->world_origin[1]; p.body_offset = in->body_offset;
+  const size_t B = in->B, n = in->n_beams, Nd = in->Nd;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.pose, in->robot_pose, B * 3));
+  SMPC_TRY(st.in(p.kind, in->beam_kind, B * n));
+  SMPC_TRY(st.in(p.cell, in->beam_cell, B * n * 2));
+  // read and written: the rows the rule does not write keep the caller's bytes on the way through device memory too
+  SMPC_TRY(st.inout(p.detections, detections, B * Nd * 5));
+  SMPC_TRY(st.out(p.det_count, det_count, B));
+  SMPC_TRY(st.inout(p.det_segment, det_segment, B * Nd * 4));
+  SMPC_TRY(st.out(p.seg_stats, seg_stats, B * 4));
+  const size_t per_block = smpc::kSpThreads / 64;
+  SMPC_TRY(st.timed([&] {
+    hipLaunchKernelGGL(smpc::smpc_scan_people_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kSpThreads), 0, h->stream, p);
     return SMPC_OK;
   }));
   return st.finish();

@@ -14,6 +14,8 @@
     line-of-sight filter (optional)          (none: the library's own rule)        -> smpc_visible_people_batch
     people detections (optional)             (the deployment's own detector; the
                                               library's own rule)                   -> smpc_detect_people_batch
+    people detections from the scan          (the deployment's own leg detector;
+      (optional, in place of the two above)   the library's own rule)               -> smpc_scan_people_batch
     people tracks (optional)                 (the deployment's own tracker behind
                                               people_msgs::People; the library's rule) -> smpc_track_people_batch
     global plans (optional, at the start and   (Nav2's planner server; the library's -> smpc_goal_field_batch,
@@ -59,7 +61,7 @@ import numpy as np
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
 from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, MonitorParams, ObstacleMemoryParams, OptimizerParams, PoolCrowdParams,
-                     PlantParams, SensorParams, TrackerParams, TrajectorizerParams, SharedWorldParams, VisibilityParams, check_scene_param_rows)
+                     PlantParams, ScanDetectorParams, SensorParams, TrackerParams, TrajectorizerParams, SharedWorldParams, VisibilityParams, check_scene_param_rows)
 from .scenes import SceneBatch, World
 from .solver import BatchSolver, point, set_od_grid
 
@@ -167,6 +169,12 @@ class TickRecord:
     monitor_ratio: np.ndarray = None          # [B]
     monitor_heading_cs: np.ndarray = None     # [B,2] cosine and sine of the heading the monitor obtained (rows of robots not finite: not written)
     monitor_step_cs: np.ndarray = None        # [B,2] ... of one simulation step's angle
+    # the scan-based people detector (BatchEpisode(scan_detector=...)): what the tick's smpc_scan_people_batch wrote, having read
+    # robot_pose, beam_kind and beam_cell; the tracker (or, without one, people_to_status) read the first two
+    scan_persons: np.ndarray = None           # [B,Nd,5] x, y, 0, 0, 0; the rows below scan_count
+    scan_count: np.ndarray = None             # [B] int32
+    scan_segment: np.ndarray = None           # [B,Nd,4] int32 start beam, beams, summed offsets
+    scan_stats: np.ndarray = None             # [B,4] int32 segments, rejected by points, rejected by width, accepted
 
 
 class BatchEpisode:
@@ -180,7 +188,7 @@ class BatchEpisode:
     FORWARDED = ("od_resolution", "device", "traj_params", "fov_angle", "order_hint", "plan_window", "obstacles_from_costmap",
                  "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost", "planner",
                  "visibility", "shared", "pool", "pool_crowd", "pool_waypoints", "pool_n_waypoints", "pool_speed", "sensor",
-                 "sensor_memory", "tracker", "detector", "plant", "monitor")
+                 "sensor_memory", "tracker", "detector", "plant", "monitor", "scan_detector")
 
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
@@ -195,7 +203,8 @@ class BatchEpisode:
                  shared: SharedWorldParams = None, pool: np.ndarray = None, pool_crowd: PoolCrowdParams = None,
                  pool_waypoints: np.ndarray = None, pool_n_waypoints: np.ndarray = None, pool_speed: np.ndarray = None,
                  sensor: SensorParams = None, sensor_memory: ObstacleMemoryParams = None, tracker: TrackerParams = None,
-                 detector: DetectorParams = None, plant: PlantParams = None, monitor: MonitorParams = None):
+                 detector: DetectorParams = None, plant: PlantParams = None, monitor: MonitorParams = None,
+                 scan_detector: ScanDetectorParams = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -331,6 +340,17 @@ class BatchEpisode:
         warm start's speed and the metrics' twist; self.cmd_vel stays the controller's command. Without a plant a robot whose
         command the monitor changed (ratio < 1) is moved by the motion model with the safe command instead of being placed
         on the first optimised pose.
+        None: nothing is allocated, nothing is launched and the episode is the one without bit for bit.
+        scan_detector: the controller is handed what its own scan shows of the people (include/smpc_scan_people.h); needs
+        `sensor`, with or without `sensor_memory`, and excludes `visibility` and `detector`: those start from the simulator's
+        person rows, this starts from the beams, and the two paths are alternatives. Every tick, right behind the sensed (or
+        memory) call and in front of the tracker, one smpc_scan_people_batch clusters the cells the tick's beams stopped at
+        (self.beam_kind / self.beam_cell) into segments and writes the person-sized ones into self.scan_persons [B,Nd,5]
+        (x, y, 0, 0, 0) and self.scan_count [B] int32, Nd = scan_detector.max_detections, with self.scan_segment [B,Nd,4] int32
+        (start beam, beams, the summed offsets) and self.scan_stats [B,4] int32 (segments, rejected by points, rejected by
+        width, accepted). The tracker reads them, or without one people_to_status does; a detection has no velocity, so
+        without a tracker the solve plans around people who stand still: use tracker=TrackerParams(). The crowd, the plant,
+        the metrics and the scan itself keep seeing the true persons.
         None: nothing is allocated, nothing is launched and the episode is the one without bit for bit."""
         import torch
 
@@ -395,6 +415,7 @@ class BatchEpisode:
         self._init_detector(detector)
         self._init_plant(plant)
         self._init_monitor(monitor)
+        self._init_scan_detector(scan_detector)
         self._bind()
         self.graph = None
         self.gstream = None
@@ -652,6 +673,33 @@ class BatchEpisode:
         self.person_outcome = self._zeros(B, Np, dtype=self.torch.uint8)
 
     @staticmethod
+    def check_scan_detector(scan_detector, sensor, visibility, detector, resolution: float):
+        """What BatchEpisode(scan_detector=...) refuses (sensor, visibility, detector: the episode's; resolution: the world's)."""
+        if not isinstance(scan_detector, ScanDetectorParams):
+            raise ValueError("scan_detector must be a ScanDetectorParams")
+        if sensor is None:
+            raise ValueError("scan_detector needs sensor=SensorParams(...): it reads the scan")
+        if visibility is not None:
+            raise ValueError("scan_detector and visibility are alternatives: the scan-based or the ground-truth path")
+        if detector is not None:
+            raise ValueError("scan_detector and detector are alternatives: the scan-based or the ground-truth path")
+        if not scan_detector.supported(resolution, sensor):
+            raise ValueError("scan_detector: more than 64 detections, or a squared cell distance beyond int32 at the world's resolution")
+
+    def _init_scan_detector(self, scan_detector):
+        """What the scan-based detector writes every tick: fixed addresses, the tracker or people_to_status reads the first
+        two. It has no state."""
+        self.scan_detector = scan_detector
+        if scan_detector is None:
+            return
+        self.check_scan_detector(scan_detector, self.sensor, self.visibility, self.detector, self.resolution)
+        B, Nd = self.B, int(scan_detector.max_detections)
+        self.scan_persons = self._zeros(B, Nd, 5)
+        self.scan_count = self._zeros(B, dtype=self.torch.int32)
+        self.scan_segment = self._zeros(B, Nd, 4, dtype=self.torch.int32)
+        self.scan_stats = self._zeros(B, 4, dtype=self.torch.int32)
+
+    @staticmethod
     def check_plant(plant, resolution: float = None):
         """What BatchEpisode(plant=...) refuses (resolution: the world's, None without one)."""
         if not isinstance(plant, PlantParams):
@@ -824,6 +872,13 @@ class BatchEpisode:
             c.detector = point(BatchSolver.detector_c(self.detector, B, Np, Nd, 1),
                                {"people": c.people.people, "count": c.people.count, "robot_pose": self.pose})
             point(c.people, {"people": self.detected_persons, "count": self.detected_count})
+            c.people.Np = Nd
+        if self.scan_detector is not None:  # what the robot's own scan shows of the people: in place of the ground-truth path
+            Nd = int(self.scan_persons.shape[1])
+            c.scan_people = point(BatchSolver.scan_people_c(self.scan_detector, B, int(self.sensor.n_beams), Nd, 1, self.resolution,
+                                                            np.asarray(self.world.origin, np.float64).reshape(2), self.sensor, self.sensor_memory),
+                                  {"robot_pose": self.pose, "beam_kind": self.beam_kind, "beam_cell": self.beam_cell})
+            point(c.people, {"people": self.scan_persons, "count": self.scan_count})
             c.people.Np = Nd
         if self.tracker is not None:  # the controller gets tracks of what is detected: the last stage in front of the filter
             c.tracker = point(BatchSolver.tracker_c(self.tracker, B, Nd, Np, prm.dt, 1),
@@ -1006,6 +1061,12 @@ class BatchEpisode:
             timed("sensed_costmap")
             if record:
                 rec.update(self._host("beam_kind", "beam_cell", sensed_costmap="costmap"))
+        if self.scan_detector is not None:  # the tick's beam hits clustered into person-sized segments: detections from the scan
+            s.scan_people_device(c.scan_people, self.scan_persons.data_ptr(), self.scan_count.data_ptr(), self.scan_segment.data_ptr(),
+                                 self.scan_stats.data_ptr())
+            timed("scan_people")
+            if record:
+                rec.update(self._host("scan_persons", "scan_count", "scan_segment", "scan_stats"))
         if self.visibility is not None:  # the persons in line of sight, directly in front of the filter that reads them
             s.visible_people_device(c.visibility, self.seen_persons.data_ptr(), self.seen_count.data_ptr(), self.person_seen.data_ptr())
             timed("visibility")

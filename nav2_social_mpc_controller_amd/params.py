@@ -377,6 +377,78 @@ class DetectorParams:
 
 
 @dataclass
+class ScanDetectorParams:
+    """People detections from the scan (include/smpc_scan_people.h; BatchEpisode(sensor=..., scan_detector=...)): every tick
+    the cells the scan's beams stopped at are clustered into segments, and a segment of a person's size is a detection.
+    Neighbouring hits within link_distance metres are linked; a segment needs at least min_points beams and a distance
+    between its first and last hit of min_width .. max_width metres; the centre of its cells is pushed body_offset metres
+    away from the robot, since the visible arc lies in front of the body's centre. subtract_map: hits on occluding cells of
+    the world map are background (a deployment's static-map subtraction); without it a pillar of a person's width is a
+    detection. max_range: hits beyond it are background; None: the sensor's marking range (SensorParams.max_range, also
+    under sensor_memory, whose beams reach further). max_detections: rows per robot (at most 64). All lengths become
+    squared cell distances rounded down, as SensorParams.agent_d2 rounds. The defaults suit discs of 0.3 m on cells of
+    0.05 m seen by 360 beams: from a link distance of 0.2 m on a lone person is one segment."""
+    link_distance: float = 0.25
+    min_points: int = 3
+    min_width: float = 0.2
+    max_width: float = 0.8
+    body_offset: float = 0.2
+    subtract_map: bool = True
+    max_range: float = None
+    max_detections: int = 16
+
+    def __post_init__(self):
+        for name in ("link_distance", "min_width", "max_width", "body_offset"):
+            v = getattr(self, name)
+            if not (np.isfinite(v) and v >= 0.0):
+                raise ValueError(f"ScanDetectorParams.{name} must be finite and >= 0, got {v}")
+        if self.min_width > self.max_width:
+            raise ValueError(f"ScanDetectorParams.min_width ({self.min_width}) must be <= max_width ({self.max_width})")
+        if self.max_range is not None and not (np.isfinite(self.max_range) and self.max_range > 0.0):
+            raise ValueError(f"ScanDetectorParams.max_range must be None or finite and > 0, got {self.max_range}")
+        if int(self.min_points) != self.min_points or self.min_points < 1:
+            raise ValueError(f"ScanDetectorParams.min_points must be an integer >= 1, got {self.min_points}")
+        if int(self.max_detections) != self.max_detections or self.max_detections < 1:
+            raise ValueError(f"ScanDetectorParams.max_detections must be an integer >= 1, got {self.max_detections}")
+        if self.subtract_map not in (False, True, 0, 1):
+            raise ValueError(f"ScanDetectorParams.subtract_map must be a bool, got {self.subtract_map!r}")
+
+    @staticmethod
+    def _d2(length: float, resolution: float) -> float:
+        r = np.float64(length) / np.float64(resolution)   # SensorParams.agent_d2's rounding
+        with np.errstate(over="ignore"):
+            return float(np.floor(r * r + 1e-9))
+
+    def link_d2(self, resolution: float) -> int:
+        """The squared link distance in cells, rounded down."""
+        return int(self._d2(self.link_distance, resolution))
+
+    def width_d2(self, resolution: float):
+        """(width_d2_min, width_d2_max): the squared widths in cells, rounded down."""
+        return int(self._d2(self.min_width, resolution)), int(self._d2(self.max_width, resolution))
+
+    def range_m(self, sensor: "SensorParams") -> float:
+        """The range in metres: max_range, or the sensor's marking range."""
+        return float(sensor.max_range if self.max_range is None else self.max_range)
+
+    def range_d2(self, resolution: float, sensor: "SensorParams") -> int:
+        """The squared range in cells, rounded down."""
+        return int(self._d2(self.range_m(sensor), resolution))
+
+    def supported(self, resolution: float = None, sensor: "SensorParams" = None) -> bool:
+        """Does the library run this detector: at most 64 rows per robot and, with a resolution, squared distances that fit
+        the struct's int32 fields (the range too when `sensor` is given or max_range is set)?"""
+        if self.max_detections > 64 or self.min_points >= 2 ** 31:
+            return False
+        if resolution is None:
+            return True
+        lengths = [self.link_distance, self.min_width, self.max_width]
+        if sensor is not None or self.max_range is not None:
+            lengths.append(self.max_range if self.max_range is not None else sensor.max_range)
+        return all(np.isfinite(d) and d < 2.0 ** 31 for d in (self._d2(v, resolution) for v in lengths))
+
+
+@dataclass
 class PlantParams:
     """The robot plant (include/smpc_plant.h; BatchEpisode(plant=...)): every tick the selected command is executed by a
     model of the base instead of being taken for the motion. The command that was selected latency_ticks periods ago is

@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from . import (_abi, _abi_collision_monitor, _abi_crowd_pool, _abi_detector, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_obstacle_memory, _abi_plant,
-               _abi_sensed_costmap, _abi_tracker, _abi_visibility)
+               _abi_scan_people, _abi_sensed_costmap, _abi_tracker, _abi_visibility)
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
@@ -24,11 +24,12 @@ from ._abi_local_costmap import SmpcLocalCostmapIn
 from ._abi_nearest import SmpcNearestIn
 from ._abi_obstacle_memory import SmpcObstacleMemoryIn
 from ._abi_plant import SmpcPlantIn
+from ._abi_scan_people import SmpcScanPeopleIn
 from ._abi_sensed_costmap import SmpcSensedCostmapIn
 from ._abi_tracker import SmpcTrackerIn
 from ._abi_visibility import SmpcVisibilityIn
 from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, MonitorParams, OptimizerParams, PlantParams, PoolCrowdParams,
-                     TrackerParams, TrajectorizerParams, VisibilityParams)
+                     ScanDetectorParams, TrackerParams, TrajectorizerParams, VisibilityParams)
 from .scenes import SceneBatch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -70,7 +71,7 @@ def load_library():
                                        **_abi_crowd_pool.FUNCTIONS, **_abi_sensed_costmap.FUNCTIONS,
                                        **_abi_obstacle_memory.FUNCTIONS, **_abi_tracker.FUNCTIONS,
                                        **_abi_detector.FUNCTIONS, **_abi_plant.FUNCTIONS,
-                                       **_abi_collision_monitor.FUNCTIONS}.items():
+                                       **_abi_collision_monitor.FUNCTIONS, **_abi_scan_people.FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -877,6 +878,52 @@ class BatchSolver:
         det_source and outcome (0: none); asynchronous on the handle's stream."""
         assert di.on_device == 1
         self._call("smpc_detect_people_batch", di, draw_state_ptr, detections_ptr, det_count_ptr, det_source_ptr or None, outcome_ptr or None)
+
+    # -- people detections from the scan (smpc_scan_people_batch, include/smpc_scan_people.h) -------------------------------
+    @staticmethod
+    def scan_people_c(sp: ScanDetectorParams, B: int, n_beams: int, Nd: int, on_device: int, resolution: float, world_origin,
+                      sensor, sensor_memory=None) -> SmpcScanPeopleIn:
+        """The call's struct without its array pointers: sp's lengths as squared cell distances of `resolution`, the cells
+        counted from world_origin. sensor: the SensorParams whose scan is read (sp.max_range None: its marking range, also
+        with sensor_memory, whose beams reach further but mark no further)."""
+        wmin, wmax = sp.width_d2(resolution)
+        si = SmpcScanPeopleIn(B=int(B), n_beams=int(n_beams), Nd=int(Nd), on_device=int(on_device), subtract_map=int(bool(sp.subtract_map)),
+                              min_points=int(sp.min_points), link_d2=sp.link_d2(resolution), width_d2_min=wmin, width_d2_max=wmax,
+                              range_d2=sp.range_d2(resolution, sensor), resolution=float(resolution), body_offset=float(sp.body_offset))
+        si.world_origin[0], si.world_origin[1] = float(world_origin[0]), float(world_origin[1])
+        return si
+
+    def scan_people(self, si: SmpcScanPeopleIn, robot_pose: np.ndarray, beam_kind: np.ndarray, beam_cell: np.ndarray,
+                    detections: np.ndarray = None, det_segment: np.ndarray = None, with_segment: bool = True, with_stats: bool = True):
+        """One call of the scan-based people detector on host arrays. si: scan_people_c(..., on_device=0) (its array pointers are
+        set here). robot_pose [B,3], beam_kind [B,n_beams] uint8, beam_cell [B,n_beams,2] int32. detections [B,Nd,5] /
+        det_segment [B,Nd,4] int32: the arrays before the call (default NaN / -99): the call writes the first det_count rows of
+        each robot and leaves the others. Returns (detections, det_count [B] int32, det_segment or None with with_segment=False,
+        seg_stats [B,4] int32 or None with with_stats=False)."""
+        robot_pose = np.ascontiguousarray(robot_pose, np.float64)
+        beam_kind = np.ascontiguousarray(beam_kind, np.uint8)
+        beam_cell = np.ascontiguousarray(beam_cell, np.int32)
+        B, n, Nd = robot_pose.shape[0], si.n_beams, si.Nd
+        assert si.on_device == 0 and si.B == B
+        assert robot_pose.shape == (B, 3) and beam_kind.shape == (B, n) and beam_cell.shape == (B, n, 2)
+        detections = np.full((B, Nd, 5), np.nan) if detections is None else np.array(detections, dtype=np.float64, order="C")
+        assert detections.shape == (B, Nd, 5)
+        if with_segment:
+            det_segment = np.full((B, Nd, 4), -99, np.int32) if det_segment is None else np.array(det_segment, dtype=np.int32, order="C")
+            assert det_segment.shape == (B, Nd, 4)
+        else:
+            det_segment = None
+        det_count = np.full(B, -1, np.int32)
+        seg_stats = np.full((B, 4), -1, np.int32) if with_stats else None
+        point(si, {"robot_pose": robot_pose, "beam_kind": beam_kind, "beam_cell": beam_cell})
+        self._call("smpc_scan_people_batch", si, _ptr(detections), _ptr(det_count), _ptr(det_segment), _ptr(seg_stats))
+        return detections, det_count, det_segment, seg_stats
+
+    def scan_people_device(self, si: SmpcScanPeopleIn, detections_ptr: int, det_count_ptr: int, det_segment_ptr: int = 0, seg_stats_ptr: int = 0):
+        """Device pointers in si (on_device == 1) and for detections, det_count, det_segment and seg_stats (0: none);
+        asynchronous on the handle's stream."""
+        assert si.on_device == 1
+        self._call("smpc_scan_people_batch", si, detections_ptr, det_count_ptr, det_segment_ptr or None, seg_stats_ptr or None)
 
     # -- robot plant (smpc_robot_plant_batch, include/smpc_plant.h) ----------------------------------------------------------
     @staticmethod

@@ -1,0 +1,470 @@
+"""People detections from the scan on the CPU: the yardstick itself (tests/scan_people_ref.py, a sequential walk written from
+include/smpc_scan_people.h) on hand-made cases with the expected rows written out, what the seeded cases exercise, the
+`__host__ __device__` rule of csrc/smpc_scan_people_rule.hpp compiled into a host-only program and composed as the kernel
+composes it (passes of 64 lanes, a segment judged where it closes, sums as differences of a running prefix, the head of the
+wrapping segment set aside) against the yardstick bit for bit, the same program under the address and undefined-behaviour
+sanitizers, the ctypes mirror against the header, ScanDetectorParams, the episode's refusals, the kernel's resource remarks,
+and what the rule does with real scans, on the yardsticks of the scan and of this stage alone."""
+import ctypes as C
+import inspect
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import scan_people_cases as MC
+import scan_people_ref as R
+import sensed_costmap_ref
+from nav2_social_mpc_controller_amd import _abi_scan_people as MA
+from nav2_social_mpc_controller_amd import solver as S
+from nav2_social_mpc_controller_amd.params import DetectorParams, ScanDetectorParams, SensorParams, VisibilityParams
+from test_kernel_budget import CSRC, HIPCC, parse_resource_remarks
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "smpc_scan_people.h")
+KERNEL = "_ZN4smpc23smpc_scan_people_kernelENS_16ScanPeopleParamsE"
+
+HAND = MC.hand_cases()
+SEEDED = MC.seeded_cases()
+
+
+def ref(c, **kw):
+    return R.run(c["p"], c["Nd"], c["pose"], c["kind"], c["cell"], **kw)
+
+
+@pytest.fixture(scope="module")
+def seeded_ref():
+    return {name: ref(c) for name, c in SEEDED.items()}
+
+
+# ---- the yardstick ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(HAND))
+def test_hand_made_cases_end_where_the_contract_says(name):
+    c = HAND[name]
+    got = ref(c)
+    MC.check_want(c, got)
+    assert got["counters"]["d_zero"] == c["want"].get("d_zero", 0)
+    assert got["detections"].dtype == np.float64 and all(got[k].dtype == np.int32 for k in ("det_count", "det_segment", "seg_stats"))
+
+
+def test_the_hand_made_cases_cover_the_list():
+    count = lambda key: sum(ref(c)["counters"][key] for c in HAND.values())
+    assert count("wrapped") == 2 and count("whole_circle") == 2 and count("crossing") >= 2 and count("dropped") == 4 and count("no_cell") == 3
+    assert {c["kind"].shape[1] for c in HAND.values()} >= {1, 2, 8, 16, 128}
+
+
+def test_the_seeded_cases_exercise_the_rule(seeded_ref):
+    """By the yardstick alone, before anything is compared with it."""
+    assert [MC.seeded_name(*s) for s in MC.SHAPES] == list(SEEDED)
+    total = {}
+    for (B, n, Nd), (name, c) in zip(MC.SHAPES, SEEDED.items()):
+        got = seeded_ref[name]
+        assert c["kind"].shape == (B, n) and c["cell"].shape == (B, n, 2) and c["pose"].shape == (B, 3) and c["Nd"] == Nd
+        assert (got["seg_stats"].sum(axis=0) > 0).all(), name                              # every column
+        assert (got["seg_stats"][:, 3] > Nd).any() and (got["seg_stats"][:, 0] == 0).any(), name   # more than Nd accepted; none at all
+        assert (got["seg_stats"][:, 1:].sum(axis=1) == got["seg_stats"][:, 0]).all()
+        assert (got["det_count"] == np.minimum(got["seg_stats"][:, 3], Nd)).all()
+        for k in ("whole_circle", "dropped", "d_zero", "crossing"):
+            assert got["counters"][k] >= 1, (name, k)
+        for k, v in got["counters"].items():
+            total[k] = total.get(k, 0) + v
+    assert all(v >= 1 for v in total.values()) and total["wrapped"] >= 10, total
+    assert {c["p"]["subtract_map"] for c in SEEDED.values()} == {0, 1}
+
+
+def test_rows_beyond_the_count_keep_what_was_there():
+    c = SEEDED[MC.seeded_name(67, 64, 8)]
+    fill = dict(detections=np.full((67, 8, 5), 7.5), det_segment=np.full((67, 8, 4), 1234, np.int32))
+    got, plain = ref(c, **fill), ref(c)
+    for b in range(67):
+        k = got["det_count"][b]
+        assert (got["detections"][b, k:] == 7.5).all() and (got["det_segment"][b, k:] == 1234).all()
+        assert got["detections"][b, :k].tobytes() == plain["detections"][b, :k].tobytes()
+
+
+# ---- the compiled rule ------------------------------------------------------------------------------------------------------
+PROBE = r"""
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+#include <string>
+#include <vector>
+#include "smpc_scan_people_rule.hpp"
+
+static double num(const std::string& s) { return std::strtod(s.c_str(), nullptr); }   // hex floats, nan, inf
+static std::string hex(double v) { char b[40]; uint64_t u; std::memcpy(&u, &v, 8); std::snprintf(b, sizeof b, "%016llx", (unsigned long long)u); return b; }
+static double rd() { std::string w; std::cin >> w; return num(w); }
+static long long ri() { long long v; std::cin >> v; return v; }
+
+// The scalars, then one robot per record, composed as the kernel composes the rule: passes of 64 "lanes", lane j of pass p
+// takes beam 64 p + j and its predecessor from the lane below or from what the pass before carried over (beam n - 1 before
+// the first); a segment is judged at the beam behind its last one, its start is the last start below that beam in the pass or
+// the one carried over, its sums are differences of the running prefix; a segment that closes with no start anywhere below it
+// is the head of the one that wraps and is set aside; what is open at beam n - 1 is judged last; the walk ends once Nd rows are
+// out when the statistics are not asked for (stats == 0: they are then printed as -1).
+constexpr int kLanes = 64;
+struct Row { int s, m, Sx, Sy; double px, py; };
+
+int main() {
+  const int n = (int)ri(), B = (int)ri(), Nd = (int)ri(), stats = (int)ri();
+  const int32_t subtract = (int32_t)ri(), min_points = (int32_t)ri(), link_d2 = (int32_t)ri(), wmin = (int32_t)ri(), wmax = (int32_t)ri(),
+                range_d2 = (int32_t)ri();
+  const double res = rd(), ox = rd(), oy = rd(), body = rd();
+  if (n < 1 || n > 4096 || Nd < 1 || Nd > 64) std::abort();
+  std::vector<long long> kind((size_t)n);
+  std::vector<int32_t> cell((size_t)n * 2);
+  for (int b = 0; b < B; ++b) {
+    const double x = rd(), y = rd();
+    for (auto& k : kind) k = ri();
+    for (auto& c : cell) c = (int32_t)ri();
+    int32_t ax = 0, ay = 0;
+    if (!smpc::sp_robot_cell(x, y, ox, oy, res, &ax, &ay)) { std::printf("0 %d %d %d %d\n", stats ? 0 : -1, stats ? 0 : -1, stats ? 0 : -1, stats ? 0 : -1); continue; }
+    std::vector<Row> rows;
+    auto write = [&](int rank, int s, int m, int Sx, int Sy) {
+      if (rank >= Nd) return;
+      Row r{s, m, Sx, Sy, 0.0, 0.0};
+      smpc::sp_position(smpc::sp_centre(Sx, m, ax, ox, res), smpc::sp_centre(Sy, m, ay, oy, res), x, y, body, &r.px, &r.py);
+      if ((int)rows.size() != rank) std::abort();   // ranks come out in order
+      rows.push_back(r);
+    };
+    const int last_x = cell[2 * (size_t)(n - 1)], last_y = cell[2 * (size_t)(n - 1) + 1];
+    const bool last_fg = smpc::sp_foreground((uint32_t)(uint8_t)kind[(size_t)(n - 1)], subtract, last_x, last_y, range_d2);
+    int pred_x = last_x, pred_y = last_y; bool pred_fg = last_fg;
+    int base_x = 0, base_y = 0;
+    bool has_start = false; int cs = 0, cEx = 0, cEy = 0, cfx = 0, cfy = 0;
+    bool has_head = false; int head_m = 0, hSx = 0, hSy = 0, hlx = 0, hly = 0;
+    int first_x = 0, first_y = 0, acc = 0, n_seg = 0, n_pts = 0, n_wid = 0;
+    bool done = false;
+    for (int p0 = 0; p0 < n; p0 += kLanes) {
+      int o_x[kLanes], o_y[kLanes], q_x[kLanes], q_y[kLanes], Ex[kLanes], Ey[kLanes];
+      bool fg[kLanes], qfg[kLanes], link[kLanes], start[kLanes], closer[kLanes];
+      for (int l = 0; l < kLanes; ++l) {
+        const int k = p0 + l;
+        o_x[l] = o_y[l] = 0; fg[l] = false;
+        if (k < n) {
+          o_x[l] = cell[2 * (size_t)k]; o_y[l] = cell[2 * (size_t)k + 1];
+          fg[l] = smpc::sp_foreground((uint32_t)(uint8_t)kind[(size_t)k], subtract, o_x[l], o_y[l], range_d2);
+        }
+      }
+      int run_x = 0, run_y = 0, last_start = -1;
+      bool any_closer = false;
+      for (int l = 0; l < kLanes; ++l) {
+        const int k = p0 + l;
+        q_x[l] = l ? o_x[l - 1] : pred_x; q_y[l] = l ? o_y[l - 1] : pred_y; qfg[l] = l ? fg[l - 1] : pred_fg;
+        link[l] = n >= 2 && fg[l] && qfg[l] && smpc::sp_linked(o_x[l], o_y[l], q_x[l], q_y[l], link_d2);
+        start[l] = fg[l] && !link[l];
+        closer[l] = k < n && k >= 1 && qfg[l] && !link[l];
+        any_closer = any_closer || closer[l];
+        Ex[l] = base_x + run_x; Ey[l] = base_y + run_y;          // exclusive
+        if (fg[l]) { run_x += o_x[l]; run_y += o_y[l]; }
+      }
+      if (any_closer) {
+        int src = -1, accepted = 0;
+        for (int l = 0; l < kLanes; ++l) {                        // src: the highest start below lane l
+          if (closer[l]) {
+            const bool local = src >= 0;
+            const int s = local ? p0 + src : cs, sEx = local ? Ex[src] : cEx, sEy = local ? Ey[src] : cEy;
+            const int fx = local ? o_x[src] : cfx, fy = local ? o_y[src] : cfy;
+            if (!local && !has_start) {
+              if (has_head) std::abort();                         // at most once
+              has_head = true; head_m = p0 + l; hSx = Ex[l]; hSy = Ey[l]; hlx = q_x[l]; hly = q_y[l];
+            } else {
+              const int m = p0 + l - s, Sx = Ex[l] - sEx, Sy = Ey[l] - sEy;
+              const int32_t gate = smpc::sp_gate(m, smpc::sp_dist2(fx, fy, q_x[l], q_y[l]), min_points, wmin, wmax);
+              if (gate == smpc::kScanAccepted) { write(acc + accepted, s, m, Sx, Sy); ++accepted; }
+              ++n_seg; n_pts += gate == smpc::kScanByPoints; n_wid += gate == smpc::kScanByWidth;
+            }
+          }
+          if (start[l]) src = l;
+        }
+        acc += accepted;
+      }
+      for (int l = 0; l < kLanes; ++l) if (start[l]) last_start = l;
+      if (last_start >= 0) { has_start = true; cs = p0 + last_start; cEx = Ex[last_start]; cEy = Ey[last_start]; cfx = o_x[last_start]; cfy = o_y[last_start]; }
+      if (p0 == 0) { first_x = o_x[0]; first_y = o_y[0]; }
+      base_x += run_x; base_y += run_y;
+      pred_x = o_x[kLanes - 1]; pred_y = o_y[kLanes - 1]; pred_fg = fg[kLanes - 1];
+      if (acc >= Nd && !stats) { done = true; break; }
+    }
+    if (!done && last_fg) {
+      int s = 0, m = n, Sx = base_x, Sy = base_y, fx = first_x, fy = first_y, lx = last_x, ly = last_y;
+      if (has_start) {
+        s = cs; m = n - cs + head_m; Sx = base_x - cEx + hSx; Sy = base_y - cEy + hSy; fx = cfx; fy = cfy;
+        if (has_head) { lx = hlx; ly = hly; }
+      }
+      const int32_t gate = smpc::sp_gate(m, smpc::sp_dist2(fx, fy, lx, ly), min_points, wmin, wmax);
+      if (gate == smpc::kScanAccepted) { write(acc, s, m, Sx, Sy); ++acc; }
+      ++n_seg; n_pts += gate == smpc::kScanByPoints; n_wid += gate == smpc::kScanByWidth;
+    }
+    if (stats) std::printf("%d %d %d %d %d", acc < Nd ? acc : Nd, n_seg, n_pts, n_wid, acc); else std::printf("%d -1 -1 -1 -1", acc < Nd ? acc : Nd);
+    for (const Row& r : rows) std::printf(" %d %d %d %d %s %s", r.s, r.m, r.Sx, r.Sy, hex(r.px).c_str(), hex(r.py).c_str());
+    std::printf("\n");
+  }
+  return 0;
+}
+"""
+
+
+def probe_input(c, stats=1):
+    hx = lambda v: float(v).hex() if np.isfinite(v) else repr(float(v))
+    p = c["p"]
+    B, n = c["kind"].shape
+    lines = [" ".join(map(str, [n, B, c["Nd"], stats, p["subtract_map"], p["min_points"], p["link_d2"], p["width_d2_min"], p["width_d2_max"],
+                                p["range_d2"], hx(p["res"]), hx(p["origin"][0]), hx(p["origin"][1]), hx(p["body_offset"])]))]
+    for b in range(B):
+        lines.append(" ".join(hx(v) for v in c["pose"][b, :2]))
+        lines.append(" ".join(map(str, c["kind"][b].tolist())))
+        lines.append(" ".join(map(str, c["cell"][b].ravel().tolist())))
+    return "\n".join(lines) + "\n"
+
+
+def probe_output(c, text):
+    """The program's lines as scan_people_ref.run's four outputs over its prefill."""
+    B, Nd = len(c["pose"]), c["Nd"]
+    out = text.splitlines()
+    assert len(out) == B
+    got = dict(detections=np.full((B, Nd, 5), np.nan), det_count=np.zeros(B, np.int32), det_segment=np.full((B, Nd, 4), -99, np.int32),
+               seg_stats=np.zeros((B, 4), np.int32))
+    for b, line in enumerate(out):
+        w = line.split()
+        got["det_count"][b], got["seg_stats"][b] = int(w[0]), [int(v) for v in w[1:5]]
+        assert len(w) == 5 + 6 * got["det_count"][b]
+        for i in range(got["det_count"][b]):
+            row = w[5 + 6 * i:11 + 6 * i]
+            got["det_segment"][b, i] = [int(v) for v in row[:4]]
+            got["detections"][b, i] = list(np.array([int(v, 16) for v in row[4:]], np.uint64).view(np.float64)) + [0.0, 0.0, 0.0]
+    return got
+
+
+def build_probe(tmp, name, extra=()):
+    src, exe = tmp / "probe.hip", tmp / name
+    src.write_text(PROBE)
+    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", *extra, "-I", CSRC, str(src), "-o", str(exe)])   # -O3 as build.sh
+    return exe
+
+
+@pytest.fixture(scope="module")
+def rule(tmp_path_factory):
+    if not os.access(HIPCC, os.X_OK):
+        pytest.skip(f"{HIPCC} (the compiler build.sh invokes) not available")
+    exe = build_probe(tmp_path_factory.mktemp("scan_people_rule"), "probe")
+    return lambda c, stats=1: probe_output(c, subprocess.run([str(exe)], input=probe_input(c, stats), capture_output=True, text=True, check=True).stdout)
+
+
+@pytest.mark.parametrize("name", sorted(HAND))
+def test_compiled_rule_is_the_yardstick_on_the_hand_made_cases(rule, name):
+    got = rule(HAND[name])
+    assert R.same(got, ref(HAND[name]))
+    MC.check_want(HAND[name], got)
+
+
+@pytest.mark.parametrize("name", list(SEEDED))
+def test_compiled_rule_is_the_yardstick_on_the_seeded_cases(rule, seeded_ref, name):
+    assert R.same(rule(SEEDED[name]), seeded_ref[name])
+
+
+@pytest.mark.parametrize("name", list(SEEDED))
+def test_the_early_end_of_the_walk_does_not_show_in_the_rows(rule, seeded_ref, name):
+    got = rule(SEEDED[name], stats=0)
+    assert R.same(got, seeded_ref[name], keys=("detections", "det_count", "det_segment"))
+
+
+def test_the_program_runs_clean_under_the_address_and_undefined_behaviour_sanitizers(tmp_path, seeded_ref):
+    """The stand-alone program (its own main, nothing loaded into Python), built once more with the sanitizers: it exits 0 and
+    prints what the plain build prints."""
+    if not os.access(HIPCC, os.X_OK):
+        pytest.skip(f"{HIPCC} (the compiler build.sh invokes) not available")
+    exe = build_probe(tmp_path, "probe_san", ("-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-g"))
+    for name in (MC.seeded_name(33, 360, 16), MC.seeded_name(67, 65, 8)):
+        r = subprocess.run([str(exe)], input=probe_input(SEEDED[name]), capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert R.same(probe_output(SEEDED[name], r.stdout), seeded_ref[name])
+
+
+def test_the_rule_header_rounds_every_operation_on_its_own():
+    text = open(os.path.join(CSRC, "smpc_scan_people_rule.hpp")).read()
+    assert text.count("#pragma clang fp contract(off)") >= 3 and "fma(" not in text and "hip_runtime" not in text
+    assert re.findall(r'#include\s+([<"][^>"]+[>"])', text) == ["<stdint.h>"]
+    kernel = open(os.path.join(CSRC, "smpc_scan_people.hpp")).read()
+    code = kernel.split("#pragma once")[1]
+    assert '#include "smpc_scan_people_rule.hpp"' in kernel and "SMPC_CHAIN_PRIORITY();" in kernel
+    assert "atomic" not in code and "__shared__" not in code and "__ballot(" in code and "__shfl_up(" in code
+    hip = open(os.path.join(CSRC, "smpc_hip.hip")).read()
+    assert '#include "smpc_scan_people.hpp"' in hip and "smpc::smpc_scan_people_kernel" in hip
+
+
+# ---- the ctypes mirror ---------------------------------------------------------------------------------------------------
+def test_mirror_matches_the_header_and_the_library_exports_the_function(tmp_path):
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    assert sorted(set(re.findall(r"\b(smpc_[a-z0-9_]+)\s*\(", src))) == sorted(MA.FUNCTIONS) == ["smpc_scan_people_batch"]
+    assert re.findall(r"\btypedef\s+struct\s+\w+\s*\{.*?\}\s*(\w+)\s*;", src, flags=re.S) == [st.c_name for st in MA.STRUCTS]
+    body = "".join(f'printf("%zu\\n", sizeof({st.c_name}));\n' + "".join(f'printf("%zu\\n", offsetof({st.c_name}, {f[0]}));\n' for f in st._fields_)
+                   for st in MA.STRUCTS)
+    body += 'printf("%d\\n%d\\n", (int)SMPC_SENSED_MAX_BEAMS, (int)SMPC_MAX_AGENTS);\n'
+    prog, exe = tmp_path / "layout.c", tmp_path / "layout"
+    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "smpc_scan_people.h"\nint main(void){\n' + body + 'return 0;}\n')
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
+    values = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
+    want = [v for st in MA.STRUCTS for v in [C.sizeof(st)] + [getattr(st, f[0]).offset for f in st._fields_]]
+    assert values == want + [MA.SMPC_SCAN_PEOPLE_MAX_BEAMS, MA.SMPC_SCAN_PEOPLE_MAX_ROWS] and values[-2:] == [4096, 64]
+    for st in MA.STRUCTS:
+        fields = re.findall(r"\b(\w+)\s*(?:\[\w+\]\s*)*(?:,|;)", re.search(r"typedef struct %s \{(.*?)\}" % st.c_name, src, flags=re.S).group(1))
+        assert fields == [f[0] for f in st._fields_], st.c_name
+    assert C.sizeof(MA.SmpcScanPeopleIn) == 10 * 4 + 4 * 8 + 3 * 8
+    assert (R.KIND_NONE, R.KIND_WORLD, R.KIND_AGENT, R.KIND_CORNER_PAIR, R.KIND_INVALID, R.KIND_NO_ROBOT) == (0, 1, 2, 3, 4, 5)
+    exported = subprocess.check_output(["nm", "-D", "--defined-only", S.LIB_PATH], text=True)
+    lib = S.load_library()
+    for name, (restype, argtypes) in MA.FUNCTIONS.items():
+        assert f" {name}\n" in exported
+        assert getattr(lib, name).restype is restype and list(getattr(lib, name).argtypes) == argtypes
+
+
+def test_the_main_abi_is_as_it_was():
+    from nav2_social_mpc_controller_amd import _abi
+    assert _abi.SMPC_ABI_VERSION == 6 and len(_abi.FUNCTIONS) == 27 and not set(MA.FUNCTIONS) & set(_abi.FUNCTIONS)
+    assert "SMPC_ABI_VERSION 6" in re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "smpc.h")).read())
+
+
+# ---- the parameters -------------------------------------------------------------------------------------------------------
+def test_scan_detector_params():
+    sp = ScanDetectorParams()
+    assert (sp.link_distance, sp.min_points, sp.min_width, sp.max_width, sp.body_offset, sp.subtract_map, sp.max_range, sp.max_detections) == \
+        (0.25, 3, 0.2, 0.8, 0.2, True, None, 16)
+    sensor = SensorParams()
+    assert sp.link_d2(0.05) == 25 and sp.width_d2(0.05) == (16, 256) and sp.range_d2(0.05, sensor) == 2500 and sp.range_m(sensor) == 2.5
+    assert sp.link_d2(0.1) == 6 and sp.width_d2(0.1) == (4, 64)                      # 2.5^2 = 6.25 rounds down
+    assert ScanDetectorParams(max_range=1.0).range_d2(0.05, sensor) == 400 and ScanDetectorParams(link_distance=0.0).link_d2(0.05) == 0
+    assert sp.link_d2(0.05) == sensor.__class__(agent_radius=0.25).agent_d2(0.05)     # the same rounding
+    assert sp.supported() and sp.supported(0.05, sensor) and ScanDetectorParams(max_detections=64).supported()
+    assert not ScanDetectorParams(max_detections=65).supported() and not sp.supported(1e-6, sensor) and not ScanDetectorParams(max_width=1e6).supported(0.05)
+    for bad in (dict(link_distance=-0.1), dict(link_distance=np.nan), dict(min_width=-1.0), dict(max_width=np.inf), dict(min_width=0.9),
+                dict(body_offset=-0.1), dict(body_offset=np.inf), dict(min_points=0), dict(min_points=2.5), dict(max_detections=0),
+                dict(max_detections=1.5), dict(max_range=0.0), dict(max_range=np.nan), dict(max_range=-1.0), dict(subtract_map=2)):
+        with pytest.raises(ValueError):
+            ScanDetectorParams(**bad)
+
+
+def test_the_struct_the_call_takes():
+    si = S.BatchSolver.scan_people_c(ScanDetectorParams(), 7, 360, 16, 1, 0.05, (-1.0, -0.5), SensorParams())
+    assert (si.B, si.n_beams, si.Nd, si.on_device, si.subtract_map, si.min_points, si.link_d2, si.width_d2_min, si.width_d2_max, si.range_d2) == \
+        (7, 360, 16, 1, 1, 3, 25, 16, 256, 2500)
+    assert (si.resolution, tuple(si.world_origin), si.body_offset) == (0.05, (-1.0, -0.5), 0.2)
+    assert not si.robot_pose and not si.beam_kind and not si.beam_cell
+    from nav2_social_mpc_controller_amd.params import ObstacleMemoryParams
+    sm = S.BatchSolver.scan_people_c(ScanDetectorParams(subtract_map=False), 1, 72, 4, 0, 0.05, (0.0, 0.0), SensorParams(), ObstacleMemoryParams())
+    assert sm.range_d2 == 2500 and sm.subtract_map == 0                                  # the marking range, not the ray-trace range
+
+
+def test_the_episode_declares_the_argument_and_refuses_what_it_must():
+    from nav2_social_mpc_controller_amd.episode import BatchEpisode, ShardedEpisode, TickRecord, shard_kwargs
+    assert "scan_detector" in BatchEpisode.FORWARDED and "scan_detector" not in BatchEpisode.PER_ROBOT
+    assert inspect.signature(BatchEpisode.__init__).parameters["scan_detector"].default is None
+    fields = TickRecord.__dataclass_fields__
+    assert all(fields[name].default is None for name in ("scan_persons", "scan_count", "scan_segment", "scan_stats"))
+    src = inspect.getsource(BatchEpisode)
+    assert 'timed("scan_people")' in src and src.index("s.scan_people_device(") < src.index("s.track_people_device(")
+    sp = ScanDetectorParams()
+    assert shard_kwargs({"scan_detector": sp}, np.arange(2), 4)["scan_detector"] is sp and "shard_kwargs" in inspect.getsource(ShardedEpisode.__init__)
+    BatchEpisode.check_scan_detector(sp, SensorParams(), None, None, 0.05)
+    with pytest.raises(ValueError, match=re.escape("scan_detector needs sensor=SensorParams(...): it reads the scan")):
+        BatchEpisode.check_scan_detector(sp, None, None, None, 0.05)
+    with pytest.raises(ValueError, match="visibility"):
+        BatchEpisode.check_scan_detector(sp, SensorParams(), VisibilityParams(), None, 0.05)
+    with pytest.raises(ValueError, match="detector"):
+        BatchEpisode.check_scan_detector(sp, SensorParams(), None, DetectorParams(), 0.05)
+    for bad in (dict(link_distance=0.25), None, ScanDetectorParams(max_detections=65)):
+        with pytest.raises(ValueError):
+            BatchEpisode.check_scan_detector(bad, SensorParams(), None, None, 0.05)
+
+
+# ---- the kernel's resources ------------------------------------------------------------------------------------------------
+def test_the_kernel_has_no_spills_no_scratch_and_no_lds(tmp_path):
+    if not os.access(HIPCC, os.X_OK):
+        pytest.skip(f"{HIPCC} (the compiler build.sh invokes) not available")
+    r = subprocess.run(["bash", os.path.join(CSRC, "build.sh"), "-DSMPC_ONLY_NB=3", "--cuda-device-only", "-c",
+                        "-Rpass-analysis=kernel-resource-usage"],
+                       env={**os.environ, "SMPC_OUT": str(tmp_path / "smpc_nb3.o")}, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    use = parse_resource_remarks(r.stderr).get(KERNEL)
+    assert use is not None, f"no resource remark for {KERNEL}"
+    print(KERNEL, use)
+    assert use["VGPRs Spill"] == 0 and use["SGPRs Spill"] == 0 and use["ScratchSize [bytes/lane]"] == 0, use   # no private segment
+    assert use["VGPRs"] == 72 and use["LDS Size [bytes/block]"] == 0, use                                      # what the build reports
+    assert use["VGPRs"] <= 128 and use["Occupancy [waves/SIMD]"] >= 4, use                                     # four waves per SIMD fit
+
+
+# ---- behaviour, on the yardsticks of the scan and of this stage alone ----------------------------------------------------------
+RES, ORIGIN = 0.05, (0.0, 0.0)
+SENSOR = SensorParams()                                  # 360 beams of 2.5 m, discs of 0.3 m
+BEAMS = SENSOR.beam_cells(RES)
+AGENT_D2 = SENSOR.agent_d2(RES)
+FLOOR = np.zeros((160, 160), np.uint8)                   # 8 m x 8 m, open
+
+
+def scan(world, robot_xy, persons):
+    """One robot's scan by tests/sensed_costmap_ref.py: (kind [1,n], cell [1,n,2])."""
+    people = np.zeros((max(len(persons), 1), 5))
+    if len(persons):
+        people[:len(persons), :2] = persons
+    occupied = sensed_costmap_ref.occupied_cells(people, len(persons), ORIGIN, RES, AGENT_D2)
+    a = sensed_costmap_ref.point_cell(robot_xy[0], robot_xy[1], ORIGIN, RES)
+    cast = [sensed_costmap_ref.cast(world, occupied, a, off) for off in BEAMS]
+    return np.array([[k for k, _, _ in cast]], np.uint8), np.array([[o for _, o, _ in cast]], np.int32)
+
+
+def detect(world, robot_xy, persons, scanned=None, **kw):
+    sp = ScanDetectorParams(**kw)
+    wmin, wmax = sp.width_d2(RES)
+    p = R.params(sp.link_d2(RES), sp.min_points, wmin, wmax, sp.range_d2(RES, SENSOR), int(sp.subtract_map), sp.body_offset, RES, ORIGIN)
+    kind, cell = scanned if scanned is not None else scan(world, robot_xy, persons)
+    return R.run(p, sp.max_detections, np.array([[robot_xy[0], robot_xy[1], 0.0]]), kind, cell)
+
+
+@pytest.fixture(scope="module")
+def lone_persons():
+    """80 seeded lone persons at 0.6 .. 2.3 m of a robot on the open floor: per person (true xy, the run with the default
+    body_offset, the run with 0)."""
+    rng = np.random.default_rng(7)
+    out = []
+    for _ in range(80):
+        robot = rng.uniform(3.5, 4.5, 2)
+        t, d = rng.uniform(0, 2 * np.pi), rng.uniform(0.6, 2.3)
+        person = robot + d * np.array([np.cos(t), np.sin(t)])
+        scanned = scan(FLOOR, robot, [person])
+        out.append((person, detect(FLOOR, robot, [person], scanned), detect(FLOOR, robot, [person], scanned, body_offset=0.0)))
+    return out
+
+
+def test_a_lone_person_is_one_detection_within_the_derivable_bound(lone_persons):
+    """The bound: a hit cell's centre lies within sqrt(agent_d2) cells of the person's cell centre, which lies within half a
+    cell's diagonal of the person, so the mean of the hit cells does too (a disc is convex); the push-back moves it by
+    body_offset at the most. Measured here (recorded in DESIGN.md, not asserted): see the printed figures."""
+    bound = np.sqrt(AGENT_D2) * RES + RES * np.sqrt(0.5) + ScanDetectorParams().body_offset
+    err, err0 = [], []
+    for person, with_offset, without in lone_persons:
+        for got, sink in ((with_offset, err), (without, err0)):
+            assert got["det_count"][0] == 1 and got["seg_stats"][0].tolist() == [1, 0, 0, 1], (person, got["seg_stats"])
+            sink.append(float(np.hypot(*(got["detections"][0, 0, :2] - person))))
+    print(f"lone persons: error with body_offset 0.2: mean {np.mean(err):.4f} max {np.max(err):.4f}; with 0: mean {np.mean(err0):.4f} max {np.max(err0):.4f}")
+    assert max(err) <= bound and max(err0) <= bound
+    assert np.mean(err) < np.mean(err0)
+
+
+def test_a_pillar_of_person_width_is_a_detection_only_while_the_map_is_not_subtracted():
+    world = FLOOR.copy()
+    world[76:84, 108:116] = 254                          # 0.4 m x 0.4 m, 1.5 m ahead of the robot at (4, 4)
+    kept, subtracted = detect(world, (4.025, 4.025), [], subtract_map=False), detect(world, (4.025, 4.025), [])
+    assert kept["det_count"][0] == 1 and kept["seg_stats"][0].tolist() == [1, 0, 0, 1]
+    assert np.hypot(*(kept["detections"][0, 0, :2] - (5.6, 4.0))) < 0.4
+    assert subtracted["det_count"][0] == 0 and subtracted["seg_stats"][0].tolist() == [0, 0, 0, 0]
+
+
+def test_two_persons_whose_discs_touch_are_one_segment_too_wide_for_a_person():
+    got = detect(FLOOR, (4.025, 4.025), [(5.525, 3.725), (5.525, 4.325)])     # side by side 1.5 m ahead, centres 0.6 m apart
+    assert got["det_count"][0] == 0 and got["seg_stats"][0].tolist() == [1, 0, 1, 0]
+    apart = detect(FLOOR, (4.025, 4.025), [(5.525, 3.425), (5.525, 4.625)])   # 1.2 m apart: two persons
+    assert apart["det_count"][0] == 2 and apart["seg_stats"][0].tolist() == [2, 0, 0, 2]

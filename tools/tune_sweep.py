@@ -5,7 +5,7 @@ BatchEpisode(scene_params=...)); the device scores every robot as it drives (Bat
 summarize_metrics means is printed per set. Nothing but the final [B,24] metrics rows leaves the device.
 
     python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]] [--tracker] [--detector] [--plant]
-                                [--world-plans [--occlusion [RANGE]] [--shared-crowd M] [--sensed-costmap [--obstacle-memory] [--collision-monitor]]]
+                                [--world-plans [--occlusion [RANGE]] [--shared-crowd M] [--sensed-costmap [--obstacle-memory] [--collision-monitor] [--scan-detector]]]
 
 --reactive: the persons are a reactive crowd (BatchEpisode(crowd=CrowdParams()), waypoints from scenes.crowd_waypoints)
 instead of walking straight on with constant velocity. --groups (with --reactive): half of the walking persons go in pairs
@@ -48,6 +48,10 @@ tick that a contact stopped.
 (BatchEpisode(monitor=MonitorParams.nav2_like(0.24))): a STOP circle just beyond the body, a SLOWDOWN polygon ahead and the
 footprint as APPROACH zone over 1.2 s, judged against the cells the tick's scan stopped at. The tuning then meets the safety layer
 a deployed controller runs under; a last column is the share of ticks in which the monitor changed the command (ratio < 1).
+--scan-detector (with --world-plans --sensed-costmap, without --occlusion and --detector): the persons the controller is handed
+are what its own scan shows (BatchEpisode(scan_detector=ScanDetectorParams())): the tick's beam hits clustered into person-sized
+segments, so a person half hidden behind another, two persons who merge into one wide blob and the grid's quantisation come
+from geometry and not from a noise model. A detection has no velocity: combine with --tracker.
 """
 import argparse
 import os
@@ -93,11 +97,17 @@ def main():
                     help="the detections are a detector's: body occlusion, misses, range-dependent noise and clutter")
     ap.add_argument("--collision-monitor", action="store_true",
                     help="the command passes scan-based stop, slowdown and approach zones (needs --world-plans --sensed-costmap)")
+    ap.add_argument("--scan-detector", action="store_true",
+                    help="the detections are segments of the tick's scan (needs --world-plans --sensed-costmap; excludes --occlusion, --detector)")
     ap.add_argument("--plant", action="store_true",
                     help="the command is executed under acceleration limits and stopped by contact with walls and persons")
     a = ap.parse_args()
     if a.collision_monitor and not (a.world_plans and a.sensed_costmap):
         ap.error("--collision-monitor needs --world-plans --sensed-costmap")
+    if a.scan_detector and not (a.world_plans and a.sensed_costmap):
+        ap.error("--scan-detector needs --world-plans --sensed-costmap")
+    if a.scan_detector and (a.occlusion is not None or a.detector):
+        ap.error("--scan-detector excludes --occlusion and --detector: the scan-based and the ground-truth path are alternatives")
     if a.obstacle_memory and not a.sensed_costmap:
         ap.error("--obstacle-memory needs --sensed-costmap")
     if a.sensed_costmap and not a.world_plans:
@@ -115,7 +125,7 @@ def main():
 
     from nav2_social_mpc_controller_amd.episode import BatchEpisode, arc_plans
     from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, ObstacleMemoryParams, OptimizerParams,
-                                                       DetectorParams, MonitorParams, PlantParams, PoolCrowdParams, SensorParams, SharedWorldParams, TrackerParams, TrajectorizerParams, VisibilityParams,
+                                                       DetectorParams, MonitorParams, PlantParams, PoolCrowdParams, ScanDetectorParams, SensorParams, SharedWorldParams, TrackerParams, TrajectorizerParams, VisibilityParams,
                                                        scene_param_rows)
     from nav2_social_mpc_controller_amd.scenes import (crowd_groups, crowd_waypoints, make_scenes, make_world, pool_waypoints, scenes_in_world,
                                                        shared_pool, uniform, world_goals)
@@ -162,6 +172,8 @@ def main():
         plans["tracker"] = TrackerParams(slots=max(16, min(64, 2 * a.agents)))
     if a.detector:
         plans["detector"] = DetectorParams(clutter_candidates=min(2, 64 - a.agents))
+    if a.scan_detector:
+        plans["scan_detector"] = ScanDetectorParams()
     if a.plant:
         plans["plant"] = PlantParams()
     if a.collision_monitor:
