@@ -16,7 +16,7 @@
 //   the probe kernels (smpc_probes.hpp);
 //   and the kernels of the tick around the solve, one header each (projection, distance, format, trajectorize, window,
 //   metrics, crowd, local costmap, global plan, visibility, nearest agents, pool crowd, sensed costmap, obstacle memory,
-//   people tracks, people detections, robot plant, collision monitor, people detections from the scan).
+//   people tracks, people detections, robot plant, collision monitor, people detections from the scan, plan repair).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -57,6 +57,7 @@
 #include "../../include/smpc_collision_monitor.h"
 #include "smpc_scan_people.hpp"
 #include "../../include/smpc_scan_people.h"
+#include "smpc_plan_repair.hpp"
 
 extern "C" {
 
@@ -1154,6 +1155,62 @@ int smpc_scan_people_batch(smpc_handle* h, const smpc_scan_people_in* in, double
   const size_t per_block = smpc::kSpThreads / 64;
   SMPC_TRY(st.timed([&] {
     hipLaunchKernelGGL(smpc::smpc_scan_people_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kSpThreads), 0, h->stream, p);
+    return SMPC_OK;
+  }));
+  return st.finish();
+}
+
+int smpc_repair_plan_batch(smpc_handle* h, const smpc_plan_repair_in* in, double* plan, int32_t* plan_len, double* workspace, int32_t* status,
+                           int32_t* info, uint32_t* field) {
+  if (!h || !in || !plan || !plan_len || !workspace || !status) { set_error("null handle / input / plan / plan_len / workspace / status"); return SMPC_ERR_INVALID_ARG; }
+  if (!in->costmap || !in->costmap_origin || !in->robot_pose) { set_error("null input array"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B < 0 || in->L < 2 || in->size_x < 1 || in->size_y < 1 || in->radius < 1 || in->stride < 1) {
+    set_error("bad B, L < 2, or a size, radius or stride < 1"); return SMPC_ERR_INVALID_ARG;
+  }
+  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) { set_error("resolution must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->clearance_d2) || !(in->clearance_d2 >= 0.0)) { set_error("clearance_d2 must be finite and >= 0"); return SMPC_ERR_INVALID_ARG; }
+  const smpc_plan_cost_params& c = in->cost;
+  if (c.neutral_cost < 1 || c.cost_weight < 0) { set_error("neutral_cost must be >= 1 and cost_weight >= 0"); return SMPC_ERR_INVALID_ARG; }
+  const int64_t w_max = (int64_t)c.neutral_cost + 255 * (int64_t)c.cost_weight;
+  if (w_max > 65535) { set_error("neutral_cost + 255 * cost_weight must be <= 65535"); return SMPC_ERR_INVALID_ARG; }
+  if (in->radius > SMPC_REPAIR_MAX_RADIUS) { set_error("radius above SMPC_REPAIR_MAX_RADIUS is not supported"); return SMPC_ERR_UNSUPPORTED; }
+  const int64_t S = 2 * (int64_t)in->radius + 1;
+  if (S * S * 7 * w_max >= ((int64_t)1 << 32) - 1) {
+    set_error("S * S * 7 * (neutral_cost + 255 * cost_weight) must stay below 2^32 - 1: potentials are 32 bits"); return SMPC_ERR_UNSUPPORTED;
+  }
+  if (in->B == 0) return SMPC_OK;
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::PlanRepairParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.B = in->B; p.L = in->L; p.size_x = in->size_x; p.size_y = in->size_y; p.costmap_shared = in->costmap_shared ? 1 : 0;
+  p.R = in->radius; p.stride = in->stride; p.res = in->resolution; p.clearance_d2 = in->clearance_d2;
+  p.cost.neutral = c.neutral_cost; p.cost.weight = c.cost_weight; p.cost.lethal_min = c.lethal_min_cost; p.cost.allow_unknown = c.allow_unknown ? 1u : 0u;
+  const size_t B = in->B, L = in->L, nmap = in->costmap_shared ? 1 : B;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.costmap, in->costmap, nmap * (size_t)in->size_x * in->size_y));
+  SMPC_TRY(st.in(p.origin, in->costmap_origin, nmap * 2));
+  SMPC_TRY(st.in(p.pose, in->robot_pose, B * 3));
+  SMPC_TRY(st.in(p.plan_start, in->plan_start, B));
+  // read and written: what the rule leaves alone keeps the caller's bytes on the way through device memory too
+  SMPC_TRY(st.inout(p.plan, plan, B * L * 2));
+  SMPC_TRY(st.inout(p.plan_len, plan_len, B));
+  SMPC_TRY(st.out(p.status, status, B));
+  SMPC_TRY(st.out(p.info, info, B * 4));
+  SMPC_TRY(st.inout(p.field, field, B * (size_t)(S * S)));
+  void* ws = workspace;  // a host-pointer call's workspace is device room of the call's own
+  SMPC_TRY(st.scratch(ws, B * L * 2 * sizeof(double)));
+  p.workspace = static_cast<double*>(ws);
+  const size_t lds = smpc::pr_field_lds_bytes(in->radius);
+  if (lds > 64 * 1024) {
+    SMPC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(smpc::smpc_repair_field_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+  // a wavefront per row of a colour: R + 1 rows at the most, 16 wavefronts at the most
+  const unsigned field_threads = 64u * (unsigned)(in->radius + 1 < smpc::kPrFieldMaxThreads / 64 ? in->radius + 1 : smpc::kPrFieldMaxThreads / 64);
+  const size_t field_grid = B < (size_t)h->num_cu * 4 ? B : (size_t)h->num_cu * 4;
+  const size_t per_block = smpc::kPrJudgeThreads / 64;
+  SMPC_TRY(st.timed([&] {
+    hipLaunchKernelGGL(smpc::smpc_repair_judge_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kPrJudgeThreads), 0, h->stream, p);
+    hipLaunchKernelGGL(smpc::smpc_repair_field_kernel, dim3((unsigned)field_grid), dim3(field_threads), lds, h->stream, p);
     return SMPC_OK;
   }));
   return st.finish();

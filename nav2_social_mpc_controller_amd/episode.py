@@ -60,7 +60,7 @@ import numpy as np
 
 from ._abi import (SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcPeopleBatch, SmpcProjectionBatch, SmpcSceneBatch,
                    SmpcTrajectorizeOut, SmpcPlanWindowBatch)
-from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, MonitorParams, ObstacleMemoryParams, OptimizerParams, PoolCrowdParams,
+from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, MonitorParams, ObstacleMemoryParams, OptimizerParams, PlanRepairParams, PoolCrowdParams,
                      PlantParams, ScanDetectorParams, SensorParams, TrackerParams, TrajectorizerParams, SharedWorldParams, VisibilityParams, check_scene_param_rows)
 from .scenes import SceneBatch, World
 from .solver import BatchSolver, point, set_od_grid
@@ -175,6 +175,15 @@ class TickRecord:
     scan_count: np.ndarray = None             # [B] int32
     scan_segment: np.ndarray = None           # [B,Nd,4] int32 start beam, beams, summed offsets
     scan_stats: np.ndarray = None             # [B,4] int32 segments, rejected by points, rejected by width, accepted
+    # the plan repair (BatchEpisode(repair=...)): the plans the tick's smpc_repair_plan_batch was handed and what it made of them,
+    # having read robot_pose, the tick's sensed costmap (or `costmap` without a sensor), costmap_origin and plan_start
+    repair_plan_before: np.ndarray = None     # [B,L,2]
+    repair_plan_len_before: np.ndarray = None  # [B] int32
+    repair_plan_after: np.ndarray = None      # [B,L,2]: what the next tick's plan stage reads
+    repair_plan_len_after: np.ndarray = None  # [B] int32
+    repair_status: np.ndarray = None          # [B] int32 enum smpc_repair_status
+    repair_info: np.ndarray = None            # [B,4] int32 i0, i1, j, m; -1 where not determined
+    repair_costmap: np.ndarray = None         # the windows the repair read, when no sensing stage recorded them
 
 
 class BatchEpisode:
@@ -188,7 +197,7 @@ class BatchEpisode:
     FORWARDED = ("od_resolution", "device", "traj_params", "fov_angle", "order_hint", "plan_window", "obstacles_from_costmap",
                  "obstacle_min_cost", "unknown_is_obstacle", "metrics", "crowd", "crowd_groups", "world", "outside_cost", "planner",
                  "visibility", "shared", "pool", "pool_crowd", "pool_waypoints", "pool_n_waypoints", "pool_speed", "sensor",
-                 "sensor_memory", "tracker", "detector", "plant", "monitor", "scan_detector")
+                 "sensor_memory", "tracker", "detector", "plant", "monitor", "scan_detector", "repair")
 
     def __init__(self, params: OptimizerParams, scenes: SceneBatch, w_ref: np.ndarray, od_indexes: np.ndarray = None,
                  od_origin: np.ndarray = None, od_resolution: float = None, device: int = 0, plan: np.ndarray = None,
@@ -204,7 +213,7 @@ class BatchEpisode:
                  pool_waypoints: np.ndarray = None, pool_n_waypoints: np.ndarray = None, pool_speed: np.ndarray = None,
                  sensor: SensorParams = None, sensor_memory: ObstacleMemoryParams = None, tracker: TrackerParams = None,
                  detector: DetectorParams = None, plant: PlantParams = None, monitor: MonitorParams = None,
-                 scan_detector: ScanDetectorParams = None):
+                 scan_detector: ScanDetectorParams = None, repair: PlanRepairParams = None):
         """scenes: the start state (pose0, people at step 0, costmaps); w_ref [B]: curvature of the arc stand-in;
         od_*: the ObstacleDistance grid of people projection: od_indexes [h,w] + od_origin [2] one grid shared by all
         scenes, od_indexes [B,h,w] + od_origin [B,2] one per scene. obstacles_from_costmap: od_* are not needed; the grids
@@ -351,6 +360,15 @@ class BatchEpisode:
         width, accepted). The tracker reads them, or without one people_to_status does; a detection has no velocity, so
         without a tracker the solve plans around people who stand still: use tracker=TrackerParams(). The crowd, the plant,
         the metrics and the scan itself keep seeing the true persons.
+        None: nothing is allocated, nothing is launched and the episode is the one without bit for bit.
+        repair: the plans give way to what the windows show (include/smpc_plan_repair.h); needs `plan` or `planner`. Every
+        tick, right behind the sensing stage (the sensed or memory call; without a sensor, the plan stage), one
+        smpc_repair_plan_batch reads self.pose, self.costmap, self.costmap_origin and, with a plan window, self.plan_start: a
+        robot whose plan runs into impassable cells of its window within repair.radius gets the least-cost detour inside that
+        region spliced into self.plan / self.plan_len in place (self.plan_scratch [B,L,2] is the call's workspace), and
+        self.repair_status [B] int32 (enum smpc_repair_status) and self.repair_info [B,4] int32 (i0, i1, j, m) say what
+        happened. The tick's own roll and trajectorizer ran before the scan, so a repaired plan takes effect at the next
+        tick's plan stage. The call is part of a captured graph. replan() replaces repaired plans like any other.
         None: nothing is allocated, nothing is launched and the episode is the one without bit for bit."""
         import torch
 
@@ -416,6 +434,7 @@ class BatchEpisode:
         self._init_plant(plant)
         self._init_monitor(monitor)
         self._init_scan_detector(scan_detector)
+        self._init_repair(repair)
         self._bind()
         self.graph = None
         self.gstream = None
@@ -700,6 +719,26 @@ class BatchEpisode:
         self.scan_stats = self._zeros(B, 4, dtype=self.torch.int32)
 
     @staticmethod
+    def check_repair(repair, planned: bool, resolution: float):
+        """What BatchEpisode(repair=...) refuses (planned: the episode has plan= or planner=; resolution: the windows')."""
+        if not isinstance(repair, PlanRepairParams):
+            raise ValueError("repair must be a PlanRepairParams")
+        if not planned:
+            raise ValueError("repair needs plan= or planner=: there is no plan to repair")
+        if not repair.supported(resolution):
+            raise ValueError("repair: a radius beyond 63 cells at the windows' resolution, or costs whose potentials do not fit 32 bits")
+
+    def _init_repair(self, repair):
+        """The plan repair's workspace and what it reports."""
+        self.repair = repair
+        if repair is None:
+            return
+        self.check_repair(repair, self.plan is not None, self.resolution)
+        self.plan_scratch = self.torch.zeros_like(self.plan)
+        self.repair_status = self._zeros(self.B, dtype=self.torch.int32)
+        self.repair_info = self.torch.full((self.B, 4), -1, dtype=self.torch.int32, device=self.dev)
+
+    @staticmethod
     def check_plant(plant, resolution: float = None):
         """What BatchEpisode(plant=...) refuses (resolution: the world's, None without one)."""
         if not isinstance(plant, PlantParams):
@@ -880,6 +919,11 @@ class BatchEpisode:
                                   {"robot_pose": self.pose, "beam_kind": self.beam_kind, "beam_cell": self.beam_cell})
             point(c.people, {"people": self.scan_persons, "count": self.scan_count})
             c.people.Np = Nd
+        if self.repair is not None:  # the plans give way to what the windows show, in place
+            c.repair = point(BatchSolver.repair_plan_c(self.repair, B, int(self.plan.shape[1]), self.size_x, self.size_y, self.costmap_shared,
+                                                       self.resolution, 1),
+                             {"costmap": self.costmap, "costmap_origin": self.costmap_origin, "robot_pose": self.pose,
+                              "plan_start": self.plan_start if self.plan_window is not None else None})
         if self.tracker is not None:  # the controller gets tracks of what is detected: the last stage in front of the filter
             c.tracker = point(BatchSolver.tracker_c(self.tracker, B, Nd, Np, prm.dt, 1),
                               {"detections": c.people.people, "det_count": c.people.count, "robot_pose": self.pose})
@@ -1061,6 +1105,16 @@ class BatchEpisode:
             timed("sensed_costmap")
             if record:
                 rec.update(self._host("beam_kind", "beam_cell", sensed_costmap="costmap"))
+        if self.repair is not None:  # behind the sensing stage: detours around what the windows show, for the next tick's plan stage
+            if record:
+                rec.update(self._host(repair_plan_before="plan", repair_plan_len_before="plan_len"))
+                if self.sensor is None:
+                    rec.update(self._host(repair_costmap="costmap"))
+            s.repair_plan_device(c.repair, self.plan.data_ptr(), self.plan_len.data_ptr(), self.plan_scratch.data_ptr(),
+                                 self.repair_status.data_ptr(), self.repair_info.data_ptr())
+            timed("repair")
+            if record:
+                rec.update(self._host("repair_status", "repair_info", repair_plan_after="plan", repair_plan_len_after="plan_len"))
         if self.scan_detector is not None:  # the tick's beam hits clustered into person-sized segments: detections from the scan
             s.scan_people_device(c.scan_people, self.scan_persons.data_ptr(), self.scan_count.data_ptr(), self.scan_segment.data_ptr(),
                                  self.scan_stats.data_ptr())
@@ -1227,6 +1281,8 @@ class BatchEpisode:
             state += ("draw_state",)
         if self.plant is not None:
             state += ("plant_queue", "plant_tick")
+        if self.repair is not None:
+            state += ("plan", "plan_len")  # the warm-up tick may have spliced a detour in
         with torch.cuda.stream(self.gstream):
             saved = {k: getattr(self, k).clone() for k in state}
             ticks = self.ticks

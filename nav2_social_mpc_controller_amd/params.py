@@ -449,6 +449,57 @@ class ScanDetectorParams:
 
 
 @dataclass
+class PlanRepairParams:
+    """Plan repair (include/smpc_plan_repair.h; BatchEpisode(repair=...)): every tick a robot whose plan runs into impassable
+    cells of its own window gets the least-cost detour inside the window, spliced into its plan. radius: half the side of the
+    square region around the robot that is searched, metres (at most 63 cells of the window's resolution). rejoin_clearance:
+    the detour comes back to the plan at the first passable pose at least this far, metres, behind the last blocked one: a
+    scan does not show an obstacle's back. stride: every stride-th cell of the detour becomes a pose. The costs are the
+    global plans' (GlobalPlanParams): w = neutral_cost + cost_weight * cost, passable below lethal_min_cost, and 255 with
+    allow_unknown."""
+    radius: float = 3.0
+    rejoin_clearance: float = 0.5
+    stride: int = 2
+    neutral_cost: int = 50
+    cost_weight: int = 1
+    lethal_min_cost: int = 253
+    allow_unknown: bool = False
+
+    MAX_RADIUS_CELLS = 63   # SMPC_REPAIR_MAX_RADIUS
+
+    def __post_init__(self):
+        if not (np.isfinite(self.radius) and self.radius > 0.0):
+            raise ValueError(f"PlanRepairParams.radius must be finite and > 0, got {self.radius}")
+        if not (np.isfinite(self.rejoin_clearance) and self.rejoin_clearance >= 0.0):
+            raise ValueError(f"PlanRepairParams.rejoin_clearance must be finite and >= 0, got {self.rejoin_clearance}")
+        if int(self.stride) != self.stride or self.stride < 1:
+            raise ValueError(f"PlanRepairParams.stride must be an integer >= 1, got {self.stride}")
+        if self.neutral_cost < 1 or self.cost_weight < 0 or self.neutral_cost + 255 * self.cost_weight > 65535:
+            raise ValueError("PlanRepairParams: neutral_cost >= 1, cost_weight >= 0 and neutral_cost + 255 * cost_weight <= 65535")
+        if not 0 <= self.lethal_min_cost <= 255:
+            raise ValueError(f"PlanRepairParams.lethal_min_cost must be 0..255, got {self.lethal_min_cost}")
+
+    def radius_cells(self, resolution: float) -> int:
+        """R: the radius in cells of `resolution`, rounded down (SensorParams.agent_d2's guard against a quotient just below an
+        integer), at least 1."""
+        r = np.floor(np.float64(self.radius) / np.float64(resolution) + 1e-9)
+        return int(max(1.0, min(r, 2.0 ** 31 - 1)))
+
+    @property
+    def clearance_d2(self) -> float:
+        """The squared rejoin clearance in metres^2: one product of doubles."""
+        return float(np.float64(self.rejoin_clearance) * np.float64(self.rejoin_clearance))
+
+    def supported(self, resolution: float = None) -> bool:
+        """Does the library run this repair (include/smpc_plan_repair.h's two SMPC_ERR_UNSUPPORTED)? With a resolution: a
+        radius of at most 63 cells, and potentials that fit 32 bits over the region, S * S * 7 * (neutral_cost + 255 *
+        cost_weight) < 2^32 - 1; without one the bound is checked for 63 cells."""
+        R = self.MAX_RADIUS_CELLS if resolution is None else self.radius_cells(resolution)
+        S = 2 * R + 1
+        return R <= self.MAX_RADIUS_CELLS and S * S * 7 * (self.neutral_cost + 255 * self.cost_weight) < 2 ** 32 - 1
+
+
+@dataclass
 class PlantParams:
     """The robot plant (include/smpc_plant.h; BatchEpisode(plant=...)): every tick the selected command is executed by a
     model of the base instead of being taken for the motion. The command that was selected latency_ticks periods ago is

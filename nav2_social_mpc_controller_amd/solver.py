@@ -11,8 +11,8 @@ import os
 
 import numpy as np
 
-from . import (_abi, _abi_collision_monitor, _abi_crowd_pool, _abi_detector, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_obstacle_memory, _abi_plant,
-               _abi_scan_people, _abi_sensed_costmap, _abi_tracker, _abi_visibility)
+from . import (_abi, _abi_collision_monitor, _abi_crowd_pool, _abi_detector, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_obstacle_memory, _abi_plan_repair,
+               _abi_plant, _abi_scan_people, _abi_sensed_costmap, _abi_tracker, _abi_visibility)
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
@@ -23,12 +23,13 @@ from ._abi_global_plan import SmpcExtractPlanIn, SmpcGoalFieldIn
 from ._abi_local_costmap import SmpcLocalCostmapIn
 from ._abi_nearest import SmpcNearestIn
 from ._abi_obstacle_memory import SmpcObstacleMemoryIn
+from ._abi_plan_repair import SmpcPlanRepairIn
 from ._abi_plant import SmpcPlantIn
 from ._abi_scan_people import SmpcScanPeopleIn
 from ._abi_sensed_costmap import SmpcSensedCostmapIn
 from ._abi_tracker import SmpcTrackerIn
 from ._abi_visibility import SmpcVisibilityIn
-from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, MonitorParams, OptimizerParams, PlantParams, PoolCrowdParams,
+from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, MonitorParams, OptimizerParams, PlanRepairParams, PlantParams, PoolCrowdParams,
                      ScanDetectorParams, TrackerParams, TrajectorizerParams, VisibilityParams)
 from .scenes import SceneBatch
 
@@ -71,7 +72,8 @@ def load_library():
                                        **_abi_crowd_pool.FUNCTIONS, **_abi_sensed_costmap.FUNCTIONS,
                                        **_abi_obstacle_memory.FUNCTIONS, **_abi_tracker.FUNCTIONS,
                                        **_abi_detector.FUNCTIONS, **_abi_plant.FUNCTIONS,
-                                       **_abi_collision_monitor.FUNCTIONS, **_abi_scan_people.FUNCTIONS}.items():
+                                       **_abi_collision_monitor.FUNCTIONS, **_abi_scan_people.FUNCTIONS,
+                                       **_abi_plan_repair.FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -924,6 +926,55 @@ class BatchSolver:
         asynchronous on the handle's stream."""
         assert si.on_device == 1
         self._call("smpc_scan_people_batch", si, detections_ptr, det_count_ptr, det_segment_ptr or None, seg_stats_ptr or None)
+
+    # -- plan repair (smpc_repair_plan_batch, include/smpc_plan_repair.h) -----------------------------------------------------
+    @staticmethod
+    def repair_plan_c(rp: PlanRepairParams, B: int, L: int, size_x: int, size_y: int, costmap_shared: bool, resolution: float,
+                      on_device: int) -> SmpcPlanRepairIn:
+        """The call's struct without its array pointers: rp's radius in cells of `resolution`, its clearance squared."""
+        ri = SmpcPlanRepairIn(B=int(B), L=int(L), on_device=int(on_device), size_x=int(size_x), size_y=int(size_y),
+                              costmap_shared=1 if costmap_shared else 0, radius=rp.radius_cells(resolution), stride=int(rp.stride),
+                              resolution=float(resolution), clearance_d2=rp.clearance_d2)
+        ri.cost.neutral_cost, ri.cost.cost_weight = int(rp.neutral_cost), int(rp.cost_weight)
+        ri.cost.lethal_min_cost, ri.cost.allow_unknown = int(rp.lethal_min_cost), 1 if rp.allow_unknown else 0
+        return ri
+
+    def repair_plan(self, ri: SmpcPlanRepairIn, costmap: np.ndarray, costmap_origin: np.ndarray, robot_pose: np.ndarray, plan: np.ndarray,
+                    plan_len: np.ndarray, plan_start: np.ndarray = None, with_info: bool = True, with_field: bool = False, field: np.ndarray = None):
+        """One call of the plan repair on host arrays. ri: repair_plan_c(..., on_device=0) (its array pointers are set here).
+        costmap [size_y,size_x] uint8 with costmap_origin [2] (ri.costmap_shared) or [B,size_y,size_x] with [B,2]; robot_pose
+        [B,3]; plan [B,L,2] and plan_len [B] int32: the plans before the call, which are not modified; plan_start [B] int32 or
+        None. field [B,S,S] uint32: the rows before the call (default 0). Returns (plan, plan_len, status [B] int32, info
+        [B,4] int32 or None, field or None): copies of the plans with the repaired robots' rows replaced."""
+        costmap = np.ascontiguousarray(costmap, np.uint8)
+        costmap_origin = np.ascontiguousarray(costmap_origin, np.float64).reshape(-1, 2)
+        robot_pose = np.ascontiguousarray(robot_pose, np.float64)
+        B, L, S = robot_pose.shape[0], ri.L, 2 * ri.radius + 1
+        assert ri.on_device == 0 and ri.B == B and robot_pose.shape == (B, 3)
+        assert costmap.shape == ((ri.size_y, ri.size_x) if ri.costmap_shared else (B, ri.size_y, ri.size_x))
+        assert costmap_origin.shape == ((1, 2) if ri.costmap_shared else (B, 2))
+        plan = np.array(plan, dtype=np.float64, order="C")
+        plan_len = np.array(plan_len, dtype=np.int32, order="C")
+        assert plan.shape == (B, L, 2) and plan_len.shape == (B,)
+        if plan_start is not None:
+            plan_start = np.ascontiguousarray(plan_start, np.int32)
+            assert plan_start.shape == (B,)
+        workspace = np.zeros((B, L, 2))
+        status = np.full(B, -1, np.int32)
+        info = np.full((B, 4), -99, np.int32) if with_info else None
+        if with_field or field is not None:
+            field = np.zeros((B, S, S), np.uint32) if field is None else np.array(field, dtype=np.uint32, order="C")
+            assert field.shape == (B, S, S)
+        point(ri, {"costmap": costmap, "costmap_origin": costmap_origin, "robot_pose": robot_pose, "plan_start": plan_start})
+        self._call("smpc_repair_plan_batch", ri, _ptr(plan), _ptr(plan_len), _ptr(workspace), _ptr(status), _ptr(info), _ptr(field))
+        return plan, plan_len, status, info, field
+
+    def repair_plan_device(self, ri: SmpcPlanRepairIn, plan_ptr: int, plan_len_ptr: int, workspace_ptr: int, status_ptr: int, info_ptr: int = 0,
+                           field_ptr: int = 0):
+        """Device pointers in ri (on_device == 1) and for plan, plan_len (both edited in place), workspace, status, info and field
+        (0: none); asynchronous on the handle's stream."""
+        assert ri.on_device == 1
+        self._call("smpc_repair_plan_batch", ri, plan_ptr, plan_len_ptr, workspace_ptr, status_ptr, info_ptr or None, field_ptr or None)
 
     # -- robot plant (smpc_robot_plant_batch, include/smpc_plant.h) ----------------------------------------------------------
     @staticmethod

@@ -5,7 +5,7 @@ BatchEpisode(scene_params=...)); the device scores every robot as it drives (Bat
 summarize_metrics means is printed per set. Nothing but the final [B,24] metrics rows leaves the device.
 
     python tools/tune_sweep.py [--scenes 256] [--agents 8] [--ticks 200] [--plan-poses 120] [--reactive [--groups]] [--tracker] [--detector] [--plant]
-                                [--world-plans [--occlusion [RANGE]] [--shared-crowd M] [--sensed-costmap [--obstacle-memory] [--collision-monitor] [--scan-detector]]]
+                                [--world-plans [--occlusion [RANGE]] [--shared-crowd M] [--sensed-costmap [--obstacle-memory] [--collision-monitor] [--scan-detector]] [--plan-repair]]
 
 --reactive: the persons are a reactive crowd (BatchEpisode(crowd=CrowdParams()), waypoints from scenes.crowd_waypoints)
 instead of walking straight on with constant velocity. --groups (with --reactive): half of the walking persons go in pairs
@@ -52,6 +52,9 @@ a deployed controller runs under; a last column is the share of ticks in which t
 are what its own scan shows (BatchEpisode(scan_detector=ScanDetectorParams())): the tick's beam hits clustered into person-sized
 segments, so a person half hidden behind another, two persons who merge into one wide blob and the grid's quantisation come
 from geometry and not from a noise model. A detection has no velocity: combine with --tracker.
+--plan-repair (with --world-plans): every tick a robot whose plan runs into impassable cells of its own window gets the least-cost
+detour inside the window spliced into its plan (BatchEpisode(repair=PlanRepairParams())); with --sensed-costmap those cells are
+what the scan marked, persons included. Last columns: the share of robot-ticks that ended with each smpc_repair_status.
 """
 import argparse
 import os
@@ -99,6 +102,8 @@ def main():
                     help="the command passes scan-based stop, slowdown and approach zones (needs --world-plans --sensed-costmap)")
     ap.add_argument("--scan-detector", action="store_true",
                     help="the detections are segments of the tick's scan (needs --world-plans --sensed-costmap; excludes --occlusion, --detector)")
+    ap.add_argument("--plan-repair", action="store_true",
+                    help="plans give way to impassable cells of the robot's window: detours spliced in every tick (needs --world-plans)")
     ap.add_argument("--plant", action="store_true",
                     help="the command is executed under acceleration limits and stopped by contact with walls and persons")
     a = ap.parse_args()
@@ -108,6 +113,8 @@ def main():
         ap.error("--scan-detector needs --world-plans --sensed-costmap")
     if a.scan_detector and (a.occlusion is not None or a.detector):
         ap.error("--scan-detector excludes --occlusion and --detector: the scan-based and the ground-truth path are alternatives")
+    if a.plan_repair and not a.world_plans:
+        ap.error("--plan-repair needs --world-plans")
     if a.obstacle_memory and not a.sensed_costmap:
         ap.error("--obstacle-memory needs --sensed-costmap")
     if a.sensed_costmap and not a.world_plans:
@@ -125,7 +132,7 @@ def main():
 
     from nav2_social_mpc_controller_amd.episode import BatchEpisode, arc_plans
     from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, ObstacleMemoryParams, OptimizerParams,
-                                                       DetectorParams, MonitorParams, PlantParams, PoolCrowdParams, ScanDetectorParams, SensorParams, SharedWorldParams, TrackerParams, TrajectorizerParams, VisibilityParams,
+                                                       DetectorParams, MonitorParams, PlanRepairParams, PlantParams, PoolCrowdParams, ScanDetectorParams, SensorParams, SharedWorldParams, TrackerParams, TrajectorizerParams, VisibilityParams,
                                                        scene_param_rows)
     from nav2_social_mpc_controller_amd.scenes import (crowd_groups, crowd_waypoints, make_scenes, make_world, pool_waypoints, scenes_in_world,
                                                        shared_pool, uniform, world_goals)
@@ -174,6 +181,8 @@ def main():
         plans["detector"] = DetectorParams(clutter_candidates=min(2, 64 - a.agents))
     if a.scan_detector:
         plans["scan_detector"] = ScanDetectorParams()
+    if a.plan_repair:
+        plans["repair"] = PlanRepairParams()
     if a.plant:
         plans["plant"] = PlantParams()
     if a.collision_monitor:
@@ -182,13 +191,20 @@ def main():
                       metrics=MetricsParams(), **plans, **crowd)
     ep.capture_graph()
     changed = ep.torch.zeros(S * n, dtype=ep.torch.int64, device=ep.dev)   # ticks in which the monitor changed the robot's command
+    n_status = 8                                                            # enum smpc_repair_status
+    repair = ep.torch.zeros(S * n, n_status, dtype=ep.torch.int64, device=ep.dev)   # robot-ticks that ended with each status
     for _ in range(a.ticks):
         ep.replay()
+        if a.plan_repair:
+            with ep.torch.cuda.stream(ep.gstream):
+                repair.scatter_add_(1, ep.repair_status.long()[:, None], ep.torch.ones_like(repair[:, :1]))
         if a.collision_monitor:
             with ep.torch.cuda.stream(ep.gstream):   # behind the tick, on its stream: nothing leaves the device
                 changed += ep.monitor_ratio < 1.0
     m = summarize_metrics(ep.metrics(), prm.dt)
     changed = changed.cpu().numpy()
+    repair = repair.cpu().numpy()
+    from nav2_social_mpc_controller_amd._abi_plan_repair import REPAIR_STATUS
     print(f"{S} parameter sets x {n} scenes, {a.agents} agents, {a.ticks} ticks of {prm.dt} s")
     stopped = (ep.plant_contact[:, 0].cpu().numpy() & 3) != 0 if a.plant else np.zeros(S * n, bool)
     for k, name in enumerate(sets):
@@ -200,7 +216,8 @@ def main():
               f"social_work/m {mean('social_work_per_metre'):8.3f}  person_coll {m['person_collision'][sl].mean():.3f}  "
               f"obstacle_coll {m['obstacle_collision'][sl].mean():.3f}  fallback {mean('fallback_share'):.3f}"
               + (f"  stopped_by_contact {stopped[sl].mean():.3f}" if a.plant else "")
-              + (f"  monitor_share {changed[sl].mean() / max(a.ticks, 1):.3f}" if a.collision_monitor else ""))
+              + (f"  monitor_share {changed[sl].mean() / max(a.ticks, 1):.3f}" if a.collision_monitor else "")
+              + ("".join(f"  {REPAIR_STATUS[i].lower()} {repair[sl, i].sum() / max(a.ticks * n, 1):.3f}" for i in range(n_status)) if a.plan_repair else ""))
 
 
 if __name__ == "__main__":
