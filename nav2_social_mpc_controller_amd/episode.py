@@ -98,6 +98,7 @@ class TickRecord:
     persons_after: np.ndarray = None  # [B,Np,5]
     cmd_vel: np.ndarray = None        # [B,2] the executed command
     cmd_source: np.ndarray = None     # [B]
+    metrics_acc: np.ndarray = None    # [B,24] the metrics rows with the tick's sample folded in (solver.METRIC_COLS)
     # the persons' waypoint cursors around the tick's crowd step (BatchEpisode(crowd=...))
     cursor_before: np.ndarray = None  # [B,Np]
     cursor_after: np.ndarray = None   # [B,Np]
@@ -1233,6 +1234,8 @@ class BatchEpisode:
                     rec.update(self._host(agents_after="agents"))
             self._metrics_sample()
             timed("metrics")
+            if record:
+                rec.update(self._host("metrics_acc"))
         if record:
             rec.update(self._host("cmd_vel", "cmd_source", pose_after="pose", persons_after="persons"))
             if crowd:
