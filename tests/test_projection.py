@@ -12,11 +12,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "nav2_social_mpc_controller_amd", "host")
 
 
-def make_case(seed, N=3, n_valid=2, T=28, grid=120):
+def make_case(seed, N=3, n_valid=2, T=28, grid=120, valid_rows=None):
+    """valid_rows: the rows of init_people that hold the valid agents (default: the first n_valid)"""
     rng = np.random.default_rng(seed)
     init = np.zeros((N, 6))
     init[:, 3] = -1.0
-    for a in range(n_valid):
+    for a in (range(n_valid) if valid_rows is None else valid_rows):
         r, phi, hd = rng.uniform(0.8, 3.0), rng.uniform(-np.pi, np.pi), rng.uniform(-np.pi, np.pi)
         lv = 0.0 if rng.uniform() < 0.2 else rng.uniform(0.2, 1.2)
         init[a] = [r * np.cos(phi), r * np.sin(phi), hd, 0.0, lv, 0.0]
@@ -106,6 +107,99 @@ def test_hip_projection_matches_restatements(hostlib):
             if N == 3 and np.max(np.abs(literal - want)) == 0.0:      # no libm-noise decision in this case
                 rc, hostres, _ = host_project(hostlib, c)
                 assert rc == 0 and np.max(np.abs(got[b].transpose(0, 2, 1) - hostres)) < 1e-9
+
+
+@pytest.fixture(scope="module")
+def projector():
+    from nav2_social_mpc_controller_amd.params import OptimizerParams
+    from nav2_social_mpc_controller_amd.solver import BatchSolver
+    s = BatchSolver(OptimizerParams.readme())
+    yield s
+    s.close()
+
+
+_want = {}
+
+
+def want_of(key, c):
+    """the checker's projection of a case (theta := 0 for exactly equal velocities), computed once per key"""
+    if key not in _want:
+        _want[key] = pyref_project(c, convention=True)            # [T+1][N][6]
+    return _want[key]
+
+
+def project_cases(s, cases):
+    got, err = s.project_people(np.stack([c["init"] for c in cases]), np.stack([c["path"] for c in cases]),
+                                np.stack([c["idx"] for c in cases]), np.stack([c["origin"] for c in cases]), cases[0]["res"],
+                                cases[0]["max_time"], cases[0]["dt"])
+    assert np.all(err == 0)
+    return got                                                    # [B][T+1][6][N]
+
+
+def check_cases(got, cases, keys, what):
+    worst = 0.0
+    for b, (c, key) in enumerate(zip(cases, keys)):
+        d = float(np.max(np.abs(got[b].transpose(0, 2, 1) - want_of(key, c))))
+        assert d < 1e-9, (what, key, d)
+        worst = max(worst, d)
+    print(f"{what}: {len(cases)} scenes, max difference {worst:.3e}")
+
+
+# The pair rounds of the kernel: lane g takes partner (g + k) mod n_act, n_act = n_valid + 1; with H copies of a scene in
+# the wavefront (H = 2 while N + 1 <= 32 lanes) copy hh takes the rounds 1 + hh, 1 + hh + H, ..., two of them per trip; for
+# even n_act the last round k = n_act / 2 is the mutual one. Which copy and which slot of a trip it lands in, and whether a
+# trip's second slot is filled, goes with n_act mod 4 (H = 2) or mod 2 (H = 1): every n_valid covers every class.
+@pytest.mark.gpu
+@pytest.mark.parametrize("N", [1, 2, 3, 7, 8, 15, 16, 31, 40, 63])
+def test_hip_projection_every_pairing_class(projector, N):
+    valid = range(N + 1) if N <= 16 else range(N - 3, N + 1)
+    cases = [make_case(3000 + 100 * N + n, N=N, n_valid=n, T=4) for n in valid]
+    if 3 <= N <= 16:
+        assert {(n + 1) % 4 for n in valid} == {0, 1, 2, 3}
+    check_cases(project_cases(projector, cases), cases, [("sweep", N, n) for n in valid], f"N = {N}, n_valid = {list(valid)}")
+
+
+PHANTOMS = {3: [[1, 2], [0, 2], [1]], 8: [[1, 2, 3, 4, 5, 6, 7], [0, 3, 4, 7], [1, 3, 5, 7], [0, 2, 4, 6], [7]],
+            16: [list(range(1, 16)), [0, 1, 14, 15], list(range(0, 16, 2)), list(range(1, 16, 2)), [5, 11, 15]]}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N", sorted(PHANTOMS))
+def test_hip_projection_phantoms_between_valid_agents(projector, N):
+    """invalid rows (t = -1) first, in the middle and alternating: step 0 is init_people as given, from step 1 on the valid
+    agents stand compacted at the front and phantoms behind them, as in the checker"""
+    cases = [make_case(4000 + 100 * N + k, N=N, T=4, valid_rows=rows) for k, rows in enumerate(PHANTOMS[N])]
+    got = project_cases(projector, cases)
+    check_cases(got, cases, [("phantoms", N, k) for k in range(len(cases))], f"N = {N}, phantoms in the middle")
+    for b, (c, rows) in enumerate(zip(cases, PHANTOMS[N])):
+        assert np.array_equal(got[b, 0].T, c["init"])
+        assert np.all(got[b, 1:, 3, :len(rows)] >= 0.0) and np.all(got[b, 1:, 3, len(rows):] == -1.0)
+        assert c["init"][rows[0], 3] == 0.0 and (c["init"][:, 3] == -1.0).sum() == N - len(rows) > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,N", [(19, 3), (35, 1), (5, 8)])
+def test_hip_projection_several_blocks_of_shared_waves(projector, B, N):
+    """8, 16 and 2 scenes per wave in 3 blocks, the last one partly filled; every scene is another one and is checked
+    against its own checker result; a scene's rows do not depend on the batch"""
+    cases = [make_case(5000 + 100 * N + b, N=N, n_valid=N - (b % 2 if N > 1 else 0), T=4) for b in range(B)]
+    per_wave = {3: 8, 1: 16, 8: 2}[N]
+    assert -(-B // per_wave) == 3 and B % per_wave != 0
+    got = project_cases(projector, cases)
+    check_cases(got, cases, [("blocks", N, b) for b in range(B)], f"B = {B}, N = {N}")
+    for b in (0, per_wave + 1, B - 1):                            # block 0, a later lane group of block 1, the last scene
+        alone = project_cases(projector, cases[b:b + 1])
+        assert alone[0].tobytes() == got[b].tobytes(), b
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("T", [1, 2])
+def test_hip_projection_shortest_horizons(projector, T):
+    """T = 1: the robot's prefetched row min(i + 1, T - 1) is row 0 again"""
+    cases = [make_case(6000 + 10 * T + k, N=3, n_valid=n, T=T) for k, n in enumerate((3, 2, 1, 0))]
+    got = project_cases(projector, cases)
+    assert got.shape == (4, T + 1, 6, 3)
+    check_cases(got, cases, [("horizon", T, k) for k in range(4)], f"T = {T}")
 
 
 @pytest.mark.gpu
