@@ -428,9 +428,9 @@ def test_the_episode_declares_the_argument_and_refuses_what_the_library_would():
     assert inspect.signature(BatchEpisode.__init__).parameters["monitor"].default is None
     fields = TickRecord.__dataclass_fields__
     assert all(fields[name].default is None for name in ("cmd_safe", "monitor_action", "monitor_points", "monitor_ratio", "monitor_heading_cs", "monitor_step_cs"))
-    src = inspect.getsource(BatchEpisode)
-    assert src.index("s.select_command_device(") < src.index("s.collision_monitor_device(") < src.index("self._crowd_step()") \
-        < src.index("s.robot_plant_device(") and 'timed("monitor")' in src
+    from nav2_social_mpc_controller_amd.episode_stages import Core, Crowd, Monitor, Plant
+    at = BatchEpisode.STAGES.index                                                              # the launch order: Core ends with the command selection
+    assert at(Core) < at(Monitor) < at(Crowd) < at(Plant) and Monitor.TIMING == "monitor"
     mp = MonitorParams.nav2_like()
     assert shard_kwargs({"monitor": mp}, np.arange(2), 4)["monitor"] is mp and "shard_kwargs" in inspect.getsource(ShardedEpisode.__init__)
     BatchEpisode.check_monitor(mp, SensorParams())

@@ -225,8 +225,11 @@ def test_the_episode_declares_the_arguments_and_refuses_them_without_a_shared_po
     for name in ("pool_crowd", "pool_waypoints", "pool_n_waypoints", "pool_speed"):
         assert name in BatchEpisode.FORWARDED and name not in BatchEpisode.PER_ROBOT and sig[name].default is None
     assert {"pool_next", "pool_cursor_before", "pool_cursor_after"} <= set(TickRecord.__dataclass_fields__)
-    src = inspect.getsource(BatchEpisode.__init__)
-    assert "pool_crowd needs shared" in src and "need pool_crowd" in src
+    from nav2_social_mpc_controller_amd.episode_stages import PoolCrowd
+    with pytest.raises(ValueError, match="pool_crowd needs shared"):
+        PoolCrowd.check(PoolCrowdParams(), None, None, None, None, None)
+    with pytest.raises(ValueError, match="need pool_crowd"):
+        PoolCrowd.check(None, None, None, np.zeros((1, 2, 2)), None, None)
     with pytest.raises(ValueError, match="independent"):
         ShardedEpisode(None, None, None, None, None, None, shared=SharedWorldParams(), pool_crowd=PoolCrowdParams())
 

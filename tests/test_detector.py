@@ -343,10 +343,11 @@ def test_the_episode_declares_the_argument():
     fields = TickRecord.__dataclass_fields__
     names = ("draw_state_before", "draw_state_after", "detected_persons", "detected_count", "detected_source", "person_outcome")
     assert all(fields[name].default is None for name in names)
-    src = inspect.getsource(BatchEpisode)
-    assert src.index("s.visible_people_device(") < src.index("s.detect_people_device(") < src.index("s.track_people_device(")
-    assert src.index("s.track_people_device(") < src.index("s.people_to_status_device(") and 'timed("detector")' in src
-    assert '"draw_state"' in inspect.getsource(BatchEpisode.capture_graph)                    # saved and restored around the warm-up tick
+    from nav2_social_mpc_controller_amd.episode_stages import Core, Detector, Tracker, Visibility
+    at = BatchEpisode.STAGES.index                                                            # the launch order: Core begins with people_to_status
+    assert at(Visibility) < at(Detector) < at(Tracker)
+    assert at(Tracker) < at(Core) and Detector.TIMING == "detector"
+    assert Detector.STATE == ("draw_state",)                                                  # saved and restored around the warm-up tick
     # a shard's robots draw by their ids in the whole batch: ShardedEpisode hands every shard its robots' stream ids
     assert callable(BatchEpisode.set_detector_streams) and "set_detector_streams(" in inspect.getsource(ShardedEpisode.__init__)
 

@@ -408,3 +408,46 @@ def test_two_shards_get_their_rows_of_every_optional_argument():
     od = (grid["indexes"], sc.costmap_origin, float(np.float32(sc.resolution)))
     host = _assert_two_shards_equal_the_single_chain(prm, sc, w_ref, od, dict(kw, od_distances=grid["distances"]))
     assert host.od_shared == 0 and host.od_distances is not None
+
+
+# ---- the optional stages' declarations --------------------------------------------------------------------------------
+def test_every_stage_declares_its_keyword_and_its_record_fields():
+    """Every optional stage (episode_stages) is one class with its keyword, its timing key and the TickRecord fields copied
+    before and after its launch. A stage whose keyword or record field was forgotten, or claimed twice, fails here: every
+    BEFORE / AFTER key is an optional TickRecord field, no field has two owners (the obstacle memory launches in the sensed
+    costmap's place and records the scan's outputs too), every optional field is a stage's or on the core's list, every
+    keyword is one of BatchEpisode.__init__ with default None, and no two stages share a timing key."""
+    import dataclasses
+    import inspect
+
+    from nav2_social_mpc_controller_amd.episode import BatchEpisode, TickRecord
+    from nav2_social_mpc_controller_amd.episode_stages import Core, ObstacleMemory, Planner, Sensed, Stage
+
+    assert BatchEpisode.STAGES.count(Core) == 1 and len(set(BatchEpisode.STAGES)) == len(BatchEpisode.STAGES)
+    stages = (Planner,) + tuple(S for S in BatchEpisode.STAGES if S is not Core)
+    assert len(stages) == 15 and all(issubclass(S, Stage) for S in stages)
+    optional = {f.name for f in dataclasses.fields(TickRecord) if f.default is None}
+    required = {f.name for f in dataclasses.fields(TickRecord) if f.default is dataclasses.MISSING}
+    assert len(optional) + len(required) == len(TickRecord.__dataclass_fields__)
+    sig = inspect.signature(BatchEpisode.__init__).parameters
+    owner = {}
+    for S in stages:
+        assert S.KEY in sig and sig[S.KEY].default is None, S
+        assert isinstance(S.STATE, tuple) and all(isinstance(a, str) for a in S.STATE), S
+        assert not set(S.BEFORE) & set(S.AFTER), S
+        for field in list(S.BEFORE) + list(S.AFTER):
+            assert field in optional, (S, field)
+            if not (S is ObstacleMemory and field in Sensed.AFTER):
+                assert field not in owner, (field, S, owner.get(field))
+                owner[field] = S
+    assert set(Sensed.AFTER) < set(ObstacleMemory.AFTER)
+    # the optional fields that tick() itself fills: the core chain's, the world before and after the move, the second gather in front
+    # of the metrics sample, and the windows a repair without a sensing stage reads
+    core = ("robot_pose", "traj_n_poses", "window", "window_len", "plan_start", "persons", "person_count", "has_people", "T_scene", "window_err",
+            "pose_after", "persons_after", "cmd_vel", "cmd_source", "agents_after", "repair_costmap")
+    assert len(set(core)) == len(core) and set(core) <= optional and not set(core) & set(owner)
+    assert set(core) | set(owner) == optional, sorted(optional - set(core) - set(owner))
+    timing = [S.TIMING for S in stages if S is not Planner]                     # the planner never launches inside a tick
+    assert all(isinstance(t, str) and t for t in timing) and len(set(timing)) == len(timing) and Planner.TIMING is None
+    for name in BatchEpisode.UINT32:                                            # the uint32 views are state, named in one place
+        assert any(name in S.STATE for S in stages), name

@@ -163,6 +163,23 @@ def assert_same_state(got, want, what):
         assert CC.same_bits(got[k], v), (what, k)
 
 
+def assert_launch_order(ep, keys):
+    """The keys of a tick's timing dict (insertion order: the real launch order) are BatchEpisode.STAGES restricted to the stages
+    the episode launches (the obstacle memory launches in the sensed costmap's place), with the core chain at Core's position."""
+    from nav2_social_mpc_controller_amd.episode import BatchEpisode
+    from nav2_social_mpc_controller_amd.episode_stages import Core, ObstacleMemory, Sensed
+    order = [S for S in BatchEpisode.STAGES if S is Core or (S in ep.stages and not (S is Sensed and ObstacleMemory in ep.stages))]
+    assert len(order) == 11                                                 # either stack launches ten optional stages
+    stage_keys = {S.TIMING + "_ms" for S in BatchEpisode.STAGES if S is not Core}
+    core = ["people_ms", "format_ms", "project_ms", "solve_ms", "store_ms"]
+    want = sum((core if S is Core else [S.TIMING + "_ms"] for S in order), [])
+    assert [k for k in keys if k in stage_keys or k in core] == want, keys
+    assert [k for k in keys if k not in want] == ["window_ms", "trajectorize_ms"] + (["nearest_after_ms"] if ep.shared is not None else []), keys
+    assert keys.index("local_costmap_ms") < keys.index("window_ms") < keys.index("trajectorize_ms") < keys.index(want[1])
+    if ep.shared is not None:
+        assert keys.index("nearest_after_ms") == keys.index("metrics_ms") - 1
+
+
 @pytest.fixture(scope="module", params=STACKS)
 def eager(request):
     ep, (world, kw, prm, presets, which) = build(request.param)
@@ -211,8 +228,13 @@ def test_every_stage_reads_what_the_stage_before_wrote(eager):
 
 @pytest.mark.gpu
 def test_graph_replay_equals_the_eager_ticks(eager):
+    from nav2_social_mpc_controller_amd.episode import BatchEpisode
     g, _ = build(eager["stack"])
+    declared = BatchEpisode.CORE_STATE + ("plan_start",) + sum((S.STATE for S in g.stages), ())   # the core's state and the present stages'
+    assert sorted(declared) == sorted(g.saved_state()) and set(declared) <= set(carried(g)) <= set(declared) | {"person_count"}
+    before = state(g, declared)
     g.capture_graph()
+    assert_same_state(state(g, declared), before, "after capture_graph: every declared state buffer holds the bytes it held before")
     assert_same_state(state(g, carried(g)), eager["start"], "after capture_graph: the warm-up tick is taken back")
     for _ in range(TICKS):
         g.replay()
@@ -242,6 +264,7 @@ def test_recording_and_timing_do_not_change_the_episode(eager):
         timing = {}
         watched.tick(record=True, timing=timing)
         assert all(v >= 0.0 for v in timing.values()) and {"solve_ms", "plant_ms", "monitor_ms", "repair_ms", "tracker_ms"} <= set(timing)
+        assert_launch_order(watched, list(timing))
     assert_same_state(state(watched), state(bare), "recorded and timed against bare")
     assert_same_state(state(bare), eager["states"][3], "bare against the recorded fixture")
 

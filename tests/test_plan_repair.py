@@ -521,8 +521,8 @@ def test_the_episode_declares_the_argument_and_refuses_what_it_must():
     fields = TickRecord.__dataclass_fields__
     assert all(fields[name].default is None for name in ("repair_plan_before", "repair_plan_len_before", "repair_plan_after", "repair_plan_len_after",
                                                          "repair_status", "repair_info"))
-    src = inspect.getsource(BatchEpisode)
-    assert 'timed("repair")' in src and src.count("s.repair_plan_device(") == 1
+    from nav2_social_mpc_controller_amd.episode_stages import Repair
+    assert Repair.TIMING == "repair" and BatchEpisode.STAGES.count(Repair) == 1
     rp = PlanRepairParams()
     assert shard_kwargs({"repair": rp}, np.arange(2), 4)["repair"] is rp and "shard_kwargs" in inspect.getsource(ShardedEpisode.__init__)
     BatchEpisode.check_repair(rp, True, 0.05)

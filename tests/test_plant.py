@@ -342,10 +342,10 @@ def test_the_episode_declares_the_argument_and_refuses_what_the_library_would():
     names = ("plant_agents", "plant_agent_count", "plant_queue_before", "plant_tick_before", "plant_queue_after", "plant_tick_after",
              "plant_contact", "heading_cs", "speed_after")
     assert all(fields[name].default is None for name in names)
-    src = inspect.getsource(BatchEpisode)
-    assert src.index("s.select_command_device(") < src.index("self._crowd_step()") < src.index("s.crowd_pool_step_device(") \
-        < src.index("s.robot_plant_device(") < src.index("self._metrics_sample()") and 'timed("plant")' in src
-    assert '"plant_queue", "plant_tick"' in inspect.getsource(BatchEpisode.capture_graph)       # saved and restored around the warm-up tick
+    from nav2_social_mpc_controller_amd.episode_stages import Core, Crowd, Metrics, Plant, PoolCrowd
+    at = BatchEpisode.STAGES.index                                                              # the launch order: Core ends with the command selection
+    assert at(Core) < at(Crowd) < at(PoolCrowd) < at(Plant) < at(Metrics) and Plant.TIMING == "plant"
+    assert Plant.STATE == ("plant_queue", "plant_tick")                                         # saved and restored around the warm-up tick
     pp = PlantParams()
     assert shard_kwargs({"plant": pp}, np.arange(2), 4)["plant"] is pp and "shard_kwargs" in inspect.getsource(ShardedEpisode.__init__)
     BatchEpisode.check_plant(pp)

@@ -365,8 +365,8 @@ def test_the_episode_declares_the_argument_and_refuses_what_it_must():
     assert inspect.signature(BatchEpisode.__init__).parameters["scan_detector"].default is None
     fields = TickRecord.__dataclass_fields__
     assert all(fields[name].default is None for name in ("scan_persons", "scan_count", "scan_segment", "scan_stats"))
-    src = inspect.getsource(BatchEpisode)
-    assert 'timed("scan_people")' in src and src.index("s.scan_people_device(") < src.index("s.track_people_device(")
+    from nav2_social_mpc_controller_amd.episode_stages import ScanPeople, Tracker
+    assert ScanPeople.TIMING == "scan_people" and BatchEpisode.STAGES.index(ScanPeople) < BatchEpisode.STAGES.index(Tracker)
     sp = ScanDetectorParams()
     assert shard_kwargs({"scan_detector": sp}, np.arange(2), 4)["scan_detector"] is sp and "shard_kwargs" in inspect.getsource(ShardedEpisode.__init__)
     BatchEpisode.check_scan_detector(sp, SensorParams(), None, None, 0.05)

@@ -308,9 +308,10 @@ def test_the_episode_declares_the_argument():
     names = ("tracks_before", "track_meta_before", "track_next_id_before", "tracks_after", "track_meta_after", "track_next_id_after",
              "tracked_persons", "tracked_count", "tracked_source")
     assert all(fields[name].default is None for name in names)
-    src = inspect.getsource(BatchEpisode)
-    assert src.index("s.track_people_device(") < src.index("s.people_to_status_device(") and 'timed("tracker")' in src
-    assert src.index("s.visible_people_device(") < src.index("s.track_people_device(")
+    from nav2_social_mpc_controller_amd.episode_stages import Core, Tracker, Visibility
+    at = BatchEpisode.STAGES.index                                                            # the launch order: Core begins with people_to_status
+    assert at(Tracker) < at(Core) and Tracker.TIMING == "tracker"
+    assert at(Visibility) < at(Tracker)
 
 
 # ---- the kernel's resources ------------------------------------------------------------------------------------------------

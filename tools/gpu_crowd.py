@@ -37,6 +37,7 @@ def main():
 
     from nav2_social_mpc_controller_amd._abi import SmpcPeopleBatch
     from nav2_social_mpc_controller_amd.episode import BatchEpisode
+    from nav2_social_mpc_controller_amd.episode_stages import Crowd, Metrics
     from nav2_social_mpc_controller_amd.params import CrowdParams, MetricsParams, OptimizerParams
     from nav2_social_mpc_controller_amd.scenes import crowd_groups, crowd_waypoints, make_scenes, uniform
 
@@ -63,14 +64,14 @@ def main():
     ms = {"crowd_step": [], "crowd_step_groups": [], "people_to_status": [], "episode_metrics": []}
     for r in range(a.reps + 2):
         ep.persons.copy_(persons0), ep.person_cursor.copy_(cursor0)
-        ep._crowd_step(groups=False)
+        Crowd.launch(ep, groups=False)
         t_c = s.last_kernel_ms()
         ep.persons.copy_(persons0), ep.person_cursor.copy_(cursor0)
-        ep._crowd_step()
+        Crowd.launch(ep)
         t_g = s.last_kernel_ms()
         s.people_to_status_device(qb, ep.people.data_ptr(), ep.has_people.data_ptr())
         t_p = s.last_kernel_ms()
-        ep._metrics_sample()
+        Metrics.launch(ep)
         t_m = s.last_kernel_ms()
         if r >= 2:   # the first launches load the code object
             ms["crowd_step"].append(t_c)

@@ -36,6 +36,7 @@ def main():
 
     from nav2_social_mpc_controller_amd._abi import SmpcPeopleBatch
     from nav2_social_mpc_controller_amd.episode import BatchEpisode
+    from nav2_social_mpc_controller_amd.episode_stages import Crowd
     from nav2_social_mpc_controller_amd.params import CrowdParams, OptimizerParams, VisibilityParams
     from nav2_social_mpc_controller_amd.scenes import crowd_waypoints, make_world, scenes_in_world, uniform
 
@@ -66,7 +67,7 @@ def main():
         t_v = s.last_kernel_ms()
         s.people_to_status_device(qb, ep.people.data_ptr(), ep.has_people.data_ptr())
         t_p = s.last_kernel_ms()
-        ep._crowd_step()
+        Crowd.launch(ep)
         t_c = s.last_kernel_ms()
         ep.persons.copy_(persons0), ep.person_cursor.copy_(cursor0)
         if r >= 2:   # the first launches load the code object
