@@ -58,6 +58,7 @@
 #include "smpc_scan_people.hpp"
 #include "../../include/smpc_scan_people.h"
 #include "smpc_plan_repair.hpp"
+#include "smpc_plan_smoother.hpp"
 
 extern "C" {
 
@@ -1211,6 +1212,54 @@ int smpc_repair_plan_batch(smpc_handle* h, const smpc_plan_repair_in* in, double
   SMPC_TRY(st.timed([&] {
     hipLaunchKernelGGL(smpc::smpc_repair_judge_kernel, dim3((unsigned)((B + per_block - 1) / per_block)), dim3(smpc::kPrJudgeThreads), 0, h->stream, p);
     hipLaunchKernelGGL(smpc::smpc_repair_field_kernel, dim3((unsigned)field_grid), dim3(field_threads), lds, h->stream, p);
+    return SMPC_OK;
+  }));
+  return st.finish();
+}
+
+int smpc_smooth_plan_batch(smpc_handle* h, const smpc_plan_smoother_in* in, double* plan, int32_t* status, int32_t* info, double* change) {
+  if (!h || !in || !plan || !status) { set_error("null handle / input / plan / status"); return SMPC_ERR_INVALID_ARG; }
+  if (!in->world || !in->world_origin || !in->plan_len) { set_error("null input array"); return SMPC_ERR_INVALID_ARG; }
+  if (in->B < 0 || in->L < 2 || in->world_x < 1 || in->world_y < 1) { set_error("bad B, L < 2, or a world side < 1"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) { set_error("resolution must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->w_data) || !(in->w_data > 0.0)) { set_error("w_data must be finite and > 0"); return SMPC_ERR_INVALID_ARG; }
+  if (!std::isfinite(in->w_smooth) || !(in->w_smooth >= 0.0)) { set_error("w_smooth must be finite and >= 0"); return SMPC_ERR_INVALID_ARG; }
+  {
+    const volatile double four = 4.0 * in->w_smooth;  // the product, rounded, then the sum
+    const volatile double sum = in->w_data + four;
+    if (!(sum < 2.0)) { set_error("w_data + 4 * w_smooth must be < 2: the sweep would not contract"); return SMPC_ERR_INVALID_ARG; }
+  }
+  if (!(in->tolerance >= 0.0)) { set_error("tolerance must be >= 0"); return SMPC_ERR_INVALID_ARG; }
+  if (in->max_its < 1 || in->refinement_num < 0) { set_error("max_its < 1 or refinement_num < 0"); return SMPC_ERR_INVALID_ARG; }
+  // the kernel's bounds: a lane holds 16 slots, the sweep counters are 32 bits, a cell index is an int32
+  if (in->L > SMPC_SMOOTH_MAX_POSES || in->max_its > SMPC_SMOOTH_MAX_ITS || in->refinement_num > SMPC_SMOOTH_MAX_REFINEMENTS) {
+    set_error("L > 1024, max_its > 100000 or refinement_num > 8 is not supported"); return SMPC_ERR_UNSUPPORTED;
+  }
+  if ((int64_t)in->world_x * in->world_y >= ((int64_t)1 << 31)) { set_error("world_x * world_y must stay below 2^31"); return SMPC_ERR_UNSUPPORTED; }
+  if (in->B == 0) return SMPC_OK;
+  SMPC_HIP_CHECK(hipSetDevice(h->device));
+  smpc::PlanSmootherParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.B = in->B; p.L = in->L; p.world_x = in->world_x; p.world_y = in->world_y; p.world_shared = in->world_shared ? 1 : 0;
+  p.max_its = in->max_its; p.refinement_num = in->refinement_num;
+  p.lethal_min = in->lethal_min_cost < 0 ? 0u : (uint32_t)in->lethal_min_cost; p.allow_unknown = in->allow_unknown ? 1u : 0u;
+  p.res = in->resolution; p.w_data = in->w_data; p.w_smooth = in->w_smooth; p.tolerance = in->tolerance;
+  const size_t B = in->B, L = in->L, nmap = in->world_shared ? 1 : B;
+  Staging st(h, in->on_device);
+  SMPC_TRY(st.in(p.world, in->world, nmap * (size_t)in->world_x * in->world_y));
+  SMPC_TRY(st.in(p.origin, in->world_origin, nmap * 2));
+  SMPC_TRY(st.in(p.plan_len, in->plan_len, B));
+  SMPC_TRY(st.in(p.range, in->range, B * 2));
+  // read and written: the rows the rule leaves alone keep the caller's bytes on the way through device memory too
+  SMPC_TRY(st.inout(p.plan, plan, B * L * 2));
+  SMPC_TRY(st.out(p.status, status, B));
+  SMPC_TRY(st.out(p.info, info, B * 4));
+  SMPC_TRY(st.out(p.change, change, B));
+  const size_t per_block = smpc::kSmThreads / 64;
+  const dim3 grid((unsigned)((B + per_block - 1) / per_block)), block(smpc::kSmThreads);
+  SMPC_TRY(st.timed([&] {
+    if (in->L <= 64 * smpc::kSmSlotsShort) hipLaunchKernelGGL(smpc::smpc_smooth_plan_kernel<smpc::kSmSlotsShort>, grid, block, 0, h->stream, p);
+    else hipLaunchKernelGGL(smpc::smpc_smooth_plan_kernel<smpc::kSmSlotsLong>, grid, block, 0, h->stream, p);
     return SMPC_OK;
   }));
   return st.finish();

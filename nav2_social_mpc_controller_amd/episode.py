@@ -6,6 +6,8 @@ optional stages are BatchEpisode.STAGES, one class each in episode_stages, [Core
     ObstacleDistance grid (optional)         (src/optimizer.cpp:593-605, 'TODO')   -> smpc_obstacle_distance_batch
     global plans (optional; Planner; again     (Nav2's planner server; the library's -> smpc_goal_field_batch,
     on replan(), never inside a tick)          own integer cost rule)                 smpc_extract_plan_batch
+      ... smoothed (planner.smoother), behind   (Nav2's smoother server; the library's
+      every walk                                own Jacobi rule)                    -> smpc_smooth_plan_batch
     every tick:
     rolling local costmap (Rolling)          (Nav2's LayeredCostmap::updateMap)    -> smpc_local_costmap_batch
     plan window, trajectorizer (with plans)  (src/social_mpc_controller.cpp:171-189,

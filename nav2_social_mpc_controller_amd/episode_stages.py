@@ -25,7 +25,8 @@ from collections import namedtuple
 
 import numpy as np
 
-from .params import CrowdGroupParams, DetectorParams, MonitorParams, PlanRepairParams, PlantParams, ScanDetectorParams, TrackerParams
+from .params import (CrowdGroupParams, DetectorParams, MonitorParams, PlanRepairParams, PlanSmootherParams, PlantParams, ScanDetectorParams,
+                     TrackerParams)
 from .solver import BatchSolver, point, set_od_grid
 
 Told = namedtuple("Told", "rows count Np")  # what the controller is told about people: two device tensors, rows per robot
@@ -66,7 +67,13 @@ class Planner(Stage):
     plan is walked down its field from its start pose (smpc_extract_plan_batch) into ep.plan [B,planner.max_poses,2],
     ep.plan_len and ep.plan_error [B] (enum smpc_plan_error; a robot with an error other than TRUNCATED has plan_len 0 and
     gets no command). From there on this is the episode that was handed these arrays as `plan`. replan() walks again from the
-    current poses. Never inside a tick, so not in BatchEpisode.STAGES. None: nothing is allocated and nothing is launched."""
+    current poses. Never inside a tick, so not in BatchEpisode.STAGES. None: nothing is allocated and nothing is launched.
+    planner.smoother (PlanSmootherParams; include/smpc_plan_smoother.h): every walk goes into ep.plan_raw (which is therefore,
+    stale rows behind plan_len included, the plan buffer of the episode without a smoother), the whole buffer is copied to
+    ep.plan and one smpc_smooth_plan_batch relaxes ep.plan in place on the world map; ep.smooth_status [B] int32
+    (enum smpc_smooth_status), ep.smooth_info [B,4] int32 (sweeps, rounds, rejected, n) and ep.smooth_change [B] say how it
+    ended. Everything behind it reads the smoothed rows. None: nothing more is allocated or launched and the episode is the
+    one without bit for bit."""
     KEY = "planner"
 
     def check(planner, plan, plan_len, world, traj_params, goal):
@@ -74,6 +81,12 @@ class Planner(Stage):
             raise ValueError("planner computes the global plans: plan / plan_len cannot be given as well")
         if world is None or traj_params is None or goal is None:
             raise ValueError("planner needs world, traj_params and goal [B,2]")
+        smoother = getattr(planner, "smoother", None)
+        if smoother is not None:
+            if not isinstance(smoother, PlanSmootherParams):
+                raise ValueError("planner.smoother must be a PlanSmootherParams")
+            if not smoother.supported(planner.max_poses):
+                raise ValueError("planner.smoother: more than 1024 poses, more than 100000 sweeps a round or more than 8 refinements")
 
     def allocate(ep, kw):
         """The goal fields of the robots' distinct goals, computed once, and the buffers every (re)plan is walked into."""
@@ -91,15 +104,33 @@ class Planner(Stage):
         ep.solver.goal_field_device(gf, ep.goal_field.data_ptr(), ep.goal_status.data_ptr())
         ep.plan_error = ep._zeros(B, dtype=i32)
         ep.plan, ep.plan_len = ep._zeros(B, ep.planner.max_poses, 2), ep._zeros(B, dtype=i32)
+        if ep.planner.smoother is not None:  # the plans as walked, and how their smoothing ended
+            ep.plan_raw = ep.torch.zeros_like(ep.plan)
+            ep.smooth_status = ep._zeros(B, dtype=i32)
+            ep.smooth_info = ep._zeros(B, 4, dtype=i32)
+            ep.smooth_change = ep._zeros(B)
 
     def bind(ep):
         ep._c.extract = point(BatchSolver.extract_plan_c(ep.planner, ep.B, int(ep.plan_goals.shape[0]), ep.world.cells_x,
                                                          ep.world.cells_y, True, ep.resolution, 1),
                               {"world": ep.world_map, "world_origin": ep.world_origin, "field": ep.goal_field,
                                "goal": ep.plan_goals, "robot_goal": ep.robot_goal, "pose": ep.pose})
+        if ep.planner.smoother is not None:
+            gp = ep.planner
+            ep._c.smooth = point(BatchSolver.smooth_plan_c(gp.smoother, ep.B, int(gp.max_poses), ep.world.cells_x, ep.world.cells_y, True,
+                                                           ep.resolution, 1, gp.lethal_min_cost, gp.allow_unknown),
+                                 {"world": ep.world_map, "world_origin": ep.world_origin, "plan_len": ep.plan_len})
 
     def launch(ep):
-        ep.solver.extract_plan_device(ep._c.extract, ep.plan.data_ptr(), ep.plan_len.data_ptr(), ep.plan_error.data_ptr())
+        if ep.planner.smoother is None:
+            ep.solver.extract_plan_device(ep._c.extract, ep.plan.data_ptr(), ep.plan_len.data_ptr(), ep.plan_error.data_ptr())
+        else:
+            # The walk goes into plan_raw and the whole buffer is copied: a walk writes its first plan_len rows only, so the rows
+            # behind a shorter new plan keep what the walk before left there, as they do without a smoother, not smoothed rows.
+            ep.solver.extract_plan_device(ep._c.extract, ep.plan_raw.data_ptr(), ep.plan_len.data_ptr(), ep.plan_error.data_ptr())
+            ep.plan.copy_(ep.plan_raw)
+            ep.solver.smooth_plan_device(ep._c.smooth, ep.plan.data_ptr(), ep.smooth_status.data_ptr(), ep.smooth_info.data_ptr(),
+                                         ep.smooth_change.data_ptr())
 
 
 class Rolling(Stage):

@@ -107,18 +107,62 @@ class CrowdGroupParams:
 
 
 @dataclass
+class PlanSmootherParams:
+    """Plan smoothing (include/smpc_plan_smoother.h; GlobalPlanParams(smoother=...)): wherever the planner has walked the plans,
+    their inner rows are relaxed towards the mean of their neighbours (w_smooth) while a data term holds them to the rows the
+    round started from (w_data), in Jacobi sweeps that never move a row into an impassable cell. A round ends at the first
+    sweep that moves no row by more than `tolerance` metres, or after max_its sweeps; refinement_num further rounds start
+    from the rows the round before ended with. The defaults are those of Nav2's simple smoother, as recalled.
+    lethal_min_cost / allow_unknown: which cells are passable; None: the planner's values."""
+    w_data: float = 0.2
+    w_smooth: float = 0.3
+    tolerance: float = 1e-10
+    max_its: int = 1000
+    refinement_num: int = 2
+    lethal_min_cost: int = None
+    allow_unknown: bool = None
+
+    MAX_POSES, MAX_ITS, MAX_REFINEMENTS = 1024, 100000, 8   # include/smpc_plan_smoother.h's limits
+
+    def __post_init__(self):
+        if not (np.isfinite(self.w_data) and self.w_data > 0.0):
+            raise ValueError(f"PlanSmootherParams.w_data must be finite and > 0, got {self.w_data}")
+        if not (np.isfinite(self.w_smooth) and self.w_smooth >= 0.0):
+            raise ValueError(f"PlanSmootherParams.w_smooth must be finite and >= 0, got {self.w_smooth}")
+        if not np.float64(self.w_data) + np.float64(4.0) * np.float64(self.w_smooth) < 2.0:
+            raise ValueError("PlanSmootherParams: w_data + 4 * w_smooth must be < 2 (the sweep would not contract)")
+        if not self.tolerance >= 0.0:
+            raise ValueError(f"PlanSmootherParams.tolerance must be >= 0, got {self.tolerance}")
+        if int(self.max_its) != self.max_its or self.max_its < 1:
+            raise ValueError(f"PlanSmootherParams.max_its must be an integer >= 1, got {self.max_its}")
+        if int(self.refinement_num) != self.refinement_num or self.refinement_num < 0:
+            raise ValueError(f"PlanSmootherParams.refinement_num must be an integer >= 0, got {self.refinement_num}")
+        if self.lethal_min_cost is not None and not 0 <= self.lethal_min_cost <= 255:
+            raise ValueError(f"PlanSmootherParams.lethal_min_cost must be 0..255 or None, got {self.lethal_min_cost}")
+
+    def supported(self, max_poses: int) -> bool:
+        """Does the library smooth plans of max_poses rows with these parameters (include/smpc_plan_smoother.h's
+        SMPC_ERR_UNSUPPORTED, the world's size apart)?"""
+        return int(max_poses) <= self.MAX_POSES and self.max_its <= self.MAX_ITS and self.refinement_num <= self.MAX_REFINEMENTS
+
+
+@dataclass
 class GlobalPlanParams:
     """Global plans on a world map (include/smpc_global_plan.h): what entering a cell costs, w = neutral_cost + cost_weight *
     cost (integers: a goal field is exact), which cells are passable (cost < lethal_min_cost, and 255 with allow_unknown),
-    the rows of a plan (max_poses) and how many path cells lie between two poses (stride)."""
+    the rows of a plan (max_poses) and how many path cells lie between two poses (stride). smoother: the plans are smoothed
+    wherever they are walked (PlanSmootherParams; None: they are handed on as walked)."""
     neutral_cost: int = 50
     cost_weight: int = 1
     lethal_min_cost: int = 253
     allow_unknown: bool = False
     max_poses: int = 400
     stride: int = 1
+    smoother: PlanSmootherParams = None
 
     def __post_init__(self):
+        if self.smoother is not None and not isinstance(self.smoother, PlanSmootherParams):
+            raise ValueError("GlobalPlanParams.smoother must be a PlanSmootherParams or None")
         if self.neutral_cost < 1 or self.cost_weight < 0 or self.neutral_cost + 255 * self.cost_weight > 65535:
             raise ValueError("GlobalPlanParams: neutral_cost >= 1, cost_weight >= 0 and neutral_cost + 255 * cost_weight <= 65535")
         if not 0 <= self.lethal_min_cost <= 255:

@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from . import (_abi, _abi_collision_monitor, _abi_crowd_pool, _abi_detector, _abi_global_plan, _abi_local_costmap, _abi_nearest, _abi_obstacle_memory, _abi_plan_repair,
-               _abi_plant, _abi_scan_people, _abi_sensed_costmap, _abi_tracker, _abi_visibility)
+               _abi_plan_smoother, _abi_plant, _abi_scan_people, _abi_sensed_costmap, _abi_tracker, _abi_visibility)
 from ._abi import (SmpcCrowdBatch, SmpcCrowdGroups, SmpcEvalOut, SmpcFormatBatch, SmpcFormatOut, SmpcMemoryBatch, SmpcMetricsBatch, SmpcObstacleDistanceIn,
                    SmpcObstacleDistanceOut, SmpcPeopleBatch, SmpcPlanWindowBatch, SmpcProjectionBatch, SmpcResultBatch, SmpcSceneBatch, SmpcTraceOut,
                    SmpcTrajectorizeBatch, SmpcTrajectorizeOut)
@@ -24,12 +24,14 @@ from ._abi_local_costmap import SmpcLocalCostmapIn
 from ._abi_nearest import SmpcNearestIn
 from ._abi_obstacle_memory import SmpcObstacleMemoryIn
 from ._abi_plan_repair import SmpcPlanRepairIn
+from ._abi_plan_smoother import SmpcPlanSmootherIn
 from ._abi_plant import SmpcPlantIn
 from ._abi_scan_people import SmpcScanPeopleIn
 from ._abi_sensed_costmap import SmpcSensedCostmapIn
 from ._abi_tracker import SmpcTrackerIn
 from ._abi_visibility import SmpcVisibilityIn
-from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, MonitorParams, OptimizerParams, PlanRepairParams, PlantParams, PoolCrowdParams,
+from .params import (CrowdGroupParams, CrowdParams, DetectorParams, GlobalPlanParams, MetricsParams, MonitorParams, OptimizerParams, PlanRepairParams, PlanSmootherParams, PlantParams,
+                     PoolCrowdParams,
                      ScanDetectorParams, TrackerParams, TrajectorizerParams, VisibilityParams)
 from .scenes import SceneBatch
 
@@ -73,7 +75,7 @@ def load_library():
                                        **_abi_obstacle_memory.FUNCTIONS, **_abi_tracker.FUNCTIONS,
                                        **_abi_detector.FUNCTIONS, **_abi_plant.FUNCTIONS,
                                        **_abi_collision_monitor.FUNCTIONS, **_abi_scan_people.FUNCTIONS,
-                                       **_abi_plan_repair.FUNCTIONS}.items():
+                                       **_abi_plan_repair.FUNCTIONS, **_abi_plan_smoother.FUNCTIONS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.smpc_abi_version() != _abi.SMPC_ABI_VERSION:
@@ -975,6 +977,50 @@ class BatchSolver:
         (0: none); asynchronous on the handle's stream."""
         assert ri.on_device == 1
         self._call("smpc_repair_plan_batch", ri, plan_ptr, plan_len_ptr, workspace_ptr, status_ptr, info_ptr or None, field_ptr or None)
+
+    # -- plan smoothing (smpc_smooth_plan_batch, include/smpc_plan_smoother.h) -------------------------------------------------
+    @staticmethod
+    def smooth_plan_c(sp: PlanSmootherParams, B: int, L: int, world_x: int, world_y: int, world_shared: bool, resolution: float,
+                      on_device: int, lethal_min_cost: int = 253, allow_unknown: bool = False) -> SmpcPlanSmootherIn:
+        """The call's struct without its array pointers. lethal_min_cost / allow_unknown: what sp's None stand for (the
+        planner's values)."""
+        lethal = sp.lethal_min_cost if sp.lethal_min_cost is not None else lethal_min_cost
+        unknown = sp.allow_unknown if sp.allow_unknown is not None else allow_unknown
+        return SmpcPlanSmootherIn(B=int(B), L=int(L), on_device=int(on_device), world_x=int(world_x), world_y=int(world_y),
+                                  world_shared=1 if world_shared else 0, max_its=int(sp.max_its), refinement_num=int(sp.refinement_num),
+                                  lethal_min_cost=int(lethal), allow_unknown=1 if unknown else 0, resolution=float(resolution),
+                                  w_data=float(sp.w_data), w_smooth=float(sp.w_smooth), tolerance=float(sp.tolerance))
+
+    def smooth_plan(self, si: SmpcPlanSmootherIn, world: np.ndarray, world_origin: np.ndarray, plan: np.ndarray, plan_len: np.ndarray,
+                    range_: np.ndarray = None, with_info: bool = True, with_change: bool = True):
+        """One call of the plan smoothing on host arrays. si: smooth_plan_c(..., on_device=0) (its array pointers are set here).
+        world [world_y,world_x] uint8 with world_origin [2] (si.world_shared) or [B,world_y,world_x] with [B,2]; plan [B,L,2]
+        and plan_len [B] int32: the plans before the call, which are not modified; range_ [B,2] int32 or None. Returns
+        (plan: a copy with the movable rows smoothed, status [B] int32: _abi_plan_smoother.SMOOTH_STATUS, info [B,4] int32 or
+        None: sweeps, rounds, rejected, n; change [B] or None)."""
+        world = np.ascontiguousarray(world, np.uint8)
+        world_origin = np.ascontiguousarray(world_origin, np.float64).reshape(-1, 2)
+        plan = np.array(plan, dtype=np.float64, order="C")
+        plan_len = np.ascontiguousarray(plan_len, np.int32)
+        B, L = si.B, si.L
+        assert si.on_device == 0 and plan.shape == (B, L, 2) and plan_len.shape == (B,)
+        assert world.shape == ((si.world_y, si.world_x) if si.world_shared else (B, si.world_y, si.world_x))
+        assert world_origin.shape == ((1, 2) if si.world_shared else (B, 2))
+        if range_ is not None:
+            range_ = np.ascontiguousarray(range_, np.int32)
+            assert range_.shape == (B, 2)
+        status = np.full(B, -1, np.int32)
+        info = np.full((B, 4), -99, np.int32) if with_info else None
+        change = np.full(B, np.nan) if with_change else None
+        point(si, {"world": world, "world_origin": world_origin, "plan_len": plan_len, "range": range_})
+        self._call("smpc_smooth_plan_batch", si, _ptr(plan), _ptr(status), _ptr(info), _ptr(change))
+        return plan, status, info, change
+
+    def smooth_plan_device(self, si: SmpcPlanSmootherIn, plan_ptr: int, status_ptr: int, info_ptr: int = 0, change_ptr: int = 0):
+        """Device pointers in si (on_device == 1) and for plan (smoothed in place), status, info and change (0: none);
+        asynchronous on the handle's stream."""
+        assert si.on_device == 1
+        self._call("smpc_smooth_plan_batch", si, plan_ptr, status_ptr, info_ptr or None, change_ptr or None)
 
     # -- robot plant (smpc_robot_plant_batch, include/smpc_plant.h) ----------------------------------------------------------
     @staticmethod

@@ -55,6 +55,11 @@ from geometry and not from a noise model. A detection has no velocity: combine w
 --plan-repair (with --world-plans): every tick a robot whose plan runs into impassable cells of its own window gets the least-cost
 detour inside the window spliced into its plan (BatchEpisode(repair=PlanRepairParams())); with --sensed-costmap those cells are
 what the scan marked, persons included. Last columns: the share of robot-ticks that ended with each smpc_repair_status.
+--smooth-plans (with --world-plans): the plans are smoothed where the planner walks them
+(GlobalPlanParams(smoother=PlanSmootherParams()), include/smpc_plan_smoother.h), so the plan window, the trajectorizer and the
+path-align critic read relaxed rows instead of the grid walk's staircase. Every run prints the mean path length and the mean
+summed heading change of the drive (the metrics' own columns); compare a run with the flag and one without. Last columns: the
+mean sweeps per plan and the share of plans with a rejected candidate.
 """
 import argparse
 import os
@@ -104,6 +109,8 @@ def main():
                     help="the detections are segments of the tick's scan (needs --world-plans --sensed-costmap; excludes --occlusion, --detector)")
     ap.add_argument("--plan-repair", action="store_true",
                     help="plans give way to impassable cells of the robot's window: detours spliced in every tick (needs --world-plans)")
+    ap.add_argument("--smooth-plans", action="store_true",
+                    help="the global plans are smoothed where the planner walks them (needs --world-plans)")
     ap.add_argument("--plant", action="store_true",
                     help="the command is executed under acceleration limits and stopped by contact with walls and persons")
     a = ap.parse_args()
@@ -115,6 +122,8 @@ def main():
         ap.error("--scan-detector excludes --occlusion and --detector: the scan-based and the ground-truth path are alternatives")
     if a.plan_repair and not a.world_plans:
         ap.error("--plan-repair needs --world-plans")
+    if a.smooth_plans and not a.world_plans:
+        ap.error("--smooth-plans needs --world-plans")
     if a.obstacle_memory and not a.sensed_costmap:
         ap.error("--obstacle-memory needs --sensed-costmap")
     if a.sensed_costmap and not a.world_plans:
@@ -132,11 +141,11 @@ def main():
 
     from nav2_social_mpc_controller_amd.episode import BatchEpisode, arc_plans
     from nav2_social_mpc_controller_amd.params import (CrowdParams, GlobalPlanParams, MetricsParams, ObstacleMemoryParams, OptimizerParams,
-                                                       DetectorParams, MonitorParams, PlanRepairParams, PlantParams, PoolCrowdParams, ScanDetectorParams, SensorParams, SharedWorldParams, TrackerParams, TrajectorizerParams, VisibilityParams,
+                                                       DetectorParams, MonitorParams, PlanRepairParams, PlanSmootherParams, PlantParams, PoolCrowdParams, ScanDetectorParams, SensorParams, SharedWorldParams, TrackerParams, TrajectorizerParams, VisibilityParams,
                                                        scene_param_rows)
     from nav2_social_mpc_controller_amd.scenes import (crowd_groups, crowd_waypoints, make_scenes, make_world, pool_waypoints, scenes_in_world,
                                                        shared_pool, uniform, world_goals)
-    from nav2_social_mpc_controller_amd.solver import summarize_metrics
+    from nav2_social_mpc_controller_amd.solver import METRIC_COLS, summarize_metrics
 
     prm = OptimizerParams.readme()
     sets = parameter_sets(prm)
@@ -149,7 +158,7 @@ def main():
     sc = one.select(np.tile(np.arange(n), S))                               # every set sees the same scenes
     w_ref = np.tile((uniform(0x5EED0001, np.arange(n), 6)[:, 0] * 2.0 - 1.0) * 0.6, S)
     if a.world_plans:                                                       # every set drives to the same goals
-        plans = dict(world=world, planner=GlobalPlanParams(stride=2), goal=np.tile(world_goals(world, one.pose0[:, :2]), (S, 1)),
+        plans = dict(world=world, planner=GlobalPlanParams(stride=2, smoother=PlanSmootherParams() if a.smooth_plans else None), goal=np.tile(world_goals(world, one.pose0[:, :2]), (S, 1)),
                      plan_window=(4.0, 10.0))
         if a.occlusion is not None:
             plans["visibility"] = VisibilityParams(max_range=a.occlusion)
@@ -201,7 +210,10 @@ def main():
         if a.collision_monitor:
             with ep.torch.cuda.stream(ep.gstream):   # behind the tick, on its stream: nothing leaves the device
                 changed += ep.monitor_ratio < 1.0
-    m = summarize_metrics(ep.metrics(), prm.dt)
+    acc = ep.metrics()
+    m = summarize_metrics(acc, prm.dt)
+    m["heading_change"] = acc[:, METRIC_COLS.index("heading_change")]
+    smooth_info = ep.smooth_info.cpu().numpy() if a.smooth_plans else np.zeros((S * n, 4), np.int32)
     changed = changed.cpu().numpy()
     repair = repair.cpu().numpy()
     from nav2_social_mpc_controller_amd._abi_plan_repair import REPAIR_STATUS
@@ -214,7 +226,9 @@ def main():
               f"mean_speed {mean('mean_speed'):.3f}  mean_min_person_dist {mean('mean_min_person_dist'):.3f}  "
               f"intimate {mean('intimate_share'):.3f}  personal {mean('personal_share'):.3f}  "
               f"social_work/m {mean('social_work_per_metre'):8.3f}  person_coll {m['person_collision'][sl].mean():.3f}  "
-              f"obstacle_coll {m['obstacle_collision'][sl].mean():.3f}  fallback {mean('fallback_share'):.3f}"
+              f"obstacle_coll {m['obstacle_collision'][sl].mean():.3f}  fallback {mean('fallback_share'):.3f}  "
+              f"path_length {mean('path_length'):6.3f} m  heading_change {mean('heading_change'):6.3f} rad"
+              + (f"  smooth_sweeps {smooth_info[sl, 0].mean():.1f}  smooth_rejecting {(smooth_info[sl, 2] > 0).mean():.3f}" if a.smooth_plans else "")
               + (f"  stopped_by_contact {stopped[sl].mean():.3f}" if a.plant else "")
               + (f"  monitor_share {changed[sl].mean() / max(a.ticks, 1):.3f}" if a.collision_monitor else "")
               + ("".join(f"  {REPAIR_STATUS[i].lower()} {repair[sl, i].sum() / max(a.ticks * n, 1):.3f}" for i in range(n_status)) if a.plan_repair else ""))
